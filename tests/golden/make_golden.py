@@ -5,7 +5,9 @@ oracle's outputs -- itself pinned by tests/test_oracle_kat.py -- on the BASELINE
   cube8.npz        cfg1, complete inputs (seeds, planes) and complete outputs
   digests.json     cfg2 / cfg3 / cfg4: counts + sha256 of every output array; urchin64 / urchin1024: the deep-lobed mesh of
                    meshgen.urchin (cells with several islands, non-convex faces) at the cell counts of cfg2 / cfg3
-Run from the repo root:  python tests/golden/make_golden.py
+  reference_models.npz  the reference's bunny (x70) and cube (x3) as engine.read_obj loads them (tests/test_reference_pin.py);
+                   written only by --models DIR, DIR being the reference's Resources/Models
+Run from the repo root:  python tests/golden/make_golden.py [--models DIR]
 """
 import hashlib
 import json
@@ -41,7 +43,17 @@ def run(sc, threads=8):
     return planes, O.event([sc["mesh"]], [sc["convex"]], sc["face_off"], planes, refit=True, render=True, threads=threads)
 
 
+def models(src):
+    from surtr_amd import engine
+    bunny = engine.read_obj(os.path.join(src, "lowpoly-bunny-closed.obj"), scale=(70.0,) * 3)
+    cube = engine.read_obj(os.path.join(src, "cube.obj"), scale=(3.0,) * 3)
+    np.savez_compressed(os.path.join(HERE, "reference_models.npz"), bunny_pos=bunny[0], bunny_tris=bunny[1], cube_pos=cube[0],
+                        cube_tris=cube[1])
+
+
 def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--models":
+        return models(sys.argv[2])
     sc = scenes.cube_scene(8)
     planes, ev = run(sc)
     np.savez_compressed(os.path.join(HERE, "cube8.npz"), seeds=sc["seeds"], face_off=sc["face_off"], v012=sc["v012"], planes=planes,

@@ -53,3 +53,23 @@ def test_world_size_must_match_gpus(emul_lib_path):
     r = _run(["--gpus", "4", "--steps", "1", "--warmup", "0", "--cells", "8", "--torus", "16", "12", "--no-cpu-baseline"],
              {"SURTR_BENCH_EMUL_LIB": emul_lib_path, "WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and r.stdout.strip() == ""
+
+
+def test_dump_outputs_are_the_last_steps_arrays_and_repeat(emul_lib_path, tmp_path):
+    """--dump-outputs DIR: the fragment arrays of the last timed step, float32 / float64, identical from run to run."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--cells", "8", "--torus", "16", "12", "--no-cpu-baseline",
+                  "--dump-outputs", str(d)], {"SURTR_BENCH_EMUL_LIB": emul_lib_path})
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert {"frag_ids", "mesh_pos", "mesh_nbr", "conv_pos", "idx", "vnc"} <= set(a) and set(a) == set(b)
+    assert a["frag_ids"].shape[0] == line["config"]["fragments"]
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k]), k
