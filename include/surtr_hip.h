@@ -264,6 +264,17 @@ int surtr_download_piece(surtr_ctx* ctx, uint32_t piece, int set, uint32_t* out_
 /* Host time of the last surtr_upload_pieces / surtr_pieces_from_event / surtr_transform_pieces call, in milliseconds,
  * and how many device allocations it made (0 in steady state: the piece buffers are pooled). */
 int surtr_upload_stats(surtr_ctx* ctx, float* ms, uint32_t* n_alloc);
+/* Diagnostic: the hand-over words of the last event's split Mesh clip (k_clip_pairs_main hands the pairs it cannot finish to
+ * k_clip_pairs_catch on another stream; a sweep launch behind both takes what nobody polled for).  Synchronises the context's
+ * three streams.  out[0] pairs handed on (pushed), [1] / [2] workgroups of the main kernel that started / signed off (both equal
+ * its grid, min(pairs, out[6]), after an event that took the split arrangement; 0 after one that did not), [3] hand-over slots
+ * claimed by polling catcher workgroups, [4] the catcher's cursor over its own classes (13..12), [5] the sweep's cursor,
+ * [6] the workgroups the last event's clip kernels could use, [7] the hand-over list's capacity (pairs + 4 096). */
+int surtr_handover_stats(surtr_ctx* ctx, uint32_t out[8]);
+/* Diagnostic: the order in which k_clip_convex takes the pairs of the last surtr_fracture_event (pairs of the cells with the most
+ * planes first; the order of surtr_fracture_pairs_async's list there): *n entries, relative to the event's first pair.  order ==
+ * NULL returns the count only; cap < *n is SURTR_E_CAPACITY. */
+int surtr_pair_order(surtr_ctx* ctx, uint32_t cap, uint32_t* n, uint32_t* order);
 
 /* ---- host-side helpers of the harness (no GPU needed) ------------------ */
 /* Poly::ExtractNeighborFromMesh, Src/Poly.cpp:128-263: welded triangle soup ->

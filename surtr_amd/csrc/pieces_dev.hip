@@ -614,4 +614,33 @@ int surtr_upload_stats(surtr_ctx* ctx, float* ms, uint32_t* n_alloc)
     return SURTR_OK;
 }
 
+int surtr_handover_stats(surtr_ctx* ctx, uint32_t out[8])
+{
+    if (!ctx || !out) return SURTR_E_INVALID;
+    (void)hipSetDevice(ctx->device);
+    // (the hand-over words are written on all three streams of the context: the event's end joins them into `stream`, but a
+    //  caller may ask before that join has been reached)
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (ctx->stream2) HIPCHK(hipStreamSynchronize(ctx->stream2));
+    if (ctx->stream3) HIPCHK(hipStreamSynchronize(ctx->stream3));
+    uint32_t c[6] = {0, 0, 0, 0, 0, 0};
+    if (ctx->arena.cursors) HIPCHK(hipMemcpy(c, ctx->arena.cursors + 146, sizeof(c), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 6; ++k) out[k] = c[k];
+    out[6] = ctx->max_wg;
+    out[7] = ctx->cap_hlist;
+    return SURTR_OK;
+}
+
+int surtr_pair_order(surtr_ctx* ctx, uint32_t cap, uint32_t* n, uint32_t* order)
+{
+    if (!ctx || !n) return SURTR_E_INVALID;
+    (void)hipSetDevice(ctx->device);
+    *n = ctx->d_pair_order ? ctx->pair_order_count : 0u;
+    if (!order || *n == 0u) return SURTR_OK;
+    if (cap < *n) return SURTR_E_CAPACITY;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpy(order, ctx->d_pair_order, (size_t)*n * 4, hipMemcpyDeviceToHost));
+    return SURTR_OK;
+}
+
 } // extern "C"

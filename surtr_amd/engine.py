@@ -193,6 +193,22 @@ class Engine:
         self._ck(lib().surtr_queue_stats(self._h, out))
         return np.frombuffer(out, dtype=np.uint32).copy()
 
+    def handover_stats(self):
+        """Hand-over words of the last event's split Mesh clip (include/surtr_hip.h: surtr_handover_stats): pushed, main workgroups
+        started, signed off, poll slots claimed, the catcher's own-class cursor, the sweep's cursor, clip workgroups, list capacity."""
+        out = (ctypes.c_uint32 * 8)()
+        self._ck(lib().surtr_handover_stats(self._h, out))
+        names = ("pushed", "main_started", "main_signed_off", "poll_claimed", "catch_own", "sweep_cursor", "max_wg", "hcap")
+        return {n: int(out[i]) for i, n in enumerate(names)}
+
+    def pair_order(self):
+        """The order k_clip_convex took the last event's pairs in (include/surtr_hip.h: surtr_pair_order)."""
+        n = ctypes.c_uint32()
+        self._ck(lib().surtr_pair_order(self._h, ctypes.c_uint32(0), ctypes.byref(n), None))
+        out = np.zeros(n.value, np.uint32)
+        self._ck(lib().surtr_pair_order(self._h, ctypes.c_uint32(n.value), ctypes.byref(n), _p(out)))
+        return out
+
     def upload_pieces(self, meshes, convexes):
         assert len(meshes) == len(convexes)
         m = pack_solids(meshes)
@@ -273,6 +289,13 @@ class Engine:
         assert pc.shape == pp.shape
         self._ck(lib().surtr_fracture_pairs_async(self._h, ctypes.c_uint32(pc.shape[0]), _p(pc), _p(pp), ctypes.c_uint32(flags)))
         return self.event_counts()
+
+    def fracture_pairs_async(self, pair_cell, pair_piece, flags=EVT_REFIT | EVT_RENDER):
+        """fracture_pairs without reading the counts back: nothing waits for the event (surtr_fracture_pairs_async)."""
+        pc = np.ascontiguousarray(pair_cell, np.uint32)
+        pp = np.ascontiguousarray(pair_piece, np.uint32)
+        assert pc.shape == pp.shape
+        self._ck(lib().surtr_fracture_pairs_async(self._h, ctypes.c_uint32(pc.shape[0]), _p(pc), _p(pp), ctypes.c_uint32(flags)))
 
     def event_regroup(self, partial=False, sphere_points=None, origin=(0, 0, 0), radius=1.0):
         """surtr_event_regroup: bind sets + MergeOutOfImpact + HandleConvexIsland of the last event, on the device."""
