@@ -113,8 +113,9 @@ int surtr_set_arena(surtr_ctx* ctx, uint64_t verts, uint64_t nbrs, uint64_t idx)
 /* Per-kernel timing with HIP events recorded on the work stream (the reference's TIMER_* phase
  * timers, Inc/pch.h:122-141, Src/Surtr.cpp:1917-1941).  ms[i] = duration of the last launch of
  * 0 clip_pairs (Mesh), 1 frag_table, 2 refit, 3 faces, 4 out_scan, 5 pack, 6 clip_convex, 7 prep_pairs,
- * 8 clip_pairs_big, 9 clip_pairs_half, 10 clip_pairs retry launch (0, 8 and 9 run side by side on the caller's and
- * two internal streams); -1 where not run. */
+ * 8 clip_pairs_big (or _wave_big), 9 clip_pairs_half, 10 clip_pairs retry launch + the catcher's sweep,
+ * 11 clip_pairs_wave (or _main), 13 clip_pairs_catch (the Mesh clip's kernels run side by side on the caller's and
+ * two internal streams); -1 where not run (slots 12, 14 and 15 never are). */
 int surtr_set_profiling(surtr_ctx* ctx, int on);
 int surtr_kernel_times(surtr_ctx* ctx, float ms[16]);
 /* The durations of the Mesh clip kernel (slot[k] = 0: k_clip_pairs, 11: k_clip_pairs_wave) over the last *n <= 16 events since

@@ -36,4 +36,4 @@ python scripts/bench_cfg23.py 2>&1 | grep -v amdgpu.ids > $OUT/cfg23.log; cut -c
 python scripts/bench_cfg5.py 2>&1 | grep -v amdgpu.ids > $OUT/cfg5.log; tail -3 $OUT/cfg5.log | cut -c1-200
 python scripts/bench_regroup.py 2>&1 | grep -v amdgpu.ids > $OUT/regroup.log; cat $OUT/regroup.log
 rm -f $OUT/switches.txt
-for e in "SURTR_SMALL=1" "SURTR_REC=0" "SURTR_PREP_SORTED=0" "SURTR_FRONT_PAR=1"; do env $e python scripts/bench_event.py 2>&1 | grep -v amdgpu.ids >> $OUT/switches.txt; done; python scripts/bench_event.py 2>&1 | grep -v amdgpu.ids >> $OUT/switches.txt; cut -c1-120 $OUT/switches.txt
+for e in "SURTR_REC=0" "SURTR_PREP_SORTED=0" "SURTR_FRONT_PAR=1"; do env $e python scripts/bench_event.py 2>&1 | grep -v amdgpu.ids >> $OUT/switches.txt; done; python scripts/bench_event.py 2>&1 | grep -v amdgpu.ids >> $OUT/switches.txt; cut -c1-120 $OUT/switches.txt

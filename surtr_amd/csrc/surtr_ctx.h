@@ -221,7 +221,6 @@ struct surtr_ctx
     // what the CUs can hold (surtr_create); max_wg* below are those, cut down to what the scratch of the current pieces leaves room for
     uint32_t hw_wg = 512, hw_wg_faces = 1024, hw_wg_prep = 1792, hw_wg_big = 48, budget_vmax = 0xFFFFFFFFu, budget_hmax = 0xFFFFFFFFu;
     uint32_t max_wg = 512, max_wg_faces = 1024, max_wg_small = 2048, max_wg_prep = 1792, max_wg_half = 1024;
-    ScratchPool pool_rec{}; uint32_t n_wg_rec = 0;          // k_clip_pairs_rec: positions of the cut points only
     uint32_t* d_hlist = nullptr; uint32_t cap_hlist = 0;    // hand-over list of the split arrangement (k_clip_pairs_main -> k_clip_pairs_catch)
     uint32_t n_wg_catch = 128;                              // workgroups of k_clip_pairs_catch (at most; scratch slots are reserved for them)
     uint32_t vmin = 0;                                      // smallest Mesh of the resident pieces

@@ -823,14 +823,12 @@ __device__ __attribute__((always_inline)) static inline void prep_pairs_body(Sha
                                                          uint32_t n_pairs, const PrepPool& pool, const Arena& A, const ImgArena& IA, uint32_t capV, uint32_t capVs,
                                                          PairRec* __restrict__ pairs, const uint2* __restrict__ pair_list,
                                                          uint32_t* __restrict__ order, const uint32_t* __restrict__ porder,
-                                                         uint32_t* __restrict__ horder, uint32_t half_on, uint32_t big_quota, uint32_t big_n, uint32_t small_cap, uint32_t heavy_need)
+                                                         uint32_t* __restrict__ horder, uint32_t half_on, uint32_t big_quota, uint32_t big_n)
 {
     // order[c * n_pairs + i]: the pairs of cost class c (0 light .. 15 heavy); k_clip_pairs starts with the heavy
     // ones, so that a pair that takes milliseconds (one that outgrows the LDS topology) is not left for the end
     auto enqueue = [&](uint32_t p, uint32_t cls) { order[(size_t)cls * n_pairs + atomicAdd(&A.cursors[16u + cls], 1u)] = p; };
     auto enqueue_half = [&](uint32_t p, uint32_t cls) { horder[(size_t)cls * n_pairs + atomicAdd(&A.cursors[64u + cls], 1u)] = p; };
-    // the small tier of the record clipper (k_clip_pairs_rec): its table follows the half kernel's
-    auto enqueue_small = [&](uint32_t p, uint32_t cls) { horder[(size_t)(16u + cls) * n_pairs + atomicAdd(&A.cursors[128u + cls], 1u)] = p; };
     const uint32_t tid = threadIdx.x;
     const bool front_par = (rec_on & 4u) != 0u;
     char* sp = pool.base + (size_t)blockIdx.x * pool.per_wg;
@@ -1004,10 +1002,6 @@ __device__ __attribute__((always_inline)) static inline void prep_pairs_body(Sha
                                                  __builtin_popcount(sh.cutmask[2]) + __builtin_popcount(sh.cutmask[3]));
                 const uint32_t cost = (41u * ncut + n / 40u) / 110u;
                 cls = !fits_with_room(n, hsum, capV, SURTR_LH) ? 14u : 1u + (cost < 11u ? cost : 11u);
-                // split arrangement (heavy_need != 0): a band the record clipper will run out of LDS on (its need at the worst plane
-                // follows the band size and the largest bucket: scripts/wave_need.py) would be handed on after a plane or two and then
-                // be the slowest task of the catcher -- it goes to the double-size general clipper (k_clip_pairs_big) from the start
-                if (cls < 12u && heavy_need != 0u && sorted_sel && (515u * n + 4185u * maxb_rec) / 100u + 393u > heavy_need) cls = 14u;
                 // a band vertex lies in a plane: the record clipper hands the pair to the general clipper, which takes longer --
                 // such pairs go first (the top regular class), not into the tail of the queue
                 if (cls < 12u && fmt == IMG_NARROW) { bool inplane = false; for (uint32_t k = 0; k < F; ++k) if (sh.nzero[k] != 0u) inplane = true; if (inplane) cls = 12u; }
@@ -1026,14 +1020,7 @@ __device__ __attribute__((always_inline)) static inline void prep_pairs_body(Sha
                 else if (cls < 12u && (fmt == IMG_NARROW || fmt == IMG_REC) && n > big_n && n < WC_MAXN) cls = 14u;
             }
             else if (cls >= 14u && fmt != IMG_EMPTY && atomicAdd(&A.cursors[84], 1u) >= big_quota) cls = 13u;
-            // The small tier takes the record images whose worst plane will fit its LDS: the need follows the band size and the largest
-            // bucket (measured on configs[3], scripts/wave_need.py: need ~ 5.15 n + 41.85 maxbucket + 393 bytes, residual sigma 2.3 KB),
-            // of which 16 bytes per vertex of the bucket are the stage, which a plane leaves in global memory when it must
-            // (wave_clip.h); what does not fit after all comes back through class 12 of the large tier
-            const uint32_t s_cap = small_cap;
-            const bool to_small = s_cap != 0u && fmt == IMG_REC && cls < 12u && (515u * n + 2585u * maxb_rec) / 100u + 393u + 4096u <= s_cap;
-            if (to_small) enqueue_small(p, cls);
-            else if (fmt == IMG_NARROW && to_half) enqueue_half(p, cls < 6u ? cls : 6u);      // (a record image is never to_half)
+            if (fmt == IMG_NARROW && to_half) enqueue_half(p, cls < 6u ? cls : 6u);      // (a record image is never to_half)
             else if (fmt != IMG_EMPTY) enqueue(p, cls);
         }
 #ifdef SURTR_STAMP
@@ -1050,12 +1037,12 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(SURTR_
                                                          uint32_t n_pairs, PrepPool pool, Arena A, ImgArena IA, uint32_t capV, uint32_t capVs,
                                                          PairRec* __restrict__ pairs, const uint2* __restrict__ pair_list,
                                                          uint32_t* __restrict__ order, const uint32_t* __restrict__ porder,
-                                                         uint32_t* __restrict__ horder, uint32_t half_on, uint32_t big_quota, uint32_t big_n, uint32_t rec_on, uint32_t small_cap, uint32_t heavy_need)
+                                                         uint32_t* __restrict__ horder, uint32_t half_on, uint32_t big_quota, uint32_t big_n, uint32_t rec_on)
 {
     __shared__ Shared sh;
     __shared__ unsigned long long lbuf[2u * SURTR_PREP_NB];      // masks (first half) + per-block pairs (second half); the sorted selection's tables
     unsigned long long* lmask = lbuf; uint2* lblk = (uint2*)(lbuf + SURTR_PREP_NB);
-    prep_pairs_body(sh, lmask, lblk, rec_on, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, capV, capVs, pairs, pair_list, order, porder, horder, half_on, big_quota, big_n, small_cap, heavy_need);
+    prep_pairs_body(sh, lmask, lblk, rec_on, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, capV, capVs, pairs, pair_list, order, porder, horder, half_on, big_quota, big_n);
 }
 
 // the same for events whose every piece takes the sorted selection
@@ -1064,12 +1051,12 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(SURTR_
                                                          uint32_t n_pairs, PrepPool pool, Arena A, ImgArena IA, uint32_t capV, uint32_t capVs,
                                                          PairRec* __restrict__ pairs, const uint2* __restrict__ pair_list,
                                                          uint32_t* __restrict__ order, const uint32_t* __restrict__ porder,
-                                                         uint32_t* __restrict__ horder, uint32_t half_on, uint32_t big_quota, uint32_t big_n, uint32_t rec_on, uint32_t small_cap, uint32_t heavy_need)
+                                                         uint32_t* __restrict__ horder, uint32_t half_on, uint32_t big_quota, uint32_t big_n, uint32_t rec_on)
 {
     __shared__ Shared sh;
     __shared__ unsigned long long lbuf[2u * SURTR_PREP_NB];      // masks (first half) + per-block pairs (second half); the sorted selection's tables
     unsigned long long* lmask = lbuf; uint2* lblk = (uint2*)(lbuf + SURTR_PREP_NB);
-    prep_pairs_body<false>(sh, lmask, lblk, rec_on, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, capV, capVs, pairs, pair_list, order, porder, horder, half_on, big_quota, big_n, small_cap, heavy_need);
+    prep_pairs_body<false>(sh, lmask, lblk, rec_on, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, capV, capVs, pairs, pair_list, order, porder, horder, half_on, big_quota, big_n);
 }
 
 // The same with four times the threads per pair, for events of so few pairs (a rank's block of a sharded event) that the
@@ -1080,12 +1067,12 @@ __global__ __launch_bounds__(SURTR_WG_WIDE) void k_prep_pairs_wide(Pieces P, con
                                                          uint32_t n_pairs, PrepPool pool, Arena A, ImgArena IA, uint32_t capV, uint32_t capVs,
                                                          PairRec* __restrict__ pairs, const uint2* __restrict__ pair_list,
                                                          uint32_t* __restrict__ order, const uint32_t* __restrict__ porder,
-                                                         uint32_t* __restrict__ horder, uint32_t half_on, uint32_t big_quota, uint32_t big_n, uint32_t rec_on, uint32_t small_cap, uint32_t heavy_need)
+                                                         uint32_t* __restrict__ horder, uint32_t half_on, uint32_t big_quota, uint32_t big_n, uint32_t rec_on)
 {
     __shared__ Shared sh;
     __shared__ unsigned long long lbuf[2u * SURTR_PREP_NB];      // masks (first half) + per-block pairs (second half); the sorted selection's tables
     unsigned long long* lmask = lbuf; uint2* lblk = (uint2*)(lbuf + SURTR_PREP_NB);
-    prep_pairs_body(sh, lmask, lblk, rec_on, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, capV, capVs, pairs, pair_list, order, porder, horder, half_on, big_quota, big_n, small_cap, heavy_need);
+    prep_pairs_body(sh, lmask, lblk, rec_on, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, capV, capVs, pairs, pair_list, order, porder, horder, half_on, big_quota, big_n);
 }
 
 // -------------------------------------------------------------- k_clip_pairs
@@ -1308,9 +1295,9 @@ __global__ __launch_bounds__(SURTR_WG) void k_clip_pairs_big(Pieces P, const flo
 // the same LDS bytes: k_prep_pairs puts the pairs it knows to be irregular into the heaviest class, so they come first.
 struct GenLds { Shared sh; LdsTopo L; };
 struct GenLdsBig { Shared sh; LdsTopoBig L; };
-// FALLBACK = false: the small tier (k_clip_pairs_rec) -- record images only, no general clipper in the kernel (its LDS and registers
-// are the record clipper's alone: three workgroups per CU); a pair it gives up on goes to class 12 of the large tier's table,
-// whose kernel runs behind this one.
+// FALLBACK = false: k_clip_pairs_main -- no general clipper in the kernel (its LDS and registers are the record clipper's alone); a
+// pair it gives up on goes to the catcher beside it through the hand-over list `hlist`, which is then required.  cbase: where the
+// class counts of the table this kernel pulls from start in A.cursors (16: the table k_prep_pairs fills for the clip kernels).
 template <class WL, class GL, bool FALLBACK = true, bool OLD_IMAGES = FALLBACK>
 __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_body(unsigned char* lds_raw, uint32_t wg, const Pieces& P, const float4* __restrict__ planes,
                                                          const uint32_t* __restrict__ plane_off, uint32_t cell_begin,
@@ -1318,7 +1305,7 @@ __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_bod
                                                          const ScratchPool& pool, const Arena& A, const ImgArena& IA, PairRec* __restrict__ pairs,
                                                          const uint2* __restrict__ pair_list, const uint32_t* __restrict__ order,
                                                          uint32_t* __restrict__ horder, int cls_hi, int cls_lo, uint32_t qcur, uint32_t walk0,
-                                                         uint32_t* __restrict__ hlist = nullptr, uint32_t cbase_arg = 0u)
+                                                         uint32_t* __restrict__ hlist, uint32_t cbase)
 {
     WL& W = *reinterpret_cast<WL*>(lds_raw);
     GL& Gn = *reinterpret_cast<GL*>(lds_raw);
@@ -1328,8 +1315,7 @@ __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_bod
     char* slot = pool.base + (size_t)wg * pool.per_wg;
     Scratch S{};
     if (FALLBACK) S = carve(pool, wg);
-    const uint32_t cbase = cbase_arg ? cbase_arg : (FALLBACK ? 16u : 128u);       // class counts of the table this kernel pulls from
-    if (!FALLBACK && hlist != nullptr && tid == 0) atomicAdd(&A.cursors[147], 1u);      // (the catcher beside this kernel: "it has started")
+    if (!FALLBACK && tid == 0) atomicAdd(&A.cursors[147], 1u);      // (the catcher beside this kernel: "it has started")
     while (true)
     {
         __syncthreads();
@@ -1424,19 +1410,10 @@ __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_bod
             else if (tid == 0)
             {
                 pairs[p] = rec;          // (a record image is spent: rec.img_fmt is IMG_NONE by now; an old image is as it was)
-                if (hlist != nullptr)
-                {
-                    // to the catcher that runs beside this kernel (k_clip_pairs_catch): a slot of its list, filled with one atomic
-                    // so that whoever polls the slot sees either nothing or the pair
-                    __threadfence();
-                    atomicExch(&hlist[atomicAdd(&A.cursors[146], 1u)], p);
-                }
-                else
-                {
-                    // to the large tier, first in its queue (class 12), whose kernel is launched behind this one
-                    horder[(size_t)12 * n_pairs + atomicAdd(&A.cursors[16u + 12u], 1u)] = p;      // (horder: the large tier's table here)
-                    atomicAdd(&A.cursors[146], 1u);
-                }
+                // to the catcher that runs beside this kernel (k_clip_pairs_catch): a slot of its list, filled with one atomic
+                // so that whoever polls the slot sees either nothing or the pair
+                __threadfence();
+                atomicExch(&hlist[atomicAdd(&A.cursors[146], 1u)], p);
             }
             continue;
         }
@@ -1445,7 +1422,7 @@ __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_bod
         if (tid == 0) pairs[p] = rec;
     }
     // the catcher stops polling when every workgroup of this kernel has said so (after its last hand-over)
-    if (!FALLBACK && hlist != nullptr && tid == 0) { __threadfence(); atomicAdd(&A.cursors[148], 1u); }
+    if (!FALLBACK && tid == 0) { __threadfence(); atomicAdd(&A.cursors[148], 1u); }
 }
 
 __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(2, 4))) void k_clip_pairs_wave(Pieces P, const float4* __restrict__ planes,
@@ -1457,33 +1434,7 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(2, 4))
 {
     constexpr size_t kBytes = sizeof(WcLds) > sizeof(GenLds) ? sizeof(WcLds) : sizeof(GenLds);
     __shared__ alignas(16) unsigned char lds_raw[kBytes];
-    clip_pairs_wave_body<WcLds, GenLds>(lds_raw, blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, pairs, pair_list, order, horder, cls_hi, cls_lo, qcur, walk0);
-}
-
-// The small tier: the record images whose worst plane fits SURTR_WR_S units of LDS (k_prep_pairs predicts it from the band size and
-// the largest bucket), three workgroups per CU -- 12 waves per CU instead of 8 for a kernel that is bound by instruction issue and
-// dependent LDS round trips (measured in round 3 on a timing-only build: -17 % for the pairs it takes).  No general clipper
-// inside: 0 bytes of private scratch, the registers of the record clipper alone.
-#ifndef SURTR_WR_S
-#define SURTR_WR_S 2240u
-#define SURTR_WNL_S 2048u
-#endif
-#ifndef SURTR_S_THREADS
-#define SURTR_S_THREADS SURTR_WG
-#endif
-#ifndef SURTR_S_WAVES_EU
-#define SURTR_S_WAVES_EU 3
-#endif
-typedef WcLdsT<SURTR_WR_S, SURTR_WNL_S, (SURTR_S_THREADS / SURTR_LANES > SURTR_NWAVE ? SURTR_S_THREADS / SURTR_LANES : SURTR_NWAVE)> WcLdsS;
-__global__ __launch_bounds__(SURTR_S_THREADS) __attribute__((amdgpu_waves_per_eu(SURTR_S_WAVES_EU, 4))) void k_clip_pairs_rec(Pieces P, const float4* __restrict__ planes,
-                                                         const uint32_t* __restrict__ plane_off, uint32_t cell_begin,
-                                                         uint32_t n_pairs,
-                                                         ScratchPool pool, Arena A, ImgArena IA, PairRec* __restrict__ pairs,
-                                                         const uint2* __restrict__ pair_list, const uint32_t* __restrict__ sorder,
-                                                         uint32_t* __restrict__ order, uint32_t walk0)
-{
-    __shared__ alignas(16) unsigned char lds_raw[sizeof(WcLdsS)];
-    clip_pairs_wave_body<WcLdsS, WcLdsS, false>(lds_raw, blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, pairs, pair_list, sorder, order, 11, 0, 144u, walk0);
+    clip_pairs_wave_body<WcLds, GenLds>(lds_raw, blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, pairs, pair_list, order, horder, cls_hi, cls_lo, qcur, walk0, nullptr, 16u);
 }
 
 // ---- The split arrangement (round 4): the regular pairs on a kernel that holds the record clipper ALONE, everything else beside it.
@@ -1605,7 +1556,7 @@ __global__ __launch_bounds__(SURTR_WG) void k_clip_pairs_wave_big(Pieces P, cons
 {
     constexpr size_t kBytes = sizeof(WcLdsBig) > sizeof(GenLdsBig) ? sizeof(WcLdsBig) : sizeof(GenLdsBig);
     __shared__ alignas(16) unsigned char lds_raw[kBytes];
-    clip_pairs_wave_body<WcLdsBig, GenLdsBig>(lds_raw, wg_base + blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, pairs, pair_list, order, nullptr, cls_hi, cls_lo, qcur, walk0);
+    clip_pairs_wave_body<WcLdsBig, GenLdsBig>(lds_raw, wg_base + blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, pairs, pair_list, order, nullptr, cls_hi, cls_lo, qcur, walk0, nullptr, 16u);
 }
 
 // -------------------------------------------------------------- k_frag_table
@@ -3203,7 +3154,7 @@ void surtr_destroy(surtr_ctx* ctx)
     free_dev(ctx->pool.base); free_dev(ctx->pool_small.base); free_dev(ctx->pool_half.base); free_dev(ctx->fs.base); free_dev(ctx->d_blk);
     free_dev(ctx->fs_big.base); free_dev(ctx->d_blk_big); free_dev(ctx->d_face_list);
     free_dev(ctx->d_pair_order); free_dev(ctx->d_face_group);
-    free_dev(ctx->prep.base); free_dev(ctx->img.base); free_dev(ctx->d_order); free_dev(ctx->d_forder); free_dev(ctx->pool_rec.base); free_dev(ctx->d_hlist);
+    free_dev(ctx->prep.base); free_dev(ctx->img.base); free_dev(ctx->d_order); free_dev(ctx->d_forder); free_dev(ctx->d_hlist);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
     if (ctx->ev_half) (void)hipEventDestroy(ctx->ev_half);
@@ -3445,7 +3396,7 @@ static int ensure_prep(surtr_ctx* ctx, uint32_t n_pairs, uint32_t n_wg)
     if (ctx->cap_order < n_pairs)
     {
         free_dev(ctx->d_order); ctx->d_order = nullptr;
-        HIPCHK(hipMalloc((void**)&ctx->d_order, (size_t)n_pairs * 64 * 4));      // four tables: clip order, pre-pass order, half clip order, small record tier
+        HIPCHK(hipMalloc((void**)&ctx->d_order, (size_t)n_pairs * 64 * 4));      // tables of 16 classes: clip order, pre-pass order, half clip order (+ one spare)
         ctx->cap_order = n_pairs;
     }
     const uint64_t full = (uint64_t)ctx->vmax * 16 + (uint64_t)ctx->hmax * 2;
@@ -3549,38 +3500,151 @@ static int upload_pair_order(surtr_ctx* ctx, const uint32_t* ord, uint32_t n_pai
     return SURTR_OK;
 }
 
-#ifndef SURTR_WAVE_BIG_N
-#define SURTR_WAVE_BIG_N 2800u
-#endif
 #ifndef SURTR_REC_MAXN
 #define SURTR_REC_MAXN 2304u
 #endif
 #ifndef SURTR_FRONT_PAR_MAX
 #define SURTR_FRONT_PAR_MAX 1024u      // pairs of an event up to which k_clip_convex and the pre-pass kernel run side by side
 #endif
+// Everything launch_event decides for one event: which kernels run, their grids, and which stream each runs on.
+struct EventPlan
+{
+    bool cell_order;                      // a cell range (no pair list): the pairs are clipped in the order of their cells' plane counts
+    decltype(&k_prep_pairs) prep;         // the pre-pass kernel (k_prep_pairs, _sorted or _wide; nullptr: no pairs)
+    uint32_t prep_threads;
+    bool wave_on, split_on, use_half, front_par, both;
+    uint32_t rec_on;                      // k_prep_pairs' mode word: 1 record images, 2 round 3's selection, 4 front_par, rec_maxn << 8
+    uint32_t big_quota, big_n, walk0, n_catch, n_poll;
+    uint32_t n_wg, n_wg_cvx, n_wg_prep, n_wg_big, n_wg_half, n_wg_retry, n_wg_sweep;      // grids
+    uint32_t g_refit, g_faces, t_faces;
+    hipStream_t st_cvx, st_main, st_bigk, st_refit;
+};
+
+// The plan of an event.  No HIP call, no allocation, nothing written to the context: it reads the capacities the ensure_* calls
+// have set.  Every environment override of the launch sequence is read here, on every event (tests set them between events).
+static EventPlan plan_event(const surtr_ctx* ctx, uint32_t n_pairs, bool pair_list, uint32_t flags)
+{
+    EventPlan pl{};
+    const uint32_t n1 = std::max(n_pairs, 1u), max_wg = ctx->max_wg;
+    pl.cell_order = !pair_list && n_pairs && ctx->n_pieces && n_pairs % ctx->n_pieces == 0 && !getenv("SURTR_NO_CELL_ORDER");
+    pl.n_wg = std::max(1u, std::min(n1, max_wg));
+    pl.n_wg_cvx = std::max(1u, std::min(n1, ctx->max_wg_small));
+    pl.n_wg_half = std::max(1u, std::min(n1, ctx->max_wg_half));
+    pl.n_wg_prep = std::max(1u, std::min(n1, ctx->max_wg_prep));
+    pl.n_wg_big = std::min(ctx->n_wg_big, n1);
+    pl.n_wg_retry = std::min(pl.n_wg, 64u);
+    pl.big_quota = ctx->wave_big ? 0xFFFFFFFFu : 2u * ctx->n_wg_big;
+    if (const char* e = getenv("SURTR_BIG_QUOTA")) pl.big_quota = (uint32_t)atoi(e);      // (tests: 0 sends every big band to the regular kernel's global scratch)
+    // (pieces of 80 000 vertices and more: bands beyond this size go to the whole-CU record clipper, see k_prep_pairs)
+    // measured at 4 096 cells with 2 800: 100 000-vertex piece 6.50 -> 5.96 ms, 150 000 vertices 10.5 -> 9.6 ms, 210 000 vertices 12.6 -> 12.8 ms
+    // (there nearly every band is beyond it and the regular kernel runs dry): applied below 180 000 vertices
+    pl.big_n = (ctx->wave_big && ctx->vmax < 180000u) ? 2800u : 0xFFFFFFFFu;
+    // the regular pairs through the record clipper (wave_clip.h) once the pairs queue up; k_prep_pairs then leaves their bands as
+    // record images (rec_on)
+    // (measured on blocks of configs[3]: the record clipper wins once the pairs queue up -- 4 096 pairs 1.88 -> 1.65 ms, 2 048 pairs
+    // 2.35 -> 2.30 ms for the event -- and loses when every pair has a workgroup to itself: 1 024 pairs 1.63 -> 1.69 ms, 512 pairs
+    // 1.33 -> 1.45 ms; its loader sorts the band, which the general clipper's image copy does not have to)
+    // (round 4, split arrangement, blocks of configs[3]: 2 048 pairs 1.83 against 2.23 ms for the event, 1 024 pairs 1.53 against 1.59,
+    //  512 pairs 1.40 against 1.32: from 3/2 of the workgroup count on)
+    // ... and for events of any size over pieces whose bands come as record images as a rule (every piece pre-passed by k_prep_pairs
+    // and small enough that a band seldom passes SURTR_REC_MAXN vertices): one pair on the record clipper alone takes 0.18 ms where
+    // the general clipper takes 0.26 (configs[1]: 0.73 -> 0.72 ms per event, configs[2]: 1.06 -> 1.00)
+    // (SURTR_HALF=1 -- tests that want the half-size general kernel -- keeps such events on it)
+    const bool half_forced = getenv("SURTR_HALF") != nullptr && atoi(getenv("SURTR_HALF")) != 0;
+    // (several contexts busy on the GPU, surtr_set_events_in_flight: the lean arrangement for events of any size whose pieces the
+    //  split arrangement takes -- the record clipper's 0.27 ms per pair against the general clipper's 0.55 leave the other events
+    //  the LDS; blocks of configs[3] with four contexts: 512 cells 0.65 -> 0.55 ms per step, 1 024 cells 0.84 -> 0.75, 2 048 cells
+    //  1.40 -> 1.21; one at a time 1.29 -> 1.37 / 1.45 -> 1.44 / 1.73 -> 1.78)
+    const bool many = ctx->events_in_flight > 1u && !half_forced;
+    pl.wave_on = 2u * n_pairs > 3u * max_wg || (!half_forced && ctx->vmin >= SURTR_PREP_MINV && ctx->vmax <= 4u * SURTR_REC_MAXN) ||
+                 (many && ctx->vmin >= SURTR_PREP_MINV && ctx->vmax <= ctx->prep.VMAX);
+    if (const char* e = getenv("SURTR_WAVE")) pl.wave_on = atoi(e) != 0;
+    pl.rec_on = pl.wave_on ? 1u : 0u;
+    if (const char* e = getenv("SURTR_REC")) pl.rec_on = (pl.wave_on && atoi(e) != 0) ? 1u : 0u;      // (tests / A-B: 0 = images + wc_load as in round 3)
+    if (const char* e = getenv("SURTR_PREP_SORTED")) { if (atoi(e) == 0) pl.rec_on = 2u; }             // (tests / A-B: 0 = round 3's selection, prepass_select)
+    // bands beyond this size keep the old image: they are the ones the record clipper runs out of room on, and a pair it gives up
+    // on is then finished in place from that image instead of from the piece
+    uint32_t rec_maxn = SURTR_REC_MAXN;
+    if (const char* e = getenv("SURTR_REC_MAXN")) rec_maxn = (uint32_t)atoi(e);
+    pl.rec_on |= (rec_maxn < 0xFFFFFFu ? rec_maxn : 0xFFFFFFu) << 8;
+    // the split arrangement (k_clip_pairs_main + k_clip_pairs_catch, see there) for events whose every pair gets an image from
+    // k_prep_pairs: pieces of fewer than SURTR_PREP_MINV vertices are pre-passed by the general clipper itself, which only the
+    // one-kernel arrangement has on every workgroup
+    pl.split_on = pl.wave_on && ctx->vmin >= SURTR_PREP_MINV && ctx->vmax <= ctx->prep.VMAX;
+    if (const char* e = getenv("SURTR_SPLIT")) pl.split_on = pl.split_on && atoi(e) != 0;
+    // (the split arrangement takes the light pairs too: the half-size general kernel stays out of it)
+    pl.use_half = ctx->half_on && (!pl.split_on || half_forced);
+    // (measured on configs[3]: 16 .. 32 workgroups end with the main kernel -- 35 pairs with a vertex in a plane + a hand-over or two;
+    //  64 and more take LDS from it: 2.50 / 2.50 / 2.56 ms per event with 16 / 32 / 64)
+    pl.n_catch = std::min(std::min(ctx->n_wg_catch, 32u), n1);
+    pl.n_wg_sweep = std::min(pl.n_catch, SURTR_CATCH_POLL);
+    // catcher workgroups that wait for hand-overs (tests: 0 = none, everything handed on is the sweep's).  With other contexts busy on
+    // the GPU (surtr_set_events_in_flight) two: a polling workgroup holds 78 KB of LDS for the length of the main kernel, which the
+    // other events' kernels want (configs[3], four contexts, 60 steps: 2.15 -> 2.09 ms per step; one poller: 2.08, but then the two
+    // hand-overs of an event wait for each other, one event 2.38 -> 2.54 ms)
+    pl.n_poll = ctx->events_in_flight > 1u ? 2u : SURTR_CATCH_POLL;
+    if (const char* e = getenv("SURTR_CATCH_POLL")) { const int v = atoi(e); if (v >= 0 && v <= 1024) pl.n_poll = (uint32_t)v; }
+    // measured on blocks of configs[3]: 512 pairs 0.60 -> 0.23 ms, 1 024 pairs 0.70 -> 0.37, 2 048 pairs 0.77 -> 0.68, 4 096 pairs 0.96 -> 1.32
+    uint32_t wide_max = 4u * ctx->max_wg;
+    if (const char* e = getenv("SURTR_PREP_WIDE_MAX")) wide_max = (uint32_t)atoi(e);
+    // The clip of the Convexes and the pre-pass of the Meshes are independent but for two things: the pre-pass skips the pairs whose
+    // Convex came out empty, and takes the others from a queue by estimated cost that k_clip_convex builds.  An event of so few pairs
+    // that every pair finds a free workgroup at once needs neither -- there the two kernels run side by side (front_par: the
+    // pre-pass takes the pairs by index and prepares the empty ones too; the clip kernels wait for both and skip those).
+    // Measured per event, one at a time: configs[1] 0.64 -> 0.58 ms, configs[2] 0.92 -> 0.875; not for the wide pre-pass of a block
+    // of large pieces (1 024 threads a pair: beside k_clip_convex it takes twice as long, 512-cell block of configs[3] 1.16 -> 1.19 ms)
+    // nor for events whose pairs queue up (configs[3]: 2.47 -> 2.71 ms, the cost order and the 761 skipped pairs are worth more).
+    const bool prep_wide = n_pairs != 0 && n_pairs <= wide_max && ctx->vmax >= 8192u && !many;      // few pairs, large meshes, nothing else on the GPU
+    pl.front_par = n_pairs != 0 && n_pairs <= SURTR_FRONT_PAR_MAX && !prep_wide;
+    if (const char* e = getenv("SURTR_FRONT_PAR")) pl.front_par = n_pairs != 0 && atoi(e) != 0;
+    if (pl.front_par) pl.rec_on |= 4u;
+    pl.prep = nullptr; pl.prep_threads = SURTR_WG;
+    if (n_pairs && prep_wide) { pl.prep = k_prep_pairs_wide; pl.prep_threads = SURTR_WG_WIDE; }
+    else if (n_pairs && !(pl.rec_on & 2u) && ctx->vmax < 0xFFFFu && ctx->vmin >= SURTR_PREP_MINV && (ctx->vmax + SURTR_LANES - 1u) / SURTR_LANES <= SURTR_PREP_NB)
+        pl.prep = k_prep_pairs_sorted;
+    else if (n_pairs) pl.prep = k_prep_pairs;
+    pl.walk0 = SURTR_WWALK0;
+    if (const char* e = getenv("SURTR_WWALK0")) { const int v = atoi(e); if (v >= 0 && v <= 64) pl.walk0 = (uint32_t)v; }
+    // k_clip_pairs_big goes first on the caller's stream, right behind k_prep_pairs, so that its few whole-CU workgroups
+    // are placed before k_clip_pairs (second stream) and k_clip_pairs_half (third) fill the CUs; all three run side by side.
+    // (front_par: the main kernel stays on the caller's stream and the whole-CU kernel goes to the second -- every wait of one
+    //  stream for another costs some 12 us, and there the main kernel is the critical path: it then waits only for k_clip_convex)
+    pl.st_cvx = pl.front_par ? ctx->stream3 : ctx->stream;
+    pl.st_main = pl.front_par ? ctx->stream : ctx->stream2;
+    pl.st_bigk = pl.front_par ? ctx->stream2 : ctx->stream;
+    // refit (Convex) and faces (Mesh) of the fragments are independent: side by side on the two streams
+    pl.both = (flags & SURTR_EVT_REFIT) && (flags & SURTR_EVT_RENDER);
+    pl.st_refit = pl.both ? ctx->stream2 : ctx->stream;
+    // side by side the two kernels share the CUs' registers and LDS: k_faces at two workgroups per CU leaves room for five
+    // of k_refit's (measured on configs[3]: 3.72 -> 3.65 ms per event against both at their stand-alone sizes)
+    pl.g_refit = ctx->n_wg_small;
+    if (pl.both) pl.g_refit = std::min(pl.g_refit, ctx->max_wg_faces / 4u * 5u);
+    if (pl.both) if (const char* e = getenv("SURTR_REFIT_WG_BOTH")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= ctx->n_wg_small) pl.g_refit = v; }
+    pl.g_faces = std::max(1u, ctx->max_wg_faces); pl.t_faces = SURTR_WG;
+    if (pl.both) pl.g_faces = std::max(1u, ctx->max_wg_faces / 2u);
+    if (pl.both) if (const char* e = getenv("SURTR_FACES_WG_BOTH")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= ctx->n_wg_faces_alloc) pl.g_faces = v; }
+    if (const char* e = getenv("SURTR_FACES_WG")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= ctx->n_wg_faces_alloc) pl.g_faces = v; }
+    if (const char* e = getenv("SURTR_FACES_THREADS")) { const uint32_t v = (uint32_t)atoi(e); if (v == 64 || v == 128 || v == 256) pl.t_faces = v; }
+    return pl;
+}
+
 static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, const uint2* d_pair_list, const uint8_t* outside, uint32_t flags)
 {
     (void)hipSetDevice(ctx->device);
     budget_workgroups(ctx);
-    const uint32_t max_wg = ctx->max_wg;
-    const uint32_t n_wg = std::max(1u, std::min(std::max(n_pairs, 1u), max_wg));
-    // scratch slots [0, max_wg) belong to k_clip_pairs, the n_wg_big after them to k_clip_pairs_big
+    const uint32_t max_wg = ctx->max_wg, n1 = std::max(n_pairs, 1u);
     // scratch slots [0, max_wg) belong to the Mesh clip's main kernel, the n_wg_big after them to k_clip_pairs_big, then k_clip_pairs_catch's
     int rc = ensure_scratch(ctx, ctx->vmax, ctx->hmax, max_wg + ctx->n_wg_big + ctx->n_wg_catch);
     if (rc) return rc;
-    const uint32_t n_wg_small = std::max(1u, std::min(std::max(n_pairs, 1u), ctx->max_wg_small));
     rc = ensure_scratch_small(ctx, std::max(ctx->max_wg_small, ctx->n_wg_small));
     if (rc) return rc;
-    const uint32_t n_wg_half = std::max(1u, std::min(std::max(n_pairs, 1u), ctx->max_wg_half));
     rc = ensure_scratch_half(ctx, std::max(ctx->max_wg_half, ctx->n_wg_half));
     if (rc) return rc;
-    rc = ensure_arena(ctx, std::max(n_pairs, 1u));
+    rc = ensure_arena(ctx, n1);
     if (rc) return rc;
-    const uint32_t n_wg_prep = std::max(1u, std::min(std::max(n_pairs, 1u), ctx->max_wg_prep));
-    rc = ensure_prep(ctx, std::max(n_pairs, 1u), std::max(n_wg_prep, ctx->n_wg_prep));
+    rc = ensure_prep(ctx, n1, std::max(std::max(1u, std::min(n1, ctx->max_wg_prep)), ctx->n_wg_prep));
     if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    // (the event's zeroes and the hand-over list's "empty" words in one launch, not four fills with a few microseconds between each)
+    hipStream_t st = ctx->stream, st2 = ctx->stream2, st3 = ctx->stream3;
     const uint32_t hcap = n_pairs + 4096u;
     if (ctx->cap_hlist < hcap)
     {
@@ -3589,6 +3653,8 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
         HIPCHK(hipMalloc((void**)&ctx->d_hlist, (size_t)hcap * 4));
         ctx->cap_hlist = hcap;
     }
+    const EventPlan pl = plan_event(ctx, n_pairs, d_pair_list != nullptr, flags);
+    // (the event's zeroes and the hand-over list's "empty" words in one launch, not four fills with a few microseconds between each)
     static_assert(sizeof(surtr_counts) % 4 == 0, "surtr_counts is cleared by words");
     hipLaunchKernelGGL(k_event_init, dim3(SURTR_LANES == 1 ? 1 : 64), dim3(SURTR_LANES == 1 ? 1 : 256), 0, st, ctx->arena.cursors, (uint32_t*)ctx->d_counts,
                        (uint32_t)(sizeof(surtr_counts) / 4), ctx->d_frag_status, ctx->cap_frags, ctx->d_hlist, hcap);
@@ -3607,7 +3673,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     for (int i = 0; i < 16; ++i) ctx->ev_valid[i] = false;
     const uint32_t* d_pair_order = nullptr;
     if (d_pair_list && ctx->pair_order_is_list && ctx->pair_order_count == n_pairs) d_pair_order = ctx->d_pair_order;      // surtr_fracture_pairs_async made it
-    else if (!d_pair_list && n_pairs && ctx->n_pieces && n_pairs % ctx->n_pieces == 0 && !getenv("SURTR_NO_CELL_ORDER"))
+    else if (pl.cell_order)
     {
         const uint32_t np = ctx->n_pieces, nc = n_pairs / np;
         if (ctx->pair_order_is_list || ctx->pair_order_begin != cell_begin || ctx->pair_order_count != n_pairs)
@@ -3624,245 +3690,122 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
         }
         d_pair_order = ctx->d_pair_order;
     }
-    uint32_t big_quota = ctx->wave_big ? 0xFFFFFFFFu : 2u * ctx->n_wg_big;
-    if (const char* e = getenv("SURTR_BIG_QUOTA")) big_quota = (uint32_t)atoi(e);      // (tests: 0 sends every big band to the regular kernel's global scratch)
-    // (pieces of 80 000 vertices and more: bands beyond this size go to the whole-CU record clipper, see k_prep_pairs)
-    // measured at 4 096 cells with 2 800: 100 000-vertex piece 6.50 -> 5.96 ms, 150 000 vertices 10.5 -> 9.6 ms, 210 000 vertices 12.6 -> 12.8 ms
-    // (there nearly every band is beyond it and the regular kernel runs dry): applied below 180 000 vertices
-    uint32_t big_n = (ctx->wave_big && ctx->vmax < 180000u) ? SURTR_WAVE_BIG_N : 0xFFFFFFFFu;
-    if (const char* e = getenv("SURTR_WAVE_BIG_N")) big_n = (uint32_t)atoi(e);
-    // the regular pairs through the record clipper (wave_clip.h) once the pairs queue up; k_prep_pairs then leaves their bands as
-    // record images (rec_on)
-    // (round 4, split arrangement, blocks of configs[3]: 2 048 pairs 1.83 against 2.23 ms for the event, 1 024 pairs 1.53 against 1.59,
-    //  512 pairs 1.40 against 1.32: from 3/2 of the workgroup count on)
-    // ... and for events of any size over pieces whose bands come as record images as a rule (every piece pre-passed by k_prep_pairs
-    // and small enough that a band seldom passes SURTR_REC_MAXN vertices): one pair on the record clipper alone takes 0.18 ms where
-    // the general clipper takes 0.26 (configs[1]: 0.73 -> 0.72 ms per event, configs[2]: 1.06 -> 1.00)
-    // (SURTR_HALF=1 -- tests that want the half-size general kernel -- keeps such events on it)
-    const bool half_forced = getenv("SURTR_HALF") != nullptr && atoi(getenv("SURTR_HALF")) != 0;
-    // (several contexts busy on the GPU, surtr_set_events_in_flight: the lean arrangement for events of any size whose pieces the
-    //  split arrangement takes -- the record clipper's 0.27 ms per pair against the general clipper's 0.55 leave the other events
-    //  the LDS; blocks of configs[3] with four contexts: 512 cells 0.65 -> 0.55 ms per step, 1 024 cells 0.84 -> 0.75, 2 048 cells
-    //  1.40 -> 1.21; one at a time 1.29 -> 1.37 / 1.45 -> 1.44 / 1.73 -> 1.78)
-    const bool many = ctx->events_in_flight > 1u && !half_forced;
-    bool wave_on = 2u * n_pairs > 3u * max_wg || (!half_forced && ctx->vmin >= SURTR_PREP_MINV && ctx->vmax <= 4u * SURTR_REC_MAXN) ||
-                   (many && ctx->vmin >= SURTR_PREP_MINV && ctx->vmax <= ctx->prep.VMAX);
-    if (const char* e = getenv("SURTR_WAVE")) wave_on = atoi(e) != 0;
-    uint32_t rec_on = wave_on ? 1u : 0u;
-    if (const char* e = getenv("SURTR_REC")) rec_on = (wave_on && atoi(e) != 0) ? 1u : 0u;      // (tests / A-B: 0 = images + wc_load as in round 3)
-    if (const char* e = getenv("SURTR_PREP_SORTED")) { if (atoi(e) == 0) rec_on = 2u; }             // (tests / A-B: 0 = round 3's selection, prepass_select)
-    // bands beyond this size keep the old image: they are the ones the record clipper runs out of room on, and a pair it gives up
-    // on is then finished in place from that image instead of from the piece
-    uint32_t rec_maxn = SURTR_REC_MAXN;
-    if (const char* e = getenv("SURTR_REC_MAXN")) rec_maxn = (uint32_t)atoi(e);
-    rec_on |= (rec_maxn < 0xFFFFFFu ? rec_maxn : 0xFFFFFFu) << 8;
-    // the small tier of the record clipper: three workgroups per CU for the record images whose worst plane fits its LDS
-    // OFF by default.  Measured on configs[3] (MI355X, round 4): the small tier's kernel has 114 registers, no private scratch and
-    // 53 680 B of LDS (three workgroups per CU) and takes 2 400 of 3 335 pairs in 0.64 ms -- but the 900 heavy pairs left for the
-    // large tier then take 1.02 ms on their own (two or three 0.4 ms pairs per workgroup: no light pairs left to level the end),
-    // 1.66 ms for the two kernels one behind the other against 1.45 ms for the one kernel; 2.51 against 2.39 ms per step with
-    // three events in flight.  Side by side on two streams the event took 2.58 ms when the two grids happened to interleave
-    // and 2.98 ms when one filled the CUs first (SURTR_SMALL_CONC, timing only).  SURTR_SMALL=1 turns the tier on.
-    uint32_t small_cap = 0u;
-    if (const char* e = getenv("SURTR_SMALL")) { if (atoi(e) != 0 && wave_on && (rec_on & 1u)) small_cap = 16u * SURTR_WR_S; }
-    // the split arrangement (k_clip_pairs_main + k_clip_pairs_catch, see there) for events whose every pair gets an image from
-    // k_prep_pairs: pieces of fewer than SURTR_PREP_MINV vertices are pre-passed by the general clipper itself, which only the
-    // one-kernel arrangement has on every workgroup
-    bool split_on = wave_on && !small_cap && ctx->vmin >= SURTR_PREP_MINV && ctx->vmax <= ctx->prep.VMAX;
-    if (const char* e = getenv("SURTR_SPLIT")) split_on = split_on && atoi(e) != 0;
-    // (the split arrangement takes the light pairs too: the half-size general kernel stays out of it)
-    const bool use_half = ctx->half_on && (!split_on || half_forced);
-    // (measured on configs[3]: 16 .. 32 workgroups end with the main kernel -- 35 pairs with a vertex in a plane + a hand-over or two;
-    //  64 and more take LDS from it: 2.50 / 2.50 / 2.56 ms per event with 16 / 32 / 64)
-    uint32_t n_catch = std::min(std::min(ctx->n_wg_catch, 32u), std::max(n_pairs, 1u));
-    if (const char* e = getenv("SURTR_CATCH_WG")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= ctx->n_wg_catch) n_catch = v; }
-    // catcher workgroups that wait for hand-overs (tests: 0 = none, everything handed on is the sweep's).  With other contexts busy on
-    // the GPU (surtr_set_events_in_flight) two: a polling workgroup holds 78 KB of LDS for the length of the main kernel, which the
-    // other events' kernels want (configs[3], four contexts, 60 steps: 2.15 -> 2.09 ms per step; one poller: 2.08, but then the two
-    // hand-overs of an event wait for each other, one event 2.38 -> 2.54 ms)
-    uint32_t n_poll = ctx->events_in_flight > 1u ? 2u : SURTR_CATCH_POLL;
-    if (const char* e = getenv("SURTR_CATCH_POLL")) { const int v = atoi(e); if (v >= 0 && v <= 1024) n_poll = (uint32_t)v; }
-    uint32_t heavy_need = 0u;      // (off: k_clip_pairs_big takes 2 x its grid of such pairs and no more -- the rest would land on the catcher)
-    if (const char* e = getenv("SURTR_HEAVY_NEED")) { if (split_on) heavy_need = (uint32_t)atoi(e); }
-    uint32_t n_wg_rec = 0;
-    if (small_cap)
+    // the class tables of the clip kernels, the pre-pass and the half-size kernel (k_prep_pairs)
+    uint32_t* const order = ctx->d_order;
+    uint32_t* const porder = ctx->d_order + (size_t)16 * ctx->cap_order;
+    uint32_t* const horder = ctx->d_order + (size_t)32 * ctx->cap_order;
+    const bool wave = n_pairs && pl.wave_on, split = wave && pl.split_on;
+
+    if (pl.front_par)
     {
-        n_wg_rec = std::max(1u, std::min(std::max(n_pairs, 1u), ctx->hw_wg / 2u * 3u));
-        if (const char* e = getenv("SURTR_SMALL_WG")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= 4096u) n_wg_rec = v; }
-        const size_t per = ((size_t)16u * 2u * SURTR_WR_S + 255u) & ~(size_t)255u;
-        if (!(ctx->pool_rec.base && ctx->pool_rec.per_wg >= per && ctx->n_wg_rec >= n_wg_rec))
-        {
-            free_dev(ctx->pool_rec.base); ctx->pool_rec.base = nullptr;
-            ctx->pool_rec.per_wg = per; ctx->pool_rec.CV = ctx->pool_rec.CH = ctx->pool_rec.VMAX = 0; ctx->n_wg_rec = n_wg_rec;
-            HIPCHK(hipMalloc((void**)&ctx->pool_rec.base, per * n_wg_rec));
-        }
-    }
-    // measured on blocks of configs[3]: 512 pairs 0.60 -> 0.23 ms, 1 024 pairs 0.70 -> 0.37, 2 048 pairs 0.77 -> 0.68, 4 096 pairs 0.96 -> 1.32
-    uint32_t wide_max = 4u * ctx->max_wg;
-    if (const char* e = getenv("SURTR_PREP_WIDE_MAX")) wide_max = (uint32_t)atoi(e);
-    // The clip of the Convexes and the pre-pass of the Meshes are independent but for two things: the pre-pass skips the pairs whose
-    // Convex came out empty, and takes the others from a queue by estimated cost that k_clip_convex builds.  An event of so few pairs
-    // that every pair finds a free workgroup at once needs neither -- there the two kernels run side by side (front_par: the
-    // pre-pass takes the pairs by index and prepares the empty ones too; the clip kernels wait for both and skip those).
-    // Measured per event, one at a time: configs[1] 0.64 -> 0.58 ms, configs[2] 0.92 -> 0.875; not for the wide pre-pass of a block
-    // of large pieces (1 024 threads a pair: beside k_clip_convex it takes twice as long, 512-cell block of configs[3] 1.16 -> 1.19 ms)
-    // nor for events whose pairs queue up (configs[3]: 2.47 -> 2.71 ms, the cost order and the 761 skipped pairs are worth more).
-    const bool prep_wide = n_pairs != 0 && n_pairs <= wide_max && ctx->vmax >= 8192u && !many;      // few pairs, large meshes, nothing else on the GPU
-    bool front_par = n_pairs != 0 && n_pairs <= SURTR_FRONT_PAR_MAX && !prep_wide;
-    if (const char* e = getenv("SURTR_FRONT_PAR")) front_par = n_pairs != 0 && atoi(e) != 0;
-    hipStream_t st_cvx = st;
-    if (front_par)
-    {
-        rec_on |= 4u;
-        st_cvx = ctx->stream3;
         HIPCHK(hipEventRecord(ctx->ev_prep, st));      // (behind the memsets above)
-        HIPCHK(hipStreamWaitEvent(st_cvx, ctx->ev_prep, 0));
+        HIPCHK(hipStreamWaitEvent(pl.st_cvx, ctx->ev_prep, 0));
     }
-    PROF_BEGIN_ON(6, st_cvx);
+    PROF_BEGIN_ON(6, pl.st_cvx);
     if (n_pairs)
-        hipLaunchKernelGGL(k_clip_convex, dim3(n_wg_small), dim3(SURTR_LANES), 0, st_cvx, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           d_out, ctx->pool_small, ctx->arena, ctx->d_pairs, d_pair_list, front_par ? (uint32_t*)nullptr : ctx->d_order + (size_t)16 * ctx->cap_order, d_pair_order,
-                           front_par ? 1u : 0u);
-    PROF_END_ON(6, st_cvx);
-    if (front_par) HIPCHK(hipEventRecord(ctx->ev_cvx, st_cvx));
+        hipLaunchKernelGGL(k_clip_convex, dim3(pl.n_wg_cvx), dim3(SURTR_LANES), 0, pl.st_cvx, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
+                           d_out, ctx->pool_small, ctx->arena, ctx->d_pairs, d_pair_list, pl.front_par ? (uint32_t*)nullptr : porder, d_pair_order,
+                           pl.front_par ? 1u : 0u);
+    PROF_END_ON(6, pl.st_cvx);
+    if (pl.front_par) HIPCHK(hipEventRecord(ctx->ev_cvx, pl.st_cvx));
     PROF_BEGIN(7);
-    if (n_pairs && prep_wide)
-        hipLaunchKernelGGL(k_prep_pairs_wide, dim3(n_wg_prep), dim3(SURTR_WG_WIDE), 0, st, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->prep, ctx->arena, ctx->img, std::min((uint32_t)SURTR_LV, ctx->pool.CV), std::min((uint32_t)SURTR_LVS, ctx->pool_half.CV), ctx->d_pairs, d_pair_list, ctx->d_order, ctx->d_order + (size_t)16 * ctx->cap_order,
-                           ctx->d_order + (size_t)32 * ctx->cap_order, use_half ? 1u : 0u, big_quota, big_n, rec_on, small_cap, heavy_need);
-    else if (n_pairs && !(rec_on & 2u) && ctx->vmax < 0xFFFFu && ctx->vmin >= SURTR_PREP_MINV && (ctx->vmax + SURTR_LANES - 1u) / SURTR_LANES <= SURTR_PREP_NB)
-        hipLaunchKernelGGL(k_prep_pairs_sorted, dim3(n_wg_prep), dim3(SURTR_WG), 0, st, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->prep, ctx->arena, ctx->img, std::min((uint32_t)SURTR_LV, ctx->pool.CV), std::min((uint32_t)SURTR_LVS, ctx->pool_half.CV), ctx->d_pairs, d_pair_list, ctx->d_order, ctx->d_order + (size_t)16 * ctx->cap_order,
-                           ctx->d_order + (size_t)32 * ctx->cap_order, use_half ? 1u : 0u, big_quota, big_n, rec_on, small_cap, heavy_need);
-    else if (n_pairs)
-        hipLaunchKernelGGL(k_prep_pairs, dim3(n_wg_prep), dim3(SURTR_WG), 0, st, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->prep, ctx->arena, ctx->img, std::min((uint32_t)SURTR_LV, ctx->pool.CV), std::min((uint32_t)SURTR_LVS, ctx->pool_half.CV), ctx->d_pairs, d_pair_list, ctx->d_order, ctx->d_order + (size_t)16 * ctx->cap_order,
-                           ctx->d_order + (size_t)32 * ctx->cap_order, use_half ? 1u : 0u, big_quota, big_n, rec_on, small_cap, heavy_need);
+    if (pl.prep)
+        hipLaunchKernelGGL(pl.prep, dim3(pl.n_wg_prep), dim3(pl.prep_threads), 0, st, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
+                           ctx->prep, ctx->arena, ctx->img, std::min((uint32_t)SURTR_LV, ctx->pool.CV), std::min((uint32_t)SURTR_LVS, ctx->pool_half.CV),
+                           ctx->d_pairs, d_pair_list, order, porder, horder, pl.use_half ? 1u : 0u, pl.big_quota, pl.big_n, pl.rec_on);
     PROF_END(7);
-    // k_clip_pairs_big goes first on the caller's stream, right behind k_prep_pairs, so that its few whole-CU workgroups
-    // are placed before k_clip_pairs (second stream) and k_clip_pairs_half (third) fill the CUs; all three run side by side.
-    // (front_par: the main kernel stays on the caller's stream and the whole-CU kernel goes to the second -- every wait of one
-    //  stream for another costs some 12 us, and there the main kernel is the critical path: it then waits only for k_clip_convex)
-    hipStream_t st2 = ctx->stream2, st3 = ctx->stream3;
-    hipStream_t st_main = front_par ? st : st2, st_bigk = front_par ? st2 : st;
     HIPCHK(hipEventRecord(ctx->ev_prep, st));
     HIPCHK(hipStreamWaitEvent(st2, ctx->ev_prep, 0));
     HIPCHK(hipStreamWaitEvent(st3, ctx->ev_prep, 0));
-    if (front_par)
+    if (pl.front_par)
     {
         HIPCHK(hipStreamWaitEvent(st, ctx->ev_cvx, 0));      // (stream3 has k_clip_convex in order)
         HIPCHK(hipStreamWaitEvent(st2, ctx->ev_cvx, 0));
     }
-    PROF_BEGIN_ON(8, st_bigk);
-    uint32_t walk0 = SURTR_WWALK0;
-    if (const char* e = getenv("SURTR_WWALK0")) { const int v = atoi(e); if (v >= 0 && v <= 64) walk0 = (uint32_t)v; }
+    PROF_BEGIN_ON(8, pl.st_bigk);
     if (n_pairs && ctx->wave_big)
-        hipLaunchKernelGGL(k_clip_pairs_wave_big, dim3(std::min(ctx->n_wg_big, std::max(n_pairs, 1u))), dim3(SURTR_WG), 0, st_bigk, P, ctx->d_planes,
-                           ctx->d_plane_off, cell_begin, n_pairs, ctx->pool, max_wg, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, ctx->d_order, 15, 14, 11u, walk0);
+        hipLaunchKernelGGL(k_clip_pairs_wave_big, dim3(pl.n_wg_big), dim3(SURTR_WG), 0, pl.st_bigk, P, ctx->d_planes,
+                           ctx->d_plane_off, cell_begin, n_pairs, ctx->pool, max_wg, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, 15, 14, 11u, pl.walk0);
     else if (n_pairs)
-        hipLaunchKernelGGL(k_clip_pairs_big, dim3(std::min(ctx->n_wg_big, std::max(n_pairs, 1u))), dim3(SURTR_WG), 0, st_bigk, P, ctx->d_planes,
-                           ctx->d_plane_off, cell_begin, n_pairs, ctx->pool, max_wg, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, ctx->d_order);
-    PROF_END_ON(8, st_bigk);
-    // the regular pairs on one wave each (wave_clip.h); what it hands on comes back through the retry launch below
-    // (measured on blocks of configs[3]: the record clipper wins once the pairs queue up -- 4 096 pairs 1.88 -> 1.65 ms, 2 048 pairs
-    // 2.35 -> 2.30 ms for the event -- and loses when every pair has a workgroup to itself: 1 024 pairs 1.63 -> 1.69 ms, 512 pairs
-    // 1.33 -> 1.45 ms; its loader sorts the band, which the general clipper's image copy does not have to)
-    hipStream_t st_rec = st_main;
-    if (getenv("SURTR_SMALL_CONC")) st_rec = st3;      // (timing experiment only: the large tier then misses late hand-overs)
-    PROF_BEGIN_ON(12, st_rec);
-    if (n_pairs && wave_on && small_cap)
-        hipLaunchKernelGGL(k_clip_pairs_rec, dim3(n_wg_rec), dim3(SURTR_S_THREADS), 0, st_rec, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->pool_rec, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list,
-                           (const uint32_t*)(ctx->d_order + (size_t)32 * ctx->cap_order + (size_t)16 * n_pairs), ctx->d_order, walk0);
-    PROF_END_ON(12, st_rec);
-    PROF_BEGIN_ON(11, st_main);
-    if (n_pairs && wave_on) PROF_HIST_BEGIN(11, st_main);
-    uint32_t n_wg_main = n_wg;
-    if (const char* e = getenv("SURTR_MAIN_WG")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= max_wg) n_wg_main = v; }
-    if (n_pairs && wave_on && split_on)
-        hipLaunchKernelGGL(k_clip_pairs_main, dim3(n_wg_main), dim3(SURTR_MAIN_THREADS), 0, st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, ctx->d_order, ctx->d_hlist, walk0);
-    else if (n_pairs && wave_on)
-        hipLaunchKernelGGL(k_clip_pairs_wave, dim3(n_wg), dim3(SURTR_WG), 0, st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, ctx->d_order, ctx->d_order + (size_t)32 * ctx->cap_order, 13, 0, 4u, walk0);
-    if (n_pairs && wave_on) PROF_HIST_END(11, st_main);
-    PROF_END_ON(11, st_main);
-    PROF_BEGIN_ON(0, st_main);
-    if (n_pairs && !wave_on) PROF_HIST_BEGIN(0, st_main);
-    if (n_pairs && !wave_on)
-        hipLaunchKernelGGL(k_clip_pairs, dim3(n_wg), dim3(SURTR_WG), 0, st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, ctx->d_order, ctx->d_order + (size_t)32 * ctx->cap_order, 13, 0, 4u);
-    if (n_pairs && !wave_on) PROF_HIST_END(0, st_main);
-    PROF_END_ON(0, st_main);
+        hipLaunchKernelGGL(k_clip_pairs_big, dim3(pl.n_wg_big), dim3(SURTR_WG), 0, pl.st_bigk, P, ctx->d_planes,
+                           ctx->d_plane_off, cell_begin, n_pairs, ctx->pool, max_wg, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order);
+    PROF_END_ON(8, pl.st_bigk);
+    // the regular pairs through the record clipper (wave_on): alone on k_clip_pairs_main with the catcher beside it (split_on), or
+    // on k_clip_pairs_wave, which carries the general clipper; otherwise on k_clip_pairs
+    PROF_BEGIN_ON(11, pl.st_main);
+    if (wave) PROF_HIST_BEGIN(11, pl.st_main);
+    if (split)
+        hipLaunchKernelGGL(k_clip_pairs_main, dim3(pl.n_wg), dim3(SURTR_MAIN_THREADS), 0, pl.st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
+                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, ctx->d_hlist, pl.walk0);
+    else if (wave)
+        hipLaunchKernelGGL(k_clip_pairs_wave, dim3(pl.n_wg), dim3(SURTR_WG), 0, pl.st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
+                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, horder, 13, 0, 4u, pl.walk0);
+    if (wave) PROF_HIST_END(11, pl.st_main);
+    PROF_END_ON(11, pl.st_main);
+    PROF_BEGIN_ON(0, pl.st_main);
+    if (n_pairs && !pl.wave_on)
+    {
+        PROF_HIST_BEGIN(0, pl.st_main);
+        hipLaunchKernelGGL(k_clip_pairs, dim3(pl.n_wg), dim3(SURTR_WG), 0, pl.st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
+                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, horder, 13, 0, 4u);
+        PROF_HIST_END(0, pl.st_main);
+    }
+    PROF_END_ON(0, pl.st_main);
     PROF_BEGIN_ON(13, st3);
-    if (n_pairs && wave_on && split_on)
-        hipLaunchKernelGGL(k_clip_pairs_catch, dim3(n_catch), dim3(SURTR_WG), 0, st3, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->pool, max_wg + ctx->n_wg_big, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, ctx->d_order, ctx->d_hlist, hcap, n_wg_main, 0u, n_poll);
+    if (split)
+        hipLaunchKernelGGL(k_clip_pairs_catch, dim3(pl.n_catch), dim3(SURTR_WG), 0, st3, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
+                           ctx->pool, max_wg + ctx->n_wg_big, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, ctx->d_hlist, hcap, pl.n_wg, 0u, pl.n_poll);
     PROF_END_ON(13, st3);
     PROF_BEGIN_ON(9, st3);
-    if (n_pairs && use_half)
-        hipLaunchKernelGGL(k_clip_pairs_half, dim3(n_wg_half), dim3(SURTR_WGS), 0, st3, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->pool_half, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, ctx->d_order + (size_t)32 * ctx->cap_order);
+    if (n_pairs && pl.use_half)
+        hipLaunchKernelGGL(k_clip_pairs_half, dim3(pl.n_wg_half), dim3(SURTR_WGS), 0, st3, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
+                           ctx->pool_half, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, horder);
     PROF_END_ON(9, st3);
     HIPCHK(hipEventRecord(ctx->ev_half, st3));
-    HIPCHK(hipStreamWaitEvent(st_main, ctx->ev_half, 0));
+    HIPCHK(hipStreamWaitEvent(pl.st_main, ctx->ev_half, 0));
     // the pairs that outgrew the half-size topology (class 0, normally none): the regular kernel once more, behind both
     // (it reuses the scratch slots of the first launch)
-    PROF_BEGIN_ON(10, st_main);
-    if (n_pairs && use_half)
-        hipLaunchKernelGGL(k_clip_pairs, dim3(std::min(n_wg, 64u)), dim3(SURTR_WG), 0, st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, ctx->d_order, ctx->d_order + (size_t)32 * ctx->cap_order, -1, 0, 13u);
+    PROF_BEGIN_ON(10, pl.st_main);
+    if (n_pairs && pl.use_half)
+        hipLaunchKernelGGL(k_clip_pairs, dim3(pl.n_wg_retry), dim3(SURTR_WG), 0, pl.st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
+                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, horder, -1, 0, 13u);
     // ... and the sweep of the hand-over list (see k_clip_pairs_catch): normally nothing is left and its workgroups return at once
-    if (n_pairs && wave_on && split_on)
-        hipLaunchKernelGGL(k_clip_pairs_catch, dim3(std::min(n_catch, SURTR_CATCH_POLL)), dim3(SURTR_WG), 0, st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->pool, max_wg + ctx->n_wg_big, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, ctx->d_order, ctx->d_hlist, hcap, n_wg_main, 1u, 0u);
-    PROF_END_ON(10, st_main);
+    if (split)
+        hipLaunchKernelGGL(k_clip_pairs_catch, dim3(pl.n_wg_sweep), dim3(SURTR_WG), 0, pl.st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
+                           ctx->pool, max_wg + ctx->n_wg_big, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, ctx->d_hlist, hcap, pl.n_wg, 1u, 0u);
+    PROF_END_ON(10, pl.st_main);
     HIPCHK(hipEventRecord(ctx->ev_big, st2));      // (the main kernel's stream, or the whole-CU kernel's when the main one runs on `st`)
     HIPCHK(hipStreamWaitEvent(st, ctx->ev_big, 0));
     PROF_BEGIN(1);
     hipLaunchKernelGGL(k_frag_table, dim3(1), dim3(SURTR_WG_WIDE), 0, st, ctx->d_pairs, n_pairs, ctx->n_pieces, cell_begin, ctx->arena,
                        ctx->d_scanblk, ctx->d_frags, ctx->cap_frags, ctx->d_counts, d_pair_list, ctx->d_forder);
     PROF_END(1);
-    // refit (Convex) and faces (Mesh) of the fragments are independent: side by side on the two streams
-    const bool both = (flags & SURTR_EVT_REFIT) && (flags & SURTR_EVT_RENDER);
-    hipStream_t st_refit = st;
-    if (both)
+    if (pl.both)
     {
         HIPCHK(hipEventRecord(ctx->ev_prep, st));
-        HIPCHK(hipStreamWaitEvent(st2, ctx->ev_prep, 0));
-        st_refit = st2;
+        HIPCHK(hipStreamWaitEvent(pl.st_refit, ctx->ev_prep, 0));
     }
     if (flags & SURTR_EVT_REFIT)
     {
-        PROF_BEGIN_ON(2, st_refit);
-        // side by side the two kernels share the CUs' registers and LDS: k_faces at two workgroups per CU leaves room for five
-        // of k_refit's (measured on configs[3]: 3.72 -> 3.65 ms per event against both at their stand-alone sizes)
-        uint32_t g_refit = ctx->n_wg_small;
-        if (both) g_refit = std::min(g_refit, ctx->max_wg_faces / 4u * 5u);
-        if (both) if (const char* e = getenv("SURTR_REFIT_WG_BOTH")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= ctx->n_wg_small) g_refit = v; }
-        hipLaunchKernelGGL(k_refit, dim3(g_refit), dim3(SURTR_LANES), 0, st_refit, ctx->d_frags, ctx->d_counts, ctx->pool_small, ctx->arena, ctx->d_forder, ctx->cap_frags, ctx->d_frag_status,
+        PROF_BEGIN_ON(2, pl.st_refit);
+        hipLaunchKernelGGL(k_refit, dim3(pl.g_refit), dim3(SURTR_LANES), 0, pl.st_refit, ctx->d_frags, ctx->d_counts, ctx->pool_small, ctx->arena, ctx->d_forder, ctx->cap_frags, ctx->d_frag_status,
                            (const float*)ctx->cset.pos, (const uint32_t*)ctx->cset.vo);
-        PROF_END_ON(2, st_refit);
+        PROF_END_ON(2, pl.st_refit);
     }
     if (flags & SURTR_EVT_RENDER)
     {
         PROF_BEGIN(3);
-        uint32_t g_faces = std::max(1u, ctx->max_wg_faces), t_faces = SURTR_WG;
-        if (both) g_faces = std::max(1u, ctx->max_wg_faces / 2u);
-        if (both) if (const char* e = getenv("SURTR_FACES_WG_BOTH")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= ctx->n_wg_faces_alloc) g_faces = v; }
-        if (const char* e = getenv("SURTR_FACES_WG")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= ctx->n_wg_faces_alloc) g_faces = v; }
-        if (const char* e = getenv("SURTR_FACES_THREADS")) { const uint32_t v = (uint32_t)atoi(e); if (v == 64 || v == 128 || v == 256) t_faces = v; }
         const bool tiers = ctx->n_wg_faces_big != 0;
-        hipLaunchKernelGGL(k_faces, dim3(g_faces), dim3(t_faces), 0, st, ctx->d_frags, ctx->d_counts, ctx->fs, ctx->d_blk,
+        hipLaunchKernelGGL(k_faces, dim3(pl.g_faces), dim3(pl.t_faces), 0, st, ctx->d_frags, ctx->d_counts, ctx->fs, ctx->d_blk,
                            ctx->blk_per_wg, ctx->arena, ctx->d_forder, ctx->cap_frags, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
                            ctx->d_frag_status, (const uint32_t*)nullptr, tiers ? ctx->d_face_list : (uint32_t*)nullptr);
         if (tiers)      // the fragments too large for the scratch of those workgroups
-            hipLaunchKernelGGL(k_faces, dim3(ctx->n_wg_faces_big), dim3(t_faces), 0, st, ctx->d_frags, ctx->d_counts, ctx->fs_big, ctx->d_blk_big,
+            hipLaunchKernelGGL(k_faces, dim3(ctx->n_wg_faces_big), dim3(pl.t_faces), 0, st, ctx->d_frags, ctx->d_counts, ctx->fs_big, ctx->d_blk_big,
                                ctx->blk_per_wg_big, ctx->arena, ctx->d_forder, ctx->cap_frags, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
                                ctx->d_frag_status, (const uint32_t*)ctx->d_face_list, (uint32_t*)nullptr);
         PROF_END(3);
     }
-    if (both)
+    if (pl.both)
     {
         HIPCHK(hipEventRecord(ctx->ev_big, st2));
         HIPCHK(hipStreamWaitEvent(st, ctx->ev_big, 0));

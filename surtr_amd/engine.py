@@ -162,8 +162,8 @@ class Engine:
     def kernel_times(self):
         ms = (ctypes.c_float * 16)()
         self._ck(lib().surtr_kernel_times(self._h, ms))
-        names = ("clip_pairs", "frag_table", "refit", "faces", "out_scan", "pack", "clip_convex", "prep_pairs", "clip_pairs_big", "clip_pairs_half", "clip_pairs_retry", "clip_pairs_wave", "clip_pairs_rec", "clip_pairs_catch")
-        return {n: float(ms[i]) for i, n in enumerate(names)}
+        names = ("clip_pairs", "frag_table", "refit", "faces", "out_scan", "pack", "clip_convex", "prep_pairs", "clip_pairs_big", "clip_pairs_half", "clip_pairs_retry", "clip_pairs_wave", None, "clip_pairs_catch")
+        return {n: float(ms[i]) for i, n in enumerate(names) if n}      # (slot 12 is unused)
 
     def set_events_in_flight(self, n):
         """Tells the context how many contexts the host keeps busy on this GPU (include/surtr_hip.h: surtr_set_events_in_flight)."""

@@ -1,5 +1,5 @@
 """The pre-pass of k_prep_pairs on the sorted copy (surtr_amd/csrc/prep_sorted.h, round 4): sphere hierarchy, first clipping planes
-by look-up, record images for the record clipper, the small tier.  Whatever selects the band and however it leaves the kernel,
+by look-up, record images for the record clipper.  Whatever selects the band and however it leaves the kernel,
 the event must be the oracle's -- Poly::ClipPolyhedron's order rules (Src/Poly.cpp:333-357, 464-495) bit for bit.
 CPU tier: the single-lane emulation (its thresholds send meshes of 48 vertices and more through k_prep_pairs); GPU tier:
 BASELINE configs[3] against the committed digests with every combination of the round's switches."""
@@ -29,10 +29,10 @@ def _quad_torus(nu=40, nv=24, R=1.0, r=0.35):
     return {"pos": pos, "off": (np.arange(nu * nv + 1) * 4).astype(np.uint32), "nbr": nbr.reshape(-1)}
 
 
+# (env4 was the small tier's case, since removed: the ids of the others stay as they were)
 @pytest.mark.parametrize("env", [{}, {"SURTR_REC_MAXN": "100000"}, {"SURTR_REC": "0"}, {"SURTR_PREP_SORTED": "0"},
-                                 {"SURTR_SMALL": "1", "SURTR_REC_MAXN": "100000"},
                                  # (an event of 256 pairs clips the Convexes and prepares the bands side by side: here one after the other)
-                                 {"SURTR_FRONT_PAR": "0"}])
+                                 pytest.param({"SURTR_FRONT_PAR": "0"}, id="env5")])
 def test_sorted_prepass_emulation_equals_oracle(emul_engine, oracle, monkeypatch, env):
     monkeypatch.setenv("SURTR_WAVE", "1")
     for k, v in env.items():
@@ -69,23 +69,6 @@ def test_events_in_flight_hint_changes_the_kernels_not_the_event(emul_engine, or
     assert int(q2[88]) > 30, "with the hint the record clipper takes the pairs"
 
 
-@pytest.mark.parametrize("lib", ["libsurtr_emul.so", "libsurtr_emul_rec.so"])
-def test_small_tier_hands_pairs_on_and_the_event_stands(emul_lib_path, oracle, monkeypatch, lib):
-    """k_clip_pairs_rec (three workgroups per CU, no general clipper inside): with little room its pairs leave their stage in
-    global memory, and what it still cannot finish comes back through the large tier from the piece."""
-    from surtr_amd import engine
-    monkeypatch.setenv("SURTR_WAVE", "1"); monkeypatch.setenv("SURTR_SMALL", "1"); monkeypatch.setenv("SURTR_REC_MAXN", "100000")
-    engine._use_library_for_tests(os.path.join(os.path.dirname(emul_lib_path), lib))
-    try:
-        sc = scenes.make_scene(*meshgen.bumpy_torus(100, 60), 256)
-        c, got, ref, qs = _event(engine, oracle, sc, 96)
-    finally:
-        engine._use_library_for_tests(None)
-    assert c.status == 0
-    assert_event_equal(got, ref)
-    assert int(qs[91]) > 20 and int(qs[88]) > 0
-
-
 def test_faces_that_are_no_triangles_take_the_face_walks(emul_engine, oracle, monkeypatch):
     monkeypatch.setenv("SURTR_WAVE", "1"); monkeypatch.setenv("SURTR_REC_MAXN", "100000")
     mesh = _quad_torus()
@@ -101,11 +84,12 @@ def test_faces_that_are_no_triangles_take_the_face_walks(emul_engine, oracle, mo
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env", [{}, {"SURTR_REC_MAXN": "100000"}, {"SURTR_REC": "0"}, {"SURTR_PREP_SORTED": "0"}, {"SURTR_SMALL": "1"},
+# (env4 was the small tier's case, since removed: the ids of the others stay as they were)
+@pytest.mark.parametrize("env", [{}, {"SURTR_REC_MAXN": "100000"}, {"SURTR_REC": "0"}, {"SURTR_PREP_SORTED": "0"},
                                  # (the arrangement of small events -- k_clip_convex beside the pre-pass kernel -- on the large one)
-                                 {"SURTR_FRONT_PAR": "1"},
+                                 pytest.param({"SURTR_FRONT_PAR": "1"}, id="env5"),
                                  # (what bench.py's contexts run with: six of them on the GPU -- two polling catchers, a quarter of the faces tier)
-                                 {"SURTR_EVENTS_IN_FLIGHT": "6"}])
+                                 pytest.param({"SURTR_EVENTS_IN_FLIGHT": "6"}, id="env6")])
 def test_torus_4096_digest_whatever_the_prepass(gpu_engine, monkeypatch, env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
