@@ -355,6 +355,48 @@ int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const fl
  * un-refitted Convex solids and refits afterwards (Src/Surtr.cpp:1921-1939). */
 int surtr_event_refit(surtr_ctx* ctx);
 
+/* ---- mass properties (mass_dev.hip) ------------------------------------ */
+/* What PxRigidBodyExt::updateMassAndInertia(body, 10.0f) gives InitCompound (Src/Surtr.cpp:2520), per closed solid.
+ * Definition: the faces are the loops Poly::ExtractFaces walks on the neighbour rings, each fanned around its lowest-numbered
+ * vertex; the volume integrals of 1, x, y, z, x^2, y^2, z^2, xy, yz, zx are taken relative to the solid's vertex 0 (the origin
+ * shift of Poly::Moments, Src/Poly.cpp:55-87), with positions converted to double and every product and sum in double.  The
+ * reductions run in a fixed order (no float atomics): two calls give the same bits whatever the stream, the events-in-flight
+ * hint or the other contexts. */
+typedef struct surtr_mass {
+    double volume;         /* signed, the integral of 1 */
+    double mass;           /* density * volume */
+    double com[3];         /* centre of mass, world space */
+    double inertia[6];     /* about com, world axes: Ixx Iyy Izz Ixy Iyz Izx as tensor entries (Ixy = -density * int (x-cx)(y-cy)) */
+    uint32_t nv;           /* vertices of the solid */
+    uint32_t status;       /* 0 ok; 1 fewer than 4 vertices (zero record, as Poly::Moments); 2 volume <= 0;
+                            * 3 a face walk did not close (a ring does not list the vertex it was reached from) */
+} surtr_mass;
+
+/* One record per fragment of the last event, in fragment order, into dev_out (device memory, capacity_bytes >= 96 * n_frag).
+ * set 0 = Mesh, 1 = Convex: the Convex the context holds (refitted after SURTR_EVT_REFIT or surtr_event_refit, un-refitted
+ * otherwise).  Enqueued on the context's stream with no host synchronisation, like surtr_event_pack_dev; it uses one temporary
+ * device allocation ordered on that stream.  SURTR_E_STATE with no event (or after an event that failed), SURTR_E_CAPACITY when
+ * the buffer is too small; nothing is written in either case.  When the host does not hold the event's counts (after
+ * surtr_fracture_event_async without surtr_event_counts) the capacity is checked on the device, which then writes nothing. */
+int surtr_event_mass_dev(surtr_ctx* ctx, int set, float density, void* dev_out, size_t capacity_bytes);
+/* The same for the resident pieces (surtr_upload_pieces / surtr_pieces_from_event), in piece order.  SURTR_E_STATE before any
+ * upload. */
+int surtr_pieces_mass_dev(surtr_ctx* ctx, int set, float density, void* dev_out, size_t capacity_bytes);
+/* Host conveniences, synchronous: *n = number of records; out == NULL returns the count only; with out, *n must hold its
+ * capacity (SURTR_E_CAPACITY and *n = the count when it is too small). */
+int surtr_event_mass(surtr_ctx* ctx, int set, float density, uint32_t* n, surtr_mass* out);
+int surtr_pieces_mass(surtr_ctx* ctx, int set, float density, uint32_t* n, surtr_mass* out);
+/* The records of compounds from those of their pieces (parallel-axis theorem; host, no GPU): compound c is
+ * compound_piece[compound_off[c] .. compound_off[c+1]), exactly as surtr_event_regroup returns them.  Its pieces are the resident
+ * pieces the event skipped (its `outside` mask, ascending) followed by the event's fragments, so build `pieces` as
+ *     pieces[k]              = surtr_pieces_mass record of the k-th skipped resident piece   (k < n_outside)
+ *     pieces[n_outside + f]  = surtr_event_mass record of fragment f
+ * taken BEFORE surtr_pieces_from_event replaces the resident pieces, with the same set and density.  volume, mass and nv add up,
+ * status is the largest of the members' (2 when the sum of the volumes is <= 0); com is mass-weighted (volume-weighted when the
+ * density is 0). */
+int surtr_combine_mass(uint32_t n_compounds, const uint32_t* compound_off, const int32_t* compound_piece, const surtr_mass* pieces,
+                       surtr_mass* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,18 @@ class Counts(ctypes.Structure):
                 ("n_frag", "mesh_verts", "mesh_nbrs", "conv_verts", "conv_nbrs", "n_idx", "n_pairs", "status", "n_failed")]
 
 
+class Mass(ctypes.Structure):
+    """surtr_mass (include/surtr_hip.h), 96 bytes."""
+    _fields_ = [("volume", ctypes.c_double), ("mass", ctypes.c_double), ("com", ctypes.c_double * 3),
+                ("inertia", ctypes.c_double * 6), ("nv", ctypes.c_uint32), ("status", ctypes.c_uint32)]
+
+
+# the same record as a numpy structured array: inertia = Ixx Iyy Izz Ixy Iyz Izx (tensor entries, about com)
+MASS_DTYPE = np.dtype([("volume", "<f8"), ("mass", "<f8"), ("com", "<f8", (3,)), ("inertia", "<f8", (6,)),
+                       ("nv", "<u4"), ("status", "<u4")])
+assert MASS_DTYPE.itemsize == ctypes.sizeof(Mass) == 96
+
+
 class Fragments(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in
                 ("frag_ids", "mesh_vert_off", "mesh_pos", "mesh_nbr_off", "mesh_nbr", "conv_vert_off", "conv_pos",
@@ -307,6 +319,33 @@ class Engine:
         co = np.zeros(n.value + 2, np.uint32); cp = np.zeros(max(n.value, 1), np.int32)
         self._ck(lib().surtr_event_regroup(*args, ctypes.byref(n), ctypes.byref(nc), _p(co), _p(cp)))
         return co[:nc.value + 1].copy(), cp[:co[nc.value]].copy()
+
+    def _mass(self, fn, set, density):
+        n = ctypes.c_uint32()
+        args = [self._h, ctypes.c_int(int(set)), ctypes.c_float(density)]
+        self._ck(fn(*args, ctypes.byref(n), None))
+        out = np.zeros(n.value, MASS_DTYPE)
+        if n.value:
+            self._ck(fn(*args, ctypes.byref(n), _p(out)))
+        return out
+
+    def event_mass(self, set=1, density=10.0):
+        """surtr_event_mass: mass, centre of mass and inertia of every fragment of the last event (set 0 = Mesh, 1 = Convex)
+        as a MASS_DTYPE array, computed on the device."""
+        return self._mass(lib().surtr_event_mass, set, density)
+
+    def pieces_mass(self, set=1, density=10.0):
+        """surtr_pieces_mass: the same for the resident pieces."""
+        return self._mass(lib().surtr_pieces_mass, set, density)
+
+    def event_mass_dev(self, dev_ptr, capacity, set=1, density=10.0):
+        """surtr_event_mass_dev: the records into a device buffer, on the context's stream, without a synchronisation."""
+        self._ck(lib().surtr_event_mass_dev(self._h, ctypes.c_int(int(set)), ctypes.c_float(density), ctypes.c_void_p(dev_ptr),
+                                            ctypes.c_size_t(capacity)))
+
+    def pieces_mass_dev(self, dev_ptr, capacity, set=1, density=10.0):
+        self._ck(lib().surtr_pieces_mass_dev(self._h, ctypes.c_int(int(set)), ctypes.c_float(density), ctypes.c_void_p(dev_ptr),
+                                             ctypes.c_size_t(capacity)))
 
     def event_refit(self):
         self._ck(lib().surtr_event_refit(self._h))
@@ -618,6 +657,22 @@ def moments(solid):
     if rc:
         raise SurtrError(rc)
     return float(vol.value), cen
+
+
+def combine_mass(compound_off, compound_piece, records):
+    """surtr_combine_mass: the records of the compounds of surtr_event_regroup (compound_off, compound_piece as it returns
+    them) from the records of its pieces (the skipped resident pieces, then the fragments; see include/surtr_hip.h)."""
+    co = np.ascontiguousarray(compound_off, np.uint32)
+    cp = np.ascontiguousarray(compound_piece, np.int32)
+    rec = np.ascontiguousarray(records, MASS_DTYPE)
+    nc = max(co.shape[0] - 1, 0)
+    if cp.size and (cp.min() < 0 or cp.max() >= rec.shape[0]):
+        raise SurtrError(E_INVALID, "compound_piece names a piece without a record")
+    out = np.zeros(nc, MASS_DTYPE)
+    rc = lib().surtr_combine_mass(ctypes.c_uint32(nc), _p(co), _p(cp), _p(rec), _p(out))
+    if rc:
+        raise SurtrError(rc)
+    return out
 
 
 def read_obj(path, scale=(1, 1, 1), translate=(0, 0, 0)):

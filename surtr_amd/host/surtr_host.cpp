@@ -532,6 +532,43 @@ void FractureEngine::Refitting(std::vector<Piece>& pieceVec)
     for (uint32_t k = 0; k < n; ++k) pieceVec[k].Convex = rebuild(cpos.data(), cno.data(), cnbr.data(), cvo[k], cvo[k + 1]);
 }
 
+std::vector<surtr_mass> FractureEngine::MassProperties(int set, float density)
+{
+    uint32_t n = 0;
+    check(surtr_event_mass(ctx_, set, density, &n, nullptr), "surtr_event_mass");
+    std::vector<surtr_mass> out(n);
+    if (n) check(surtr_event_mass(ctx_, set, density, &n, out.data()), "surtr_event_mass");
+    return out;
+}
+
+std::vector<surtr_mass> FractureEngine::PieceMassProperties(int set, float density)
+{
+    uint32_t n = 0;
+    check(surtr_pieces_mass(ctx_, set, density, &n, nullptr), "surtr_pieces_mass");
+    std::vector<surtr_mass> out(n);
+    if (n) check(surtr_pieces_mass(ctx_, set, density, &n, out.data()), "surtr_pieces_mass");
+    return out;
+}
+
+std::vector<surtr_mass> CompoundMass(const std::vector<std::set<int>>& bind, const std::vector<surtr_mass>& pieces)
+{
+    std::vector<uint32_t> off(1, 0u);
+    std::vector<int32_t> members;
+    for (const auto& b : bind)
+    {
+        for (int p : b)
+        {
+            if (p < 0 || (size_t)p >= pieces.size()) throw Error(SURTR_E_INVALID, "CompoundMass: piece without a record");
+            members.push_back(p);
+        }
+        off.push_back((uint32_t)members.size());
+    }
+    std::vector<surtr_mass> out(bind.size());
+    const int rc = bind.empty() ? SURTR_OK : surtr_combine_mass((uint32_t)bind.size(), off.data(), members.data(), pieces.data(), out.data());
+    if (rc) throw Error(rc, std::string("surtr_combine_mass: ") + surtr_strerror(rc));
+    return out;
+}
+
 Poly::Polyhedron FractureEngine::RefitSolid(const Poly::Polyhedron& mesh, const Poly::Polyhedron& convex)
 {
     Flat m, c; m.add(mesh); c.add(convex);

@@ -169,6 +169,10 @@ InitCompoundResult InitCompoundTask(const Piece* piece, const Poly::Extract* ext
 struct Fragment { int cell, piece, island; Piece piece_data; FragmentRender render; int status = 0; };
 
 // One engine per GPU (wraps surtr_ctx).  Mirrors the calls of Surtr::DoFracture (Src/Surtr.cpp:1885-1959).
+// The records of compounds from the records of their pieces (surtr_combine_mass: parallel-axis theorem, host).  bind = the
+// bind sets of surtr_event_regroup / FractureTrace::CompoundBind; pieces numbered as there.
+std::vector<surtr_mass> CompoundMass(const std::vector<std::set<int>>& bind, const std::vector<surtr_mass>& pieces);
+
 class FractureEngine
 {
 public:
@@ -228,6 +232,11 @@ public:
     // pattern is the engine's (SetPattern / GenerateVoronoi / GenerateFracturePattern), in pattern space.
     std::vector<Compound> DoFracture(const Compound& targetCompound, float maxAxisScale, const FractureArgs& args,
                                      const std::vector<Vector3>& spherePointCloud, FractureTrace* trace = nullptr);
+    // PxRigidBodyExt::updateMassAndInertia(body, 10.0f) of InitCompound (Src/Surtr.cpp:2520) without PhysX: volume, mass,
+    // centre of mass and inertia tensor of every fragment of the last event (set 0 = Mesh, 1 = Convex), on the device
+    // (surtr_event_mass; definition in include/surtr_hip.h).  PieceMassProperties: the same for the resident pieces.
+    std::vector<surtr_mass> MassProperties(int set, float density = 10.f);
+    std::vector<surtr_mass> PieceMassProperties(int set, float density = 10.f);
     surtr_counts LastCounts() const { return counts_; }
     // The degenerate policy at this level (include/surtr_hip.h, surtr_counts::n_failed): where the reference leaves its own
     // arrays the engine flags the unit instead of emulating what the reference's memory happens to hold -- a flagged (cell,
