@@ -856,103 +856,140 @@ static void refit(Solid& convex, const Solid& mesh, int pointLimit)
 // starts at the face's vertex that comes first in (x,y,z) lexicographic order
 // and is wound so that (v1-v0)x(v2-v0) points out of the cell (the state after
 // PolygonFace::Rewind, :2062).  This is an independent convex-polytope
-// construction (vertex enumeration from plane triples is avoided; a convex
-// polygon soup is clipped instead), used to cross-check surtr_amd's host builder.
+// construction (no cell topology: every face is its generator's plane clipped
+// by all the other half-spaces), used to cross-check surtr_amd's host builder.
 struct D3 { double x, y, z; };
 struct CellFace { int gen; std::vector<D3> loop; };
 
-static std::vector<CellFace> voronoi_cell(const std::vector<D3>& seeds, int self)
+struct CellGen { int id; D3 n; double c; };                      // n.x <= c, n pointing out of the cell
+
+// Every face on its own: a large square in the generator's plane, clipped (Sutherland-Hodgman) by the half-spaces of
+// all the other generators.  No cell topology is carried from cut to cut, so a bisector through a vertex cannot leave
+// the faces inconsistent; a plane that only touches the cell gives a degenerate loop, dropped by the caller.
+static std::vector<CellFace> cell_faces(const std::vector<CellGen>& gens, int C)
 {
-    // start: 6 wall quads, outward winding
     std::vector<CellFace> fs;
-    const double h = 0.5;
-    auto quad = [&](int gen, D3 a, D3 b, D3 c, D3 d) { CellFace f; f.gen = gen; f.loop = {a, b, c, d}; fs.push_back(f); };
-    const int C = (int)seeds.size();
-    quad(C + 0, D3{-h, -h, -h}, D3{-h, -h, h}, D3{-h, h, h}, D3{-h, h, -h});   // -x
-    quad(C + 1, D3{h, -h, -h}, D3{h, h, -h}, D3{h, h, h}, D3{h, -h, h});       // +x
-    quad(C + 2, D3{-h, -h, -h}, D3{h, -h, -h}, D3{h, -h, h}, D3{-h, -h, h});   // -y
-    quad(C + 3, D3{-h, h, -h}, D3{-h, h, h}, D3{h, h, h}, D3{h, h, -h});       // +y
-    quad(C + 4, D3{-h, -h, -h}, D3{-h, h, -h}, D3{h, h, -h}, D3{h, -h, -h});   // -z
-    quad(C + 5, D3{-h, -h, h}, D3{h, -h, h}, D3{h, h, h}, D3{-h, h, h});       // +z
-    const D3 s = seeds[self];
-    for (int o = 0; o < C; ++o)
+    for (const CellGen& g : gens)
     {
-        if (o == self) continue;
-        const D3 q = seeds[o];
-        // half-space n.x <= c with n = q - s, c = (|q|^2-|s|^2)/2
-        const D3 n{q.x - s.x, q.y - s.y, q.z - s.z};
-        const double c = 0.5 * ((q.x * q.x + q.y * q.y + q.z * q.z) - (s.x * s.x + s.y * s.y + s.z * s.z));
-        auto sd = [&](const D3& p) { return n.x * p.x + n.y * p.y + n.z * p.z - c; };
-        bool cuts = false;
-        for (const auto& f : fs) for (const auto& p : f.loop) if (sd(p) > 1e-12) cuts = true;
-        if (!cuts) continue;
-        std::vector<CellFace> keep;
-        std::vector<std::pair<D3, D3>> capseg;
-        for (const auto& f : fs)
+        const double nn = g.n.x * g.n.x + g.n.y * g.n.y + g.n.z * g.n.z, ln = std::sqrt(nn);
+        const D3 u{g.n.x / ln, g.n.y / ln, g.n.z / ln};
+        const D3 p0{g.n.x * g.c / nn, g.n.y * g.c / nn, g.n.z * g.c / nn};
+        const D3 t = std::fabs(u.x) < 0.6 ? D3{1, 0, 0} : D3{0, 1, 0};
+        D3 e1{u.y * t.z - u.z * t.y, u.z * t.x - u.x * t.z, u.x * t.y - u.y * t.x};
+        const double l1 = std::sqrt(e1.x * e1.x + e1.y * e1.y + e1.z * e1.z);
+        e1 = D3{e1.x / l1, e1.y / l1, e1.z / l1};
+        const D3 e2{u.y * e1.z - u.z * e1.y, u.z * e1.x - u.x * e1.z, u.x * e1.y - u.y * e1.x};
+        CellFace f; f.gen = g.id;
+        const double R = 4.0, sq[4][2] = {{R, R}, {-R, R}, {-R, -R}, {R, -R}};     // counter-clockwise about n
+        for (int k = 0; k < 4; ++k)
+            f.loop.push_back(D3{p0.x + sq[k][0] * e1.x + sq[k][1] * e2.x, p0.y + sq[k][0] * e1.y + sq[k][1] * e2.y, p0.z + sq[k][0] * e1.z + sq[k][1] * e2.z});
+        for (const CellGen& h : gens)
         {
-            CellFace g; g.gen = f.gen;
+            if (h.id == g.id || f.loop.empty()) continue;
+            auto sd = [&](const D3& p) { return h.n.x * p.x + h.n.y * p.y + h.n.z * p.z - h.c; };
+            std::vector<D3> out;
             const size_t m = f.loop.size();
-            D3 enter{0, 0, 0}, leave{0, 0, 0}; bool he = false, hl = false;
             for (size_t i = 0; i < m; ++i)
             {
                 const D3& a = f.loop[i]; const D3& b = f.loop[(i + 1) % m];
                 const double da = sd(a), db = sd(b);
-                if (da <= 0) g.loop.push_back(a);
+                if (da <= 0) out.push_back(a);
                 if ((da <= 0) != (db <= 0))
                 {
-                    const double t = da / (da - db);
-                    D3 x{a.x + t * (b.x - a.x), a.y + t * (b.y - a.y), a.z + t * (b.z - a.z)};
-                    g.loop.push_back(x);
-                    if (da <= 0) { leave = x; hl = true; } else { enter = x; he = true; }
+                    const double tt = da / (da - db);
+                    D3 x{a.x + tt * (b.x - a.x), a.y + tt * (b.y - a.y), a.z + tt * (b.z - a.z)};
+                    if (h.id >= C)      // on a wall exactly, as the box's own vertices and edges are
+                    {
+                        const int w = h.id - C;
+                        (w < 2 ? x.x : w < 4 ? x.y : x.z) = (w & 1) ? 0.5 : -0.5;
+                    }
+                    out.push_back(x);
                 }
             }
-            if (g.loop.size() >= 3) keep.push_back(g);
-            if (he && hl) capseg.push_back({leave, enter});   // the cut edge, in face order leave -> enter
+            f.loop.swap(out);
         }
-        if (capseg.size() >= 3)
-        {
-            // chain the cut segments into the cap loop; reversed so the cap winds outward
-            CellFace cap; cap.gen = o;
-            std::vector<char> usedseg(capseg.size(), 0);
-            D3 curp = capseg[0].second; cap.loop.push_back(capseg[0].first); usedseg[0] = 1;
-            for (size_t it = 1; it < capseg.size(); ++it)
-            {
-                size_t best = capseg.size(); double bd = 1e300;
-                for (size_t j = 0; j < capseg.size(); ++j)
-                {
-                    if (usedseg[j]) continue;
-                    const D3& a = capseg[j].first;
-                    double d = (a.x - curp.x) * (a.x - curp.x) + (a.y - curp.y) * (a.y - curp.y) + (a.z - curp.z) * (a.z - curp.z);
-                    if (d < bd) { bd = d; best = j; }
-                }
-                if (best == capseg.size()) break;
-                usedseg[best] = 1; cap.loop.push_back(capseg[best].first); curp = capseg[best].second;
-            }
-            std::reverse(cap.loop.begin(), cap.loop.end());
-            keep.push_back(cap);
-        }
-        fs.swap(keep);
+        if (f.loop.size() >= 3) fs.push_back(std::move(f));
     }
-    // drop degenerate duplicates inside loops, canonical start + order
+    return fs;
+}
+
+static std::vector<CellFace> voronoi_cell(const std::vector<D3>& seeds, int self)
+{
+    const int C = (int)seeds.size();
+    const D3 s = seeds[self];
+    std::vector<std::pair<double, int>> near;                      // the other seeds, nearest first
+    for (int o = 0; o < C; ++o)
+        if (o != self)
+        {
+            const D3 q = seeds[o];
+            near.push_back({(q.x - s.x) * (q.x - s.x) + (q.y - s.y) * (q.y - s.y) + (q.z - s.z) * (q.z - s.z), o});
+        }
+    std::sort(near.begin(), near.end());
+    // the walls and the k nearest seeds bound a cell that holds the true one; a seed farther than twice that cell's
+    // radius has a bisector that misses it.  Double k until the next seed is that far.
+    std::vector<CellFace> fs;
+    for (size_t k = std::min<size_t>(32, near.size());; k = std::min(2 * k, near.size()))
+    {
+        std::vector<CellGen> gens;
+        for (size_t i = 0; i < k; ++i)
+        {
+            const D3 q = seeds[near[i].second];
+            gens.push_back({near[i].second, D3{q.x - s.x, q.y - s.y, q.z - s.z},
+                            0.5 * ((q.x * q.x + q.y * q.y + q.z * q.z) - (s.x * s.x + s.y * s.y + s.z * s.z))});
+        }
+        const double WN[6][3] = {{-1, 0, 0}, {1, 0, 0}, {0, -1, 0}, {0, 1, 0}, {0, 0, -1}, {0, 0, 1}};
+        for (int w = 0; w < 6; ++w) gens.push_back({C + w, D3{WN[w][0], WN[w][1], WN[w][2]}, 0.5});
+        fs = cell_faces(gens, C);
+        if (k == near.size()) break;
+        double r2 = 0;
+        for (const auto& f : fs)
+            for (const D3& p : f.loop) r2 = std::max(r2, (p.x - s.x) * (p.x - s.x) + (p.y - s.y) * (p.y - s.y) + (p.z - s.z) * (p.z - s.z));
+        if (near[k].first > 4.0 * r2 * (1.0 + 1e-9) + 1e-18) break;
+    }
+    // canonical loops: consecutive vertices within 1e-12 merge; vertices within 1e-12 of the line
+    // through their loop neighbours go until none is left; loops of fewer than 3 vertices go (zero area)
+    const double tol2 = 1e-24;
+    auto d2 = [](const D3& a, const D3& b) { return (a.x - b.x) * (a.x - b.x) + (a.y - b.y) * (a.y - b.y) + (a.z - b.z) * (a.z - b.z); };
+    auto crs = [](const D3& u, const D3& w) { return D3{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x}; };
+    auto dif = [](const D3& a, const D3& b) { return D3{a.x - b.x, a.y - b.y, a.z - b.z}; };
+    auto nrm2 = [](const D3& a) { return a.x * a.x + a.y * a.y + a.z * a.z; };
     for (auto& f : fs)
     {
         std::vector<D3> u;
-        for (const auto& p : f.loop)
+        for (const auto& p : f.loop) if (u.empty() || d2(u.back(), p) > tol2) u.push_back(p);
+        while (u.size() > 1 && d2(u.back(), u.front()) <= tol2) u.pop_back();
+        for (bool changed = true; changed && u.size() >= 3;)
         {
-            bool dup = false;
-            for (const auto& r : u)
-                if (std::fabs(r.x - p.x) + std::fabs(r.y - p.y) + std::fabs(r.z - p.z) < 1e-13) dup = true;
-            if (!dup) u.push_back(p);
+            changed = false;
+            for (size_t i = 0; i < u.size() && u.size() >= 3;)
+            {
+                const size_t m = u.size();
+                const D3& a = u[(i + m - 1) % m]; const D3& c = u[(i + 1) % m];
+                if (nrm2(crs(dif(u[i], a), dif(c, a))) <= tol2 * nrm2(dif(c, a))) { u.erase(u.begin() + i); changed = true; }
+                else ++i;
+            }
         }
         f.loop.swap(u);
-        if (f.loop.empty()) continue;
+        if (f.loop.size() < 3) continue;
         size_t st = 0;
         for (size_t i = 1; i < f.loop.size(); ++i)
         {
             const D3& a = f.loop[i]; const D3& b = f.loop[st];
             if (a.x < b.x || (a.x == b.x && (a.y < b.y || (a.y == b.y && a.z < b.z)))) st = i;
         }
-        std::rotate(f.loop.begin(), f.loop.begin() + st, f.loop.end());
+        // the start's first three vertices narrowed to float must span a plane facing away from the seed; else advance
+        // the start, and drop a face where no start does (its whole extent is below float resolution)
+        auto nar = [](const D3& p) { return D3{(double)(float)p.x, (double)(float)p.y, (double)(float)p.z}; };
+        const size_t m = f.loop.size();
+        size_t k = 0;
+        for (; k < m; ++k)
+        {
+            const D3 a = nar(f.loop[(st + k) % m]), b = nar(f.loop[(st + k + 1) % m]), c = nar(f.loop[(st + k + 2) % m]);
+            const D3 n = crs(dif(b, a), dif(c, a));
+            if ((n.x != 0 || n.y != 0 || n.z != 0) && n.x * (a.x - s.x) + n.y * (a.y - s.y) + n.z * (a.z - s.z) >= 0) break;
+        }
+        if (k == m) { f.loop.clear(); continue; }
+        std::rotate(f.loop.begin(), f.loop.begin() + (st + k) % m, f.loop.end());
     }
     fs.erase(std::remove_if(fs.begin(), fs.end(), [](const CellFace& f) { return f.loop.size() < 3; }), fs.end());
     std::stable_sort(fs.begin(), fs.end(), [](const CellFace& a, const CellFace& b) { return a.gen < b.gen; });

@@ -8,8 +8,9 @@
 //     than twice the cell's radius cannot touch it; then the exact "some vertex is on its side" test of the host code);
 //   - the lowest seed that touches the cell cuts it (cell = at most SURTR_CELL_V vertices of degree 3 in LDS), the lanes
 //     above it test again against the smaller cell: exactly the sequential order;
-//   - faces: loops over unseen directed edges, generator = best-fitting plane, outward winding, start at the
-//     lexicographically smallest vertex, stable order by generator id (seeds ascending, then the walls -x +x -y +y -z +z).
+//   - faces: loops over unseen directed edges, coincident and collinear vertices dropped, generator = best-fitting plane,
+//     outward winding, start at the lexicographically smallest vertex (advanced until its float triangle is valid), stable
+//     order by generator id (seeds ascending, then the walls -x +x -y +y -z +z).
 // The cells go straight into the context as the fracture pattern (v012 + face offsets = surtr_upload_pattern).
 #include <chrono>
 #include <cstdio>
@@ -21,6 +22,8 @@
 #define SURTR_CELL_G 448u      // generators that cut a cell (6 walls + seeds)
 #define SURTR_CELL_F 64u       // faces of a finished cell
 #define SURTR_CELL_FV 384u     // face vertices of a finished cell (3 per vertex)
+
+enum { LIMIT_V = 1, LIMIT_G, LIMIT_F, LIMIT_FV };       // the limit a refused cell ran into (heads[4 * cell + 3])
 
 namespace {
 
@@ -44,7 +47,7 @@ struct CellLds
     int32_t gid[SURTR_CELL_G]; D3 gn[SURTR_CELL_G]; double gc[SURTR_CELL_G];
     uint8_t seen[SURTR_CELL_V][3];
     int16_t loop[SURTR_CELL_FV]; uint16_t flo[SURTR_CELL_F + 1]; int32_t fgen[SURTR_CELL_F]; uint8_t forder[SURTR_CELL_F];
-    uint32_t nv, ng, err, nfaces, flag[2], cut_lane;
+    uint32_t nv, ng, err, limit, nfaces, flag[2], cut_lane;      // limit: the LIMIT_* an E_CAPACITY ran into
     double r2; D3 cut_n; double cut_c;
 };
 
@@ -56,6 +59,59 @@ __device__ __forceinline__ int ring_prev3(const int16_t* r, int who)
 }
 
 __device__ __forceinline__ double plane_side(const D3 n, double cc, const D3 p) { return n.x * p.x + n.y * p.y + n.z * p.z - cc; }
+
+// DESIGN.md section 5 rules 1 and 2, operation for operation those of canonical_loop() / float_start_ok() in host_geom.cpp
+#define SURTR_CELL_TOL2 1e-24
+
+__device__ __forceinline__ double dist2(const D3 a, const D3 b)
+{
+    const double dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
+    return dx * dx + dy * dy + dz * dz;
+}
+
+__device__ __forceinline__ bool on_line(const D3 p, const D3 a, const D3 c)
+{
+    const D3 u{p.x - a.x, p.y - a.y, p.z - a.z}, w{c.x - a.x, c.y - a.y, c.z - a.z};
+    const D3 n{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
+    return n.x * n.x + n.y * n.y + n.z * n.z <= SURTR_CELL_TOL2 * (w.x * w.x + w.y * w.y + w.z * w.z);
+}
+
+// rule 1 on the loop lp[0, m): merge consecutive vertices within 1e-12, then drop vertices on the line through their
+// neighbours until none is left; returns the new length
+__device__ int canonical_loop(const D3* p, int16_t* lp, int m)
+{
+    int k = 0;
+    for (int i = 0; i < m; ++i)
+        if (k == 0 || dist2(p[lp[k - 1]], p[lp[i]]) > SURTR_CELL_TOL2) lp[k++] = lp[i];
+    while (k > 1 && dist2(p[lp[k - 1]], p[lp[0]]) <= SURTR_CELL_TOL2) --k;
+    bool changed = true;
+    while (changed && k >= 3)
+    {
+        changed = false;
+        for (int i = 0; i < k && k >= 3;)
+        {
+            if (on_line(p[lp[i]], p[lp[(i + k - 1) % k]], p[lp[(i + 1) % k]]))
+            {
+                for (int j = i; j + 1 < k; ++j) lp[j] = lp[j + 1];
+                --k; changed = true;
+            }
+            else ++i;
+        }
+    }
+    return k;
+}
+
+// rule 2: the float triangle (v0, v1, v2) as k_pack_cells stores it has a nonzero normal not pointing towards the seed
+__device__ __forceinline__ bool float_start_ok(const D3 a0, const D3 b0, const D3 c0, const D3 s)
+{
+    const D3 a{(double)(float)a0.x, (double)(float)a0.y, (double)(float)a0.z};
+    const D3 b{(double)(float)b0.x, (double)(float)b0.y, (double)(float)b0.z};
+    const D3 c{(double)(float)c0.x, (double)(float)c0.y, (double)(float)c0.z};
+    const D3 u{b.x - a.x, b.y - a.y, b.z - a.z}, w{c.x - a.x, c.y - a.y, c.z - a.z};
+    const D3 n{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
+    if (n.x == 0 && n.y == 0 && n.z == 0) return false;
+    return n.x * (a.x - s.x) + n.y * (a.y - s.y) + n.z * (a.z - s.z) >= 0;
+}
 
 // cut_cell() of host_geom.cpp over the lanes of the wave: keep n.x <= cc.  Same results as the sequential code: new
 // vertices are numbered in (cut vertex, ring slot) order by a prefix sum, every other step touches disjoint entries.
@@ -91,7 +147,7 @@ __device__ void cut_cell_wave(CellLds& L, const D3 n, const double cc)
         carry += lane_bcast(inc.x, SURTR_LANES - 1u);
     }
     const int n1 = n0 + (int)carry;
-    if (n1 > (int)SURTR_CELL_V) { if (lane == 0) L.err = SURTR_E_CAPACITY; __syncthreads(); return; }
+    if (n1 > (int)SURTR_CELL_V) { if (lane == 0) { L.err = SURTR_E_CAPACITY; L.limit = LIMIT_V; } __syncthreads(); return; }
     __syncthreads();
     for (int i = (int)lane; i < n0; i += SURTR_LANES)
     {
@@ -165,19 +221,23 @@ __device__ void cell_loops_serial(CellLds& L)
         for (int j = 0; j < 3; ++j)
         {
             if (L.seen[i][j]) continue;
-            if (nf >= (int)SURTR_CELL_F || lo >= (int)SURTR_CELL_FV) { L.err = SURTR_E_CAPACITY; break; }
+            if (nf >= (int)SURTR_CELL_F || lo >= (int)SURTR_CELL_FV) { L.err = SURTR_E_CAPACITY; L.limit = nf >= (int)SURTR_CELL_F ? LIMIT_F : LIMIT_FV; break; }
             const int start = lo;
             int prev = i, cur = L.ring[i][j], len = 1;
             L.seen[i][j] = 1;
             L.loop[lo++] = (int16_t)i;
             while (cur != i && len <= nvert)
             {
-                if (lo >= (int)SURTR_CELL_FV) { L.err = SURTR_E_CAPACITY; break; }
+                if (lo >= (int)SURTR_CELL_FV) { L.err = SURTR_E_CAPACITY; L.limit = LIMIT_FV; break; }
                 L.loop[lo++] = (int16_t)cur; ++len;
                 const int nx = ring_prev3(L.ring[cur], prev);
                 for (int q = 0; q < 3; ++q) if (L.ring[cur][q] == nx) L.seen[cur][q] = 1;
                 prev = cur; cur = nx;
             }
+            if (L.err) break;
+            const int m = canonical_loop(L.p, L.loop + start, lo - start);
+            if (m < 3) { lo = start; continue; }      // zero area
+            lo = start + m;
             L.flo[nf] = (uint16_t)start;
             ++nf;
         }
@@ -223,8 +283,7 @@ __device__ void cell_output_serial(CellLds& L, const D3 s, CellOut& o)
         while (at > 0 && L.fgen[L.forder[at - 1]] > L.fgen[f]) { L.forder[at] = L.forder[at - 1]; --at; }
         L.forder[at] = (uint8_t)f;
     }
-    o.nf = (uint32_t)nf; o.nfv = (uint32_t)L.flo[nf];
-    uint32_t w = 0;
+    uint32_t w = 0, kept = 0;
     for (int k = 0; k < nf; ++k)
     {
         const int f = L.forder[k];
@@ -245,14 +304,20 @@ __device__ void cell_output_serial(CellLds& L, const D3 s, CellOut& o)
             const D3 p = at(i), q = at(st);
             if (p.x < q.x || (p.x == q.x && (p.y < q.y || (p.y == q.y && p.z < q.z)))) st = i;
         }
-        o.gen[k] = L.fgen[f]; o.fvo[k] = (uint16_t)w;
+        // rule 2: advance the start until its float triangle is valid; no valid start = the face is below float resolution
+        int adv = 0;
+        while (adv < len && !float_start_ok(at((st + adv) % len), at((st + adv + 1) % len), at((st + adv + 2) % len), s)) ++adv;
+        if (adv == len) continue;
+        st = (st + adv) % len;
+        o.gen[kept] = L.fgen[f]; o.fvo[kept] = (uint16_t)w; ++kept;
         for (int i = 0; i < len; ++i)
         {
             const D3 p = at((st + i) % len);
             o.v[3 * w] = p.x; o.v[3 * w + 1] = p.y; o.v[3 * w + 2] = p.z; ++w;
         }
     }
-    o.fvo[nf] = (uint16_t)w;
+    o.fvo[kept] = (uint16_t)w;
+    o.nf = kept; o.nfv = w;
 }
 
 // cell c of group g: seeds [goff[g], goff[g+1]); one wave per cell
@@ -271,7 +336,7 @@ __global__ __launch_bounds__(SURTR_LANES) void k_build_cells(uint32_t n_cells, u
         const double P[8][3] = {{-.5, -.5, -.5}, {.5, -.5, -.5}, {.5, .5, -.5}, {-.5, .5, -.5}, {-.5, -.5, .5}, {.5, -.5, .5}, {.5, .5, .5}, {-.5, .5, .5}};
         const int NB[8][3] = {{1, 4, 3}, {5, 0, 2}, {3, 6, 1}, {7, 2, 0}, {5, 7, 0}, {1, 6, 4}, {5, 2, 7}, {4, 6, 3}};
         for (int i = 0; i < 8; ++i) { L.p[i] = D3{P[i][0], P[i][1], P[i][2]}; for (int e = 0; e < 3; ++e) L.ring[i][e] = (int16_t)NB[i][e]; }
-        L.nv = 8; L.err = 0;
+        L.nv = 8; L.err = 0; L.limit = 0;
         const double WN[6][3] = {{-1, 0, 0}, {1, 0, 0}, {0, -1, 0}, {0, 1, 0}, {0, 0, -1}, {0, 0, 1}};
         for (int w = 0; w < 6; ++w) { L.gid[w] = (int32_t)(C + (uint32_t)w); L.gn[w] = D3{WN[w][0], WN[w][1], WN[w][2]}; L.gc[w] = 0.5; }
         L.ng = 6;
@@ -316,7 +381,7 @@ __global__ __launch_bounds__(SURTR_LANES) void k_build_cells(uint32_t n_cells, u
             {
                 L.cut_n = n; L.cut_c = cc;
                 if (L.ng < SURTR_CELL_G) { L.gid[L.ng] = (int32_t)o; L.gn[L.ng] = n; L.gc[L.ng] = cc; ++L.ng; }
-                else L.err = SURTR_E_CAPACITY;
+                else { L.err = SURTR_E_CAPACITY; L.limit = LIMIT_G; }
             }
             __syncthreads();
             cut_cell_wave(L, L.cut_n, L.cut_c);      // (all lanes: the plane of the lowest touching seed)
@@ -336,6 +401,7 @@ __global__ __launch_bounds__(SURTR_LANES) void k_build_cells(uint32_t n_cells, u
         if (L.err == 0) cell_output_serial(L, s, o);
         o.err = L.err;
         heads[4 * (size_t)cell] = o.nf; heads[4 * (size_t)cell + 1] = o.nfv; heads[4 * (size_t)cell + 2] = o.err;      // one contiguous read-back
+        heads[4 * (size_t)cell + 3] = L.limit;
     }
 }
 
@@ -379,11 +445,10 @@ int surtr_build_cells(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* group_s
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     CellBuffers& B = ctx->cells;
+    // the build's own scratch first: the previous cells (cfo, gen, fvo, verts) stay readable until every cell is known to fit
     int rc = grow(ctx, &B.seeds, B.c_seeds, 3 * (size_t)n);
     if (rc == 0) rc = grow(ctx, &B.goff, B.c_goff, (size_t)n_groups + 1);
     if (rc == 0) rc = grow(ctx, &B.slots, B.c_slots, (size_t)n * sizeof(CellOut));
-    if (rc == 0) rc = grow(ctx, &B.cfo, B.c_cfo, (size_t)n + 1);
-    if (rc == 0) rc = grow(ctx, &B.cvo, B.c_cvo, (size_t)n + 1);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(st));      // an event may still be reading the old pattern
     HIPCHK(hipMemcpyAsync(B.seeds, seeds, (size_t)n * 24, hipMemcpyHostToDevice, st));
@@ -402,12 +467,28 @@ int surtr_build_cells(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* group_s
     std::vector<uint32_t> cfo(n + 1, 0u), cvo(n + 1, 0u);
     for (uint32_t c = 0; c < n; ++c)
     {
-        if (head[4 * (size_t)c + 2]) return (int)head[4 * (size_t)c + 2];
-        if (head[4 * (size_t)c] > SURTR_MAXF) return SURTR_E_INVALID;
+        if (head[4 * (size_t)c + 2])
+        {
+            const uint32_t lim = head[4 * (size_t)c + 3];
+            const std::string what = lim == LIMIT_V ? "SURTR_CELL_V = " + std::to_string(SURTR_CELL_V) + " vertices while it is cut"
+                                   : lim == LIMIT_G ? "SURTR_CELL_G = " + std::to_string(SURTR_CELL_G) + " cutting planes"
+                                   : lim == LIMIT_F ? "SURTR_CELL_F = " + std::to_string(SURTR_CELL_F) + " faces"
+                                   : "SURTR_CELL_FV = " + std::to_string(SURTR_CELL_FV) + " face vertices";
+            ctx->err = "surtr_build_cells: cell " + std::to_string(c) + " needs more than " + what + "; the previous cells are kept";
+            return (int)head[4 * (size_t)c + 2];
+        }
+        if (head[4 * (size_t)c] > SURTR_MAXF)
+        {
+            ctx->err = "surtr_build_cells: cell " + std::to_string(c) + " has more than SURTR_MAXF faces; the previous cells are kept";
+            return SURTR_E_INVALID;
+        }
         cfo[c + 1] = cfo[c] + head[4 * (size_t)c]; cvo[c + 1] = cvo[c] + head[4 * (size_t)c + 1];
     }
     const uint32_t nf = cfo[n], nfv = cvo[n];
-    rc = grow(ctx, &B.gen, B.c_gen, nf);
+    B.n = 0;      // from here on the previous cells are replaced: none are readable until the new ones are complete
+    rc = grow(ctx, &B.cfo, B.c_cfo, (size_t)n + 1);
+    if (rc == 0) rc = grow(ctx, &B.cvo, B.c_cvo, (size_t)n + 1);
+    if (rc == 0) rc = grow(ctx, &B.gen, B.c_gen, nf);
     if (rc == 0) rc = grow(ctx, &B.fvo, B.c_fvo, (size_t)nf + 1);
     if (rc == 0) rc = grow(ctx, &B.verts, B.c_verts, 3 * (size_t)nfv);
     if (rc) return rc;

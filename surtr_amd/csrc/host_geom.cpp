@@ -182,6 +182,58 @@ bool cut_cell(ConvexCell& c, D3 n, double cc)
 
 struct CellFace { int gen; std::vector<D3> loop; };
 
+// DESIGN.md section 5, rule 1: a bisector through a cell vertex leaves copies of it (new vertices at t = 0) and zero-area
+// faces along real edges.  Consecutive loop vertices within 1e-12 merge (the earlier stays); then a vertex within 1e-12 of
+// the line through its two loop neighbours goes, in loop order, until none is left.  k_build_cells does the same.
+const double kCellTol2 = 1e-24;
+
+inline double dist2(const D3& a, const D3& b)
+{
+    const double dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
+    return dx * dx + dy * dy + dz * dz;
+}
+
+// p within sqrt(kCellTol2) of the line through a and c (or a == c)
+inline bool on_line(const D3& p, const D3& a, const D3& c)
+{
+    const D3 u{p.x - a.x, p.y - a.y, p.z - a.z}, w{c.x - a.x, c.y - a.y, c.z - a.z};
+    const D3 n{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
+    return n.x * n.x + n.y * n.y + n.z * n.z <= kCellTol2 * (w.x * w.x + w.y * w.y + w.z * w.z);
+}
+
+void canonical_loop(std::vector<int>& loop, const std::vector<D3>& p)
+{
+    size_t k = 0;
+    for (size_t i = 0; i < loop.size(); ++i)
+        if (k == 0 || dist2(p[loop[k - 1]], p[loop[i]]) > kCellTol2) loop[k++] = loop[i];
+    while (k > 1 && dist2(p[loop[k - 1]], p[loop[0]]) <= kCellTol2) --k;
+    loop.resize(k);
+    bool changed = true;
+    while (changed && loop.size() >= 3)
+    {
+        changed = false;
+        for (size_t i = 0; i < loop.size() && loop.size() >= 3;)
+        {
+            const size_t m = loop.size();
+            if (on_line(p[loop[i]], p[loop[(i + m - 1) % m]], p[loop[(i + 1) % m]])) { loop.erase(loop.begin() + i); changed = true; }
+            else ++i;
+        }
+    }
+}
+
+// DESIGN.md section 5, rule 2: the triangle (v0, v1, v2) narrowed to float, as pattern_from_cells / k_pack_cells store it,
+// must have a nonzero normal that does not point towards the seed (ConstructFacePlane reads these three).
+inline bool float_start_ok(const D3& a0, const D3& b0, const D3& c0, const D3& s)
+{
+    const D3 a{(double)(float)a0.x, (double)(float)a0.y, (double)(float)a0.z};
+    const D3 b{(double)(float)b0.x, (double)(float)b0.y, (double)(float)b0.z};
+    const D3 c{(double)(float)c0.x, (double)(float)c0.y, (double)(float)c0.z};
+    const D3 u{b.x - a.x, b.y - a.y, b.z - a.z}, w{c.x - a.x, c.y - a.y, c.z - a.z};
+    const D3 n{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
+    if (n.x == 0 && n.y == 0 && n.z == 0) return false;
+    return n.x * (a.x - s.x) + n.y * (a.y - s.y) + n.z * (a.z - s.z) >= 0;
+}
+
 std::vector<CellFace> build_cell(const std::vector<D3>& seeds, int self)
 {
     const int C = (int)seeds.size();
@@ -225,6 +277,8 @@ std::vector<CellFace> build_cell(const std::vector<D3>& seeds, int self)
                 for (size_t q = 0; q < cell.ring[cur].size(); ++q) if (cell.ring[cur][q] == nx) seen[cur][q] = 1;
                 prev = cur; cur = nx;
             }
+            canonical_loop(loop, cell.p);
+            if (loop.size() < 3) continue;      // zero area
             // generator = the plane all loop vertices lie on
             int best = -1; double bestErr = 1e300;
             for (const Gen& g : gens)
@@ -252,8 +306,14 @@ std::vector<CellFace> build_cell(const std::vector<D3>& seeds, int self)
             const D3& p = f.loop[i]; const D3& q = f.loop[st];
             if (p.x < q.x || (p.x == q.x && (p.y < q.y || (p.y == q.y && p.z < q.z)))) st = i;
         }
-        std::rotate(f.loop.begin(), f.loop.begin() + st, f.loop.end());
+        // rule 2: advance the start until its float triangle is valid; no valid start = the face is below float resolution
+        const size_t m = f.loop.size();
+        size_t k = 0;
+        while (k < m && !float_start_ok(f.loop[(st + k) % m], f.loop[(st + k + 1) % m], f.loop[(st + k + 2) % m], s)) ++k;
+        if (k == m) { f.loop.clear(); continue; }
+        std::rotate(f.loop.begin(), f.loop.begin() + (st + k) % m, f.loop.end());
     }
+    faces.erase(std::remove_if(faces.begin(), faces.end(), [](const CellFace& f) { return f.loop.empty(); }), faces.end());
     std::stable_sort(faces.begin(), faces.end(), [](const CellFace& x, const CellFace& y) { return x.gen < y.gen; });
     return faces;
 }

@@ -1,5 +1,5 @@
 """surtr_build_cells (Voronoi cells on the device, row A2) against the ORACLE's cells (oracle.voronoi_cells: the canonical
-cell of DESIGN section 5 built as a polygon soup -- structure equal, coordinates to 1e-12; Src/Surtr.cpp:2003-2070 with voro++
+cell of DESIGN section 5 built face by face -- structure equal, coordinates to 1e-12; Src/Surtr.cpp:2003-2070 with voro++
 replaced by the canonical order) and against the host builder surtr_voronoi_cells (bit for bit: same float program).
 `check_cells` runs on the emulation here and on the MI355X in test_gpu_parity.py."""
 import numpy as np
