@@ -423,15 +423,9 @@ __global__ __launch_bounds__(SURTR_LANES) void k_pack_cells(uint32_t n_cells, co
     if (cell + 1u == n_cells && threadIdx.x == 0) fvo[f0 + o.nf] = v0 + o.nfv;
 }
 
+// a cell buffer holds at least 16 elements
 template <class T>
-int grow(surtr_ctx* ctx, T** p, size_t& cap, size_t need)
-{
-    if (*p && cap >= need) return SURTR_OK;
-    free_dev(*p); *p = nullptr; cap = 0;
-    if (hipMalloc((void**)p, std::max<size_t>(need, 16) * sizeof(T)) != hipSuccess) { ctx->err = "cell buffer allocation failed"; return SURTR_E_HIP; }
-    cap = std::max<size_t>(need, 16);
-    return SURTR_OK;
-}
+int grow_cells(surtr_ctx* ctx, DevBuf<T>& b, size_t need) { return b.grow(ctx, need, 16); }
 
 } // namespace
 
@@ -446,16 +440,13 @@ int surtr_build_cells(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* group_s
     hipStream_t st = ctx->stream;
     CellBuffers& B = ctx->cells;
     // the build's own scratch first: the previous cells (cfo, gen, fvo, verts) stay readable until every cell is known to fit
-    int rc = grow(ctx, &B.seeds, B.c_seeds, 3 * (size_t)n);
-    if (rc == 0) rc = grow(ctx, &B.goff, B.c_goff, (size_t)n_groups + 1);
-    if (rc == 0) rc = grow(ctx, &B.slots, B.c_slots, (size_t)n * sizeof(CellOut));
-    if (rc) return rc;
+    if (grow_cells(ctx, B.seeds, 3 * (size_t)n) || grow_cells(ctx, B.goff, (size_t)n_groups + 1) || grow_cells(ctx, B.slots, (size_t)n * sizeof(CellOut)))
+        return SURTR_E_HIP;
     HIPCHK(hipStreamSynchronize(st));      // an event may still be reading the old pattern
     HIPCHK(hipMemcpyAsync(B.seeds, seeds, (size_t)n * 24, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(B.goff, group_seed_off, ((size_t)n_groups + 1) * 4, hipMemcpyHostToDevice, st));
-    CellOut* slots = (CellOut*)B.slots;
-    rc = grow(ctx, &B.heads, B.c_heads, 4 * (size_t)n);
-    if (rc) return rc;
+    CellOut* slots = (CellOut*)B.slots.p;
+    if (grow_cells(ctx, B.heads, 4 * (size_t)n)) return SURTR_E_HIP;
     const auto t0 = std::chrono::steady_clock::now();
     hipLaunchKernelGGL(k_build_cells, dim3(n), dim3(SURTR_LANES), 0, st, n, n_groups, B.goff, B.seeds, slots, B.heads);
     HIPCHK(hipGetLastError());
@@ -486,22 +477,16 @@ int surtr_build_cells(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* group_s
     }
     const uint32_t nf = cfo[n], nfv = cvo[n];
     B.n = 0;      // from here on the previous cells are replaced: none are readable until the new ones are complete
-    rc = grow(ctx, &B.cfo, B.c_cfo, (size_t)n + 1);
-    if (rc == 0) rc = grow(ctx, &B.cvo, B.c_cvo, (size_t)n + 1);
-    if (rc == 0) rc = grow(ctx, &B.gen, B.c_gen, nf);
-    if (rc == 0) rc = grow(ctx, &B.fvo, B.c_fvo, (size_t)nf + 1);
-    if (rc == 0) rc = grow(ctx, &B.verts, B.c_verts, 3 * (size_t)nfv);
-    if (rc) return rc;
-    // the pattern buffers of the context (what surtr_upload_pattern fills)
-    if (!(ctx->d_v012 && ctx->d_planes && ctx->d_plane_off && ctx->cap_pattern_faces >= nf && ctx->cap_pattern_cells >= n))
+    if (grow_cells(ctx, B.cfo, (size_t)n + 1) || grow_cells(ctx, B.cvo, (size_t)n + 1) || grow_cells(ctx, B.gen, nf) ||
+        grow_cells(ctx, B.fvo, (size_t)nf + 1) || grow_cells(ctx, B.verts, 3 * (size_t)nfv))
+        return SURTR_E_HIP;
+    // the pattern buffers of the context (what surtr_upload_pattern fills), with room for a slightly larger pattern
+    ctx->planes_ready = false;
+    const size_t capf = nf + nf / 8 + 16, capc = n + n / 8 + 16;
+    if (ctx->d_v012.grow(ctx, 9 * (size_t)nf, 9 * capf) || ctx->d_planes.grow(ctx, nf, capf) || ctx->d_plane_off.grow(ctx, (size_t)n + 1, capc + 1))
     {
-        free_dev(ctx->d_v012); free_dev(ctx->d_planes); free_dev(ctx->d_plane_off);
-        ctx->d_v012 = nullptr; ctx->d_planes = nullptr; ctx->d_plane_off = nullptr; ctx->cap_pattern_faces = 0; ctx->cap_pattern_cells = 0;
-        const uint32_t capf = nf + nf / 8 + 16, capc = n + n / 8 + 16;
-        HIPCHK(hipMalloc((void**)&ctx->d_v012, (size_t)capf * 36));
-        HIPCHK(hipMalloc((void**)&ctx->d_planes, (size_t)capf * 16));
-        HIPCHK(hipMalloc((void**)&ctx->d_plane_off, (size_t)(capc + 1) * 4));
-        ctx->cap_pattern_faces = capf; ctx->cap_pattern_cells = capc;
+        ctx->d_v012.reset(); ctx->d_planes.reset(); ctx->d_plane_off.reset();
+        return SURTR_E_HIP;
     }
     HIPCHK(hipMemcpyAsync(B.cfo, cfo.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(B.cvo, cvo.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));

@@ -491,7 +491,7 @@ extern "C" int surtr_pieces_mass_dev(surtr_ctx* ctx, int set, float density, voi
     if ((size_t)ctx->n_pieces * sizeof(surtr_mass) > capacity_bytes) return SURTR_E_CAPACITY;
     if (ctx->n_pieces == 0) return SURTR_OK;
     (void)hipSetDevice(ctx->device);
-    return ms_launch(ctx, ms_pieces_src(ctx, set), ctx->n_pieces, P.c_pos / 3u, P.c_nbr, density, dev_out, capacity_bytes);
+    return ms_launch(ctx, ms_pieces_src(ctx, set), ctx->n_pieces, P.pos.cap / 3u, P.nbr.cap, density, dev_out, capacity_bytes);
 }
 
 namespace {
@@ -499,12 +499,11 @@ template <class F>
 int ms_host(surtr_ctx* ctx, uint32_t n, surtr_mass* out, F dev_call)
 {
     if (!out || n == 0) return SURTR_OK;
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, (size_t)n * sizeof(surtr_mass)));
-    int rc = dev_call(d, (size_t)n * sizeof(surtr_mass));
+    DevBuf<surtr_mass> d;
+    int rc = d.grow(ctx, n);
+    if (rc == SURTR_OK) rc = dev_call(d.p, (size_t)n * sizeof(surtr_mass));
     if (rc == SURTR_OK && hipMemcpyAsync(out, d, (size_t)n * sizeof(surtr_mass), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = SURTR_E_HIP;
     if (rc == SURTR_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = SURTR_E_HIP;
-    (void)hipFree(d);
     return rc;
 }
 } // namespace

@@ -107,13 +107,11 @@ extern "C" int surtr_neighbors_from_mesh_dev(surtr_ctx* ctx, uint32_t nv, uint32
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     uint32_t cap = 16; while (cap < 6u * nt) cap <<= 1;      // load factor <= 1/2
-    int32_t *d_tris = nullptr, *d_third = nullptr, *d_nbr = nullptr; unsigned long long* d_keys = nullptr;
-    uint32_t *d_first = nullptr, *d_deg = nullptr, *d_off = nullptr, *d_err = nullptr; void* d_tmp = nullptr;
-    auto cleanup = [&]() { free_dev(d_tris); free_dev(d_third); free_dev(d_nbr); free_dev(d_keys); free_dev(d_first); free_dev(d_deg); free_dev(d_off); free_dev(d_err); free_dev(d_tmp); };
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ctx->err = hipGetErrorString(e_); cleanup(); return SURTR_E_HIP; } } while (0)
-    CK(hipMalloc((void**)&d_tris, (size_t)nt * 12)); CK(hipMalloc((void**)&d_third, (size_t)cap * 4)); CK(hipMalloc((void**)&d_keys, (size_t)cap * 8));
-    CK(hipMalloc((void**)&d_first, (size_t)nv * 4)); CK(hipMalloc((void**)&d_deg, ((size_t)nv + 1) * 4)); CK(hipMalloc((void**)&d_off, ((size_t)nv + 1) * 4));
-    CK(hipMalloc((void**)&d_nbr, (size_t)nt * 12 + 16)); CK(hipMalloc((void**)&d_err, 16));
+    DevBuf<int32_t> d_tris, d_third, d_nbr; DevBuf<unsigned long long> d_keys; DevBuf<uint32_t> d_first, d_deg, d_off, d_err; DevBuf<char> d_tmp;
+    if (d_tris.grow(ctx, (size_t)nt * 3) || d_third.grow(ctx, cap) || d_keys.grow(ctx, cap) || d_first.grow(ctx, nv) || d_deg.grow(ctx, (size_t)nv + 1) ||
+        d_off.grow(ctx, (size_t)nv + 1) || d_nbr.grow(ctx, (size_t)nt * 3 + 4) || d_err.grow(ctx, 4))
+        return SURTR_E_HIP;
+#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ctx->err = hipGetErrorString(e_); return SURTR_E_HIP; } } while (0)
     CK(hipMemcpyAsync(d_tris, tris, (size_t)nt * 12, hipMemcpyHostToDevice, st));
     CK(hipMemsetAsync(d_keys, 0xFF, (size_t)cap * 8, st)); CK(hipMemsetAsync(d_first, 0xFF, (size_t)nv * 4, st)); CK(hipMemsetAsync(d_err, 0, 4, st));
     CK(hipMemsetAsync(d_deg, 0, ((size_t)nv + 1) * 4, st));
@@ -124,9 +122,9 @@ extern "C" int surtr_neighbors_from_mesh_dev(surtr_ctx* ctx, uint32_t nv, uint32
     hipLaunchKernelGGL(k_fans, dim3((nv + 255) / 256), blk, 0, st, nv, nt, d_tris, d_keys, d_third, cap - 1u, d_first, d_deg, d_off, d_nbr, 0u, d_err);
     uint32_t err = 0;
     size_t tmp_bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_deg, d_off, (int)nv + 1, st);
-    CK(hipMalloc(&d_tmp, tmp_bytes + 16));
-    if (hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_deg, d_off, (int)nv + 1, st) != hipSuccess) { cleanup(); return SURTR_E_HIP; }
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_deg.p, d_off.p, (int)nv + 1, st);
+    if (d_tmp.grow(ctx, tmp_bytes + 16)) return SURTR_E_HIP;
+    if (hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_deg.p, d_off.p, (int)nv + 1, st) != hipSuccess) return SURTR_E_HIP;
     // sum of the ring lengths = 3 T on a closed manifold; anything else was an error (checked before the rings are written)
     uint32_t total = 0;
     CK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st)); CK(hipMemcpyAsync(&total, d_off + nv, 4, hipMemcpyDeviceToHost, st));
@@ -149,6 +147,5 @@ extern "C" int surtr_neighbors_from_mesh_dev(surtr_ctx* ctx, uint32_t nv, uint32
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }
 #undef CK
-    cleanup();
     return (int)err;
 }

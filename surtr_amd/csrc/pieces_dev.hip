@@ -305,32 +305,29 @@ __global__ __launch_bounds__(SURTR_WG) void k_pieces_from_frags(uint32_t n, From
 }
 
 // ------------------------------------------------------------------- host
+// The buffers of the pieces keep a little room, so that slightly larger pieces fit too; surtr_upload_stats counts their allocations.
 template <class T>
-int pool_reserve(surtr_ctx* ctx, T** p, size_t& cap, size_t need)
+int grow_pieces(surtr_ctx* ctx, DevBuf<T>& b, size_t need)
 {
-    if (*p && cap >= need) return SURTR_OK;
-    free_dev(*p); *p = nullptr; cap = 0;
-    const size_t want = std::max<size_t>(need + need / 4, 64);      // a little room, so that slightly larger pieces fit too
-    if (hipMalloc((void**)p, want * sizeof(T)) != hipSuccess) { ctx->err = "piece pool allocation failed"; return SURTR_E_HIP; }
-    cap = want; ++ctx->upload_allocs;
-    return SURTR_OK;
+    const size_t cap0 = b.cap;
+    const int rc = b.grow(ctx, need, std::max<size_t>(need + need / 4, 64));
+    if (rc == SURTR_OK && b.cap != cap0) ++ctx->upload_allocs;
+    return rc;
 }
 
 static inline uint32_t up_count(uint32_t m) { return (m + SURTR_SPH_FAN - 1u) / SURTR_SPH_FAN; }
 
 int reserve_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, uint32_t H, uint32_t NB)
 {
-    int rc = 0;
-#define R(ptr, cap, need) do { rc = pool_reserve(ctx, &S.ptr, S.cap, (size_t)(need)); if (rc) return rc; } while (0)
-    R(pos, c_pos, 3 * (size_t)V + 3); R(loff, c_loff, (size_t)V + 1); R(llen, c_llen, V); R(nbr, c_nbr, (size_t)H + 1); R(vo, c_vo, n + 1);
-    R(tri, c_tri, V); R(rad, c_rad, V); R(perm, c_perm, V); R(posr_s, c_posr_s, (size_t)V + 1);
-    R(bsph, c_bsph, NB + 1); R(bo, c_bo, n + 1); R(box, c_box, 6 * (size_t)n); R(key, c_key, V); R(key2, c_key2, V); R(val, c_val, V);
-    R(dup, c_dup, n + 1);
-    // (every piece has at least one sphere per level: NB / 8 + n and NB / 64 + n bound the coarser levels)
-    R(iperm, c_iperm, V); R(row_s, c_row_s, (size_t)V + 1);
-    R(bsph2, c_bsph2, (size_t)NB / SURTR_SPH_FAN + n + 1); R(bo2, c_bo2, n + 1);
-    R(bsph3, c_bsph3, (size_t)NB / (SURTR_SPH_FAN * SURTR_SPH_FAN) + n + 1); R(bo3, c_bo3, n + 1);
-#undef R
+    if (grow_pieces(ctx, S.pos, 3 * (size_t)V + 3) || grow_pieces(ctx, S.loff, (size_t)V + 1) || grow_pieces(ctx, S.llen, V) ||
+        grow_pieces(ctx, S.nbr, (size_t)H + 1) || grow_pieces(ctx, S.vo, n + 1) || grow_pieces(ctx, S.tri, V) || grow_pieces(ctx, S.rad, V) ||
+        grow_pieces(ctx, S.perm, V) || grow_pieces(ctx, S.posr_s, (size_t)V + 1) || grow_pieces(ctx, S.bsph, NB + 1) ||
+        grow_pieces(ctx, S.bo, n + 1) || grow_pieces(ctx, S.box, 6 * (size_t)n) || grow_pieces(ctx, S.key, V) || grow_pieces(ctx, S.key2, V) ||
+        grow_pieces(ctx, S.val, V) || grow_pieces(ctx, S.dup, n + 1) || grow_pieces(ctx, S.iperm, V) || grow_pieces(ctx, S.row_s, (size_t)V + 1) ||
+        // (every piece has at least one sphere per level: NB / 8 + n and NB / 64 + n bound the coarser levels)
+        grow_pieces(ctx, S.bsph2, (size_t)NB / SURTR_SPH_FAN + n + 1) || grow_pieces(ctx, S.bo2, n + 1) ||
+        grow_pieces(ctx, S.bsph3, (size_t)NB / (SURTR_SPH_FAN * SURTR_SPH_FAN) + n + 1) || grow_pieces(ctx, S.bo3, n + 1))
+        return SURTR_E_HIP;
     return SURTR_OK;
 }
 
@@ -350,10 +347,10 @@ int derive_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, const std::v
     int end_bit = 32;
     while (end_bit < 64 && (n >> (end_bit - 32)) != 0u) ++end_bit;
     size_t tmp_bytes = 0;
-    if (hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, S.key, S.key2, S.val, S.perm, (int)V, 0, end_bit, st) != hipSuccess) return SURTR_E_HIP;
-    int rc = pool_reserve(ctx, &ctx->sort_tmp, ctx->c_sort_tmp, tmp_bytes + 16);
+    if (hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, S.key.p, S.key2.p, S.val.p, S.perm.p, (int)V, 0, end_bit, st) != hipSuccess) return SURTR_E_HIP;
+    int rc = grow_pieces(ctx, ctx->sort_tmp, tmp_bytes + 16);
     if (rc) return rc;
-    if (hipcub::DeviceRadixSort::SortPairs(ctx->sort_tmp, tmp_bytes, S.key, S.key2, S.val, S.perm, (int)V, 0, end_bit, st) != hipSuccess) return SURTR_E_HIP;
+    if (hipcub::DeviceRadixSort::SortPairs(ctx->sort_tmp.p, tmp_bytes, S.key.p, S.key2.p, S.val.p, S.perm.p, (int)V, 0, end_bit, st) != hipSuccess) return SURTR_E_HIP;
     hipLaunchKernelGGL(k_piece_sorted, gridV, blk, 0, st, V, n, S.vo, S.pos, S.rad, S.perm, S.posr_s);
     if (NB) hipLaunchKernelGGL(k_piece_spheres, dim3((NB + 255) / 256), blk, 0, st, NB, n, S.vo, S.bo, S.posr_s, S.bsph);
     // two coarser sphere levels for the hierarchical cull of the pre-pass
@@ -398,12 +395,8 @@ void set_piece_stats(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const uint
 
 int finish_upload(surtr_ctx* ctx, uint32_t n, bool check)
 {
-    if (!ctx->d_outside || ctx->cap_outside < n)
-    {
-        free_dev(ctx->d_outside); ctx->d_outside = nullptr;
-        HIPCHK(hipMalloc((void**)&ctx->d_outside, std::max<uint32_t>(n + n / 4, 64)));
-        ctx->cap_outside = std::max<uint32_t>(n + n / 4, 64); ++ctx->upload_allocs;
-    }
+    const int rc = grow_pieces(ctx, ctx->d_outside, n);
+    if (rc) return rc;
     uint32_t err = 0;
     HIPCHK(hipMemcpyAsync(&err, ctx->d_upload_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -444,7 +437,7 @@ int surtr_upload_pieces(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const f
     }
     hipStream_t st = ctx->stream;
     HIPCHK(hipStreamSynchronize(st));       // an event may still be reading the pieces
-    if (!ctx->d_upload_err) { HIPCHK(hipMalloc((void**)&ctx->d_upload_err, 16)); ++ctx->upload_allocs; }
+    if (!ctx->d_upload_err) { if (ctx->d_upload_err.grow(ctx, 4)) return SURTR_E_HIP; ++ctx->upload_allocs; }
     HIPCHK(hipMemsetAsync(ctx->d_upload_err, 0, 4, st));
     for (int set = 0; set < 2; ++set)
     {
@@ -472,7 +465,7 @@ int surtr_transform_pieces(surtr_ctx* ctx, uint32_t n, const float* world)
     (void)hipSetDevice(ctx->device);
     Timer timer(ctx);
     hipStream_t st = ctx->stream;
-    int rc = pool_reserve(ctx, &ctx->d_world, ctx->c_world, (size_t)16 * n);
+    int rc = grow_pieces(ctx, ctx->d_world, (size_t)16 * n);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipMemcpyAsync(ctx->d_world, world, (size_t)64 * n, hipMemcpyHostToDevice, st));
@@ -522,7 +515,7 @@ int surtr_pieces_from_event(surtr_ctx* ctx, const uint8_t* keep, uint32_t* n_out
     const uint32_t n = (uint32_t)frag.size();
     if (n_out) *n_out = n;
     if (n == 0) return SURTR_E_INVALID;
-    if (!ctx->d_upload_err) { HIPCHK(hipMalloc((void**)&ctx->d_upload_err, 16)); ++ctx->upload_allocs; }
+    if (!ctx->d_upload_err) { if (ctx->d_upload_err.grow(ctx, 4)) return SURTR_E_HIP; ++ctx->upload_allocs; }
     HIPCHK(hipMemsetAsync(ctx->d_upload_err, 0, 4, st));
     std::vector<uint32_t> bo[2] = {sphere_offsets(n, vo[0].data()), sphere_offsets(n, vo[1].data())};
     for (int set = 0; set < 2; ++set)
@@ -530,7 +523,7 @@ int surtr_pieces_from_event(surtr_ctx* ctx, const uint8_t* keep, uint32_t* n_out
         rc = reserve_set(ctx, set ? ctx->cset : ctx->mset, n, vo[set][n], ho[set][n], bo[set][n]);
         if (rc) return rc;
     }
-    rc = pool_reserve(ctx, &ctx->d_from, ctx->c_from, (size_t)5 * (n + 1));
+    rc = grow_pieces(ctx, ctx->d_from, (size_t)5 * (n + 1));
     if (rc) return rc;
     uint32_t* d = ctx->d_from;
     FromEvent E{d, {d + (n + 1), d + 2 * (size_t)(n + 1)}, {d + 3 * (size_t)(n + 1), d + 4 * (size_t)(n + 1)}};
@@ -573,7 +566,7 @@ int surtr_place_cells_in_pieces(surtr_ctx* ctx, uint32_t n_groups, const uint32_
     if (!ctx->n_pieces || !ctx->d_v012) return SURTR_E_STATE;
     if (n_groups != ctx->n_pieces) return SURTR_E_INVALID;
     (void)hipSetDevice(ctx->device);
-    int rc = pool_reserve(ctx, &ctx->d_group_xf, ctx->c_group_xf, (size_t)6 * n_groups);
+    int rc = grow_pieces(ctx, ctx->d_group_xf, (size_t)6 * n_groups);
     if (rc) return rc;
     float* sc = ctx->d_group_xf; float* sh = sc + 3 * (size_t)n_groups;
     hipLaunchKernelGGL(k_group_boxes, dim3((n_groups + 255) / 256), dim3(256), 0, ctx->stream, n_groups, ctx->mset.box, sc, sh);
@@ -627,7 +620,7 @@ int surtr_handover_stats(surtr_ctx* ctx, uint32_t out[8])
     if (ctx->arena.cursors) HIPCHK(hipMemcpy(c, ctx->arena.cursors + 146, sizeof(c), hipMemcpyDeviceToHost));
     for (int k = 0; k < 6; ++k) out[k] = c[k];
     out[6] = ctx->max_wg;
-    out[7] = ctx->cap_hlist;
+    out[7] = (uint32_t)ctx->d_hlist.cap;
     return SURTR_OK;
 }
 

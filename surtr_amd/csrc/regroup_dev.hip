@@ -269,14 +269,6 @@ __global__ __launch_bounds__(RG_LABEL_THREADS) void k_rg_labels_all(uint32_t ne,
     if (tid == 0u) *rounds_out = round < n_pieces + 8u ? round + 1u : 0xFFFFFFFFu;
 }
 
-template <class T>
-struct Tmp
-{
-    T* p = nullptr;
-    bool alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 4) * sizeof(T)) == hipSuccess; }
-    ~Tmp() { if (p) (void)hipFree(p); }
-};
-
 } // namespace
 
 extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
@@ -309,9 +301,11 @@ extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_spher
         bind.back().insert((int)(n_outside + f));
     }
     if (n == 0) { *n_compounds = 1; compound_off[0] = compound_off[1] = 0; return SURTR_OK; }
-    Tmp<uint32_t> d_kind, d_index, d_cnt, d_foff, d_poff, d_set, d_val, d_order, d_lab, d_flag32; Tmp<uint8_t> d_out; Tmp<float> d_sph;
-    if (!d_kind.alloc(n) || !d_index.alloc(n) || !d_cnt.alloc(2 * (size_t)n) || !d_foff.alloc(n + 1) || !d_poff.alloc(n + 1) || !d_set.alloc(n) ||
-        !d_lab.alloc(n) || !d_flag32.alloc(4) || !d_out.alloc(n) || !d_sph.alloc(3 * (size_t)n_sphere + 3)) return SURTR_E_HIP;
+    // (the call's temporaries: at least 4 elements each)
+    auto alloc = [&](auto& b, size_t k) { return b.grow(ctx, std::max<size_t>(k, 4)) == SURTR_OK; };
+    DevBuf<uint32_t> d_kind, d_index, d_cnt, d_foff, d_poff, d_set, d_val, d_order, d_lab, d_flag32; DevBuf<uint8_t> d_out; DevBuf<float> d_sph;
+    if (!alloc(d_kind, n) || !alloc(d_index, n) || !alloc(d_cnt, 2 * (size_t)n) || !alloc(d_foff, n + 1) || !alloc(d_poff, n + 1) || !alloc(d_set, n) ||
+        !alloc(d_lab, n) || !alloc(d_flag32, 4) || !alloc(d_out, n) || !alloc(d_sph, 3 * (size_t)n_sphere + 3)) return SURTR_E_HIP;
     HIPCHK(hipMemcpyAsync(d_kind.p, kind.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_index.p, index.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_flag32.p, 0, 16, st));
@@ -328,9 +322,9 @@ extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_spher
     HIPCHK(hipStreamSynchronize(st));
     for (uint32_t p = 0; p < n; ++p) { foff[p + 1] = foff[p] + cnt[2 * p]; poff[p + 1] = poff[p] + cnt[2 * p + 1]; }
     const uint32_t nf = foff[n], npts = poff[n];
-    Tmp<FaceNode> d_nodes; Tmp<P3> d_pts; Tmp<unsigned long long> d_key, d_key2; Tmp<uint2> d_edges;
+    DevBuf<FaceNode> d_nodes; DevBuf<P3> d_pts; DevBuf<unsigned long long> d_key, d_key2; DevBuf<uint2> d_edges;
     const uint32_t cap_edges = 16u * nf + 1024u;
-    if (!d_nodes.alloc(nf) || !d_pts.alloc(npts) || !d_key.alloc(nf) || !d_key2.alloc(nf) || !d_val.alloc(nf) || !d_order.alloc(nf) || !d_edges.alloc(cap_edges))
+    if (!alloc(d_nodes, nf) || !alloc(d_pts, npts) || !alloc(d_key, nf) || !alloc(d_key2, nf) || !alloc(d_val, nf) || !alloc(d_order, nf) || !alloc(d_edges, cap_edges))
         return SURTR_E_HIP;
     HIPCHK(hipMemcpyAsync(d_foff.p, foff.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_poff.p, poff.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
@@ -362,8 +356,8 @@ extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_spher
         hipLaunchKernelGGL(k_rg_keys, grid, blk, 0, st, nf, d_nodes.p, d_set.p, d_key.p, d_val.p);
         size_t tmp_bytes = 0;
         (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_key.p, d_key2.p, d_val.p, d_order.p, (int)nf, 0, 64, st);
-        Tmp<char> d_tmp;
-        if (!d_tmp.alloc(tmp_bytes + 16)) return SURTR_E_HIP;
+        DevBuf<char> d_tmp;
+        if (!alloc(d_tmp, tmp_bytes + 16)) return SURTR_E_HIP;
         if (hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, d_key.p, d_key2.p, d_val.p, d_order.p, (int)nf, 0, 64, st) != hipSuccess) return SURTR_E_HIP;
         HIPCHK(hipStreamSynchronize(st));
         hipLaunchKernelGGL(k_rg_pairs, grid, blk, 0, st, nf, d_order.p, d_key2.p, d_nodes.p, d_pts.p, d_edges.p, cap_edges, d_err + 1);

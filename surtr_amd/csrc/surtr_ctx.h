@@ -165,41 +165,44 @@ struct FaceScratch
     int32_t* base; size_t per_wg; uint32_t HF;   // HF = max half-edges of one fragment
 };
 
+struct surtr_ctx;
+
+// Device memory owned by the context or by one call: grow-only, move-only, freed when destroyed.  grow() frees the old
+// block before it allocates the new one (the peak is the larger of the two, not their sum) and records the capacity only
+// once the allocation has succeeded: after a failure the buffer is empty and ctx->err says why.
+template <class T>
+struct DevBuf
+{
+    T* p = nullptr;
+    size_t cap = 0;      // elements of T
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~DevBuf() { reset(); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    operator T*() const { return p; }
+    // at least `need` elements; a smaller buffer is replaced by one of `alloc` (>= need; 0: need) elements
+    int grow(surtr_ctx* ctx, size_t need, size_t alloc = 0);
+};
+
 // One set of resident solids (all Mesh solids, or all Convex solids, of the pieces) in a grow-only pool.
 struct PieceSet
 {
-    float* pos = nullptr; uint32_t* loff = nullptr; uint32_t* llen = nullptr; int32_t* nbr = nullptr; uint32_t* vo = nullptr;
-    uint8_t* tri = nullptr; float* rad = nullptr;
-    uint32_t* perm = nullptr; float4* posr_s = nullptr; float4* bsph = nullptr; uint32_t* bo = nullptr;
-    float* box = nullptr; unsigned long long* key = nullptr; unsigned long long* key2 = nullptr; uint32_t* val = nullptr;    // Morton sort
-    uint8_t* dup = nullptr; size_t c_dup = 0;       // per piece: a ring lists a neighbour twice
+    DevBuf<float> pos; DevBuf<uint32_t> loff, llen; DevBuf<int32_t> nbr; DevBuf<uint32_t> vo; DevBuf<uint8_t> tri; DevBuf<float> rad;
+    DevBuf<uint32_t> perm; DevBuf<float4> posr_s, bsph; DevBuf<uint32_t> bo;
+    DevBuf<float> box; DevBuf<unsigned long long> key, key2; DevBuf<uint32_t> val;    // Morton sort
+    DevBuf<uint8_t> dup;       // per piece: a ring lists a neighbour twice
     // rings in sorted space + two coarser sphere levels (see Pieces)
-    uint32_t* iperm = nullptr; SRow* row_s = nullptr;
-    float4* bsph2 = nullptr; uint32_t* bo2 = nullptr; float4* bsph3 = nullptr; uint32_t* bo3 = nullptr;
-    size_t c_iperm = 0, c_row_s = 0, c_bsph2 = 0, c_bo2 = 0, c_bsph3 = 0, c_bo3 = 0;
-    size_t c_pos = 0, c_loff = 0, c_llen = 0, c_nbr = 0, c_vo = 0, c_tri = 0, c_rad = 0, c_perm = 0, c_posr_s = 0, c_bsph = 0,
-           c_bo = 0, c_box = 0, c_key = 0, c_key2 = 0, c_val = 0;
-    void release()
-    {
-        void* all[] = {pos, loff, llen, nbr, vo, tri, rad, perm, posr_s, bsph, bo, box, key, key2, val, dup, iperm, row_s, bsph2, bo2, bsph3, bo3};
-        for (void* p : all) if (p) (void)hipFree(p);
-        *this = PieceSet();
-    }
+    DevBuf<uint32_t> iperm; DevBuf<SRow> row_s;
+    DevBuf<float4> bsph2; DevBuf<uint32_t> bo2; DevBuf<float4> bsph3; DevBuf<uint32_t> bo3;
 };
 
 // Device buffers of surtr_build_cells (cells_dev.hip): seeds, per-cell slots, and the compact cell arrays.
 struct CellBuffers
 {
-    double* seeds = nullptr; uint32_t* goff = nullptr; char* slots = nullptr; uint32_t* cfo = nullptr; uint32_t* cvo = nullptr;
-    int32_t* gen = nullptr; uint32_t* fvo = nullptr; double* verts = nullptr; uint32_t* heads = nullptr;
-    size_t c_heads = 0, c_seeds = 0, c_goff = 0, c_slots = 0, c_cfo = 0, c_cvo = 0, c_gen = 0, c_fvo = 0, c_verts = 0;
+    DevBuf<double> seeds; DevBuf<uint32_t> goff; DevBuf<char> slots; DevBuf<uint32_t> cfo, cvo;
+    DevBuf<int32_t> gen; DevBuf<uint32_t> fvo; DevBuf<double> verts; DevBuf<uint32_t> heads;
     uint32_t n = 0, nf = 0, nfv = 0;
-    void release()
-    {
-        void* all[] = {seeds, goff, slots, cfo, cvo, gen, fvo, verts, heads};
-        for (void* p : all) if (p) (void)hipFree(p);
-        *this = CellBuffers();
-    }
 };
 
 // Half-size LDS topology of k_clip_pairs_half (capacities; the kernel is in surtr_hip.hip).
@@ -216,23 +219,21 @@ static inline bool surtr_fits_half(uint32_t n, uint32_t h) { return fits_half(n,
 struct surtr_ctx
 {
     int device = 0;
-    uint32_t n_wg_faces_alloc = 0;
     bool frags_of_pieces = false;      // the current fragments are an event's over the resident pieces (k_refit may look at the piece a Convex came from)
     // what the CUs can hold (surtr_create); max_wg* below are those, cut down to what the scratch of the current pieces leaves room for
     uint32_t hw_wg = 512, hw_wg_faces = 1024, hw_wg_prep = 1792, hw_wg_big = 48, budget_vmax = 0xFFFFFFFFu, budget_hmax = 0xFFFFFFFFu;
     uint32_t max_wg = 512, max_wg_faces = 1024, max_wg_small = 2048, max_wg_prep = 1792, max_wg_half = 1024;
-    uint32_t* d_hlist = nullptr; uint32_t cap_hlist = 0;    // hand-over list of the split arrangement (k_clip_pairs_main -> k_clip_pairs_catch)
-    uint32_t n_wg_catch = 128;                              // workgroups of k_clip_pairs_catch (at most; scratch slots are reserved for them)
+    DevBuf<uint32_t> d_hlist;                               // hand-over list of the split arrangement (k_clip_pairs_main -> k_clip_pairs_catch)
     uint32_t vmin = 0;                                      // smallest Mesh of the resident pieces
-    ScratchPool pool_half{}; uint32_t n_wg_half = 0;       // k_clip_pairs_half: scratch for the half-size LDS topology only
+    ScratchPool pool_half{}; uint32_t n_wg_half = 0; DevBuf<char> pool_half_buf;     // k_clip_pairs_half: scratch for the half-size LDS topology only
     // Light pairs go to k_clip_pairs_half only when they are most of the event (small pieces: refracture).  Beside a
     // full k_clip_pairs a third kernel costs more than it gains (configs[3]: +0.2 ms even when its workgroups exit at
     // once), and what a large piece leaves of itself in a cell is seldom small enough.  Decided per upload from the piece sizes.
     bool half_on = false;
-    PrepPool prep{nullptr, 0, 0}; uint32_t n_wg_prep = 0;
-    ImgArena img{nullptr, 0};
-    uint32_t* d_order = nullptr; uint32_t cap_order = 0;
-    uint32_t* d_forder = nullptr;    // fragments by size class, 16 x cap_frags
+    PrepPool prep{nullptr, 0, 0}; uint32_t n_wg_prep = 0; DevBuf<char> prep_buf;
+    ImgArena img{nullptr, 0}; DevBuf<char> img_buf;
+    DevBuf<uint32_t> d_order;        // 64 x the pairs it has room for: class tables of 16 each (clip order, pre-pass order, half clip order, spare)
+    DevBuf<uint32_t> d_forder;       // fragments by size class, 16 x cap_frags
     bool wave_big = false;           // the large bands through k_clip_pairs_wave_big (one workgroup per CU) instead of k_clip_pairs_big
     uint32_t n_wg_big = 48;          // workgroups of k_clip_pairs_big
     hipStream_t stream2 = nullptr;   // k_clip_pairs runs here, beside k_clip_pairs_big on the caller's stream
@@ -245,45 +246,49 @@ struct surtr_ctx
     uint32_t n_pieces = 0, vmax = 0, hmax = 0, cvmax = 0, chmax = 0;
     CellBuffers cells;               // surtr_build_cells
     PieceSet mset, cset;             // the resident pieces: Mesh and Convex solids + what the pre-pass derives from them (pieces_dev.hip)
-    uint32_t* d_upload_err = nullptr; uint32_t cap_outside = 0;
-    float* d_group_xf = nullptr; size_t c_group_xf = 0;  // surtr_place_cells_in_pieces: per-group scale / shift
-    float* d_world = nullptr; size_t c_world = 0;        // surtr_transform_pieces: the world matrices
-    char* sort_tmp = nullptr; size_t c_sort_tmp = 0;      // radix-sort scratch of the Morton sort
-    uint32_t* d_from = nullptr; size_t c_from = 0;       // surtr_pieces_from_event: fragment list and offsets
+    DevBuf<uint32_t> d_upload_err;
+    DevBuf<float> d_group_xf;        // surtr_place_cells_in_pieces: per-group scale / shift
+    DevBuf<float> d_world;           // surtr_transform_pieces: the world matrices
+    DevBuf<char> sort_tmp;           // radix-sort scratch of the Morton sort
+    DevBuf<uint32_t> d_from;         // surtr_pieces_from_event: fragment list and offsets
     float upload_ms = 0.f; uint32_t upload_allocs = 0;   // surtr_upload_stats
     uint32_t regroup_rounds = 0;                         // label rounds of the last surtr_event_regroup (one launch)
     uint64_t tot_mv = 0, tot_mh = 0;
     // cells
-    uint32_t n_cells = 0, n_faces = 0, cap_pattern_faces = 0, cap_pattern_cells = 0;      // (capacities: set by surtr_build_cells only)
-    uint32_t* d_pair_order = nullptr; uint32_t pair_order_begin = 0, pair_order_count = 0, cap_pair_order = 0;   // k_clip_convex: pairs by plane count
+    uint32_t n_cells = 0, n_faces = 0;
+    DevBuf<uint32_t> d_pair_order; uint32_t pair_order_begin = 0, pair_order_count = 0;   // k_clip_convex: pairs by plane count
     bool pair_order_is_list = false;
-    float* d_v012 = nullptr; float4* d_planes = nullptr; uint32_t* d_plane_off = nullptr;
+    DevBuf<float> d_v012; DevBuf<float4> d_planes; DevBuf<uint32_t> d_plane_off;
     std::vector<uint32_t> h_plane_off;
     bool planes_ready = false;
     // scratch + arena
     uint32_t user_cv = 0, user_ch = 0;
     uint64_t user_av = 0, user_ah = 0, user_ai = 0;
-    ScratchPool pool{}; uint32_t n_wg = 0;
-    ScratchPool pool_small{}; uint32_t n_wg_small = 0;      // one-wave kernels (Convex clip, refit)
-    FaceScratch fs{}; uint2* d_blk = nullptr; uint32_t blk_per_wg = 0;
+    // (the kernels' views -- pool, fs, arena, ... -- and the sizes beside them describe what their buffers hold: ensure_scratch and
+    //  ensure_arena set them once every buffer of the group exists, and clear them when they free the group)
+    ScratchPool pool{}; uint32_t n_wg = 0; DevBuf<char> pool_buf;
+    ScratchPool pool_small{}; uint32_t n_wg_small = 0; DevBuf<char> pool_small_buf;      // one-wave kernels (Convex clip, refit)
+    FaceScratch fs{}; DevBuf<int32_t> fs_buf; DevBuf<uint2> d_blk; uint32_t blk_per_wg = 0, n_wg_faces_alloc = 0;
     // second tier of k_faces scratch (pieces of more than SURTR_FACES_TIER half-edges): a few workgroups with room for a fragment
     // as large as the largest piece; the first launch hands them the fragments that do not fit its own (d_face_list)
-    FaceScratch fs_big{}; uint2* d_blk_big = nullptr; uint32_t blk_per_wg_big = 0, n_wg_faces_big = 0; uint32_t* d_face_list = nullptr;
+    FaceScratch fs_big{}; DevBuf<int32_t> fs_big_buf; DevBuf<uint2> d_blk_big; uint32_t blk_per_wg_big = 0, n_wg_faces_big = 0;
+    DevBuf<uint32_t> d_face_list;
     Arena arena{};
-    PairRec* d_pairs = nullptr; uint32_t cap_pairs = 0;
-    FragRec* d_frags = nullptr; uint32_t cap_frags = 0;
-    uint32_t* d_frag_status = nullptr;      // per fragment: SURTR_OK or why it has no triangles (u32[cap_frags])
-    uint2* d_scanblk = nullptr; uint32_t cap_scanblk = 0;
-    surtr_counts* d_counts = nullptr;
-    uint32_t* d_face_group = nullptr; uint32_t cap_face_group = 0;      // surtr_place_cells_groups: group of every pattern face
-    uint8_t* d_outside = nullptr;
+    struct { DevBuf<float> pos; DevBuf<uint32_t> loff, llen, idx, cursors; DevBuf<int32_t> nbr; DevBuf<uint2> isl; } arena_buf;
+    DevBuf<PairRec> d_pairs;
+    DevBuf<FragRec> d_frags; uint32_t cap_frags = 0;
+    DevBuf<uint32_t> d_frag_status;      // per fragment: SURTR_OK or why it has no triangles (u32[cap_frags])
+    DevBuf<uint2> d_scanblk;
+    DevBuf<surtr_counts> d_counts;
+    DevBuf<uint32_t> d_face_group;       // surtr_place_cells_groups: group of every pattern face
+    DevBuf<uint8_t> d_outside;
     std::vector<uint8_t> last_outside;       // the `outside` mask of the last event (empty: none), for surtr_event_regroup
-    uint2* d_pair_list = nullptr; uint32_t cap_pair_list = 0;
+    DevBuf<uint2> d_pair_list;
     float color[3] = {0.25f, 0.25f, 0.25f};      // VertexNormalColor::Color written by k_pack (Inc/Poly.h:68 default)
     surtr_counts last{}; bool last_current = false;     // `last` holds the counts of the event in the arena
     bool have_event = false; uint32_t last_flags = 0;
     // staging for downloads
-    void* d_blob = nullptr; size_t blob_cap = 0;
+    DevBuf<char> d_blob;
     // per-kernel timing with HIP events on the work stream (surtr_set_profiling)
     bool profiling = false;
     // history of the Mesh clip kernel (slot 0: k_clip_pairs, slot 11: k_clip_pairs_wave) over the last events, read without a
@@ -307,7 +312,23 @@ struct surtr_ctx
         if (e_ != hipSuccess) { ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); return SURTR_E_HIP; } \
     } while (0)
 
-static inline void free_dev(void* p) { if (p) (void)hipFree(p); }
+template <class T>
+int DevBuf<T>::grow(surtr_ctx* ctx, size_t need, size_t alloc)
+{
+    if (p && cap >= need) return SURTR_OK;
+    reset();
+    const size_t n = std::max(need, alloc);
+    const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
+    if (e != hipSuccess)
+    {
+        p = nullptr;
+        (void)hipGetLastError();      // (the runtime keeps the failure as its last error: a later launch check is not to report it again)
+        ctx->err = "device allocation of " + std::to_string(n * sizeof(T)) + " bytes: " + hipGetErrorString(e);
+        return SURTR_E_HIP;
+    }
+    cap = n;
+    return SURTR_OK;
+}
 
 // placement of cell groups with per-group scale / shift already in device memory (surtr_hip.hip)
 extern "C" int surtr_place_cells_groups_dev(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* group_cell_off, const float* d_scale3, const float* d_shift3);

@@ -1451,6 +1451,7 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(2, 4))
 #ifndef SURTR_CATCH_POLL
 #define SURTR_CATCH_POLL 8u       // workgroups of k_clip_pairs_catch that wait for hand-overs
 #endif
+#define SURTR_CATCH_WG_MAX 32u        // workgroups of k_clip_pairs_catch at most (its grid, and the scratch slots reserved for it)
 #ifndef SURTR_WR_MAIN
 #define SURTR_WR_MAIN 3072u       // (a plane that needs more stages its originals in global memory: the lists get the room instead)
 #define SURTR_WNL_MAIN 3584u
@@ -3129,14 +3130,14 @@ int surtr_create(int device, surtr_ctx** out)
         ctx->hw_wg = ctx->max_wg; ctx->hw_wg_faces = ctx->max_wg_faces; ctx->hw_wg_prep = ctx->max_wg_prep; ctx->hw_wg_big = ctx->n_wg_big;
     }
     // (surtr_destroy releases whatever was created so far: no leak on a failure half-way)
-    if (hipMalloc((void**)&ctx->d_counts, sizeof(surtr_counts)) != hipSuccess ||
-        hipMalloc((void**)&ctx->arena.cursors, 1024) != hipSuccess ||
+    if (ctx->d_counts.grow(ctx, 1) != SURTR_OK || ctx->arena_buf.cursors.grow(ctx, 256) != SURTR_OK ||
         hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_half, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_cvx, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_big, hipEventDisableTiming) != hipSuccess) { surtr_destroy(ctx); return SURTR_E_HIP; }
+    ctx->arena.cursors = ctx->arena_buf.cursors;
     // (tests / fuzzers: the arrangement of several busy contexts without the call)
     if (const char* e = getenv("SURTR_EVENTS_IN_FLIGHT")) { const int v = atoi(e); if (v > 0) ctx->events_in_flight = (uint32_t)v; }
     *out = ctx;
@@ -3148,13 +3149,6 @@ void surtr_destroy(surtr_ctx* ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    ctx->mset.release(); ctx->cset.release(); ctx->cells.release();
-    free_dev(ctx->d_upload_err); free_dev(ctx->d_group_xf); free_dev(ctx->d_world); free_dev(ctx->sort_tmp); free_dev(ctx->d_from);
-    free_dev(ctx->d_v012); free_dev(ctx->d_planes); free_dev(ctx->d_plane_off);
-    free_dev(ctx->pool.base); free_dev(ctx->pool_small.base); free_dev(ctx->pool_half.base); free_dev(ctx->fs.base); free_dev(ctx->d_blk);
-    free_dev(ctx->fs_big.base); free_dev(ctx->d_blk_big); free_dev(ctx->d_face_list);
-    free_dev(ctx->d_pair_order); free_dev(ctx->d_face_group);
-    free_dev(ctx->prep.base); free_dev(ctx->img.base); free_dev(ctx->d_order); free_dev(ctx->d_forder); free_dev(ctx->d_hlist);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
     if (ctx->ev_half) (void)hipEventDestroy(ctx->ev_half);
@@ -3163,11 +3157,7 @@ void surtr_destroy(surtr_ctx* ctx)
     if (ctx->ev_big) (void)hipEventDestroy(ctx->ev_big);
     for (int i = 0; i < 32; ++i) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
     for (int i = 0; i < 16; ++i) for (int q = 0; q < 2; ++q) if (ctx->hev[i][q]) (void)hipEventDestroy(ctx->hev[i][q]);
-    free_dev(ctx->arena.pos); free_dev(ctx->arena.loff); free_dev(ctx->arena.llen); free_dev(ctx->arena.nbr);
-    free_dev(ctx->arena.idx); free_dev(ctx->arena.isl); free_dev(ctx->arena.cursors);
-    free_dev(ctx->d_pairs); free_dev(ctx->d_frags); free_dev(ctx->d_frag_status); free_dev(ctx->d_scanblk); free_dev(ctx->d_counts);
-    free_dev(ctx->d_outside); free_dev(ctx->d_blob); free_dev(ctx->d_pair_list);
-    delete ctx;
+    delete ctx;      // (its buffers free themselves)
 }
 
 const char* surtr_last_error(surtr_ctx* ctx) { return ctx ? ctx->err.c_str() : ""; }
@@ -3186,11 +3176,14 @@ int surtr_get_stream(surtr_ctx* ctx, void** s)
     return SURTR_OK;
 }
 
+static void free_scratch(surtr_ctx* ctx);
+static void free_arena(surtr_ctx* ctx);
+
 int surtr_set_scratch(surtr_ctx* ctx, uint32_t mv, uint32_t mh)
 {
     if (!ctx) return SURTR_E_INVALID;
     ctx->user_cv = mv; ctx->user_ch = mh;
-    free_dev(ctx->pool.base); ctx->pool.base = nullptr;
+    free_scratch(ctx);
     return SURTR_OK;
 }
 
@@ -3198,7 +3191,7 @@ int surtr_set_arena(surtr_ctx* ctx, uint64_t v, uint64_t h, uint64_t i)
 {
     if (!ctx) return SURTR_E_INVALID;
     ctx->user_av = v; ctx->user_ah = h; ctx->user_ai = i;
-    free_dev(ctx->arena.pos); ctx->arena.pos = nullptr;
+    free_arena(ctx);
     return SURTR_OK;
 }
 
@@ -3229,11 +3222,12 @@ int surtr_upload_pattern(surtr_ctx* ctx, uint32_t n_cells, const uint32_t* face_
     const uint32_t nf = face_off[n_cells];
     for (uint32_t c = 0; c < n_cells; ++c)
         if (face_off[c + 1] < face_off[c] || face_off[c + 1] - face_off[c] > SURTR_MAXF) return SURTR_E_INVALID;
-    free_dev(ctx->d_v012); free_dev(ctx->d_planes); free_dev(ctx->d_plane_off);
-    ctx->d_v012 = nullptr; ctx->d_planes = nullptr; ctx->d_plane_off = nullptr; ctx->cap_pattern_faces = 0; ctx->cap_pattern_cells = 0;
-    HIPCHK(hipMalloc((void**)&ctx->d_v012, std::max<size_t>(16, (size_t)nf * 36)));
-    HIPCHK(hipMalloc((void**)&ctx->d_planes, std::max<size_t>(16, (size_t)nf * 16)));
-    HIPCHK(hipMalloc((void**)&ctx->d_plane_off, (size_t)(n_cells + 1) * 4));
+    ctx->planes_ready = false;
+    ctx->d_v012.reset(); ctx->d_planes.reset(); ctx->d_plane_off.reset();
+    int rc = ctx->d_v012.grow(ctx, std::max<size_t>(4, (size_t)nf * 9));
+    if (rc == SURTR_OK) rc = ctx->d_planes.grow(ctx, std::max(nf, 1u));
+    if (rc == SURTR_OK) rc = ctx->d_plane_off.grow(ctx, (size_t)n_cells + 1);
+    if (rc) { ctx->d_v012.reset(); ctx->d_planes.reset(); return rc; }
     HIPCHK(hipMemcpy(ctx->d_v012, v012, (size_t)nf * 36, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ctx->d_plane_off, face_off, (size_t)(n_cells + 1) * 4, hipMemcpyHostToDevice));
     ctx->h_plane_off.assign(face_off, face_off + n_cells + 1);
@@ -3262,10 +3256,11 @@ int surtr_upload_planes(surtr_ctx* ctx, uint32_t n_cells, const uint32_t* plane_
     const uint32_t nf = plane_off[n_cells];
     for (uint32_t c = 0; c < n_cells; ++c)
         if (plane_off[c + 1] < plane_off[c] || plane_off[c + 1] - plane_off[c] > SURTR_MAXF) return SURTR_E_INVALID;
-    free_dev(ctx->d_v012); free_dev(ctx->d_planes); free_dev(ctx->d_plane_off);
-    ctx->d_v012 = nullptr; ctx->d_planes = nullptr; ctx->d_plane_off = nullptr; ctx->cap_pattern_faces = 0; ctx->cap_pattern_cells = 0;
-    HIPCHK(hipMalloc((void**)&ctx->d_planes, std::max<size_t>(16, (size_t)nf * 16)));
-    HIPCHK(hipMalloc((void**)&ctx->d_plane_off, (size_t)(n_cells + 1) * 4));
+    ctx->planes_ready = false;
+    ctx->d_v012.reset(); ctx->d_planes.reset(); ctx->d_plane_off.reset();
+    int rc = ctx->d_planes.grow(ctx, std::max(nf, 1u));
+    if (rc == SURTR_OK) rc = ctx->d_plane_off.grow(ctx, (size_t)n_cells + 1);
+    if (rc) { ctx->d_planes.reset(); return rc; }
     HIPCHK(hipMemcpy(ctx->d_planes, planes, (size_t)nf * 16, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ctx->d_plane_off, plane_off, (size_t)(n_cells + 1) * 4, hipMemcpyHostToDevice));
     ctx->h_plane_off.assign(plane_off, plane_off + n_cells + 1);
@@ -3311,6 +3306,26 @@ static void budget_workgroups(surtr_ctx* ctx)
     ctx->max_wg_prep = fit(total_b / 16, prep_bytes_per_wg(std::max(ctx->vmax, 64u)), 16u, ctx->hw_wg_prep);
 }
 
+// (Re)allocates a scratch pool of n_wg workgroups; its view and workgroup count are set once the memory exists.
+static int alloc_pool(surtr_ctx* ctx, DevBuf<char>& buf, ScratchPool& view, uint32_t& view_wg, uint32_t CV, uint32_t CH, uint32_t VMAX, uint32_t n_wg)
+{
+    view = ScratchPool{}; view_wg = 0;
+    buf.reset();
+    const ScratchPool P{nullptr, scratch_bytes_per_wg(CV, CH, VMAX), CV, CH, VMAX};
+    const int rc = buf.grow(ctx, P.per_wg * n_wg);
+    if (rc) return rc;
+    view = P; view.base = buf; view_wg = n_wg;
+    return SURTR_OK;
+}
+
+// The Mesh clip's scratch and both tiers of k_faces' are one group: it exists as a whole or not at all.
+static void free_scratch(surtr_ctx* ctx)
+{
+    ctx->pool_buf.reset(); ctx->fs_buf.reset(); ctx->d_blk.reset(); ctx->fs_big_buf.reset(); ctx->d_blk_big.reset();
+    ctx->pool = ScratchPool{}; ctx->fs = FaceScratch{}; ctx->fs_big = FaceScratch{};
+    ctx->n_wg = ctx->n_wg_faces_alloc = ctx->n_wg_faces_big = ctx->blk_per_wg = ctx->blk_per_wg_big = 0;
+}
+
 static int ensure_scratch(surtr_ctx* ctx, uint32_t need_v, uint32_t need_h, uint32_t n_wg)
 {
     uint32_t n_wg_faces = std::max(1u, ctx->max_wg_faces);
@@ -3322,36 +3337,35 @@ static int ensure_scratch(surtr_ctx* ctx, uint32_t need_v, uint32_t need_h, uint
     if (CV < 64) CV = 64;
     const uint32_t VMAX = need_v;
     if (ctx->pool.base && ctx->pool.CV >= CV && ctx->pool.CH >= CH && ctx->pool.VMAX >= VMAX && ctx->n_wg >= n_wg && ctx->n_wg_faces_alloc >= n_wg_faces) return SURTR_OK;
-    ctx->n_wg_faces_alloc = n_wg_faces;
-    free_dev(ctx->pool.base); free_dev(ctx->fs.base); free_dev(ctx->d_blk);
-    ctx->pool.base = nullptr; ctx->fs.base = nullptr; ctx->d_blk = nullptr;
-    ctx->pool.CV = CV; ctx->pool.CH = CH; ctx->pool.VMAX = VMAX;
-    ctx->pool.per_wg = scratch_bytes_per_wg(CV, CH, VMAX);
-    ctx->n_wg = n_wg;
-    HIPCHK(hipMalloc((void**)&ctx->pool.base, ctx->pool.per_wg * n_wg));
+    free_scratch(ctx);
+    int rc = alloc_pool(ctx, ctx->pool_buf, ctx->pool, ctx->n_wg, CV, CH, VMAX, n_wg);
     const uint32_t HF_full = need_h + need_h / 2 + 8192;
     uint32_t tier = SURTR_FACES_TIER_DEFAULT;
     // (several contexts on the GPU, surtr_set_events_in_flight: every one of them holds this scratch -- 22 GB at configs[3] with the
     //  full tier, sized for a fragment as large as the piece; a quarter of it, and the second tier takes the fragments beyond)
     if (ctx->events_in_flight > 1u) tier /= 4u;
     if (const char* e = getenv("SURTR_FACES_TIER_HE")) { const long v = atol(e); if (v >= 64) tier = (uint32_t)v; }
-    ctx->fs.HF = std::min(HF_full, tier);
-    ctx->fs.per_wg = (size_t)12 * ctx->fs.HF;
-    HIPCHK(hipMalloc((void**)&ctx->fs.base, ctx->fs.per_wg * 4 * n_wg_faces));
-    ctx->blk_per_wg = ctx->fs.HF / SURTR_LANES + 4;
-    HIPCHK(hipMalloc((void**)&ctx->d_blk, (size_t)ctx->blk_per_wg * 8 * n_wg_faces));
-    free_dev(ctx->fs_big.base); free_dev(ctx->d_blk_big); ctx->fs_big.base = nullptr; ctx->d_blk_big = nullptr; ctx->n_wg_faces_big = 0;
-    if (HF_full > ctx->fs.HF)
+    FaceScratch fs{nullptr, 0, std::min(HF_full, tier)};
+    fs.per_wg = (size_t)12 * fs.HF;
+    const uint32_t blk_per_wg = fs.HF / SURTR_LANES + 4;
+    if (rc == SURTR_OK) rc = ctx->fs_buf.grow(ctx, fs.per_wg * n_wg_faces);
+    if (rc == SURTR_OK) rc = ctx->d_blk.grow(ctx, (size_t)blk_per_wg * n_wg_faces);
+    FaceScratch fs_big{}; uint32_t n_wg_big = 0, blk_per_wg_big = 0;
+    if (rc == SURTR_OK && HF_full > fs.HF)
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) total_b = (size_t)64 << 30;
         if (const char* e = getenv("SURTR_MEM_BUDGET_MB")) { const long v = atol(e); if (v > 0) total_b = (size_t)v << 20; }
-        ctx->fs_big.HF = HF_full; ctx->fs_big.per_wg = (size_t)12 * HF_full;
-        ctx->n_wg_faces_big = (uint32_t)std::min<size_t>(64, std::max<size_t>(2, (total_b / 16) / (ctx->fs_big.per_wg * 4)));
-        HIPCHK(hipMalloc((void**)&ctx->fs_big.base, ctx->fs_big.per_wg * 4 * ctx->n_wg_faces_big));
-        ctx->blk_per_wg_big = HF_full / SURTR_LANES + 4;
-        HIPCHK(hipMalloc((void**)&ctx->d_blk_big, (size_t)ctx->blk_per_wg_big * 8 * ctx->n_wg_faces_big));
+        fs_big.HF = HF_full; fs_big.per_wg = (size_t)12 * HF_full;
+        n_wg_big = (uint32_t)std::min<size_t>(64, std::max<size_t>(2, (total_b / 16) / (fs_big.per_wg * 4)));
+        blk_per_wg_big = HF_full / SURTR_LANES + 4;
+        rc = ctx->fs_big_buf.grow(ctx, fs_big.per_wg * n_wg_big);
+        if (rc == SURTR_OK) rc = ctx->d_blk_big.grow(ctx, (size_t)blk_per_wg_big * n_wg_big);
     }
+    if (rc) { free_scratch(ctx); return rc; }
+    fs.base = ctx->fs_buf; fs_big.base = ctx->fs_big_buf;
+    ctx->fs = fs; ctx->blk_per_wg = blk_per_wg; ctx->n_wg_faces_alloc = n_wg_faces;
+    ctx->fs_big = fs_big; ctx->blk_per_wg_big = blk_per_wg_big; ctx->n_wg_faces_big = n_wg_big;
     return SURTR_OK;
 }
 
@@ -3361,25 +3375,14 @@ static int ensure_scratch_small(surtr_ctx* ctx, uint32_t n_wg)
     const uint32_t need_v = 2 * ctx->cvmax + 4 * SURTR_MAXF + 256, need_h = 2 * ctx->chmax + 12 * SURTR_MAXF + 1024;
     const uint32_t CV = 2 * need_v + 1024, CH = 3 * need_h + 4096, VMAX = need_v;
     if (ctx->pool_small.base && ctx->pool_small.CV >= CV && ctx->pool_small.CH >= CH && ctx->n_wg_small >= n_wg) return SURTR_OK;
-    free_dev(ctx->pool_small.base); ctx->pool_small.base = nullptr;
-    ctx->pool_small.CV = CV; ctx->pool_small.CH = CH; ctx->pool_small.VMAX = VMAX;
-    ctx->pool_small.per_wg = scratch_bytes_per_wg(CV, CH, VMAX);
-    ctx->n_wg_small = n_wg;
-    HIPCHK(hipMalloc((void**)&ctx->pool_small.base, ctx->pool_small.per_wg * n_wg));
-    return SURTR_OK;
+    return alloc_pool(ctx, ctx->pool_small_buf, ctx->pool_small, ctx->n_wg_small, CV, CH, VMAX, n_wg);
 }
 
 static int ensure_scratch_half(surtr_ctx* ctx, uint32_t n_wg)
 {
     // k_clip_pairs_half never leaves its LDS topology: positions, work lists and squeeze staging for SURTR_LVS / SURTR_LHS
-    const uint32_t CV = SURTR_LVS + 256u, CH = SURTR_LHS + 256u, VMAX = SURTR_LVS + 64u;
     if (ctx->pool_half.base && ctx->n_wg_half >= n_wg) return SURTR_OK;
-    free_dev(ctx->pool_half.base); ctx->pool_half.base = nullptr;
-    ctx->pool_half.CV = CV; ctx->pool_half.CH = CH; ctx->pool_half.VMAX = VMAX;
-    ctx->pool_half.per_wg = scratch_bytes_per_wg(CV, CH, VMAX);
-    ctx->n_wg_half = n_wg;
-    HIPCHK(hipMalloc((void**)&ctx->pool_half.base, ctx->pool_half.per_wg * n_wg));
-    return SURTR_OK;
+    return alloc_pool(ctx, ctx->pool_half_buf, ctx->pool_half, ctx->n_wg_half, SURTR_LVS + 256u, SURTR_LHS + 256u, SURTR_LVS + 64u, n_wg);
 }
 
 // Scratch of k_prep_pairs and the arena its images go to.  An image is at most the LDS topology plus masks; when the
@@ -3389,16 +3392,15 @@ static int ensure_prep(surtr_ctx* ctx, uint32_t n_pairs, uint32_t n_wg)
     const uint32_t VMAX = std::max(ctx->vmax, 64u);
     if (!(ctx->prep.base && ctx->prep.VMAX >= VMAX && ctx->n_wg_prep >= n_wg))
     {
-        free_dev(ctx->prep.base); ctx->prep.base = nullptr;
-        ctx->prep.VMAX = VMAX; ctx->prep.per_wg = prep_bytes_per_wg(VMAX); ctx->n_wg_prep = n_wg;
-        HIPCHK(hipMalloc((void**)&ctx->prep.base, ctx->prep.per_wg * n_wg));
+        ctx->prep = PrepPool{nullptr, 0, 0}; ctx->n_wg_prep = 0;
+        ctx->prep_buf.reset();
+        const size_t per_wg = prep_bytes_per_wg(VMAX);
+        const int rc = ctx->prep_buf.grow(ctx, per_wg * n_wg);
+        if (rc) return rc;
+        ctx->prep = PrepPool{ctx->prep_buf, per_wg, VMAX}; ctx->n_wg_prep = n_wg;
     }
-    if (ctx->cap_order < n_pairs)
-    {
-        free_dev(ctx->d_order); ctx->d_order = nullptr;
-        HIPCHK(hipMalloc((void**)&ctx->d_order, (size_t)n_pairs * 64 * 4));      // tables of 16 classes: clip order, pre-pass order, half clip order (+ one spare)
-        ctx->cap_order = n_pairs;
-    }
+    int rc = ctx->d_order.grow(ctx, (size_t)n_pairs * 64);      // tables of 16 classes: clip order, pre-pass order, half clip order (+ one spare)
+    if (rc) return rc;
     const uint64_t full = (uint64_t)ctx->vmax * 16 + (uint64_t)ctx->hmax * 2;
     const uint64_t lds = (uint64_t)SURTR_LV * 16 + (uint64_t)SURTR_LH * 2;
     const uint64_t per_pair = std::min(full, lds) + ctx->vmax / 8 + 2048;
@@ -3407,11 +3409,22 @@ static int ensure_prep(surtr_ctx* ctx, uint32_t n_pairs, uint32_t n_wg)
     const uint32_t cap16 = (uint32_t)(bytes / 16);
     if (!(ctx->img.base && ctx->img.cap16 >= cap16) || (getenv("SURTR_IMG_BYTES") && ctx->img.cap16 != cap16))
     {
-        free_dev(ctx->img.base); ctx->img.base = nullptr;
-        HIPCHK(hipMalloc((void**)&ctx->img.base, (size_t)cap16 * 16));
-        ctx->img.cap16 = cap16;
+        ctx->img = ImgArena{nullptr, 0};
+        ctx->img_buf.reset();
+        rc = ctx->img_buf.grow(ctx, (size_t)cap16 * 16);
+        if (rc) return rc;
+        ctx->img = ImgArena{ctx->img_buf, cap16};
     }
     return SURTR_OK;
+}
+
+// The arena and the per-fragment tables sized with it are one group: it exists as a whole or not at all.
+static void free_arena(surtr_ctx* ctx)
+{
+    auto& B = ctx->arena_buf;
+    B.pos.reset(); B.loff.reset(); B.llen.reset(); B.nbr.reset(); B.idx.reset(); B.isl.reset();
+    ctx->d_frags.reset(); ctx->d_forder.reset(); ctx->d_frag_status.reset(); ctx->d_face_list.reset();
+    ctx->arena = Arena{}; ctx->arena.cursors = B.cursors; ctx->cap_frags = 0;
 }
 
 static int ensure_arena(surtr_ctx* ctx, uint32_t n_pairs, uint64_t min_v = 0, uint64_t min_h = 0, uint64_t min_i = 0)
@@ -3427,51 +3440,25 @@ static int ensure_arena(surtr_ctx* ctx, uint32_t n_pairs, uint64_t min_v = 0, ui
     const uint32_t capIsl = (uint32_t)std::min<uint64_t>((uint64_t)n_pairs * 4 + 1024, 0x7FFFFFFFull);
     if (!(ctx->arena.pos && ctx->arena.capV >= av && ctx->arena.capH >= ah && ctx->arena.capI >= ai && ctx->arena.capIsl >= capIsl))
     {
-        free_dev(ctx->arena.pos); free_dev(ctx->arena.loff); free_dev(ctx->arena.llen); free_dev(ctx->arena.nbr);
-        free_dev(ctx->arena.idx); free_dev(ctx->arena.isl); free_dev(ctx->d_frags); free_dev(ctx->d_frag_status);
-        ctx->arena.pos = nullptr; ctx->arena.loff = nullptr; ctx->arena.llen = nullptr; ctx->arena.nbr = nullptr;
-        ctx->arena.idx = nullptr; ctx->arena.isl = nullptr; ctx->d_frags = nullptr; ctx->d_frag_status = nullptr;
-        ctx->arena.capV = ctx->arena.capH = ctx->arena.capI = ctx->arena.capIsl = 0; ctx->cap_frags = 0;
-        free_dev(ctx->d_forder); ctx->d_forder = nullptr;
-        hipError_t e = hipMalloc((void**)&ctx->arena.pos, av * 12);
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->arena.loff, av * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->arena.llen, av * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->arena.nbr, ah * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->arena.idx, ai * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->arena.isl, (size_t)capIsl * 8);
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_frags, (size_t)capIsl * sizeof(FragRec));
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_forder, (size_t)capIsl * 16 * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_frag_status, (size_t)capIsl * 4);
-        if (e == hipSuccess) { free_dev(ctx->d_face_list); ctx->d_face_list = nullptr; e = hipMalloc((void**)&ctx->d_face_list, (size_t)capIsl * 4); }
-        if (e != hipSuccess)
-        {
-            // out of memory half-way: leave no buffer behind, so that a later, smaller event allocates afresh
-            free_dev(ctx->arena.pos); free_dev(ctx->arena.loff); free_dev(ctx->arena.llen); free_dev(ctx->arena.nbr);
-            free_dev(ctx->arena.idx); free_dev(ctx->arena.isl); free_dev(ctx->d_frags); free_dev(ctx->d_forder); free_dev(ctx->d_frag_status);
-            ctx->d_frag_status = nullptr;
-            free_dev(ctx->d_face_list); ctx->d_face_list = nullptr;
-            ctx->arena.pos = nullptr; ctx->arena.loff = nullptr; ctx->arena.llen = nullptr; ctx->arena.nbr = nullptr;
-            ctx->arena.idx = nullptr; ctx->arena.isl = nullptr; ctx->d_frags = nullptr; ctx->d_forder = nullptr;
-            ctx->err = std::string("arena allocation: ") + hipGetErrorString(e);
-            return SURTR_E_HIP;
-        }
-        ctx->arena.capV = (uint32_t)av; ctx->arena.capH = (uint32_t)ah; ctx->arena.capI = (uint32_t)ai; ctx->arena.capIsl = capIsl;
+        free_arena(ctx);
+        auto& B = ctx->arena_buf;
+        int rc = B.pos.grow(ctx, av * 3);
+        if (rc == SURTR_OK) rc = B.loff.grow(ctx, av);
+        if (rc == SURTR_OK) rc = B.llen.grow(ctx, av);
+        if (rc == SURTR_OK) rc = B.nbr.grow(ctx, ah);
+        if (rc == SURTR_OK) rc = B.idx.grow(ctx, ai);
+        if (rc == SURTR_OK) rc = B.isl.grow(ctx, capIsl);
+        if (rc == SURTR_OK) rc = ctx->d_frags.grow(ctx, capIsl);
+        if (rc == SURTR_OK) rc = ctx->d_forder.grow(ctx, (size_t)capIsl * 16);
+        if (rc == SURTR_OK) rc = ctx->d_frag_status.grow(ctx, capIsl);
+        if (rc == SURTR_OK) rc = ctx->d_face_list.grow(ctx, capIsl);
+        if (rc) { free_arena(ctx); return rc; }      // (out of memory half-way: a later, smaller event allocates afresh)
+        ctx->arena = Arena{B.pos, B.loff, B.llen, B.nbr, B.idx, B.isl, (uint32_t)av, (uint32_t)ah, (uint32_t)ai, capIsl, B.cursors};
         ctx->cap_frags = capIsl;
     }
-    if (ctx->cap_pairs < n_pairs)
-    {
-        free_dev(ctx->d_pairs); ctx->d_pairs = nullptr;
-        HIPCHK(hipMalloc((void**)&ctx->d_pairs, (size_t)n_pairs * sizeof(PairRec)));
-        ctx->cap_pairs = n_pairs;
-    }
-    const uint32_t need_blk = std::max(n_pairs, ctx->cap_frags) / SURTR_LANES + 4;
-    if (ctx->cap_scanblk < need_blk)
-    {
-        free_dev(ctx->d_scanblk); ctx->d_scanblk = nullptr;
-        HIPCHK(hipMalloc((void**)&ctx->d_scanblk, (size_t)need_blk * 8));
-        ctx->cap_scanblk = need_blk;
-    }
-    return SURTR_OK;
+    const int rc = ctx->d_pairs.grow(ctx, n_pairs);
+    if (rc) return rc;
+    return ctx->d_scanblk.grow(ctx, std::max(n_pairs, ctx->cap_frags) / SURTR_LANES + 4);
 }
 
 // Start of an event: queue cursors and counters to zero, fragment status words to zero, hand-over list to "empty".
@@ -3487,12 +3474,8 @@ __global__ void k_event_init(uint32_t* __restrict__ cursors, uint32_t* __restric
 
 static int upload_pair_order(surtr_ctx* ctx, const uint32_t* ord, uint32_t n_pairs)
 {
-    if (ctx->cap_pair_order < n_pairs)
-    {
-        free_dev(ctx->d_pair_order); ctx->d_pair_order = nullptr; ctx->cap_pair_order = 0;
-        HIPCHK(hipMalloc((void**)&ctx->d_pair_order, (size_t)n_pairs * 4));
-        ctx->cap_pair_order = n_pairs;
-    }
+    const int rc = ctx->d_pair_order.grow(ctx, n_pairs);
+    if (rc) return rc;
     // a previous event (possibly still running on a non-blocking stream) may be reading the table
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_pair_order, ord, (size_t)n_pairs * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -3576,7 +3559,7 @@ static EventPlan plan_event(const surtr_ctx* ctx, uint32_t n_pairs, bool pair_li
     pl.use_half = ctx->half_on && (!pl.split_on || half_forced);
     // (measured on configs[3]: 16 .. 32 workgroups end with the main kernel -- 35 pairs with a vertex in a plane + a hand-over or two;
     //  64 and more take LDS from it: 2.50 / 2.50 / 2.56 ms per event with 16 / 32 / 64)
-    pl.n_catch = std::min(std::min(ctx->n_wg_catch, 32u), n1);
+    pl.n_catch = std::min(SURTR_CATCH_WG_MAX, n1);
     pl.n_wg_sweep = std::min(pl.n_catch, SURTR_CATCH_POLL);
     // catcher workgroups that wait for hand-overs (tests: 0 = none, everything handed on is the sweep's).  With other contexts busy on
     // the GPU (surtr_set_events_in_flight) two: a polling workgroup holds 78 KB of LDS for the length of the main kernel, which the
@@ -3634,7 +3617,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     budget_workgroups(ctx);
     const uint32_t max_wg = ctx->max_wg, n1 = std::max(n_pairs, 1u);
     // scratch slots [0, max_wg) belong to the Mesh clip's main kernel, the n_wg_big after them to k_clip_pairs_big, then k_clip_pairs_catch's
-    int rc = ensure_scratch(ctx, ctx->vmax, ctx->hmax, max_wg + ctx->n_wg_big + ctx->n_wg_catch);
+    int rc = ensure_scratch(ctx, ctx->vmax, ctx->hmax, max_wg + ctx->n_wg_big + SURTR_CATCH_WG_MAX);
     if (rc) return rc;
     rc = ensure_scratch_small(ctx, std::max(ctx->max_wg_small, ctx->n_wg_small));
     if (rc) return rc;
@@ -3646,17 +3629,16 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     if (rc) return rc;
     hipStream_t st = ctx->stream, st2 = ctx->stream2, st3 = ctx->stream3;
     const uint32_t hcap = n_pairs + 4096u;
-    if (ctx->cap_hlist < hcap)
+    if (ctx->d_hlist.cap < hcap)
     {
         HIPCHK(hipStreamSynchronize(st));      // (a previous event may still read the list)
-        free_dev(ctx->d_hlist); ctx->d_hlist = nullptr; ctx->cap_hlist = 0;
-        HIPCHK(hipMalloc((void**)&ctx->d_hlist, (size_t)hcap * 4));
-        ctx->cap_hlist = hcap;
+        rc = ctx->d_hlist.grow(ctx, hcap);
+        if (rc) return rc;
     }
     const EventPlan pl = plan_event(ctx, n_pairs, d_pair_list != nullptr, flags);
     // (the event's zeroes and the hand-over list's "empty" words in one launch, not four fills with a few microseconds between each)
     static_assert(sizeof(surtr_counts) % 4 == 0, "surtr_counts is cleared by words");
-    hipLaunchKernelGGL(k_event_init, dim3(SURTR_LANES == 1 ? 1 : 64), dim3(SURTR_LANES == 1 ? 1 : 256), 0, st, ctx->arena.cursors, (uint32_t*)ctx->d_counts,
+    hipLaunchKernelGGL(k_event_init, dim3(SURTR_LANES == 1 ? 1 : 64), dim3(SURTR_LANES == 1 ? 1 : 256), 0, st, ctx->arena.cursors, (uint32_t*)ctx->d_counts.p,
                        (uint32_t)(sizeof(surtr_counts) / 4), ctx->d_frag_status, ctx->cap_frags, ctx->d_hlist, hcap);
     const uint8_t* d_out = nullptr;
     ctx->last_outside.clear();
@@ -3692,8 +3674,9 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     }
     // the class tables of the clip kernels, the pre-pass and the half-size kernel (k_prep_pairs)
     uint32_t* const order = ctx->d_order;
-    uint32_t* const porder = ctx->d_order + (size_t)16 * ctx->cap_order;
-    uint32_t* const horder = ctx->d_order + (size_t)32 * ctx->cap_order;
+    const size_t cap_order = ctx->d_order.cap / 64;
+    uint32_t* const porder = ctx->d_order + 16 * cap_order;
+    uint32_t* const horder = ctx->d_order + 32 * cap_order;
     const bool wave = n_pairs && pl.wave_on, split = wave && pl.split_on;
 
     if (pl.front_par)
@@ -3837,12 +3820,8 @@ int surtr_fracture_pairs_async(surtr_ctx* ctx, uint32_t n_pairs, const uint32_t*
         if (pair_cell[i] >= ctx->n_cells || pair_piece[i] >= ctx->n_pieces) return SURTR_E_INVALID;
         list[i].x = pair_cell[i]; list[i].y = pair_piece[i];
     }
-    if (ctx->cap_pair_list < std::max(n_pairs, 1u))
-    {
-        free_dev(ctx->d_pair_list); ctx->d_pair_list = nullptr;
-        HIPCHK(hipMalloc((void**)&ctx->d_pair_list, (size_t)std::max(n_pairs, 1u) * sizeof(uint2)));
-        ctx->cap_pair_list = std::max(n_pairs, 1u);
-    }
+    const int rc = ctx->d_pair_list.grow(ctx, std::max(n_pairs, 1u));
+    if (rc) return rc;
     if (n_pairs) HIPCHK(hipMemcpyAsync(ctx->d_pair_list, list.data(), (size_t)n_pairs * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));     // `list` is a stack-owned staging buffer
     ctx->pair_order_count = 0;
@@ -3877,12 +3856,8 @@ int surtr_place_cells_groups_dev(surtr_ctx* ctx, uint32_t n_groups, const uint32
         for (uint32_t c = group_cell_off[g]; c < group_cell_off[g + 1]; ++c)
             for (uint32_t f = ctx->h_plane_off[c]; f < ctx->h_plane_off[c + 1]; ++f) face_group[f] = g;
     }
-    if (ctx->cap_face_group < std::max(nf, 1u))
-    {
-        free_dev(ctx->d_face_group); ctx->d_face_group = nullptr; ctx->cap_face_group = 0;
-        HIPCHK(hipMalloc((void**)&ctx->d_face_group, (size_t)(nf + nf / 4 + 64) * 4));
-        ctx->cap_face_group = nf + nf / 4 + 64;
-    }
+    const int rc = ctx->d_face_group.grow(ctx, std::max(nf, 1u), (size_t)nf + nf / 4 + 64);
+    if (rc) return rc;
     HIPCHK(hipMemcpyAsync(ctx->d_face_group, face_group.data(), (size_t)nf * 4, hipMemcpyHostToDevice, ctx->stream));
     if (nf)
         hipLaunchKernelGGL(k_place_cells_groups, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, nf, ctx->d_v012, ctx->d_face_group, d_scale3, d_shift3, ctx->d_planes);
@@ -3896,13 +3871,12 @@ int surtr_place_cells_groups(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* 
 {
     if (!ctx || !n_groups || !group_cell_off || !scale3 || !translate3) return SURTR_E_INVALID;
     (void)hipSetDevice(ctx->device);
-    float* d = nullptr;
-    if (hipMalloc((void**)&d, (size_t)n_groups * 24) != hipSuccess) return SURTR_E_HIP;
-    hipError_t e = hipMemcpy(d, scale3, (size_t)n_groups * 12, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + 3 * (size_t)n_groups, translate3, (size_t)n_groups * 12, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? surtr_place_cells_groups_dev(ctx, n_groups, group_cell_off, d, d + 3 * (size_t)n_groups) : SURTR_E_HIP;
-    free_dev(d);
-    return rc;
+    DevBuf<float> d;
+    const int rc = d.grow(ctx, (size_t)n_groups * 6);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(d, scale3, (size_t)n_groups * 12, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + 3 * (size_t)n_groups, translate3, (size_t)n_groups * 12, hipMemcpyHostToDevice));
+    return surtr_place_cells_groups_dev(ctx, n_groups, group_cell_off, d, d + 3 * (size_t)n_groups);
 }
 
 int surtr_event_refit(surtr_ctx* ctx)
@@ -4071,10 +4045,8 @@ int surtr_extract_faces(surtr_ctx* ctx, uint32_t nv, const float* pos, const uin
     int rc = load_one(ctx, nv, pos, off, nbr, nv, pos, off, nbr);
     if (rc) return rc;
     const uint32_t H = off[nv];
-    uint32_t *d_n = nullptr, *d_off = nullptr; int32_t* d_idx = nullptr;
-    auto cleanup = [&]() { free_dev(d_n); free_dev(d_off); free_dev(d_idx); };
-    if (hipMalloc((void**)&d_n, 16) != hipSuccess || hipMalloc((void**)&d_off, ((size_t)H + 2) * 4) != hipSuccess ||
-        hipMalloc((void**)&d_idx, ((size_t)std::max(ctx->fs.HF, ctx->fs_big.base ? ctx->fs_big.HF : 0u) + 2) * 4) != hipSuccess) { cleanup(); return SURTR_E_HIP; }
+    DevBuf<uint32_t> d_n, d_off; DevBuf<int32_t> d_idx;
+    if (d_n.grow(ctx, 4) || d_off.grow(ctx, (size_t)H + 2) || d_idx.grow(ctx, (size_t)std::max(ctx->fs.HF, ctx->fs_big.HF) + 2)) return SURTR_E_HIP;
     (void)hipMemsetAsync(d_n, 0, 16, ctx->stream);
     rc = launch_faces(ctx, 0u, d_n, d_off, d_idx);
     surtr_counts c;
@@ -4089,7 +4061,6 @@ int surtr_extract_faces(surtr_ctx* ctx, uint32_t nv, const float* pos, const uin
         if (face_off && hipMemcpy(face_off, d_off, ((size_t)cnt[0] + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SURTR_E_HIP;
         if (rc == 0 && face_idx && cnt[1] && hipMemcpy(face_idx, d_idx, (size_t)cnt[1] * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SURTR_E_HIP;
     }
-    cleanup();
     return rc;
 }
 
@@ -4264,7 +4235,7 @@ int surtr_kernel_history(surtr_ctx* ctx, float ms[16], int slot[16], uint32_t* n
 int surtr_pair_status(surtr_ctx* ctx, uint32_t n_pairs, uint32_t* status)
 {
     if (!ctx || !status) return SURTR_E_INVALID;
-    if (!ctx->have_event || n_pairs > ctx->cap_pairs) return SURTR_E_STATE;
+    if (!ctx->have_event || n_pairs > ctx->d_pairs.cap) return SURTR_E_STATE;
     (void)hipSetDevice(ctx->device);
     HIPCHK(hipStreamSynchronize(ctx->stream));
     std::vector<PairRec> recs(n_pairs);
@@ -4276,7 +4247,7 @@ int surtr_pair_status(surtr_ctx* ctx, uint32_t n_pairs, uint32_t* status)
 int surtr_event_pair_costs(surtr_ctx* ctx, uint32_t n_pairs, uint32_t* cost)
 {
     if (!ctx || !cost) return SURTR_E_INVALID;
-    if (!ctx->have_event || n_pairs > ctx->cap_pairs) return SURTR_E_STATE;
+    if (!ctx->have_event || n_pairs > ctx->d_pairs.cap) return SURTR_E_STATE;
     (void)hipSetDevice(ctx->device);
     HIPCHK(hipStreamSynchronize(ctx->stream));
     std::vector<PairRec> recs(n_pairs);
@@ -4337,13 +4308,9 @@ int surtr_event_download(surtr_ctx* ctx, surtr_fragments* out)
     int rc = surtr_event_counts(ctx, &c);
     if (rc) return rc;
     const size_t need = blob_layout(c).total;
-    if (ctx->blob_cap < need)
-    {
-        free_dev(ctx->d_blob); ctx->d_blob = nullptr;
-        HIPCHK(hipMalloc(&ctx->d_blob, need));
-        ctx->blob_cap = need;
-    }
-    rc = surtr_event_pack_dev(ctx, ctx->d_blob, ctx->blob_cap);
+    rc = ctx->d_blob.grow(ctx, need);
+    if (rc) return rc;
+    rc = surtr_event_pack_dev(ctx, ctx->d_blob, ctx->d_blob.cap);
     if (rc) return rc;
     std::vector<char> host(need);
     HIPCHK(hipMemcpyAsync(host.data(), ctx->d_blob, need, hipMemcpyDeviceToHost, ctx->stream));
@@ -4363,18 +4330,14 @@ int surtr_clip_polyhedron(surtr_ctx* ctx, uint32_t nv, const float* pos, const u
     rc = ensure_scratch(ctx, std::max(nv, ctx->vmax), std::max(H, ctx->hmax), std::max(1u, ctx->n_wg));
     if (rc) return rc;
     const uint32_t capv = ctx->pool.CV, caph = ctx->pool.CH;
-    float *d_pos = nullptr, *d_opos = nullptr; uint32_t *d_loff = nullptr, *d_llen = nullptr, *d_ooff = nullptr, *d_res = nullptr, *d_ollen = nullptr;
-    int32_t *d_nbr = nullptr, *d_onbr = nullptr; float4* d_pl = nullptr;
+    DevBuf<float> d_pos, d_opos; DevBuf<uint32_t> d_loff, d_llen, d_ooff, d_res, d_ollen; DevBuf<int32_t> d_nbr, d_onbr; DevBuf<float4> d_pl;
     std::vector<uint32_t> llen(nv);
     for (uint32_t v = 0; v < nv; ++v) llen[v] = off[v + 1] - off[v];
-    auto cleanup = [&]() { free_dev(d_pos); free_dev(d_opos); free_dev(d_loff); free_dev(d_llen); free_dev(d_ooff); free_dev(d_res);
-                           free_dev(d_nbr); free_dev(d_onbr); free_dev(d_pl); free_dev(d_ollen); };
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ctx->err = hipGetErrorString(e_); cleanup(); return SURTR_E_HIP; } } while (0)
-    CK(hipMalloc((void**)&d_pos, (size_t)nv * 12)); CK(hipMalloc((void**)&d_loff, (size_t)(nv + 1) * 4));
-    CK(hipMalloc((void**)&d_llen, (size_t)nv * 4)); CK(hipMalloc((void**)&d_nbr, std::max<size_t>(16, (size_t)H * 4)));
-    CK(hipMalloc((void**)&d_pl, std::max<size_t>(16, (size_t)n_planes * 16)));
-    CK(hipMalloc((void**)&d_opos, (size_t)capv * 12)); CK(hipMalloc((void**)&d_ooff, (size_t)(capv + 1) * 4));
-    CK(hipMalloc((void**)&d_onbr, (size_t)caph * 4)); CK(hipMalloc((void**)&d_res, 16)); CK(hipMalloc((void**)&d_ollen, (size_t)(capv + 1) * 4));
+    if (d_pos.grow(ctx, (size_t)nv * 3) || d_loff.grow(ctx, (size_t)nv + 1) || d_llen.grow(ctx, nv) || d_nbr.grow(ctx, std::max<size_t>(4, H)) ||
+        d_pl.grow(ctx, std::max(n_planes, 1u)) || d_opos.grow(ctx, (size_t)capv * 3) || d_ooff.grow(ctx, (size_t)capv + 1) ||
+        d_onbr.grow(ctx, caph) || d_res.grow(ctx, 4) || d_ollen.grow(ctx, (size_t)capv + 1))
+        return SURTR_E_HIP;
+#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ctx->err = hipGetErrorString(e_); return SURTR_E_HIP; } } while (0)
     CK(hipMemcpy(d_pos, pos, (size_t)nv * 12, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_loff, off, (size_t)(nv + 1) * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_llen, llen.data(), (size_t)nv * 4, hipMemcpyHostToDevice));
@@ -4397,7 +4360,6 @@ int surtr_clip_polyhedron(surtr_ctx* ctx, uint32_t nv, const float* pos, const u
         if (out_off && res[0] == 0) out_off[0] = 0;
     }
 #undef CK
-    cleanup();
     return (int)res[2];
 }
 

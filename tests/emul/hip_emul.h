@@ -85,8 +85,23 @@ static inline hipError_t hipGetLastError() { return hipSuccess; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { p->multiProcessorCount = 1; return hipSuccess; }
 static inline hipError_t hipMemGetInfo(size_t* f, size_t* t) { *f = (size_t)8 << 30; *t = (size_t)16 << 30; return hipSuccess; }
-static inline hipError_t hipMalloc(void** p, size_t n) { *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : 1; }
-static inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+// Allocation bookkeeping shared by every translation unit of the library (tests/test_alloc_failures.py reaches it through ctypes):
+// the number of live allocations, the hipMalloc calls since the last surtr_emul_fail_alloc, and the one of them (0-based; -1: none)
+// that fails.
+struct EmulAllocs { long live = 0, calls = 0, fail_at = -1; };
+inline EmulAllocs& emul_allocs() { static EmulAllocs a; return a; }
+extern "C" __attribute__((used, visibility("default"))) inline long surtr_emul_live_allocs() { return emul_allocs().live; }
+extern "C" __attribute__((used, visibility("default"))) inline long surtr_emul_alloc_calls() { return emul_allocs().calls; }
+extern "C" __attribute__((used, visibility("default"))) inline void surtr_emul_fail_alloc(long k) { emul_allocs().calls = 0; emul_allocs().fail_at = k; }
+static inline hipError_t hipMalloc(void** p, size_t n)
+{
+    EmulAllocs& a = emul_allocs();
+    if (a.calls++ == a.fail_at) { *p = nullptr; return 2; }      // (hipErrorOutOfMemory)
+    *p = calloc(n ? n : 1, 1);
+    if (*p) ++a.live;
+    return *p ? hipSuccess : 1;
+}
+static inline hipError_t hipFree(void* p) { if (p) --emul_allocs().live; free(p); return hipSuccess; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { if (n) memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
