@@ -240,7 +240,8 @@ int surtr_triangulate(surtr_ctx* ctx, uint32_t nv, const float* pos, const uint3
 
 /* Presents n host pieces as the fragments of an event (fragment k = Mesh k + Convex k, ids = frag_ids[3k..] or
  * (k, 0, 0) when NULL), so that surtr_event_refit / surtr_event_triangulate / surtr_event_download /
- * surtr_pieces_from_event work on solids that did not come out of surtr_fracture_event. */
+ * surtr_pieces_from_event work on solids that did not come out of surtr_fracture_event.  The `outside` mask of an earlier
+ * event is dropped: surtr_event_regroup after this call regroups these n fragments alone (bind 0 starts empty). */
 int surtr_load_fragments(surtr_ctx* ctx, uint32_t n,
                          const uint32_t* mesh_vert_off, const float* mesh_pos, const uint32_t* mesh_nbr_off, const int32_t* mesh_nbr,
                          const uint32_t* conv_vert_off, const float* conv_pos, const uint32_t* conv_nbr_off, const int32_t* conv_nbr,
@@ -272,6 +273,13 @@ int surtr_upload_stats(surtr_ctx* ctx, float* ms, uint32_t* n_alloc);
  * claimed by polling catcher workgroups, [4] the catcher's cursor over its own classes (13..12), [5] the sweep's cursor,
  * [6] the workgroups the last event's clip kernels could use, [7] the hand-over list's capacity (pairs + 4 096). */
 int surtr_handover_stats(surtr_ctx* ctx, uint32_t out[8]);
+/* Diagnostic: what the last surtr_event_regroup of the context that filled its arrays counted (zeros before the first).  Host
+ * values the call had read back anyway: no launch, no copy, no synchronisation.  out[0] pieces, [1] faces of three points or more,
+ * [2] points of those faces, [3] touching pairs of faces found (one per pair of FACES, both orders of a pair of pieces included;
+ * may exceed [4] when the call returned SURTR_E_CAPACITY), [4] room for them (16 * faces + 1024), [5] rounds of the label
+ * propagation including the last, which changes nothing (1 when no pair touched), [6] fragments moved to compound 0 by
+ * ConvexOutOfSphere, [7] 0. */
+int surtr_regroup_stats(surtr_ctx* ctx, uint32_t out[8]);
 /* Diagnostic: the order in which k_clip_convex takes the pairs of the last surtr_fracture_event (pairs of the cells with the most
  * planes first; the order of surtr_fracture_pairs_async's list there): *n entries, relative to the event's first pair.  order ==
  * NULL returns the count only; cap < *n is SURTR_E_CAPACITY. */
@@ -347,7 +355,13 @@ int surtr_regroup(uint32_t n_pieces, uint32_t n_outside, const int32_t* piece_ce
  * run in kernels; only per-piece flags and labels come back.  Pieces are numbered as for surtr_regroup: the resident pieces
  * the event skipped (its `outside` mask, ascending), then the event's fragments in output order.  Call it BEFORE
  * surtr_event_refit (the reference regroups on the un-refitted Convex solids).  compound_off needs *n_pieces + 2 entries,
- * compound_piece *n_pieces (call with both NULL to get n_pieces). */
+ * compound_piece *n_pieces (call with both NULL to get n_pieces).
+ * Limits: a Convex of more than 4096 half-edges (or vertices), or more than 16 * faces + 1024 touching pairs of faces (only solids
+ * thinner than the rule's 1e-3 window get there), give SURTR_E_CAPACITY; the context stays usable.
+ * State: the skipped pieces are read from the resident pieces, so they must still be the ones the event ran over.  After
+ * surtr_load_fragments there is no mask (see there).  After surtr_pieces_from_event the fragments are still the event's but its
+ * pieces are gone: if the event's mask kept any piece out, the call returns SURTR_E_STATE (regroup before handing the fragments
+ * on); an event without a mask, or with a mask of zeros, regroups as before. */
 int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
                         uint32_t* n_pieces, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece);
 

@@ -1047,6 +1047,7 @@ static bool convex_out_of_sphere(const Solid& S, const Faces& ext, const std::ve
         bool contain = true;
         for (const auto& f : ext)
         {
+            if (f.size() < 3) continue;      // (the reference reads f[2] past the end of such a face: flagged, not emulated)
             V3 n = normalize(cross(sub(S.pos[f[1]], S.pos[f[0]]), sub(S.pos[f[2]], S.pos[f[0]])));
             float d = -dot(S.pos[f[0]], n);
             float dist = dot(n, po) + d;
@@ -1091,6 +1092,7 @@ static void handle_convex_island(std::vector<std::set<int>>& bind, const std::ve
             {
                 Node nd; nd.cid = cid;
                 for (int v : poly) nd.pts.push_back(conv[cid].pos[v]);
+                if (nd.pts.size() < 3) continue;      // (points[2] of the reference is past the end: flagged, not emulated)
                 nd.plane = plane_from_points(nd.pts[0], nd.pts[1], nd.pts[2]);
                 nd.absd = std::abs(nd.plane.w);
                 nodes.push_back(nd);

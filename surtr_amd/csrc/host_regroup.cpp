@@ -78,6 +78,7 @@ bool out_of_sphere(const SolidView& S, const std::vector<std::vector<int>>& face
         bool contain = true;
         for (const auto& f : faces)
         {
+            if (f.size() < 3) continue;      // (no plane: the reference reads past the end of the face here; skipped as in the island step)
             const P3 n = unit(cross(sub(S.p(f[1]), S.p(f[0])), sub(S.p(f[2]), S.p(f[0]))));
             const float d = -dot(S.p(f[0]), n);
             if (dot(n, po) + d > 0.f) { contain = false; break; }

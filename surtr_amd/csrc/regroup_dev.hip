@@ -11,8 +11,11 @@
 // Only per-piece flags and labels (a few bytes per piece) cross the bus; the host turns them into the reference's bind sets
 // (first group of a compound stays, the others are appended in discovery order).  Pieces are numbered as in
 // surtr_regroup: the resident pieces the event skipped (its `outside` mask), ascending, then the event's fragments.
+#include <array>
 #include <cstring>
+#include <mutex>
 #include <set>
+#include <unordered_map>
 
 #include "surtr_ctx.h"
 #include <hipcub/hipcub.hpp>
@@ -269,7 +272,35 @@ __global__ __launch_bounds__(RG_LABEL_THREADS) void k_rg_labels_all(uint32_t ne,
     if (tid == 0u) *rounds_out = round < n_pieces + 8u ? round + 1u : 0xFFFFFFFFu;
 }
 
+// surtr_regroup_stats: what the last surtr_event_regroup of a context counted, kept on the host beside the context (filled from
+// values the call reads back anyway: no launch, no copy and no synchronisation of its own)
+enum { RGS_PIECES, RGS_FACES, RGS_POINTS, RGS_EDGES, RGS_CAP_EDGES, RGS_ROUNDS, RGS_OUT, RGS_SPARE };
+std::mutex g_stats_lock;
+std::unordered_map<const surtr_ctx*, std::array<uint32_t, 8>> g_stats;
+struct StatsScope       // collects during the call, publishes when it returns (whatever it returns)
+{
+    const surtr_ctx* ctx; std::array<uint32_t, 8> v{};
+    explicit StatsScope(const surtr_ctx* c) : ctx(c) {}
+    ~StatsScope() { std::lock_guard<std::mutex> g(g_stats_lock); g_stats[ctx] = v; }
+};
+
 } // namespace
+
+extern "C" int surtr_regroup_stats(surtr_ctx* ctx, uint32_t out[8])
+{
+    if (!ctx || !out) return SURTR_E_INVALID;
+    std::lock_guard<std::mutex> g(g_stats_lock);
+    const auto it = g_stats.find(ctx);
+    for (int k = 0; k < 8; ++k) out[k] = it == g_stats.end() ? 0u : it->second[k];
+    return SURTR_OK;
+}
+
+// surtr_destroy: the context's entry goes with it (a later context at the same address starts from zeros)
+extern "C" void surtr_regroup_forget(const surtr_ctx* ctx)
+{
+    std::lock_guard<std::mutex> g(g_stats_lock);
+    g_stats.erase(ctx);
+}
 
 extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
                                    uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece)
@@ -282,9 +313,18 @@ extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_spher
     surtr_counts c;
     int rc = surtr_event_counts(ctx, &c);
     if (rc) return rc;
-    // pieces: the resident pieces the event skipped, then its fragments; bind sets as ApplyFracture leaves them
+    // pieces: the resident pieces the event skipped, then its fragments; bind sets as ApplyFracture leaves them.  The `outside`
+    // mask belongs to the event that took it and to the pieces it ran over: surtr_load_fragments drops it (its fragments are
+    // nobody's event), and once surtr_pieces_from_event has replaced the pieces a mask that kept any of them out names solids
+    // that are gone -- the compounds of that event can no longer be formed (include/surtr_hip.h)
     std::vector<uint32_t> kind, index, set_of;
-    for (uint32_t p = 0; p < ctx->n_pieces && ctx->last_outside.size() == ctx->n_pieces; ++p)
+    const bool masked = std::find_if(ctx->last_outside.begin(), ctx->last_outside.end(), [](uint8_t o) { return o != 0; }) != ctx->last_outside.end();
+    if (masked && (!ctx->frags_of_pieces || ctx->last_outside.size() != ctx->n_pieces))
+    {
+        ctx->err = "surtr_event_regroup: the event kept pieces out of the impact, and the resident pieces have been replaced since";
+        return SURTR_E_STATE;
+    }
+    for (uint32_t p = 0; masked && p < ctx->n_pieces; ++p)
         if (ctx->last_outside[p]) { kind.push_back(0u); index.push_back(p); }
     const uint32_t n_outside = (uint32_t)kind.size();
     std::vector<FragRec> fr(c.n_frag);
@@ -293,6 +333,8 @@ extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_spher
     const uint32_t n = (uint32_t)kind.size();
     if (n_pieces_out) *n_pieces_out = n;
     if (!compound_off || !compound_piece) { *n_compounds = 0; return SURTR_OK; }      // sizes only: n + 2 / n entries are enough
+    StatsScope stats(ctx);
+    stats.v[RGS_PIECES] = n;
     std::vector<std::set<int>> bind(1);
     for (uint32_t p = 0; p < n_outside; ++p) bind[0].insert((int)p);
     for (uint32_t f = 0; f < c.n_frag; ++f)
@@ -323,7 +365,13 @@ extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_spher
     for (uint32_t p = 0; p < n; ++p) { foff[p + 1] = foff[p] + cnt[2 * p]; poff[p + 1] = poff[p] + cnt[2 * p + 1]; }
     const uint32_t nf = foff[n], npts = poff[n];
     DevBuf<FaceNode> d_nodes; DevBuf<P3> d_pts; DevBuf<unsigned long long> d_key, d_key2; DevBuf<uint2> d_edges;
+    // One entry per touching PAIR OF FACES (k_rg_pairs does not merge the pairs of two pieces).  Solids that meet face to face
+    // give a face a handful of partners, but the rule has no such bound: every face within 1e-3 of its |d| with the opposite
+    // normal and an overlapping projection counts, so a stack of plates thinner than the window (2^-18 thick: up to 262
+    // partners of every large face) passes 16 per face.  Such an input gets SURTR_E_CAPACITY, like a Convex of more than
+    // RG_MAXH half-edges (tests/test_regroup_scenes.py: test_limit_edges_of_a_stack_of_thin_plates).
     const uint32_t cap_edges = 16u * nf + 1024u;
+    stats.v[RGS_FACES] = nf; stats.v[RGS_POINTS] = npts; stats.v[RGS_CAP_EDGES] = cap_edges;
     if (!alloc(d_nodes, nf) || !alloc(d_pts, npts) || !alloc(d_key, nf) || !alloc(d_key2, nf) || !alloc(d_val, nf) || !alloc(d_order, nf) || !alloc(d_edges, cap_edges))
         return SURTR_E_HIP;
     HIPCHK(hipMemcpyAsync(d_foff.p, foff.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
@@ -341,6 +389,7 @@ extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_spher
             std::set<int> outside;
             for (int cpi : bind[i]) if (flag[cpi]) outside.insert(cpi);
             for (int cpi : outside) { bind[i].erase(cpi); bind[0].insert(cpi); }
+            stats.v[RGS_OUT] += (uint32_t)outside.size();
         }
         bind.erase(std::remove_if(bind.begin() + 1, bind.end(), [](const std::set<int>& s) { return s.empty(); }), bind.end());
     }
@@ -364,6 +413,7 @@ extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_spher
         uint32_t head[3] = {0, 0, 0};
         HIPCHK(hipMemcpyAsync(head, d_err, 12, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
+        stats.v[RGS_EDGES] = head[1];
         if (head[0]) return (int)head[0];
         if (head[1] > cap_edges) return SURTR_E_CAPACITY;
         const uint32_t ne = head[1];
@@ -380,6 +430,7 @@ extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_spher
         HIPCHK(hipStreamSynchronize(st));        // (the one synchronisation of the label phase)
         if (rounds == 0xFFFFFFFFu) return SURTR_E_STATE;      // (cannot happen: see the bound in the kernel; never hand out unconverged labels)
         ctx->regroup_rounds = rounds;
+        stats.v[RGS_ROUNDS] = rounds;
     }
     // HandleConvexIsland's outcome: per compound, groups = label classes in order of their lowest piece; the first stays
     std::vector<std::set<int>> extra;

@@ -3144,9 +3144,12 @@ int surtr_create(int device, surtr_ctx** out)
     return SURTR_OK;
 }
 
+void surtr_regroup_forget(const surtr_ctx* ctx);      // regroup_dev.hip: what it keeps beside the context
+
 void surtr_destroy(surtr_ctx* ctx)
 {
     if (!ctx) return;
+    surtr_regroup_forget(ctx);
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -4001,6 +4004,7 @@ int surtr_load_fragments(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const 
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));       // the staging vectors go out of scope
     ctx->have_event = true; ctx->last_flags = 0; ctx->last_current = false; ctx->frags_of_pieces = false;
+    ctx->last_outside.clear();      // (the mask of an earlier event says nothing about these fragments: surtr_event_regroup)
     return SURTR_OK;
 }
 

@@ -320,6 +320,13 @@ class Engine:
         self._ck(lib().surtr_event_regroup(*args, ctypes.byref(n), ctypes.byref(nc), _p(co), _p(cp)))
         return co[:nc.value + 1].copy(), cp[:co[nc.value]].copy()
 
+    def regroup_stats(self):
+        """What the last event_regroup counted (include/surtr_hip.h: surtr_regroup_stats); no synchronisation."""
+        out = (ctypes.c_uint32 * 8)()
+        self._ck(lib().surtr_regroup_stats(self._h, out))
+        names = ("pieces", "faces", "face_points", "edges", "cap_edges", "rounds", "out_of_sphere")
+        return {n: int(out[i]) for i, n in enumerate(names)}
+
     def _mass(self, fn, set, density):
         n = ctypes.c_uint32()
         args = [self._h, ctypes.c_int(int(set)), ctypes.c_float(density)]
