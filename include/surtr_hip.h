@@ -67,7 +67,12 @@ typedef struct surtr_counts {
                             * flags: a pair whose Mesh clip has no valid answer yields no fragment (surtr_pair_status names it); a
                             * fragment whose refit has no valid answer keeps its un-refitted Convex, one whose faces cannot be
                             * extracted has no triangles (frag_status names them).  Asked for one solid (surtr_clip_polyhedron,
-                            * surtr_refit_solid, ...), the call returns SURTR_E_TOPOLOGY instead. */
+                            * surtr_refit_solid, ...), the call returns SURTR_E_TOPOLOGY instead.
+                            * AN ENGINE LIMIT is flagged the same way, with SURTR_E_CAPACITY in frag_status: a refit at a
+                            * RefittingPointLimit above 4 (surtr_set_refit_point_limit) whose limited hull has more than 63 faces --
+                            * two slab planes each, 127 planes per clip at most --, overflows the hull kernel's tables or has a
+                            * coordinate beyond the range of its edge keys.  The fragment keeps its un-refitted Convex;
+                            * surtr_queue_stats out[95] counts these apart. */
 } surtr_counts;
 
 /* Host-side view used by surtr_event_download: every pointer may be NULL to
@@ -128,7 +133,8 @@ int surtr_kernel_history(surtr_ctx* ctx, float ms[16], int slot[16], uint32_t* n
  * its half-size LDS topology and were redone by k_clip_pairs, [88] / [89] pairs the record clipper took / handed on to the
  * general clipper ([96+r]: by rule r), [90] solids that were too large for the literal last-resort clipper (more than 32 ring
  * entries at a vertex, or more vertices than its scratch): their pair / fragment is flagged like one without a valid result in
- * the reference -- this counter is how to tell the engine's limit from the reference's undefined behaviour. */
+ * the reference -- this counter is how to tell the engine's limit from the reference's undefined behaviour; [95] fragments a
+ * refit at a RefittingPointLimit above 4 left un-refitted and flagged SURTR_E_CAPACITY (see n_failed). */
 int surtr_queue_stats(surtr_ctx* ctx, uint32_t out[128]);
 /* Diagnostic: the status of every pair of the last event (0, or the SURTR_E_* code that pair raised), in pair order
  * (cell-major for surtr_fracture_event, list order for surtr_fracture_pairs).  Works after an event that failed. */
@@ -223,8 +229,9 @@ int surtr_clip_polyhedron(surtr_ctx* ctx, uint32_t nv, const float* pos, const u
 /* The three per-Piece tasks for ONE solid (what m_refittingTask and m_initCompoundTask do to a Piece, Inc/Surtr.h:270-271),
  * run by the same kernels as the event.  They use the event arena: the fragments of the last event are gone afterwards.
  *
- * m_refittingTask (Src/Surtr.cpp:1449-1455): ConvexHull(mesh points, min(n, 4)) -> Kdop::Calc(mesh) ->
- * ClipWithPolyhedron(convex).  Count-then-fill like surtr_clip_polyhedron. */
+ * m_refittingTask (Src/Surtr.cpp:1449-1455): ConvexHull(mesh points, min(n, RefittingPointLimit)) -> Kdop::Calc(mesh) ->
+ * ClipWithPolyhedron(convex), with the limit of surtr_set_refit_point_limit (4 by default).  Count-then-fill like
+ * surtr_clip_polyhedron.  SURTR_E_CAPACITY: the hull is beyond the engine's limits (see n_failed). */
 int surtr_refit_solid(surtr_ctx* ctx, uint32_t mesh_nv, const float* mesh_pos, const uint32_t* mesh_nbr_off, const int32_t* mesh_nbr,
                       uint32_t conv_nv, const float* conv_pos, const uint32_t* conv_nbr_off, const int32_t* conv_nbr,
                       uint32_t* out_nv, uint32_t* out_nh, float* out_pos, uint32_t* out_nbr_off, int32_t* out_nbr);
@@ -368,6 +375,18 @@ int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const fl
 /* Runs m_refittingTask (and the output scan) on the fragments of the last event: the reference regroups on the
  * un-refitted Convex solids and refits afterwards (Src/Surtr.cpp:1921-1939). */
 int surtr_event_refit(surtr_ctx* ctx);
+
+/* FractureArgs::RefittingPointLimit (Inc/Surtr.h:93): the points of the limited hull whose face normals give a fragment's
+ * slab planes, per fragment min(mesh vertices, n).  4 (the default) to 32; anything else returns SURTR_E_INVALID and leaves
+ * the setting as it was.  Read by SURTR_EVT_REFIT, surtr_event_refit and surtr_refit_solid.  A larger limit means more planes
+ * per clip and larger Convex solids: set it before the event (or surtr_load_fragments) whose arena is to have room for them. */
+int surtr_set_refit_point_limit(surtr_ctx* ctx, uint32_t n);
+int surtr_get_refit_point_limit(surtr_ctx* ctx, uint32_t* n);
+/* For tests: the device's limited hull (the one k_refit_n builds per fragment) of one cloud of n >= 4 points, as
+ * surtr_hull_normals returns the host's; and the key of one coordinate in its edge keys -- the digits of printf("%f"):
+ * sign bit, |x| * 10^6 rounded half-to-even on the exact value (SURTR_E_CAPACITY: out of range). */
+int surtr_hull_normals_device(surtr_ctx* ctx, uint32_t n, const float* points, uint32_t limit, uint32_t capacity, float* normals, uint32_t* count);
+int surtr_coord_key(float x, uint32_t* neg, uint64_t* scaled);
 
 /* ---- mass properties (mass_dev.hip) ------------------------------------ */
 /* What PxRigidBodyExt::updateMassAndInertia(body, 10.0f) gives InitCompound (Src/Surtr.cpp:2520), per closed solid.

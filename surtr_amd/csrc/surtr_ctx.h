@@ -284,6 +284,8 @@ struct surtr_ctx
     DevBuf<uint8_t> d_outside;
     std::vector<uint8_t> last_outside;       // the `outside` mask of the last event (empty: none), for surtr_event_regroup
     DevBuf<uint2> d_pair_list;
+    uint32_t refit_limit = 4;            // FractureArgs::RefittingPointLimit (surtr_set_refit_point_limit): above 4, k_refit_n refits
+    DevBuf<uint32_t> d_hull_ws;          // k_refit_n: gain and "processed" mark of every arena vertex (2 x capV words)
     float color[3] = {0.25f, 0.25f, 0.25f};      // VertexNormalColor::Color written by k_pack (Inc/Poly.h:68 default)
     surtr_counts last{}; bool last_current = false;     // `last` holds the counts of the event in the arena
     bool have_event = false; uint32_t last_flags = 0;

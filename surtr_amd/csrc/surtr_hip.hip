@@ -1942,6 +1942,228 @@ __global__ __launch_bounds__(SURTR_LANES) void k_refit(FragRec* __restrict__ fra
 #endif
 }
 
+#include "refit_hull.h"
+
+// k_refit at a RefittingPointLimit above 4 (surtr_set_refit_point_limit): the hull is the greedy hull of min(n, limit) points
+// of refit_hull.h, F faces, and the Convex is clipped by 2F planes through the clipper chain of k_refit.  hull_ws = 2 * A.capV
+// words: the gain and the "processed" mark of every point of every fragment's Mesh (a fragment's points are the arena
+// vertices mv_off .. mv_off + mv_n: the ranges are disjoint).
+__global__ __launch_bounds__(SURTR_LANES) void k_refit_n(FragRec* __restrict__ frags, const surtr_counts* __restrict__ counts,
+                                                      ScratchPool pool, Arena A, const uint32_t* __restrict__ forder, uint32_t cap_frags,
+                                                      uint32_t* __restrict__ frag_status, const float* __restrict__ piece_cpos,
+                                                      const uint32_t* __restrict__ piece_cvo, uint32_t limit, uint32_t* __restrict__ hull_ws)
+{
+    __shared__ RhLds Hs;
+    RhLds* const Hp = &Hs;
+    __shared__ Shared sh;
+    __shared__ ArgF slotF[SURTR_NWAVE];
+    __shared__ ArgD slotD[SURTR_NWAVE];
+    __shared__ OneWaveLds U;      // (the one-wave clipper of regular planes shares the bytes of the general one's arrays)
+    LdsTopoSmall& L = U.g.L; LdsWorkSmall& W = U.g.W;
+    Scratch S = carve(pool, blockIdx.x);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nf = counts->n_frag;
+#ifdef SURTR_STAMP
+    const unsigned long long wg_t0 = __builtin_readcyclecounter();
+    unsigned long long wg_tasks = 0;
+#endif
+    while (true)
+    {
+        __syncthreads();
+        if (tid == 0) sh.misc[7] = frag_of_ticket(A, forder, cap_frags, atomicAdd(&A.cursors[6], 1u));
+        __syncthreads();
+        const uint32_t f = sh.misc[7];
+        if (f >= nf) break;
+        FragRec fr = frags[f];
+        const float* mpg = A.pos + 3 * (size_t)fr.mv_off;
+        const uint32_t n = fr.mv_n;
+#ifdef SURTR_STAMP
+        const unsigned long long r0 = __builtin_readcyclecounter();
+#endif
+        // The fragment's vertices are read a dozen times (four hull passes, eight slab extremes): a fragment of up to
+        // 2 * LdsWorkSmall::kN vertices is staged once in the LDS work arrays, which nothing uses before the clip below.
+#ifdef SURTR_STAMP
+        unsigned long long r1 = 0;
+#endif
+        static_assert(offsetof(LdsWorkSmall, aux0) == sizeof(float) * 3 * LdsWorkSmall::kN && offsetof(LdsWorkSmall, aux1) == sizeof(float) * 4 * LdsWorkSmall::kN &&
+                      offsetof(LdsWorkSmall, aux2) == sizeof(float) * 5 * LdsWorkSmall::kN, "pos, aux0, aux1, aux2 are contiguous");
+        uint32_t hull_planes = 8u;
+        int herr = 0;
+        auto slabs = [&](const auto* mp) {
+            RhLds& H = *Hp;
+            herr = rh_build(mp, n, n < limit ? n : limit, (float*)hull_ws + fr.mv_off, hull_ws + A.capV + fr.mv_off, H, slotF, slotD);
+            if (herr != 0) return;
+            const uint32_t F = H.nLive;
+            hull_planes = 2u * F;
+            // ---- Kdop::Calc(Polyhedron) (Src/Kdop.cpp:92-115), as in k_refit, for F normals ----
+            for (uint32_t k = 0; k < F; ++k)
+            {
+                ArgF lo, hi; lo.i = hi.i = 0xFFFFFFFFu; lo.v = hi.v = 0.f;
+                const float nx = H.nrm[k][0], ny = H.nrm[k][1], nz = H.nrm[k][2];
+                for (uint32_t v = tid; v < n; v += group_size())
+                {
+                    const float t = dot3(mp[3 * v], mp[3 * v + 1], mp[3 * v + 2], nx, ny, nz);
+                    if (hi.i == 0xFFFFFFFFu || t > hi.v) { hi.v = t; hi.i = v; }
+                    if (lo.i == 0xFFFFFFFFu || -t > lo.v) { lo.v = -t; lo.i = v; }
+                }
+                hi = wg_argmax<float, ArgF>(hi, slotF);
+                lo = wg_argmax<float, ArgF>(lo, slotF);
+                if (tid == 0)
+                {
+                    const auto* a0 = mp + 3 * lo.i; const auto* a1 = mp + 3 * hi.i;
+                    sh.planes[2 * k] = make_float4(-nx, -ny, -nz, -dot3(a0[0], a0[1], a0[2], -nx, -ny, -nz));
+                    sh.planes[2 * k + 1] = make_float4(nx, ny, nz, -dot3(a1[0], a1[1], a1[2], nx, ny, nz));
+                }
+            }
+            __syncthreads();
+        };
+        if (n <= 2u * LdsWorkSmall::kN)
+        {
+            float* lp = W.pos;
+            for (uint32_t i = tid; i < 3u * n; i += group_size()) lp[i] = mpg[i];
+            __syncthreads();
+            slabs((const float*)lp);
+            __syncthreads();
+        }
+        else slabs(mpg);
+#ifdef SURTR_STAMP
+        const unsigned long long r2 = __builtin_readcyclecounter();
+        if (tid == 0) { atomicAdd(&g_stamp[94], r1 - r0); atomicAdd(&g_stamp[95], r2 - r1); }
+        int dbg_path = 0;
+#endif
+        const uint32_t nP = hull_planes;      // planes of the clip: Min and Max plane per hull face
+        SolidIn cin{A.pos + 3 * (size_t)fr.cv_off, A.loff + fr.cv_off, A.llen + fr.cv_off, A.nbr, fr.cv_n, nullptr, nullptr, nullptr, nullptr, nullptr};
+        // arena rings are absolute offsets into A.nbr, which is what SolidIn expects
+        uint32_t nvoff = 0, ncn = 0, nhoff = 0, nchn = 0;
+        // (no small_clip attempt here: the slab planes pass through extreme vertices of the fragment, which are vertices of its
+        // Convex as often as not -- measured on configs[3]: 2 385 of 2 692 refits have a vertex exactly in a plane)
+        int err = SURTR_E_TOPOLOGY;      // a sliver Convex: the literal clipper below, from the start
+        if (herr != 0) err = herr;      // (no hull within the engine's limits: the fragment is flagged below)
+        else if (!solid_is_sliver(cin))
+        {
+            // the regular clipper first: it takes the Convex whose slab planes either cut no vertex (the plane through an extreme
+            // vertex of the fragment that is an extreme vertex of its Convex too) or cut with no vertex in the plane
+            uint32_t which = 0, stop = 0xFFFFFFFFu;
+            err = small_clip(cin, nP, sh, U.f, &which, &stop);
+            if (tid == 0) atomicAdd(&A.cursors[err == 0 ? 82 : 83], 1u);       // (diagnostic: refits the regular clipper took / handed on)
+            if (err == 0)
+            {
+                const uint32_t nv = U.f.nv[which];
+                if (nv != 0u) err = sc_park(U.f.buf[which], nv, sh, A.cursors, A.pos, A.loff, A.llen, A.nbr, A.capV, A.capH, nvoff, ncn, nhoff, nchn);
+            }
+            __syncthreads();
+            if (err == SC_FALLBACK)
+            {
+                // (as in k_clip_convex: the general clipper goes on from the plane the regular one stopped at)
+                SolidIn cx = cin; uint32_t Fx = nP;
+                const bool resumed = SC_RESUME && stop != 0xFFFFFFFFu && stop > 0u && stop < nP;
+                float4* const keep = Hp->keep;      // (up to 126 planes: in the hull's LDS, which is done with)
+                if (resumed)
+                {
+                    const uint32_t nvs = U.f.nv[which];
+                    cx = sc_stage(U.f.buf[which], nvs, S.pos, S.g_loff, S.g_llen, S.g_ring);
+                    Fx = nP - stop;
+                    for (uint32_t k = tid; k < nP; k += group_size()) { keep[k] = sh.planes[k]; sh.pmar[k] = sh.planes[k]; }
+                    __syncthreads();
+                    for (uint32_t k = tid; k < Fx; k += group_size()) sh.planes[k] = sh.pmar[k + stop];
+                    __syncthreads();
+                    if (tid == 0) atomicAdd(&A.cursors[79], 1u);       // (diagnostic)
+                }
+                err = clip_any<false>(cx, Fx, S, sh, L, [&](auto& T) -> int {
+                    if (T.nLive == 0) return 0;
+                    return park_topo(T, sh, A, nvoff, ncn, nhoff, nchn);
+                }, &W);
+                __syncthreads();
+                if (resumed)
+                {
+                    for (uint32_t k = tid; k < nP; k += group_size()) sh.planes[k] = keep[k];      // (the fall-backs below start over with all of them)
+                    __syncthreads();
+                }
+            }
+            __syncthreads();
+#ifdef SURTR_STAMP
+            if (err == SURTR_OVERFLOW) dbg_path |= 1;
+            if (err == SURTR_E_TOPOLOGY) dbg_path |= 2;
+#endif
+            if (err == SURTR_OVERFLOW)
+            {
+                const ParkOut o = solid_global(cin, nP, pool, blockIdx.x, A, &sh);
+                err = o.err; nvoff = o.voff; ncn = o.n; nhoff = o.hoff; nchn = o.nh;
+                __syncthreads();
+            }
+        }
+#ifdef SURTR_STAMP
+        if (err == SURTR_E_TOPOLOGY) dbg_path |= 4;
+#endif
+        if (err == SURTR_E_TOPOLOGY)
+        {
+            // The Convex is the result of the pair's clip: its vertices carry the IDs of that clip's last compaction, their own
+            // indices -- unless no cell plane cut the piece's Convex, which then is a copy of the piece's with the IDs it came
+            // with (-1: built from arrays).  A cut changes the vertex set, so "uncut" = same vertices as the piece's Convex.
+            bool ids_set = piece_cpos != nullptr;
+            if (piece_cpos != nullptr)
+            {
+                const uint32_t c0 = piece_cvo[fr.piece], pn = piece_cvo[fr.piece + 1] - c0;
+                bool differs = pn != fr.cv_n;
+                if (!differs)
+                    for (uint32_t i = tid; i < 3u * pn; i += group_size()) if (piece_cpos[3 * (size_t)c0 + i] != cin.pos[i]) differs = true;
+                ids_set = __syncthreads_or(differs ? 1 : 0) != 0;
+            }
+            const ParkOut o = solid_literal(cin, nP, pool, blockIdx.x, A, &sh, ids_set);
+            if (o.err == 0) { err = 0; nvoff = o.voff; ncn = o.n; nhoff = o.hoff; nchn = o.nh; }
+            else if (o.err != SURTR_E_TOPOLOGY) err = o.err;
+            __syncthreads();
+        }
+        if (err == 0 && tid == 0)
+        {
+            // field-wise: k_faces updates other fields of the same record at the same time
+            frags[f].cv_off = nvoff; frags[f].cv_n = ncn; frags[f].ch_off = nhoff; frags[f].ch_n = nchn;
+        }
+        if (herr != 0 && frag_status != nullptr)
+        {
+            // An engine limit (refit_hull.h: a hull of more than 63 faces, a full table, a key out of range): the fragment keeps
+            // its un-refitted Convex and is flagged SURTR_E_CAPACITY; counted apart (surtr_queue_stats out[95]).
+            if (tid == 0 && atomicExch(&frag_status[f], (uint32_t)SURTR_E_CAPACITY) == 0u) { atomicAdd(&A.cursors[14], 1u); atomicAdd(&A.cursors[95], 1u); }
+        }
+        else if (err == SURTR_E_TOPOLOGY && frag_status != nullptr)
+        {
+            // Where the reference's own clip of this Convex by the slabs is no polyhedron any more (a link to a clipped vertex
+            // that survives, renumbered through a stale ID), the fragment keeps the Convex it had -- a superset of the refitted
+            // one -- and is flagged; the event and the other fragments stand (as for a fragment without triangles in k_faces).
+            if (tid == 0 && atomicExch(&frag_status[f], (uint32_t)SURTR_E_TOPOLOGY) == 0u) atomicAdd(&A.cursors[14], 1u);
+        }
+        else if (err != 0 && tid == 0) atomicMax(&A.cursors[5], (uint32_t)err);
+#ifdef SURTR_STAMP
+        if (tid == 0)
+        {
+            const unsigned long long d = __builtin_readcyclecounter() - r0; ++wg_tasks;
+            int bkt = 0; while ((d >> bkt) > 1 && bkt < 40) ++bkt; bkt = bkt < 12 ? 0 : bkt - 12; if (bkt > 15) bkt = 15;
+            atomicAdd(&g_stamp2[bkt], 1ull); atomicAdd(&g_stamp2[19], d);
+            const unsigned long long old = atomicMax(&g_stamp2[16], d);
+            if (d > old) { g_stamp2[17] = n; g_stamp2[18] = fr.cv_n; g_stamp2[60] = r1 - r0; g_stamp2[61] = r2 - r1; g_stamp2[62] = (unsigned long long)dbg_path; g_stamp2[63] = ncn; }
+            if (dbg_path & 1) atomicAdd(&g_stamp2[30], 1ull);
+            if (dbg_path & 6) atomicAdd(&g_stamp2[31], 1ull);
+        }
+#endif
+    }
+#ifdef SURTR_STAMP
+    if (tid == 0) { const unsigned long long d = __builtin_readcyclecounter() - wg_t0; atomicAdd(&g_stamp2[20], d); atomicMax(&g_stamp2[21], d); atomicAdd(&g_stamp2[22], 1ull); atomicMax(&g_stamp2[23], wg_tasks); }
+#endif
+}
+
+// Test entry: the hull normals of one cloud (surtr_hull_normals_device).  One wave; ws = 2 * n words.
+__global__ __launch_bounds__(SURTR_LANES) void k_hull_probe(const float* __restrict__ pts, uint32_t n, uint32_t limit, uint32_t* __restrict__ ws,
+                                                         float* __restrict__ normals, uint32_t* __restrict__ out /* [0] status, [1] count */)
+{
+    __shared__ RhLds H;
+    __shared__ ArgF slotF[SURTR_NWAVE];
+    __shared__ ArgD slotD[SURTR_NWAVE];
+    const int rc = rh_build(pts, n, n < limit ? n : limit, (float*)ws, ws + n, H, slotF, slotD);
+    if (rc == 0)
+        for (uint32_t i = threadIdx.x; i < 3u * H.nLive; i += group_size()) normals[i] = (&H.nrm[0][0])[i];
+    if (threadIdx.x == 0) { out[0] = (uint32_t)rc; out[1] = rc == 0 ? H.nLive : 0u; }
+}
+
 // ------------------------------------------------------------------ k_faces
 
 __device__ __forceinline__ bool on_right(const float* a, const float* b, const float* c, float nx, float ny, float nz)
@@ -3430,13 +3652,19 @@ static void free_arena(surtr_ctx* ctx)
     ctx->arena = Arena{}; ctx->arena.cursors = B.cursors; ctx->cap_frags = 0;
 }
 
+// Slab planes a refit clips a Convex by, as the arena estimates count them: 8 at RefittingPointLimit 4; above it the greedy
+// hull does not stay within 2L - 4 faces (DESIGN 3.14 measures about 3L - 8), and 63 faces are the engine's limit.
+static uint32_t refit_planes(const surtr_ctx* ctx) { return std::min(2u * RH_MAXFACE, 2u * (3u * ctx->refit_limit - 8u)); }
+
 static int ensure_arena(surtr_ctx* ctx, uint32_t n_pairs, uint64_t min_v = 0, uint64_t min_h = 0, uint64_t min_i = 0)
 {
     // Result sizes are data dependent.  Cells partition space, so the Mesh fragments of an event add up to the pieces plus
     // their cut points: the default reserves three times all pieces (at least eight times the largest one) plus slack per pair
     // (Convex results); surtr_set_arena overrides it, SURTR_E_CAPACITY reports a default that was too small.
-    uint64_t av = ctx->user_av ? ctx->user_av : std::max<uint64_t>(std::max<uint64_t>((uint64_t)ctx->vmax * 8, ctx->tot_mv * 3) + (uint64_t)n_pairs * 256, 1u << 16);
-    uint64_t ah = ctx->user_ah ? ctx->user_ah : std::max<uint64_t>(std::max<uint64_t>((uint64_t)ctx->hmax * 8, ctx->tot_mh * 3) + (uint64_t)n_pairs * 1024, 1u << 18);
+    // (a refit at a RefittingPointLimit above 4 clips by more than 8 planes: 8 vertices and 32 ring entries more per plane and pair)
+    const uint64_t xp = refit_planes(ctx) - 8u;
+    uint64_t av = ctx->user_av ? ctx->user_av : std::max<uint64_t>(std::max<uint64_t>((uint64_t)ctx->vmax * 8, ctx->tot_mv * 3) + (uint64_t)n_pairs * (256 + 8 * xp), 1u << 16);
+    uint64_t ah = ctx->user_ah ? ctx->user_ah : std::max<uint64_t>(std::max<uint64_t>((uint64_t)ctx->hmax * 8, ctx->tot_mh * 3) + (uint64_t)n_pairs * (1024 + 32 * xp), 1u << 18);
     uint64_t ai = ctx->user_ai ? ctx->user_ai : ah * 2;
     av = std::max(av, min_v); ah = std::max(ah, min_h); ai = std::max(ai, min_i);
     av = std::min<uint64_t>(av, 0xFFFFFFF0ull); ah = std::min<uint64_t>(ah, 0xFFFFFFF0ull); ai = std::min<uint64_t>(ai, 0xFFFFFFF0ull);
@@ -3614,6 +3842,27 @@ static EventPlan plan_event(const surtr_ctx* ctx, uint32_t n_pairs, bool pair_li
     return pl;
 }
 
+// k_refit_n's words per arena vertex (RefittingPointLimit above 4 only)
+static int ensure_hull_ws(surtr_ctx* ctx)
+{
+    if (ctx->refit_limit <= 4u || ctx->d_hull_ws.cap >= 2 * (size_t)ctx->arena.capV) return SURTR_OK;
+    HIPCHK(hipStreamSynchronize(ctx->stream));      // (a previous refit may still use the smaller one)
+    return ctx->d_hull_ws.grow(ctx, 2 * (size_t)ctx->arena.capV);
+}
+
+// k_refit, or k_refit_n where the context's RefittingPointLimit is above 4, on the current fragments
+static void launch_refit(surtr_ctx* ctx, uint32_t grid, hipStream_t st, bool of_pieces)
+{
+    const float* cpos = of_pieces ? (const float*)ctx->cset.pos : (const float*)nullptr;
+    const uint32_t* cvo = of_pieces ? (const uint32_t*)ctx->cset.vo : (const uint32_t*)nullptr;
+    if (ctx->refit_limit <= 4u)
+        hipLaunchKernelGGL(k_refit, dim3(grid), dim3(SURTR_LANES), 0, st, ctx->d_frags, ctx->d_counts, ctx->pool_small, ctx->arena, ctx->d_forder, ctx->cap_frags, ctx->d_frag_status,
+                           cpos, cvo);
+    else
+        hipLaunchKernelGGL(k_refit_n, dim3(grid), dim3(SURTR_LANES), 0, st, ctx->d_frags, ctx->d_counts, ctx->pool_small, ctx->arena, ctx->d_forder, ctx->cap_frags, ctx->d_frag_status,
+                           cpos, cvo, ctx->refit_limit, (uint32_t*)ctx->d_hull_ws);
+}
+
 static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, const uint2* d_pair_list, const uint8_t* outside, uint32_t flags)
 {
     (void)hipSetDevice(ctx->device);
@@ -3628,6 +3877,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     if (rc) return rc;
     rc = ensure_arena(ctx, n1);
     if (rc) return rc;
+    if (flags & SURTR_EVT_REFIT) { rc = ensure_hull_ws(ctx); if (rc) return rc; }
     rc = ensure_prep(ctx, n1, std::max(std::max(1u, std::min(n1, ctx->max_wg_prep)), ctx->n_wg_prep));
     if (rc) return rc;
     hipStream_t st = ctx->stream, st2 = ctx->stream2, st3 = ctx->stream3;
@@ -3774,8 +4024,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     if (flags & SURTR_EVT_REFIT)
     {
         PROF_BEGIN_ON(2, pl.st_refit);
-        hipLaunchKernelGGL(k_refit, dim3(pl.g_refit), dim3(SURTR_LANES), 0, pl.st_refit, ctx->d_frags, ctx->d_counts, ctx->pool_small, ctx->arena, ctx->d_forder, ctx->cap_frags, ctx->d_frag_status,
-                           (const float*)ctx->cset.pos, (const uint32_t*)ctx->cset.vo);
+        launch_refit(ctx, pl.g_refit, pl.st_refit, true);
         PROF_END_ON(2, pl.st_refit);
     }
     if (flags & SURTR_EVT_RENDER)
@@ -3888,11 +4137,12 @@ int surtr_event_refit(surtr_ctx* ctx)
     if (!ctx->have_event) return SURTR_E_STATE;
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
+    const int rc = ensure_hull_ws(ctx);
+    if (rc) return rc;
     // k_refit pulls fragments from work queue 6
     HIPCHK(hipMemsetAsync(ctx->arena.cursors + 6, 0, 4, st));
     PROF_BEGIN(2);
-    hipLaunchKernelGGL(k_refit, dim3(ctx->n_wg_small), dim3(SURTR_LANES), 0, st, ctx->d_frags, ctx->d_counts, ctx->pool_small, ctx->arena, ctx->d_forder, ctx->cap_frags, ctx->d_frag_status,
-                       ctx->frags_of_pieces ? (const float*)ctx->cset.pos : (const float*)nullptr, ctx->frags_of_pieces ? (const uint32_t*)ctx->cset.vo : (const uint32_t*)nullptr);
+    launch_refit(ctx, ctx->n_wg_small, st, ctx->frags_of_pieces);
     PROF_END(2);
     hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(SURTR_WG_WIDE), 0, st, ctx->d_frags, ctx->d_scanblk, ctx->d_counts, ctx->arena);
     HIPCHK(hipGetLastError());
@@ -3966,8 +4216,10 @@ int surtr_load_fragments(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const 
     if (rc) return rc;
     rc = ensure_scratch_small(ctx, std::max(ctx->max_wg_small, ctx->n_wg_small));
     if (rc) return rc;
-    // the solids, the refitted Convex solids (a clip by 8 planes adds a few vertices per plane), 3 indices per half-edge at most
-    rc = ensure_arena(ctx, n, (uint64_t)MV + 3ull * CV + 64ull * n, (uint64_t)MH + 4ull * CH + 256ull * n, 3ull * MH + 64);
+    // the solids, the refitted Convex solids (a clip by 8 planes -- 2F at a RefittingPointLimit above 4, refit_planes -- adds a
+    // few vertices per plane), 3 indices per half-edge at most
+    const uint64_t rp = refit_planes(ctx);
+    rc = ensure_arena(ctx, n, (uint64_t)MV + 3ull * CV + 8ull * rp * n, (uint64_t)MH + 4ull * CH + 32ull * rp * n, 3ull * MH + 64);
     if (rc) return rc;
     if (n > ctx->cap_frags) return SURTR_E_CAPACITY;
     hipStream_t st = ctx->stream;
@@ -4028,8 +4280,15 @@ int surtr_refit_solid(surtr_ctx* ctx, uint32_t mnv, const float* mpos, const uin
     surtr_counts c;
     rc = surtr_event_counts(ctx, &c);
     if (rc) return rc;
-    if (c.n_failed != 0)      // one solid was asked for: the reference's clip of it by the slabs is no polyhedron
+    if (c.n_failed != 0)      // one solid was asked for: the reference's clip of it by the slabs is no polyhedron, or its hull is beyond the engine's limits
     {
+        uint32_t why = 0;
+        if (hipMemcpy(&why, ctx->d_frag_status, 4, hipMemcpyDeviceToHost) != hipSuccess) return SURTR_E_HIP;
+        if (why == (uint32_t)SURTR_E_CAPACITY)
+        {
+            ctx->err = "refit: the limited hull of this solid has more than 63 faces (or a coordinate out of the edge keys' range)";
+            return SURTR_E_CAPACITY;
+        }
         ctx->err = "refit: the reference's result for this solid is not a polyhedron";
         return SURTR_E_TOPOLOGY;
     }
@@ -4266,6 +4525,47 @@ int surtr_event_pair_costs(surtr_ctx* ctx, uint32_t n_pairs, uint32_t* cost)
         if (r.cv_n != 0) c += (r.img_fmt == IMG_NARROW || r.img_fmt == IMG_WIDE ? r.img_n : 256u) + 4u * r.mv_n + 64u;
         cost[i] = c;
     }
+    return SURTR_OK;
+}
+
+int surtr_set_refit_point_limit(surtr_ctx* ctx, uint32_t n)
+{
+    if (!ctx || n < 4u || n > RH_MAXPT) return SURTR_E_INVALID;
+    ctx->refit_limit = n;
+    return SURTR_OK;
+}
+
+int surtr_get_refit_point_limit(surtr_ctx* ctx, uint32_t* n)
+{
+    if (!ctx || !n) return SURTR_E_INVALID;
+    *n = ctx->refit_limit;
+    return SURTR_OK;
+}
+
+int surtr_coord_key(float x, uint32_t* neg, uint64_t* scaled)
+{
+    if (!neg || !scaled) return SURTR_E_INVALID;
+    return rh_coord_key(x, scaled, neg) ? SURTR_OK : SURTR_E_CAPACITY;
+}
+
+int surtr_hull_normals_device(surtr_ctx* ctx, uint32_t n, const float* points, uint32_t limit, uint32_t capacity, float* normals, uint32_t* count)
+{
+    if (!ctx || !points || !count || n < 4u || limit < 4u || limit > RH_MAXPT) return SURTR_E_INVALID;
+    (void)hipSetDevice(ctx->device);
+    DevBuf<float> d_pts, d_nrm; DevBuf<uint32_t> d_ws, d_out;
+    if (d_pts.grow(ctx, 3 * (size_t)n) || d_nrm.grow(ctx, 3 * RH_MAXFACE) || d_ws.grow(ctx, 2 * (size_t)n) || d_out.grow(ctx, 2)) return SURTR_E_HIP;
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipMemcpyAsync(d_pts, points, (size_t)n * 12, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_hull_probe, dim3(1), dim3(SURTR_LANES), 0, st, (const float*)d_pts, n, limit, (uint32_t*)d_ws, (float*)d_nrm, (uint32_t*)d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    uint32_t out[2] = {0u, 0u};
+    HIPCHK(hipMemcpy(out, d_out, 8, hipMemcpyDeviceToHost));
+    if (out[0] != 0u) return (int)out[0];
+    *count = out[1];
+    if (!normals) return SURTR_OK;
+    if (out[1] > capacity) return SURTR_E_CAPACITY;
+    if (out[1]) HIPCHK(hipMemcpy(normals, d_nrm, (size_t)out[1] * 12, hipMemcpyDeviceToHost));
     return SURTR_OK;
 }
 

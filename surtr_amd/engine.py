@@ -357,6 +357,25 @@ class Engine:
     def event_refit(self):
         self._ck(lib().surtr_event_refit(self._h))
 
+    def set_refit_point_limit(self, n):
+        """FractureArgs::RefittingPointLimit, 4 (default) .. 32 (surtr_set_refit_point_limit): read by EVT_REFIT events,
+        event_refit and refit_solid."""
+        self._ck(lib().surtr_set_refit_point_limit(self._h, ctypes.c_uint32(int(n))))
+
+    def get_refit_point_limit(self):
+        n = ctypes.c_uint32()
+        self._ck(lib().surtr_get_refit_point_limit(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def hull_normals_device(self, points, limit):
+        """For tests: face normals of the limited hull as the refit kernel builds it (surtr_hull_normals_device)."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        cnt = ctypes.c_uint32()
+        out = np.zeros((63, 3), np.float32)
+        self._ck(lib().surtr_hull_normals_device(self._h, ctypes.c_uint32(p.shape[0]), _p(p), ctypes.c_uint32(int(limit)), ctypes.c_uint32(63),
+                                                 _p(out), ctypes.byref(cnt)))
+        return out[:cnt.value].copy()
+
     def event_counts(self):
         c = Counts()
         self._ck(lib().surtr_event_counts(self._h, ctypes.byref(c)))
@@ -596,6 +615,15 @@ def pair_block(rank, world, n_pairs):
     return (rank * n_pairs) // world, ((rank + 1) * n_pairs) // world
 
 
+def coord_key(x):
+    """For tests: (sign bit, |x| * 10^6 rounded half-to-even) of a float32, the key of a coordinate in the device hull's edge keys."""
+    neg, scaled = ctypes.c_uint32(), ctypes.c_uint64()
+    rc = lib().surtr_coord_key(ctypes.c_float(x), ctypes.byref(neg), ctypes.byref(scaled))
+    if rc:
+        raise SurtrError(rc)
+    return int(neg.value), int(scaled.value)
+
+
 def hull_normals(points, limit):
     """VMACH::ConvexHull(points, limit) face normals (host helper)."""
     p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
@@ -605,6 +633,17 @@ def hull_normals(points, limit):
         raise SurtrError(rc)
     out = np.zeros((cnt.value, 3), np.float32)
     rc = lib().surtr_hull_normals(ctypes.c_uint32(p.shape[0]), _p(p), ctypes.c_uint32(limit), ctypes.c_uint32(cnt.value), _p(out), ctypes.byref(cnt))
+    if rc:
+        raise SurtrError(rc)
+    return out
+
+
+def kdop_planes(points, normals):
+    """Kdop::Calc(Polyhedron) slab planes (host helper surtr_kdop_planes): Min plane then Max plane per normal."""
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    out = np.zeros((2 * n.shape[0], 4), np.float32)
+    rc = lib().surtr_kdop_planes(ctypes.c_uint32(p.shape[0]), _p(p), ctypes.c_uint32(n.shape[0]), _p(n), _p(out))
     if rc:
         raise SurtrError(rc)
     return out

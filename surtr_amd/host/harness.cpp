@@ -98,6 +98,10 @@ static void api_dump(const char* path, const std::vector<Fragment>& frags, const
             kdop.Calc(pc.Mesh);
             fprintf(f, ", "); js_solid(f, "refit_kdop", kdop.ClipWithPolyhedron(pc.Convex));
             fprintf(f, ", "); js_solid(f, "refit_task", DefaultEngine().RefitSolid(pc.Mesh, pc.Convex));
+            // the same task at FractureArgs::RefittingPointLimit = 8 (the device's limited hull), and back to the default
+            DefaultEngine().SetRefittingPointLimit(8);
+            fprintf(f, ", "); js_solid(f, "refit_task_limit8", DefaultEngine().RefitSolid(pc.Mesh, pc.Convex));
+            DefaultEngine().SetRefittingPointLimit(4);
         }
         // Poly::Moments, Poly::Transform
         double vol = 0; Vector3 c1;

@@ -703,6 +703,7 @@ std::vector<Compound> FractureEngine::DoFracture(const Compound& targetCompound,
 {
     // Scale + alignment of the pattern (Src/Surtr.cpp:1890-1896): every cell scaled by MaxAxisScale * 2, moved to the impact
     const float s2 = maxAxisScale * 2.f;
+    SetRefittingPointLimit(args.RefittingPointLimit);      // (before the event: its arena is sized for the refit's planes)
     PlacePattern(Vector3(s2, s2, s2), args.ImpactPosition);
     // the sphere point cloud: v *= ImpactRadius; v += ImpactPosition (:1911-1915)
     std::vector<Vector3> cloud = spherePointCloud;
@@ -773,7 +774,7 @@ std::vector<Piece*> FractureTask(const VMACH::Polygon3D& voroPoly, const std::ve
 
 void RefittingTask(Piece* piece)
 {
-    // m_refittingTask (Src/Surtr.cpp:1449-1455)
+    // m_refittingTask (Src/Surtr.cpp:1449-1455), at the default engine's RefittingPointLimit
     piece->Convex = DefaultEngine().RefitSolid(piece->Mesh, piece->Convex);
 }
 

@@ -144,6 +144,7 @@ struct FractureArgs
     Vector3 ImpactPosition;
     float ImpactRadius = 1.f;
     int Seed = 46354;
+    int RefittingPointLimit = 4;      // points of the limited hull behind a fragment's slab planes (Inc/Surtr.h:93): 4 .. 32 here
 };
 
 struct FragmentRender { std::vector<VertexNormalColor> vertexData; std::vector<uint32_t> indexData; };
@@ -249,6 +250,10 @@ public:
     const FlaggedUnits& LastFlagged() const { return flagged_; }
     // How many engines the host keeps busy on this GPU at once (surtr_set_events_in_flight: no result changes, events of a few
     // hundred pairs then take the kernels that leave the other engines room).  The reference runs one event at a time.
+    // FractureArgs::RefittingPointLimit for RefitSolid, RefittingTask (on the default engine) and events with refit; DoFracture
+    // sets it from its `args`.  4 .. 32, anything else throws Error(SURTR_E_INVALID).
+    void SetRefittingPointLimit(int n) { check(surtr_set_refit_point_limit(ctx_, n < 0 ? 0u : (uint32_t)n), "surtr_set_refit_point_limit"); }
+    int RefittingPointLimit() { uint32_t n = 4; check(surtr_get_refit_point_limit(ctx_, &n), "surtr_get_refit_point_limit"); return (int)n; }
     void SetEventsInFlight(uint32_t n) { check(surtr_set_events_in_flight(ctx_, n), "surtr_set_events_in_flight"); }
     surtr_ctx* Raw() { return ctx_; }
 
