@@ -528,7 +528,8 @@ __device__ __attribute__((noinline)) static ParkOut solid_global(SolidIn in, uin
 // everything by value (see pair_global).  o.err: 0 (o.n == 0: the reference's answer is "empty") or the error that stands.
 // True (uniform over the workgroup) when some ring of the solid lists a neighbour twice, or a link has no way back (the result
 // of a clip that went through a stale ID): a solid the literal clipper takes from the start (see Pieces::mdup).
-__device__ static bool solid_is_sliver(const SolidIn in)
+// (the body apart and inlined where a by-value copy of the solid in the caller's frame counts: the refit kernels)
+__device__ __forceinline__ static bool solid_is_sliver_inl(const SolidIn& in)
 {
     bool odd = false;
     for (uint32_t v = threadIdx.x; v < in.nv; v += group_size())
@@ -549,6 +550,7 @@ __device__ static bool solid_is_sliver(const SolidIn in)
     }
     return __syncthreads_or(odd ? 1 : 0) != 0;
 }
+__device__ static bool solid_is_sliver(const SolidIn in) { return solid_is_sliver_inl(in); }
 
 struct LitRun { int err; uint32_t n, nh; LitSolid LS; const uint32_t* off; bool stale; };
 __device__ __attribute__((noinline)) static LitRun literal_run(SolidIn in, uint32_t F, ScratchPool pool, uint32_t wg, Shared* shp, bool ids_set = false,
@@ -602,6 +604,118 @@ __device__ __attribute__((noinline)) static ParkOut solid_literal(SolidIn in, ui
     return o;
 }
 
+// ---------------------------------------------------------------- the clip of one Convex by the planes in sh.planes
+// k_clip_convex (a piece's Convex by a cell's planes) and the refit kernels (a fragment's Convex by its slab planes) clip through
+// this one chain of four clippers, each taking what the one before cannot answer for:
+//   1. small_clip, the one-wave clipper of regular planes, parked by sc_park.  It hands on (SC_FALLBACK) at the first plane it does
+//      not take, and says which.
+//   2. clip_any<false>, the general one-wave clipper, parked by park_topo.  It goes on where the regular one stopped: from the solid
+//      before that plane (the reference's compacted solid, :464-495), staged through this workgroup's global scratch (the arrays of
+//      the wide topology, which the LDS variant leaves alone), with the remaining planes.  Anything but success there starts over
+//      from the caller's Convex and all planes, so all of them are brought back to sh.planes afterwards.
+//   3. solid_global on SURTR_OVERFLOW: the wide topology in global scratch.
+//   4. solid_literal on SURTR_E_TOPOLOGY: the parallel relink met a walk it cannot follow (a degenerate sliver); the literal
+//      single-lane clip has the reference's answer wherever the reference has one (mostly "empty").  A Convex whose ring lists a
+//      neighbour twice (literal_first) comes here from the start: the parallel clippers differ from the reference on it.
+// The result is what was parked in the arena; an err of SURTR_E_TOPOLOGY that is left means the reference itself has no valid
+// result, and what becomes of the pair or fragment then is the caller's business.
+struct ChainCaller
+{
+    uint32_t slot_took, slot_resumed;      // A.cursors (diagnostic): slot_took counts what small_clip took, slot_took + 1 what it handed
+                                           // on; slot_resumed the general clips resumed from a later plane
+    bool count_literal_first;              // slot_took + 1 counts the solids that start on the literal clipper too
+    float4* keep;                          // all F planes are saved here before a resumed general clip (nullptr: not saved) ...
+    const float4* restore_from;            // ... and come back from here after it (keep, or wherever the caller has them anyway)
+};
+struct LiteralArg { SolidIn in; bool ids_set; };
+struct ChainStamp { unsigned long long t_small, t_park; int path; };      // (SURTR_STAMP builds)
+// literal(): what step 4 is given, asked for there only: the Convex once more (k_clip_convex derives it from the piece again: ten
+// pointers fewer to keep across the calls of step 3, which is what holds that kernel at two waves per SIMD) and ids_set, what
+// literal_clip wants to know of it (do its vertices carry the IDs of a compaction).
+// Inlined into its three kernels: F is a constant in k_refit, and the register budget of all three is two waves per SIMD.
+template <class Literal>
+__device__ __forceinline__ ParkOut convex_chain(const SolidIn cin, const uint32_t F, bool literal_first, const ChainCaller who, Literal&& literal,
+                                                Shared& sh, OneWaveLds& U, Scratch& S, const ScratchPool& pool, const Arena& A, ChainStamp& st)
+{
+    const uint32_t tid = threadIdx.x;
+    ParkOut o{SURTR_E_TOPOLOGY, 0u, 0u, 0u, 0u, false};
+    uint32_t which = 0, stop = 0xFFFFFFFFu;
+#ifdef SURTR_NO_SMALL_CLIP      // (diagnostic builds: the general clipper alone)
+    literal_first = false;
+    o.err = SC_FALLBACK;
+#else
+    if (!literal_first) o.err = small_clip(cin, F, sh, U.f, &which, &stop);
+#endif
+    if (tid == 0 && (!literal_first || who.count_literal_first)) atomicAdd(&A.cursors[who.slot_took + (o.err == 0 ? 0u : 1u)], 1u);
+#ifdef SURTR_STAMP
+    st.t_small = st.t_park = __builtin_readcyclecounter();
+#endif
+    if (!literal_first)
+    {
+        if (o.err == 0)
+        {
+            const uint32_t nv = U.f.nv[which];
+            if (nv != 0u) o.err = sc_park(U.f.buf[which], nv, sh, A.cursors, A.pos, A.loff, A.llen, A.nbr, A.capV, A.capH, o.voff, o.n, o.hoff, o.nh);
+        }
+        __syncthreads();
+#ifdef SURTR_STAMP
+        st.t_park = __builtin_readcyclecounter();
+#endif
+        if (o.err == SC_FALLBACK)
+        {
+            SolidIn cx = cin; uint32_t Fx = F;
+            const bool resumed = SC_RESUME && stop != 0xFFFFFFFFu && stop > 0u && stop < F;
+            if (resumed)
+            {
+                const uint32_t nvs = U.f.nv[which];
+                cx = sc_stage(U.f.buf[which], nvs, S.pos, S.g_loff, S.g_llen, S.g_ring);
+                Fx = F - stop;
+                for (uint32_t k = tid; k < F; k += group_size())      // (pmar: free in all three kernels while a Convex is clipped)
+                {
+                    const float4 pk = sh.planes[k];
+                    if (who.keep != nullptr) who.keep[k] = pk;
+                    sh.pmar[k] = pk;
+                }
+                __syncthreads();
+                for (uint32_t k = tid; k < Fx; k += group_size()) sh.planes[k] = sh.pmar[k + stop];
+                __syncthreads();
+                if (tid == 0) atomicAdd(&A.cursors[who.slot_resumed], 1u);
+            }
+            o.err = clip_any<false>(cx, Fx, S, sh, U.g.L, [&](auto& T) -> int {
+                if (T.nLive == 0) return 0;
+                return park_topo(T, sh, A, o.voff, o.n, o.hoff, o.nh);
+            }, &U.g.W);
+            __syncthreads();
+            if (resumed)
+            {
+                for (uint32_t k = tid; k < F; k += group_size()) sh.planes[k] = who.restore_from[k];
+                __syncthreads();
+            }
+        }
+#ifdef SURTR_STAMP
+        if (o.err == SURTR_OVERFLOW) st.path |= 1;
+        if (o.err == SURTR_E_TOPOLOGY) st.path |= 2;
+#endif
+        if (o.err == SURTR_OVERFLOW)
+        {
+            o = solid_global(cin, F, pool, blockIdx.x, A, &sh);
+            __syncthreads();
+        }
+    }
+    if (o.err == SURTR_E_TOPOLOGY)
+    {
+#ifdef SURTR_STAMP
+        st.path |= 4;
+#endif
+        const LiteralArg la = literal();
+        const ParkOut l = solid_literal(la.in, F, pool, blockIdx.x, A, &sh, la.ids_set);
+        if (l.err == 0) o = l;
+        else if (l.err != SURTR_E_TOPOLOGY) o.err = l.err;
+        __syncthreads();
+    }
+    return o;
+}
+
 #ifndef SURTR_LITERAL_MESH_V
 #define SURTR_LITERAL_MESH_V 2048u      // Mesh solids up to this size may take the literal clip after a topology error (one lane: slow)
 #define SURTR_LITERAL_START_V 64u       // Mesh solids up to this size take it from the start when a ring lists a neighbour twice
@@ -642,86 +756,25 @@ __global__ __launch_bounds__(SURTR_LANES) __attribute__((amdgpu_waves_per_eu(SUR
         const uint32_t f0 = plane_off[cell], F = plane_off[cell + 1] - f0;
         if (F > SURTR_MAXF) { rec.status = SURTR_E_INVALID; skip = true; }
         int err = 0;
+        ChainStamp cst{};      // (SURTR_STAMP builds: when the regular clipper and its parking were done)
 #ifdef SURTR_STAMP
         const unsigned long long cx0 = __builtin_readcyclecounter();
-        unsigned long long cx1 = cx0, cx2 = cx0, cx3 = cx0;
+        cst.t_small = cst.t_park = cx0;
 #endif
         if (!skip)
         {
             for (uint32_t k = tid; k < F; k += group_size()) sh.planes[k] = planes[f0 + k];
             __syncthreads();
-            const uint32_t c0 = P.cvo[piece];
-            SolidIn cin{P.cpos + 3 * (size_t)c0, P.cloff + c0, P.cllen + c0, P.cnbr, P.cvo[piece + 1] - c0, P.ctri + c0, P.crad + c0,
-                        P.cperm + c0, P.cposr_s + c0, P.cbsph + P.cbo[piece]};
-            uint32_t which = 0;
-            const bool sliver = P.cdup[piece] != 0;      // a ring lists a neighbour twice: the literal clipper below, from the start
-#ifdef SURTR_NO_SMALL_CLIP      // (diagnostic builds: the general clipper alone)
-            err = SC_FALLBACK;
-#else
-            uint32_t stop = 0xFFFFFFFFu;
-            err = sliver ? SURTR_E_TOPOLOGY : small_clip(cin, F, sh, U.f, &which, &stop);
-#endif
-            if (tid == 0) atomicAdd(&A.cursors[err == 0 ? 80 : 81], 1u);       // (diagnostic: tasks the regular clipper took / handed on)
-#ifdef SURTR_STAMP
-            cx1 = __builtin_readcyclecounter();
-#endif
-            if (err == 0)
-            {
-                const uint32_t nv = U.f.nv[which];
-                if (nv != 0u) err = sc_park(U.f.buf[which], nv, sh, A.cursors, A.pos, A.loff, A.llen, A.nbr, A.capV, A.capH, rec.cv_off, rec.cv_n, rec.ch_off, rec.ch_n);
-            }
-            __syncthreads();
-#ifdef SURTR_STAMP
-            cx2 = __builtin_readcyclecounter();
-#endif
-            if (err == SC_FALLBACK)
-            {
-                // The general clipper goes on where the regular one stopped: from the solid before that plane (the reference's
-                // compacted solid, :464-495), staged through this workgroup's global scratch (the arrays of the wide topology,
-                // which the LDS variant leaves alone), with the remaining planes.  Anything but success there starts over from
-                // the piece's Convex and all planes, as before.
-                SolidIn cx = cin; uint32_t Fx = F;
-                const bool resumed = SC_RESUME && stop != 0xFFFFFFFFu && stop > 0u && stop < F;
-                if (resumed)
-                {
-                    const uint32_t nvs = U.f.nv[which];
-                    cx = sc_stage(U.f.buf[which], nvs, S.pos, S.g_loff, S.g_llen, S.g_ring);
-                    Fx = F - stop;
-                    for (uint32_t k = tid; k < Fx; k += group_size()) sh.pmar[k] = sh.planes[k + stop];      // (pmar: free until the estimate below)
-                    __syncthreads();
-                    for (uint32_t k = tid; k < Fx; k += group_size()) sh.planes[k] = sh.pmar[k];
-                    __syncthreads();
-                    if (tid == 0) atomicAdd(&A.cursors[78], 1u);       // (diagnostic: general clips resumed from a later plane)
-                }
-                err = clip_any<false>(cx, Fx, S, sh, L, [&](auto& T) -> int {
-                    if (T.nLive == 0) return 0;
-                    return park_topo(T, sh, A, rec.cv_off, rec.cv_n, rec.ch_off, rec.ch_n);
-                }, &W);
-                __syncthreads();
-                if (resumed)
-                {
-                    for (uint32_t k = tid; k < F; k += group_size()) sh.planes[k] = planes[f0 + k];      // (the cost estimate below and the fall-backs want them all)
-                    __syncthreads();
-                }
-            }
-            if (err == SURTR_OVERFLOW)
-            {
-                const ParkOut o = solid_global(cin, F, pool, blockIdx.x, A, &sh);
-                err = o.err; rec.cv_off = o.voff; rec.cv_n = o.n; rec.ch_off = o.hoff; rec.ch_n = o.nh;
-                __syncthreads();
-            }
-        }
-        if (err == SURTR_E_TOPOLOGY)
-        {
-            // the parallel relink met a walk it cannot follow (a degenerate sliver): the literal single-lane clip has the
-            // reference's answer wherever the reference has one (mostly "empty")
-            const uint32_t c0 = P.cvo[piece];
-            const SolidIn cin{P.cpos + 3 * (size_t)c0, P.cloff + c0, P.cllen + c0, P.cnbr, P.cvo[piece + 1] - c0, P.ctri + c0, P.crad + c0,
-                              P.cperm + c0, P.cposr_s + c0, P.cbsph + P.cbo[piece]};
-            const ParkOut o = solid_literal(cin, F, pool, blockIdx.x, A, &sh);
-            if (o.err == 0) { err = 0; rec.cv_off = o.voff; rec.cv_n = o.n; rec.ch_off = o.hoff; rec.ch_n = o.nh; }
-            else if (o.err != SURTR_E_TOPOLOGY) err = o.err;
-            __syncthreads();
+            auto convex = [&] {
+                const uint32_t c0 = P.cvo[piece];
+                return SolidIn{P.cpos + 3 * (size_t)c0, P.cloff + c0, P.cllen + c0, P.cnbr, P.cvo[piece + 1] - c0, P.ctri + c0, P.crad + c0,
+                               P.cperm + c0, P.cposr_s + c0, P.cbsph + P.cbo[piece]};
+            };
+            // a ring that lists a neighbour twice: the literal clipper from the start.  All planes come back from the cell's list
+            // (the cost estimate below wants them too).
+            const ChainCaller who{80u, 78u, true, nullptr, planes + f0};
+            const ParkOut o = convex_chain(convex(), F, P.cdup[piece] != 0, who, [&] { return LiteralArg{convex(), false}; }, sh, U, S, pool, A, cst);
+            err = o.err; rec.cv_off = o.voff; rec.cv_n = o.n; rec.ch_off = o.hoff; rec.ch_n = o.nh;
         }
         if (err == SURTR_E_TOPOLOGY) { rec.cv_bad = 1; rec.cv_off = 0; rec.cv_n = 1; rec.ch_off = 0; rec.ch_n = 0; err = 0; }
         if (err != 0) { rec.status = (uint32_t)err; rec.cv_n = 0; if (tid == 0) atomicMax(&A.cursors[5], (uint32_t)err); }
@@ -786,7 +839,7 @@ __global__ __launch_bounds__(SURTR_LANES) __attribute__((amdgpu_waves_per_eu(SUR
         if (tid == 0)
         {
             // the slowest pair of the launch: where its time went (scripts/stamps_convex.py)
-            cx3 = __builtin_readcyclecounter();
+            const unsigned long long cx1 = cst.t_small, cx2 = cst.t_park, cx3 = __builtin_readcyclecounter();
             const unsigned long long d = cx3 - cx0;
             atomicAdd(&g_stamp2[32], d); atomicAdd(&g_stamp2[33], 1ull);
             const unsigned long long old = atomicMax(&g_stamp2[34], d);
@@ -1689,45 +1742,21 @@ __device__ __forceinline__ float hull_vol(const float* a, const float* b, const 
     return ax * (by * cz - bz * cy) + ay * (bz * cx - bx * cz) + az * (bx * cy - by * cx);
 }
 
-__global__ __launch_bounds__(SURTR_LANES) void k_refit(FragRec* __restrict__ frags, const surtr_counts* __restrict__ counts,
-                                                    ScratchPool pool, Arena A, const uint32_t* __restrict__ forder, uint32_t cap_frags,
-                                                    uint32_t* __restrict__ frag_status, const float* __restrict__ piece_cpos,
-                                                    const uint32_t* __restrict__ piece_cvo)
+#include "refit_hull.h"
+
+// ------------------------------------------------------------------ refit
+// The hull front end of a refit: the face normals whose slabs clip the fragment's Convex.  Lds is what it keeps in LDS, build()
+// leaves faces(H) unit normals in H.nrm (non-zero: no hull within the engine's limits), keep() is where the 2 * faces slab planes
+// wait while the general clipper runs on a rest of them (ChainCaller::keep).
+struct HullFirst4      // RefittingPointLimit 4: the first tetrahedron
 {
-    __shared__ Shared sh;
-    __shared__ ArgF slotF[SURTR_NWAVE];
-    __shared__ ArgD slotD[SURTR_NWAVE];
-    __shared__ float nrm[4][3];
-    __shared__ OneWaveLds U;      // (the one-wave clipper of regular planes shares the bytes of the general one's arrays)
-    LdsTopoSmall& L = U.g.L; LdsWorkSmall& W = U.g.W;
-    Scratch S = carve(pool, blockIdx.x);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t nf = counts->n_frag;
-#ifdef SURTR_STAMP
-    const unsigned long long wg_t0 = __builtin_readcyclecounter();
-    unsigned long long wg_tasks = 0;
-#endif
-    while (true)
+    struct Lds { float nrm[4][3]; };
+    __device__ __forceinline__ static uint32_t faces(const Lds&) { return 4u; }
+    __device__ __forceinline__ static float4* keep(Lds&, const Scratch& S) { return (float4*)S.g_comp; }      // (a byte array of the wide topology: 128 bytes of it)
+    // (out of line: inlined into both instances of the slab step, LDS and global points, it doubles k_refit's code and costs it 7 registers)
+    __device__ __attribute__((noinline)) int build(const float* mp, const uint32_t n, uint32_t /* mv_off */, Lds& H, ArgF* slotF, ArgD* slotD) const
     {
-        __syncthreads();
-        if (tid == 0) sh.misc[7] = frag_of_ticket(A, forder, cap_frags, atomicAdd(&A.cursors[6], 1u));
-        __syncthreads();
-        const uint32_t f = sh.misc[7];
-        if (f >= nf) break;
-        FragRec fr = frags[f];
-        const float* mpg = A.pos + 3 * (size_t)fr.mv_off;
-        const uint32_t n = fr.mv_n;
-#ifdef SURTR_STAMP
-        const unsigned long long r0 = __builtin_readcyclecounter();
-#endif
-        // The fragment's vertices are read a dozen times (four hull passes, eight slab extremes): a fragment of up to
-        // 2 * LdsWorkSmall::kN vertices is staged once in the LDS work arrays, which nothing uses before the clip below.
-#ifdef SURTR_STAMP
-        unsigned long long r1 = 0;
-#endif
-        static_assert(offsetof(LdsWorkSmall, aux0) == sizeof(float) * 3 * LdsWorkSmall::kN && offsetof(LdsWorkSmall, aux1) == sizeof(float) * 4 * LdsWorkSmall::kN &&
-                      offsetof(LdsWorkSmall, aux2) == sizeof(float) * 5 * LdsWorkSmall::kN, "pos, aux0, aux1, aux2 are contiguous");
-        auto slabs = [&](const auto* mp) {
+        const uint32_t tid = threadIdx.x;
         // ---- BuildFirstHull (Src/VMACH.cpp:1036-1085) with limit min(n,4) = 4 ----
         ArgF a; a.i = 0xFFFFFFFFu; a.v = 0.f;
         for (uint32_t v = tid; v < n; v += group_size())
@@ -1786,180 +1815,55 @@ __global__ __launch_bounds__(SURTR_LANES) void k_refit(FragRec* __restrict__ fra
                 float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
                 const float len = sqrtf(dot3(nx, ny, nz, nx, ny, nz));
                 if (len != 0.f) { nx = nx / len; ny = ny / len; nz = nz / len; } else { nx = ny = nz = 0.f; }
-                nrm[k][0] = nx; nrm[k][1] = ny; nrm[k][2] = nz;
+                H.nrm[k][0] = nx; H.nrm[k][1] = ny; H.nrm[k][2] = nz;
             }
         }
         __syncthreads();
-#ifdef SURTR_STAMP
-        r1 = __builtin_readcyclecounter();
-#endif
-        // ---- Kdop::Calc(Polyhedron) (Src/Kdop.cpp:92-115): first minimum / first maximum of n.v ----
-        for (int k = 0; k < 4; ++k)
-        {
-            ArgF lo, hi; lo.i = hi.i = 0xFFFFFFFFu; lo.v = hi.v = 0.f;
-            const float nx = nrm[k][0], ny = nrm[k][1], nz = nrm[k][2];
-            for (uint32_t v = tid; v < n; v += group_size())
-            {
-                const float t = dot3(mp[3 * v], mp[3 * v + 1], mp[3 * v + 2], nx, ny, nz);
-                if (hi.i == 0xFFFFFFFFu || t > hi.v) { hi.v = t; hi.i = v; }
-                if (lo.i == 0xFFFFFFFFu || -t > lo.v) { lo.v = -t; lo.i = v; }
-            }
-            hi = wg_argmax<float, ArgF>(hi, slotF);
-            lo = wg_argmax<float, ArgF>(lo, slotF);
-            if (tid == 0)
-            {
-                // MinPlane = Plane(vert, -n), MaxPlane = Plane(vert, n); order Min, Max (:166-179)
-                const float* a0 = mp + 3 * lo.i; const float* a1 = mp + 3 * hi.i;
-                sh.planes[2 * k] = make_float4(-nx, -ny, -nz, -dot3(a0[0], a0[1], a0[2], -nx, -ny, -nz));
-                sh.planes[2 * k + 1] = make_float4(nx, ny, nz, -dot3(a1[0], a1[1], a1[2], nx, ny, nz));
-            }
-        }
-        __syncthreads();
-        };
-        if (n <= 2u * LdsWorkSmall::kN)
-        {
-            float* lp = W.pos;
-            for (uint32_t i = tid; i < 3u * n; i += group_size()) lp[i] = mpg[i];
-            __syncthreads();
-            slabs((const float*)lp);
-            __syncthreads();
-        }
-        else slabs(mpg);
-#ifdef SURTR_STAMP
-        const unsigned long long r2 = __builtin_readcyclecounter();
-        if (tid == 0) { atomicAdd(&g_stamp[94], r1 - r0); atomicAdd(&g_stamp[95], r2 - r1); }
-        int dbg_path = 0;
-#endif
-        SolidIn cin{A.pos + 3 * (size_t)fr.cv_off, A.loff + fr.cv_off, A.llen + fr.cv_off, A.nbr, fr.cv_n, nullptr, nullptr, nullptr, nullptr, nullptr};
-        // arena rings are absolute offsets into A.nbr, which is what SolidIn expects
-        uint32_t nvoff = 0, ncn = 0, nhoff = 0, nchn = 0;
-        // (no small_clip attempt here: the slab planes pass through extreme vertices of the fragment, which are vertices of its
-        // Convex as often as not -- measured on configs[3]: 2 385 of 2 692 refits have a vertex exactly in a plane)
-        int err = SURTR_E_TOPOLOGY;      // a sliver Convex: the literal clipper below, from the start
-        if (!solid_is_sliver(cin))
-        {
-            // the regular clipper first: it takes the Convex whose slab planes either cut no vertex (the plane through an extreme
-            // vertex of the fragment that is an extreme vertex of its Convex too) or cut with no vertex in the plane
-            uint32_t which = 0, stop = 0xFFFFFFFFu;
-            err = small_clip(cin, 8, sh, U.f, &which, &stop);
-            if (tid == 0) atomicAdd(&A.cursors[err == 0 ? 82 : 83], 1u);       // (diagnostic: refits the regular clipper took / handed on)
-            if (err == 0)
-            {
-                const uint32_t nv = U.f.nv[which];
-                if (nv != 0u) err = sc_park(U.f.buf[which], nv, sh, A.cursors, A.pos, A.loff, A.llen, A.nbr, A.capV, A.capH, nvoff, ncn, nhoff, nchn);
-            }
-            __syncthreads();
-            if (err == SC_FALLBACK)
-            {
-                // (as in k_clip_convex: the general clipper goes on from the plane the regular one stopped at)
-                SolidIn cx = cin; uint32_t Fx = 8u;
-                const bool resumed = SC_RESUME && stop != 0xFFFFFFFFu && stop > 0u && stop < 8u;
-                float4* const keep = (float4*)S.g_comp;      // (a byte array of the wide topology: 128 bytes of it hold the eight planes meanwhile)
-                if (resumed)
-                {
-                    const uint32_t nvs = U.f.nv[which];
-                    cx = sc_stage(U.f.buf[which], nvs, S.pos, S.g_loff, S.g_llen, S.g_ring);
-                    Fx = 8u - stop;
-                    for (uint32_t k = tid; k < 8u; k += group_size()) { keep[k] = sh.planes[k]; sh.pmar[k] = sh.planes[k]; }
-                    __syncthreads();
-                    for (uint32_t k = tid; k < Fx; k += group_size()) sh.planes[k] = sh.pmar[k + stop];
-                    __syncthreads();
-                    if (tid == 0) atomicAdd(&A.cursors[79], 1u);       // (diagnostic)
-                }
-                err = clip_any<false>(cx, Fx, S, sh, L, [&](auto& T) -> int {
-                    if (T.nLive == 0) return 0;
-                    return park_topo(T, sh, A, nvoff, ncn, nhoff, nchn);
-                }, &W);
-                __syncthreads();
-                if (resumed)
-                {
-                    for (uint32_t k = tid; k < 8u; k += group_size()) sh.planes[k] = keep[k];      // (the fall-backs below start over with all eight)
-                    __syncthreads();
-                }
-            }
-            __syncthreads();
-#ifdef SURTR_STAMP
-            if (err == SURTR_OVERFLOW) dbg_path |= 1;
-            if (err == SURTR_E_TOPOLOGY) dbg_path |= 2;
-#endif
-            if (err == SURTR_OVERFLOW)
-            {
-                const ParkOut o = solid_global(cin, 8, pool, blockIdx.x, A, &sh);
-                err = o.err; nvoff = o.voff; ncn = o.n; nhoff = o.hoff; nchn = o.nh;
-                __syncthreads();
-            }
-        }
-#ifdef SURTR_STAMP
-        if (err == SURTR_E_TOPOLOGY) dbg_path |= 4;
-#endif
-        if (err == SURTR_E_TOPOLOGY)
-        {
-            // The Convex is the result of the pair's clip: its vertices carry the IDs of that clip's last compaction, their own
-            // indices -- unless no cell plane cut the piece's Convex, which then is a copy of the piece's with the IDs it came
-            // with (-1: built from arrays).  A cut changes the vertex set, so "uncut" = same vertices as the piece's Convex.
-            bool ids_set = piece_cpos != nullptr;
-            if (piece_cpos != nullptr)
-            {
-                const uint32_t c0 = piece_cvo[fr.piece], pn = piece_cvo[fr.piece + 1] - c0;
-                bool differs = pn != fr.cv_n;
-                if (!differs)
-                    for (uint32_t i = tid; i < 3u * pn; i += group_size()) if (piece_cpos[3 * (size_t)c0 + i] != cin.pos[i]) differs = true;
-                ids_set = __syncthreads_or(differs ? 1 : 0) != 0;
-            }
-            const ParkOut o = solid_literal(cin, 8, pool, blockIdx.x, A, &sh, ids_set);
-            if (o.err == 0) { err = 0; nvoff = o.voff; ncn = o.n; nhoff = o.hoff; nchn = o.nh; }
-            else if (o.err != SURTR_E_TOPOLOGY) err = o.err;
-            __syncthreads();
-        }
-        if (err == 0 && tid == 0)
-        {
-            // field-wise: k_faces updates other fields of the same record at the same time
-            frags[f].cv_off = nvoff; frags[f].cv_n = ncn; frags[f].ch_off = nhoff; frags[f].ch_n = nchn;
-        }
-        if (err == SURTR_E_TOPOLOGY && frag_status != nullptr)
-        {
-            // Where the reference's own clip of this Convex by the slabs is no polyhedron any more (a link to a clipped vertex
-            // that survives, renumbered through a stale ID), the fragment keeps the Convex it had -- a superset of the refitted
-            // one -- and is flagged; the event and the other fragments stand (as for a fragment without triangles in k_faces).
-            if (tid == 0 && atomicExch(&frag_status[f], (uint32_t)SURTR_E_TOPOLOGY) == 0u) atomicAdd(&A.cursors[14], 1u);
-        }
-        else if (err != 0 && tid == 0) atomicMax(&A.cursors[5], (uint32_t)err);
-#ifdef SURTR_STAMP
-        if (tid == 0)
-        {
-            const unsigned long long d = __builtin_readcyclecounter() - r0; ++wg_tasks;
-            int bkt = 0; while ((d >> bkt) > 1 && bkt < 40) ++bkt; bkt = bkt < 12 ? 0 : bkt - 12; if (bkt > 15) bkt = 15;
-            atomicAdd(&g_stamp2[bkt], 1ull); atomicAdd(&g_stamp2[19], d);
-            const unsigned long long old = atomicMax(&g_stamp2[16], d);
-            if (d > old) { g_stamp2[17] = n; g_stamp2[18] = fr.cv_n; g_stamp2[60] = r1 - r0; g_stamp2[61] = r2 - r1; g_stamp2[62] = (unsigned long long)dbg_path; g_stamp2[63] = ncn; }
-            if (dbg_path & 1) atomicAdd(&g_stamp2[30], 1ull);
-            if (dbg_path & 6) atomicAdd(&g_stamp2[31], 1ull);
-        }
-#endif
+        return 0;
     }
-#ifdef SURTR_STAMP
-    if (tid == 0) { const unsigned long long d = __builtin_readcyclecounter() - wg_t0; atomicAdd(&g_stamp2[20], d); atomicMax(&g_stamp2[21], d); atomicAdd(&g_stamp2[22], 1ull); atomicMax(&g_stamp2[23], wg_tasks); }
-#endif
+};
+struct HullLimited      // a limit above 4: the greedy hull of min(n, limit) points of refit_hull.h
+{
+    using Lds = RhLds;
+    uint32_t limit, capV;
+    uint32_t* ws;      // 2 * capV words: the gain and the "processed" mark of every point of every fragment's Mesh (a fragment's
+                       // points are the arena vertices mv_off .. mv_off + mv_n: the ranges are disjoint)
+    __device__ __forceinline__ static uint32_t faces(const Lds& H) { return H.nLive; }
+    __device__ __forceinline__ static float4* keep(Lds& H, const Scratch&) { return H.keep; }      // (up to 126 planes: in the hull's LDS, which is done with)
+    template <class MP>
+    __device__ int build(const MP* mp, const uint32_t n, const uint32_t mv_off, Lds& H, ArgF* slotF, ArgD* slotD) const
+    {
+        return rh_build(mp, n, n < limit ? n : limit, (float*)ws + mv_off, ws + capV + mv_off, H, slotF, slotD);
+    }
+};
+
+// What literal_clip wants to know of a fragment's Convex.  It is the result of the pair's clip: its vertices carry the IDs of that
+// clip's last compaction, their own indices -- unless no cell plane cut the piece's Convex, which then is a copy of the piece's with
+// the IDs it came with (-1: built from arrays).  A cut changes the vertex set, so "uncut" = same vertices as the piece's Convex.
+__device__ __forceinline__ bool refit_ids_set(const SolidIn& cin, const FragRec& fr, const float* __restrict__ piece_cpos, const uint32_t* __restrict__ piece_cvo)
+{
+    if (piece_cpos == nullptr) return false;
+    const uint32_t c0 = piece_cvo[fr.piece], pn = piece_cvo[fr.piece + 1] - c0;
+    bool differs = pn != fr.cv_n;
+    if (!differs)
+        for (uint32_t i = threadIdx.x; i < 3u * pn; i += group_size()) if (piece_cpos[3 * (size_t)c0 + i] != cin.pos[i]) differs = true;
+    return __syncthreads_or(differs ? 1 : 0) != 0;
 }
 
-#include "refit_hull.h"
-
-// k_refit at a RefittingPointLimit above 4 (surtr_set_refit_point_limit): the hull is the greedy hull of min(n, limit) points
-// of refit_hull.h, F faces, and the Convex is clipped by 2F planes through the clipper chain of k_refit.  hull_ws = 2 * A.capV
-// words: the gain and the "processed" mark of every point of every fragment's Mesh (a fragment's points are the arena
-// vertices mv_off .. mv_off + mv_n: the ranges are disjoint).
-__global__ __launch_bounds__(SURTR_LANES) void k_refit_n(FragRec* __restrict__ frags, const surtr_counts* __restrict__ counts,
-                                                      ScratchPool pool, Arena A, const uint32_t* __restrict__ forder, uint32_t cap_frags,
-                                                      uint32_t* __restrict__ frag_status, const float* __restrict__ piece_cpos,
-                                                      const uint32_t* __restrict__ piece_cvo, uint32_t limit, uint32_t* __restrict__ hull_ws)
+// m_refittingTask (Src/Surtr.cpp:1449-1455) for the fragments of the queue, one wave per fragment: the hull of the fragment's
+// Mesh, the k-DOP of its face normals, and the fragment's Convex clipped by the 2F slab planes through convex_chain.
+template <class Hull>
+__device__ __forceinline__ void refit_fragments(const Hull hull, FragRec* __restrict__ frags, const surtr_counts* __restrict__ counts,
+                                                const ScratchPool& pool, const Arena& A, const uint32_t* __restrict__ forder, uint32_t cap_frags,
+                                                uint32_t* __restrict__ frag_status, const float* __restrict__ piece_cpos,
+                                                const uint32_t* __restrict__ piece_cvo)
 {
-    __shared__ RhLds Hs;
-    RhLds* const Hp = &Hs;
+    __shared__ typename Hull::Lds H;
     __shared__ Shared sh;
     __shared__ ArgF slotF[SURTR_NWAVE];
     __shared__ ArgD slotD[SURTR_NWAVE];
     __shared__ OneWaveLds U;      // (the one-wave clipper of regular planes shares the bytes of the general one's arrays)
-    LdsTopoSmall& L = U.g.L; LdsWorkSmall& W = U.g.W;
+    LdsWorkSmall& W = U.g.W;
     Scratch S = carve(pool, blockIdx.x);
     const uint32_t tid = threadIdx.x;
     const uint32_t nf = counts->n_frag;
@@ -1979,23 +1883,17 @@ __global__ __launch_bounds__(SURTR_LANES) void k_refit_n(FragRec* __restrict__ f
         const uint32_t n = fr.mv_n;
 #ifdef SURTR_STAMP
         const unsigned long long r0 = __builtin_readcyclecounter();
-#endif
-        // The fragment's vertices are read a dozen times (four hull passes, eight slab extremes): a fragment of up to
-        // 2 * LdsWorkSmall::kN vertices is staged once in the LDS work arrays, which nothing uses before the clip below.
-#ifdef SURTR_STAMP
         unsigned long long r1 = 0;
 #endif
-        static_assert(offsetof(LdsWorkSmall, aux0) == sizeof(float) * 3 * LdsWorkSmall::kN && offsetof(LdsWorkSmall, aux1) == sizeof(float) * 4 * LdsWorkSmall::kN &&
-                      offsetof(LdsWorkSmall, aux2) == sizeof(float) * 5 * LdsWorkSmall::kN, "pos, aux0, aux1, aux2 are contiguous");
-        uint32_t hull_planes = 8u;
-        int herr = 0;
-        auto slabs = [&](const auto* mp) {
-            RhLds& H = *Hp;
-            herr = rh_build(mp, n, n < limit ? n : limit, (float*)hull_ws + fr.mv_off, hull_ws + A.capV + fr.mv_off, H, slotF, slotD);
-            if (herr != 0) return;
-            const uint32_t F = H.nLive;
-            hull_planes = 2u * F;
-            // ---- Kdop::Calc(Polyhedron) (Src/Kdop.cpp:92-115), as in k_refit, for F normals ----
+        const uint32_t mv_off = fr.mv_off;
+        auto slabs = [&](const auto* mp) -> int {
+            const int herr = hull.build(mp, n, mv_off, H, slotF, slotD);
+#ifdef SURTR_STAMP
+            r1 = __builtin_readcyclecounter();
+#endif
+            if (herr != 0) return herr;      // (no hull within the engine's limits)
+            const uint32_t F = Hull::faces(H);
+            // ---- Kdop::Calc(Polyhedron) (Src/Kdop.cpp:92-115): first minimum / first maximum of n.v ----
             for (uint32_t k = 0; k < F; ++k)
             {
                 ArgF lo, hi; lo.i = hi.i = 0xFFFFFFFFu; lo.v = hi.v = 0.f;
@@ -2010,114 +1908,52 @@ __global__ __launch_bounds__(SURTR_LANES) void k_refit_n(FragRec* __restrict__ f
                 lo = wg_argmax<float, ArgF>(lo, slotF);
                 if (tid == 0)
                 {
+                    // MinPlane = Plane(vert, -n), MaxPlane = Plane(vert, n); order Min, Max (:166-179)
                     const auto* a0 = mp + 3 * lo.i; const auto* a1 = mp + 3 * hi.i;
                     sh.planes[2 * k] = make_float4(-nx, -ny, -nz, -dot3(a0[0], a0[1], a0[2], -nx, -ny, -nz));
                     sh.planes[2 * k + 1] = make_float4(nx, ny, nz, -dot3(a1[0], a1[1], a1[2], nx, ny, nz));
                 }
             }
             __syncthreads();
+            return 0;
         };
+        // The fragment's vertices are read a dozen times and more (the hull passes, two slab extremes per face): a fragment of up
+        // to 2 * LdsWorkSmall::kN vertices is staged once in the LDS work arrays, which nothing uses before the clip below.
+        static_assert(offsetof(LdsWorkSmall, aux0) == sizeof(float) * 3 * LdsWorkSmall::kN && offsetof(LdsWorkSmall, aux1) == sizeof(float) * 4 * LdsWorkSmall::kN &&
+                      offsetof(LdsWorkSmall, aux2) == sizeof(float) * 5 * LdsWorkSmall::kN, "pos, aux0, aux1, aux2 are contiguous");
+        int herr;
         if (n <= 2u * LdsWorkSmall::kN)
         {
             float* lp = W.pos;
             for (uint32_t i = tid; i < 3u * n; i += group_size()) lp[i] = mpg[i];
             __syncthreads();
-            slabs((const float*)lp);
+            herr = slabs((const float*)lp);
             __syncthreads();
         }
-        else slabs(mpg);
+        else herr = slabs(mpg);
+        const uint32_t nP = 2u * Hull::faces(H);      // planes of the clip: Min and Max plane per hull face
+        ChainStamp cst{};
 #ifdef SURTR_STAMP
         const unsigned long long r2 = __builtin_readcyclecounter();
         if (tid == 0) { atomicAdd(&g_stamp[94], r1 - r0); atomicAdd(&g_stamp[95], r2 - r1); }
-        int dbg_path = 0;
 #endif
-        const uint32_t nP = hull_planes;      // planes of the clip: Min and Max plane per hull face
-        SolidIn cin{A.pos + 3 * (size_t)fr.cv_off, A.loff + fr.cv_off, A.llen + fr.cv_off, A.nbr, fr.cv_n, nullptr, nullptr, nullptr, nullptr, nullptr};
         // arena rings are absolute offsets into A.nbr, which is what SolidIn expects
-        uint32_t nvoff = 0, ncn = 0, nhoff = 0, nchn = 0;
-        // (no small_clip attempt here: the slab planes pass through extreme vertices of the fragment, which are vertices of its
-        // Convex as often as not -- measured on configs[3]: 2 385 of 2 692 refits have a vertex exactly in a plane)
-        int err = SURTR_E_TOPOLOGY;      // a sliver Convex: the literal clipper below, from the start
-        if (herr != 0) err = herr;      // (no hull within the engine's limits: the fragment is flagged below)
-        else if (!solid_is_sliver(cin))
+        SolidIn cin{A.pos + 3 * (size_t)fr.cv_off, A.loff + fr.cv_off, A.llen + fr.cv_off, A.nbr, fr.cv_n, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ParkOut o{herr, 0u, 0u, 0u, 0u, false};      // (no hull within the engine's limits: no clip, the fragment is flagged below)
+        if (herr == 0)
         {
-            // the regular clipper first: it takes the Convex whose slab planes either cut no vertex (the plane through an extreme
-            // vertex of the fragment that is an extreme vertex of its Convex too) or cut with no vertex in the plane
-            uint32_t which = 0, stop = 0xFFFFFFFFu;
-            err = small_clip(cin, nP, sh, U.f, &which, &stop);
-            if (tid == 0) atomicAdd(&A.cursors[err == 0 ? 82 : 83], 1u);       // (diagnostic: refits the regular clipper took / handed on)
-            if (err == 0)
-            {
-                const uint32_t nv = U.f.nv[which];
-                if (nv != 0u) err = sc_park(U.f.buf[which], nv, sh, A.cursors, A.pos, A.loff, A.llen, A.nbr, A.capV, A.capH, nvoff, ncn, nhoff, nchn);
-            }
-            __syncthreads();
-            if (err == SC_FALLBACK)
-            {
-                // (as in k_clip_convex: the general clipper goes on from the plane the regular one stopped at)
-                SolidIn cx = cin; uint32_t Fx = nP;
-                const bool resumed = SC_RESUME && stop != 0xFFFFFFFFu && stop > 0u && stop < nP;
-                float4* const keep = Hp->keep;      // (up to 126 planes: in the hull's LDS, which is done with)
-                if (resumed)
-                {
-                    const uint32_t nvs = U.f.nv[which];
-                    cx = sc_stage(U.f.buf[which], nvs, S.pos, S.g_loff, S.g_llen, S.g_ring);
-                    Fx = nP - stop;
-                    for (uint32_t k = tid; k < nP; k += group_size()) { keep[k] = sh.planes[k]; sh.pmar[k] = sh.planes[k]; }
-                    __syncthreads();
-                    for (uint32_t k = tid; k < Fx; k += group_size()) sh.planes[k] = sh.pmar[k + stop];
-                    __syncthreads();
-                    if (tid == 0) atomicAdd(&A.cursors[79], 1u);       // (diagnostic)
-                }
-                err = clip_any<false>(cx, Fx, S, sh, L, [&](auto& T) -> int {
-                    if (T.nLive == 0) return 0;
-                    return park_topo(T, sh, A, nvoff, ncn, nhoff, nchn);
-                }, &W);
-                __syncthreads();
-                if (resumed)
-                {
-                    for (uint32_t k = tid; k < nP; k += group_size()) sh.planes[k] = keep[k];      // (the fall-backs below start over with all of them)
-                    __syncthreads();
-                }
-            }
-            __syncthreads();
-#ifdef SURTR_STAMP
-            if (err == SURTR_OVERFLOW) dbg_path |= 1;
-            if (err == SURTR_E_TOPOLOGY) dbg_path |= 2;
-#endif
-            if (err == SURTR_OVERFLOW)
-            {
-                const ParkOut o = solid_global(cin, nP, pool, blockIdx.x, A, &sh);
-                err = o.err; nvoff = o.voff; ncn = o.n; nhoff = o.hoff; nchn = o.nh;
-                __syncthreads();
-            }
+            // The regular clipper is worth its attempt although the slab planes pass through extreme vertices of the fragment, which
+            // are vertices of its Convex as often as not (configs[3]: 2 385 of 2 692 refits have a vertex exactly in a plane): it
+            // takes the Convex whose planes either cut no vertex or cut with no vertex in the plane, and the general one resumes.
+            float4* const keep = Hull::keep(H, S);
+            const bool sliver = solid_is_sliver_inl(cin);
+            const ChainCaller who{82u, 79u, false, keep, keep};
+            o = convex_chain(cin, nP, sliver, who, [&] { return LiteralArg{cin, refit_ids_set(cin, fr, piece_cpos, piece_cvo)}; }, sh, U, S, pool, A, cst);
         }
-#ifdef SURTR_STAMP
-        if (err == SURTR_E_TOPOLOGY) dbg_path |= 4;
-#endif
-        if (err == SURTR_E_TOPOLOGY)
-        {
-            // The Convex is the result of the pair's clip: its vertices carry the IDs of that clip's last compaction, their own
-            // indices -- unless no cell plane cut the piece's Convex, which then is a copy of the piece's with the IDs it came
-            // with (-1: built from arrays).  A cut changes the vertex set, so "uncut" = same vertices as the piece's Convex.
-            bool ids_set = piece_cpos != nullptr;
-            if (piece_cpos != nullptr)
-            {
-                const uint32_t c0 = piece_cvo[fr.piece], pn = piece_cvo[fr.piece + 1] - c0;
-                bool differs = pn != fr.cv_n;
-                if (!differs)
-                    for (uint32_t i = tid; i < 3u * pn; i += group_size()) if (piece_cpos[3 * (size_t)c0 + i] != cin.pos[i]) differs = true;
-                ids_set = __syncthreads_or(differs ? 1 : 0) != 0;
-            }
-            const ParkOut o = solid_literal(cin, nP, pool, blockIdx.x, A, &sh, ids_set);
-            if (o.err == 0) { err = 0; nvoff = o.voff; ncn = o.n; nhoff = o.hoff; nchn = o.nh; }
-            else if (o.err != SURTR_E_TOPOLOGY) err = o.err;
-            __syncthreads();
-        }
-        if (err == 0 && tid == 0)
+        if (o.err == 0 && tid == 0)
         {
             // field-wise: k_faces updates other fields of the same record at the same time
-            frags[f].cv_off = nvoff; frags[f].cv_n = ncn; frags[f].ch_off = nhoff; frags[f].ch_n = nchn;
+            frags[f].cv_off = o.voff; frags[f].cv_n = o.n; frags[f].ch_off = o.hoff; frags[f].ch_n = o.nh;
         }
         if (herr != 0 && frag_status != nullptr)
         {
@@ -2125,14 +1961,14 @@ __global__ __launch_bounds__(SURTR_LANES) void k_refit_n(FragRec* __restrict__ f
             // its un-refitted Convex and is flagged SURTR_E_CAPACITY; counted apart (surtr_queue_stats out[95]).
             if (tid == 0 && atomicExch(&frag_status[f], (uint32_t)SURTR_E_CAPACITY) == 0u) { atomicAdd(&A.cursors[14], 1u); atomicAdd(&A.cursors[95], 1u); }
         }
-        else if (err == SURTR_E_TOPOLOGY && frag_status != nullptr)
+        else if (o.err == SURTR_E_TOPOLOGY && frag_status != nullptr)
         {
             // Where the reference's own clip of this Convex by the slabs is no polyhedron any more (a link to a clipped vertex
             // that survives, renumbered through a stale ID), the fragment keeps the Convex it had -- a superset of the refitted
             // one -- and is flagged; the event and the other fragments stand (as for a fragment without triangles in k_faces).
             if (tid == 0 && atomicExch(&frag_status[f], (uint32_t)SURTR_E_TOPOLOGY) == 0u) atomicAdd(&A.cursors[14], 1u);
         }
-        else if (err != 0 && tid == 0) atomicMax(&A.cursors[5], (uint32_t)err);
+        else if (o.err != 0 && tid == 0) atomicMax(&A.cursors[5], (uint32_t)o.err);
 #ifdef SURTR_STAMP
         if (tid == 0)
         {
@@ -2140,15 +1976,32 @@ __global__ __launch_bounds__(SURTR_LANES) void k_refit_n(FragRec* __restrict__ f
             int bkt = 0; while ((d >> bkt) > 1 && bkt < 40) ++bkt; bkt = bkt < 12 ? 0 : bkt - 12; if (bkt > 15) bkt = 15;
             atomicAdd(&g_stamp2[bkt], 1ull); atomicAdd(&g_stamp2[19], d);
             const unsigned long long old = atomicMax(&g_stamp2[16], d);
-            if (d > old) { g_stamp2[17] = n; g_stamp2[18] = fr.cv_n; g_stamp2[60] = r1 - r0; g_stamp2[61] = r2 - r1; g_stamp2[62] = (unsigned long long)dbg_path; g_stamp2[63] = ncn; }
-            if (dbg_path & 1) atomicAdd(&g_stamp2[30], 1ull);
-            if (dbg_path & 6) atomicAdd(&g_stamp2[31], 1ull);
+            if (d > old) { g_stamp2[17] = n; g_stamp2[18] = fr.cv_n; g_stamp2[60] = r1 - r0; g_stamp2[61] = r2 - r1; g_stamp2[62] = (unsigned long long)cst.path; g_stamp2[63] = o.n; }
+            if (cst.path & 1) atomicAdd(&g_stamp2[30], 1ull);
+            if (cst.path & 6) atomicAdd(&g_stamp2[31], 1ull);
         }
 #endif
     }
 #ifdef SURTR_STAMP
     if (tid == 0) { const unsigned long long d = __builtin_readcyclecounter() - wg_t0; atomicAdd(&g_stamp2[20], d); atomicMax(&g_stamp2[21], d); atomicAdd(&g_stamp2[22], 1ull); atomicMax(&g_stamp2[23], wg_tasks); }
 #endif
+}
+
+__global__ __launch_bounds__(SURTR_LANES) void k_refit(FragRec* __restrict__ frags, const surtr_counts* __restrict__ counts,
+                                                    ScratchPool pool, Arena A, const uint32_t* __restrict__ forder, uint32_t cap_frags,
+                                                    uint32_t* __restrict__ frag_status, const float* __restrict__ piece_cpos,
+                                                    const uint32_t* __restrict__ piece_cvo)
+{
+    refit_fragments(HullFirst4{}, frags, counts, pool, A, forder, cap_frags, frag_status, piece_cpos, piece_cvo);
+}
+
+// k_refit at a RefittingPointLimit above 4 (surtr_set_refit_point_limit).  hull_ws = 2 * A.capV words.
+__global__ __launch_bounds__(SURTR_LANES) void k_refit_n(FragRec* __restrict__ frags, const surtr_counts* __restrict__ counts,
+                                                      ScratchPool pool, Arena A, const uint32_t* __restrict__ forder, uint32_t cap_frags,
+                                                      uint32_t* __restrict__ frag_status, const float* __restrict__ piece_cpos,
+                                                      const uint32_t* __restrict__ piece_cvo, uint32_t limit, uint32_t* __restrict__ hull_ws)
+{
+    refit_fragments(HullLimited{limit, A.capV, hull_ws}, frags, counts, pool, A, forder, cap_frags, frag_status, piece_cpos, piece_cvo);
 }
 
 // Test entry: the hull normals of one cloud (surtr_hull_normals_device).  One wave; ws = 2 * n words.
