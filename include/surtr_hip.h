@@ -430,6 +430,61 @@ int surtr_pieces_mass(surtr_ctx* ctx, int set, float density, uint32_t* n, surtr
 int surtr_combine_mass(uint32_t n_compounds, const uint32_t* compound_off, const int32_t* compound_piece, const surtr_mass* pieces,
                        surtr_mass* out);
 
+/* ---- picking: ray cast and sphere overlap on the resident pieces (query_dev.hip) ---- */
+/* What OnMouseDown asks of PhysX (gScene->raycast, gScene->overlap, Src/Surtr.cpp:178-254), on the Convex solids of the resident
+ * pieces in world space as they stand (after surtr_transform_pieces / surtr_pieces_from_event), without a download.
+ * Definition: the faces of a solid are the loops Poly::ExtractFaces walks; a face's plane is surtr_plane_from_points through the
+ * loop's smallest-numbered vertex and the two that follow it in loop order; inside is n.x + d <= 0.
+ *   ray (origin o, direction d -- unit length if t is to be a distance; it is not normalised here --, max_dist >= 0, +inf allowed):
+ *     the interval [0, max_dist] is clipped by every half-space (Cyrus-Beck); a solid is hit when t_enter <= t_exit, at
+ *     t = max(t_enter, 0) with the normal of the entering plane.  An origin inside every half-space gives t = 0, pos = o,
+ *     normal = -d and SURTR_RAY_STARTS_INSIDE (PhysX's initial overlap).  Over the pieces: the smallest t, the lowest piece on a tie.
+ *   sphere (centre c, radius r >= 0): a solid is touched when the distance from c to it is <= r (0 inside; else the minimum over
+ *     its edges and over the faces onto which c projects inside the face).
+ * A piece is hit (touched) only if the ray crosses (the sphere reaches) the box of its vertices: no difference for a convex solid;
+ * it bounds what a face plane through three nearly collinear vertices can claim.  Everything is evaluated in double from the
+ * float positions; the records are float.
+ * Max, min and lowest index are order-independent: two calls give the same bits whatever the stream or the other work on the GPU.
+ * A solid that cannot be queried is never hit and never touched, and surtr_pieces_query_status says why. */
+typedef struct surtr_ray_hit {
+    int32_t piece;         /* resident piece hit, -1: none */
+    uint32_t status;       /* SURTR_RAY_* bits */
+    float t;               /* parameter of the hit along d */
+    float pos[3];          /* o + t * d */
+    float normal[3];       /* unit normal of the face entered (-d when the ray starts inside) */
+    uint32_t reserved[3];  /* zero; the record is 48 bytes */
+} surtr_ray_hit;
+enum {
+    SURTR_RAY_STARTS_INSIDE = 1,   /* the origin is inside the piece: t = 0 */
+    SURTR_RAY_INVALID = 2          /* zero or non-finite direction, non-finite origin, max_dist negative or NaN: no hit (_dev forms) */
+};
+enum {                             /* per-piece status of a query; 0 = the solid was queried */
+    SURTR_QUERY_FEW = 1,           /* fewer than four vertices */
+    SURTR_QUERY_OPEN = 2,          /* a ring entry names no vertex, or a face walk does not close (or closes after two steps) */
+    SURTR_QUERY_FLAT = 4,          /* a face of zero (or non-finite) normal */
+    SURTR_QUERY_LONG = 8           /* a face loop of more than 256 vertices */
+};
+/* n_rays >= 1 rays of 7 floats (o, d, max_dist) in device memory -> n_rays records in dev_hits (capacity_bytes >= 48 * n_rays,
+ * else SURTR_E_CAPACITY and nothing is written).  Enqueued on the context's stream with no host synchronisation; one temporary
+ * device allocation ordered on that stream.  SURTR_E_STATE without resident pieces.  An invalid ray gets SURTR_RAY_INVALID. */
+int surtr_pieces_raycast_dev(surtr_ctx* ctx, uint32_t n_rays, const float* dev_rays, void* dev_hits, size_t capacity_bytes);
+/* The same from and to host arrays; synchronises.  An invalid ray is SURTR_E_INVALID here and nothing is run. */
+int surtr_pieces_raycast(surtr_ctx* ctx, uint32_t n_rays, const float* rays, surtr_ray_hit* hits);
+/* n_spheres >= 1 spheres of 4 floats (c, r) -> dev_mask[s * n_pieces + p] (capacity_bytes >= n_spheres * n_pieces): 0 not touched,
+ * 1 touched.  With dev_mass_or_null (the n_pieces surtr_mass records surtr_pieces_mass_dev wrote) a touched piece of
+ * mass <= min_mass gets 2 instead: touched but too light to fracture (Src/Surtr.cpp:228).  A sphere that is not finite or has a
+ * negative radius touches nothing. */
+int surtr_pieces_overlap_dev(surtr_ctx* ctx, uint32_t n_spheres, const float* dev_spheres, const void* dev_mass_or_null, float min_mass,
+                             uint8_t* dev_mask, size_t capacity_bytes);
+/* The same from and to host arrays; synchronises.  mask == NULL returns the number of resident pieces in *n_pieces; with mask,
+ * *n_pieces must hold the pieces a row has room for (SURTR_E_CAPACITY and the count when too small).  A sphere that is not finite
+ * or has a negative radius is SURTR_E_INVALID. */
+int surtr_pieces_overlap(surtr_ctx* ctx, uint32_t n_spheres, const float* spheres, const surtr_mass* mass_or_null, float min_mass,
+                         uint32_t* n_pieces, uint8_t* mask);
+/* The SURTR_QUERY_* bits of every piece as the last query found them (n >= the pieces of that query; synchronises).
+ * SURTR_E_STATE before the first query. */
+int surtr_pieces_query_status(surtr_ctx* ctx, uint32_t n, uint32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

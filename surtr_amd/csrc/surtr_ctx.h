@@ -251,6 +251,7 @@ struct surtr_ctx
     DevBuf<float> d_world;           // surtr_transform_pieces: the world matrices
     DevBuf<char> sort_tmp;           // radix-sort scratch of the Morton sort
     DevBuf<uint32_t> d_from;         // surtr_pieces_from_event: fragment list and offsets
+    DevBuf<uint32_t> d_qstatus; uint32_t qstatus_n = 0;   // query_dev.hip: per-piece status of the last ray cast / overlap
     float upload_ms = 0.f; uint32_t upload_allocs = 0;   // surtr_upload_stats
     uint32_t regroup_rounds = 0;                         // label rounds of the last surtr_event_regroup (one launch)
     uint64_t tot_mv = 0, tot_mh = 0;

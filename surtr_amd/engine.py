@@ -39,6 +39,14 @@ MASS_DTYPE = np.dtype([("volume", "<f8"), ("mass", "<f8"), ("com", "<f8", (3,)),
 assert MASS_DTYPE.itemsize == ctypes.sizeof(Mass) == 96
 
 
+# surtr_ray_hit (include/surtr_hip.h), 48 bytes; status bits and the per-piece status bits of a query
+RAY_HIT_DTYPE = np.dtype([("piece", "<i4"), ("status", "<u4"), ("t", "<f4"), ("pos", "<f4", (3,)), ("normal", "<f4", (3,)),
+                          ("reserved", "<u4", (3,))])
+assert RAY_HIT_DTYPE.itemsize == 48
+RAY_STARTS_INSIDE, RAY_INVALID = 1, 2
+QUERY_FEW, QUERY_OPEN, QUERY_FLAT, QUERY_LONG = 1, 2, 4, 8
+
+
 class Fragments(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in
                 ("frag_ids", "mesh_vert_off", "mesh_pos", "mesh_nbr_off", "mesh_nbr", "conv_vert_off", "conv_pos",
@@ -353,6 +361,53 @@ class Engine:
     def pieces_mass_dev(self, dev_ptr, capacity, set=1, density=10.0):
         self._ck(lib().surtr_pieces_mass_dev(self._h, ctypes.c_int(int(set)), ctypes.c_float(density), ctypes.c_void_p(dev_ptr),
                                              ctypes.c_size_t(capacity)))
+
+    def pieces_raycast(self, rays):
+        """surtr_pieces_raycast: rays f32[n, 7] (origin, direction, max_dist) against the Convex solids of the resident pieces,
+        on the device -> RAY_HIT_DTYPE[n] (piece -1: no hit)."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 7)
+        out = np.zeros(r.shape[0], RAY_HIT_DTYPE)
+        self._ck(lib().surtr_pieces_raycast(self._h, ctypes.c_uint32(r.shape[0]), _p(r), _p(out)))
+        return out
+
+    def pieces_overlap(self, spheres, mass=None, min_mass=1e-4):
+        """surtr_pieces_overlap: spheres f32[n, 4] (centre, radius) -> uint8[n, n_pieces]: 0 not touched, 1 touched, 2 touched
+        but mass <= min_mass (mass: the MASS_DTYPE records of pieces_mass; None: no gate)."""
+        sp = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+        m = None if mass is None else np.ascontiguousarray(mass, MASS_DTYPE)
+        n = ctypes.c_uint32()
+        args = [self._h, ctypes.c_uint32(sp.shape[0]), _p(sp), _p(m), ctypes.c_float(min_mass)]
+        self._ck(lib().surtr_pieces_overlap(*args, ctypes.byref(n), None))
+        if m is not None and m.shape[0] != n.value:
+            raise SurtrError(E_INVALID, "mass holds %d records for %d pieces" % (m.shape[0], n.value))
+        out = np.zeros((sp.shape[0], n.value), np.uint8)
+        self._ck(lib().surtr_pieces_overlap(*args, ctypes.byref(n), _p(out)))
+        return out
+
+    def pieces_raycast_dev(self, n_rays, dev_rays, dev_hits, capacity):
+        """surtr_pieces_raycast_dev: device pointers, the context's stream, no synchronisation."""
+        self._ck(lib().surtr_pieces_raycast_dev(self._h, ctypes.c_uint32(int(n_rays)), ctypes.c_void_p(dev_rays), ctypes.c_void_p(dev_hits),
+                                                ctypes.c_size_t(capacity)))
+
+    def pieces_overlap_dev(self, n_spheres, dev_spheres, dev_mask, capacity, dev_mass=None, min_mass=1e-4):
+        self._ck(lib().surtr_pieces_overlap_dev(self._h, ctypes.c_uint32(int(n_spheres)), ctypes.c_void_p(dev_spheres),
+                                                ctypes.c_void_p(dev_mass), ctypes.c_float(min_mass), ctypes.c_void_p(dev_mask),
+                                                ctypes.c_size_t(capacity)))
+
+    def pieces_query_status(self, n):
+        """surtr_pieces_query_status: the QUERY_* bits of every piece as the last ray cast / overlap found them."""
+        out = np.zeros(int(n), np.uint32)
+        self._ck(lib().surtr_pieces_query_status(self._h, ctypes.c_uint32(int(n)), _p(out)))
+        return out
+
+    def download_piece(self, piece, set=1):
+        """surtr_download_piece: resident piece `piece` read back (set 0 = Mesh, 1 = Convex) as a solid."""
+        nv, nh = ctypes.c_uint32(), ctypes.c_uint32()
+        args = [self._h, ctypes.c_uint32(int(piece)), ctypes.c_int(int(set))]
+        self._ck(lib().surtr_download_piece(*args, ctypes.byref(nv), ctypes.byref(nh), None, None, None))
+        pos = np.zeros((nv.value, 3), np.float32); off = np.zeros(nv.value + 1, np.uint32); nbr = np.zeros(nh.value, np.int32)
+        self._ck(lib().surtr_download_piece(*args, ctypes.byref(nv), ctypes.byref(nh), _p(pos), _p(off), _p(nbr)))
+        return {"pos": pos, "off": off, "nbr": nbr}
 
     def event_refit(self):
         self._ck(lib().surtr_event_refit(self._h))

@@ -2,6 +2,9 @@
 // builds a synthetic closed mesh, a Voronoi pattern, runs ONE fracture event on the GPU and prints a
 // JSON summary (optionally writes the fragments as an OBJ).  Usage:
 //   surtr_harness [--mesh cube|torus | --obj-in mesh.obj [--scale S]] [--cells N] [--nu A --nv B] [--ach] [--obj out.obj]
+//                 [--pick ox,oy,oz,dx,dy,dz [--impact-radius R]]
+// --pick: the event's fragments become the resident pieces (piece k in compound k / 2) and the ray is cast into them as
+// OnMouseDown does (Src/Surtr.cpp:207-240): the hit, the impact position, the overlap mask and the affected compounds, as JSON.
 // --ach runs Surtr::PrepareFracture end to end (ACH convex instead of the plain 2x box).
 #include <cmath>
 #include <cstdio>
@@ -265,11 +268,58 @@ static void api_dump(const char* path, const std::vector<Fragment>& frags, const
     fclose(f);
 }
 
+// --pick: Raycast / OverlapSphere / PickImpact / ConvexRayIntersection on the event's fragments, resident.
+static void pick(FractureEngine& eng, const std::vector<Fragment>& frags, const float q[6], float impact_radius)
+{
+    const uint32_t n = eng.CompoundFromLastEvent();
+    const Vector3 o(q[0], q[1], q[2]), d(q[3], q[4], q[5]);
+    const surtr_ray_hit hit = eng.Raycast(o, d, 1e30f);
+    std::vector<int> compound(n);
+    for (uint32_t k = 0; k < n; ++k) compound[k] = (int)k / 2;
+    FractureArgs radial, single;
+    radial.ImpactRadius = single.ImpactRadius = impact_radius; single.RadialMode = false;
+    const std::vector<int> cr = eng.PickImpact(o, d, radial, compound), cs = eng.PickImpact(o, d, single, compound);
+    printf("{\"pick\": {\"pieces\": %u, \"raycast\": {\"piece\": %d, \"status\": %u, \"t\": %.9g, \"pos\": [%.9g, %.9g, %.9g], \"normal\": [%.9g, %.9g, %.9g]}",
+           n, hit.piece, hit.status, hit.t, hit.pos[0], hit.pos[1], hit.pos[2], hit.normal[0], hit.normal[1], hit.normal[2]);
+    printf(", \"impact_position\": [%.9g, %.9g, %.9g], \"overlap\": [", radial.ImpactPosition.x, radial.ImpactPosition.y, radial.ImpactPosition.z);
+    if (hit.piece >= 0)
+    {
+        const std::vector<uint8_t> mask = eng.OverlapSphere(radial.ImpactPosition, impact_radius / 2.f, 1e-4f);
+        for (size_t p = 0; p < mask.size(); ++p) printf("%s%u", p ? ", " : "", mask[p]);
+    }
+    printf("], \"radial\": [");
+    for (size_t i = 0; i < cr.size(); ++i) printf("%s%d", i ? ", " : "", cr[i]);
+    printf("], \"single\": [");
+    for (size_t i = 0; i < cs.size(); ++i) printf("%s%d", i ? ", " : "", cs[i]);
+    printf("]");
+    // the hit piece's Convex as a Polygon3D (faces from Poly::ExtractFaces, each from its smallest vertex) against the host helper.
+    // Resident piece k is the k-th fragment with a solid Mesh and Convex.
+    int at = -1; const Fragment* hf = nullptr;
+    for (const auto& f : frags) if (f.piece_data.Mesh.size() >= 4 && f.piece_data.Convex.size() >= 4 && ++at == hit.piece) { hf = &f; break; }
+    if (hf)
+    {
+        Poly::Extract* ex = Poly::ExtractFaces(hf->piece_data.Convex);
+        VMACH::Polygon3D poly;
+        for (const auto& loop : *ex)
+        {
+            const size_t m = std::min_element(loop.begin(), loop.end()) - loop.begin();
+            VMACH::PolygonFace face(true);
+            for (size_t j = 0; j < loop.size(); ++j) face.AddVertex(hf->piece_data.Convex[loop[(m + j) % loop.size()]].Position);
+            poly.AddFace(face);
+        }
+        delete ex;
+        float dist = -1.f;
+        const bool h = ConvexRayIntersection(poly, Ray(o, d), dist);
+        printf(", \"host_ray\": {\"hit\": %s, \"dist\": %.9g}", h ? "true" : "false", dist);
+    }
+    printf("}}\n");
+}
+
 int main(int argc, char** argv)
 {
     std::string mesh = "cube", obj, obj_in, dump;
     int cells = 8, nu = 250, nv = 200;
-    bool ach = false; float in_scale = 1.f;
+    bool ach = false, do_pick = false; float in_scale = 1.f, pick_ray[6] = {0, 0, 0, 1, 0, 0}, impact_radius = 1.f;
     for (int i = 1; i < argc; ++i)
     {
         if (!strcmp(argv[i], "--mesh") && i + 1 < argc) mesh = argv[++i];
@@ -281,6 +331,12 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--scale") && i + 1 < argc) in_scale = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--ach")) ach = true;
         else if (!strcmp(argv[i], "--api-dump") && i + 1 < argc) dump = argv[++i];
+        else if (!strcmp(argv[i], "--impact-radius") && i + 1 < argc) impact_radius = (float)atof(argv[++i]);
+        else if (!strcmp(argv[i], "--pick") && i + 1 < argc)
+        {
+            do_pick = sscanf(argv[++i], "%f,%f,%f,%f,%f,%f", pick_ray, pick_ray + 1, pick_ray + 2, pick_ray + 3, pick_ray + 4, pick_ray + 5) == 6;
+            if (!do_pick) { fprintf(stderr, "surtr_harness: --pick takes ox,oy,oz,dx,dy,dz\n"); return 2; }
+        }
     }
     try
     {
@@ -319,6 +375,7 @@ int main(int argc, char** argv)
         printf("{\"mesh\": \"%s\", \"verts\": %zu, \"tris\": %zu, \"cells\": %d, \"fragments\": %u, \"mesh_verts\": %u, \"mesh_nbrs\": %u, "
                "\"conv_verts\": %u, \"indices\": %u}\n", mesh.c_str(), verts.size(), tris.size() / 3, cells, c.n_frag, c.mesh_verts,
                c.mesh_nbrs, c.conv_verts, c.n_idx);
+        if (do_pick) pick(eng, frags, pick_ray, impact_radius);
         if (!obj.empty())
         {
             FILE* f = fopen(obj.c_str(), "w");

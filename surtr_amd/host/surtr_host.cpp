@@ -550,6 +550,61 @@ std::vector<surtr_mass> FractureEngine::PieceMassProperties(int set, float densi
     return out;
 }
 
+surtr_ray_hit FractureEngine::Raycast(const Vector3& origin, const Vector3& dir, float maxDist)
+{
+    const float ray[7] = {origin.x, origin.y, origin.z, dir.x, dir.y, dir.z, maxDist};
+    surtr_ray_hit hit;
+    check(surtr_pieces_raycast(ctx_, 1, ray, &hit), "surtr_pieces_raycast");
+    return hit;
+}
+
+std::vector<uint8_t> FractureEngine::OverlapSphere(const Vector3& centre, float radius, float minMass)
+{
+    const float sphere[4] = {centre.x, centre.y, centre.z, radius};
+    uint32_t n = 0;
+    check(surtr_pieces_overlap(ctx_, 1, sphere, nullptr, 0.f, &n, nullptr), "surtr_pieces_overlap");
+    std::vector<uint8_t> mask(n);
+    std::vector<surtr_mass> mass;
+    if (minMass >= 0.f) mass = PieceMassProperties(1);
+    check(surtr_pieces_overlap(ctx_, 1, sphere, mass.empty() ? nullptr : mass.data(), minMass, &n, mask.data()), "surtr_pieces_overlap");
+    return mask;
+}
+
+std::vector<int> FractureEngine::PickImpact(const Vector3& origin, const Vector3& dir, FractureArgs& args, const std::vector<int>& pieceCompound)
+{
+    const surtr_ray_hit hit = Raycast(origin, dir);
+    if (hit.piece < 0) return {};
+    if ((size_t)hit.piece >= pieceCompound.size()) throw Error(SURTR_E_INVALID, "PickImpact: pieceCompound is shorter than the resident pieces");
+    args.ImpactPosition = Vector3(hit.pos[0] + dir.x * args.TargetAdder, hit.pos[1] + dir.y * args.TargetAdder, hit.pos[2] + dir.z * args.TargetAdder);
+    if (!args.RadialMode) return {pieceCompound[hit.piece]};
+    const std::vector<uint8_t> mask = OverlapSphere(args.ImpactPosition, args.ImpactRadius / 2.f, 1e-4f);
+    if (mask.size() > pieceCompound.size()) throw Error(SURTR_E_INVALID, "PickImpact: pieceCompound is shorter than the resident pieces");
+    std::set<int> out;
+    for (size_t p = 0; p < mask.size(); ++p) if (mask[p] == 1) out.insert(pieceCompound[p]);
+    return std::vector<int>(out.begin(), out.end());
+}
+
+bool ConvexRayIntersection(const VMACH::Polygon3D& convex, const Ray ray, float& dist)
+{
+    const double o[3] = {ray.position.x, ray.position.y, ray.position.z}, d[3] = {ray.direction.x, ray.direction.y, ray.direction.z};
+    double t_in = 0.0, t_ex = DBL_MAX;
+    bool any = false;
+    for (const auto& f : convex.FaceVec)
+    {
+        if (f.VertexVec.size() < 3) continue;
+        const Plane pl = f.FacePlaneConstructed ? f.FacePlane : VMACH::ConstructFacePlane(f);
+        const double den = pl.x * d[0] + pl.y * d[1] + pl.z * d[2], dst = pl.x * o[0] + pl.y * o[1] + pl.z * o[2] + pl.w;
+        any = true;
+        if (den == 0.0) { if (dst > 0.0) return false; continue; }
+        const double t = -dst / den;
+        if (den < 0.0) { if (t > t_in) t_in = t; }
+        else if (t < t_ex) t_ex = t;
+    }
+    if (!any || !(t_in <= t_ex)) return false;
+    dist = (float)t_in;
+    return true;
+}
+
 std::vector<surtr_mass> CompoundMass(const std::vector<std::set<int>>& bind, const std::vector<surtr_mass>& pieces)
 {
     std::vector<uint32_t> off(1, 0u);

@@ -145,7 +145,16 @@ struct FractureArgs
     float ImpactRadius = 1.f;
     int Seed = 46354;
     int RefittingPointLimit = 4;      // points of the limited hull behind a fragment's slab planes (Inc/Surtr.h:93): 4 .. 32 here
+    bool RadialMode = true;           // Inc/Surtr.h:100: an impact takes every body its sphere touches, not only the one hit
+    float TargetAdder = 0.01f;        // Inc/Surtr.h:109: how far behind the hit the impact is placed, along the ray
 };
+
+// DirectX::SimpleMath::Ray as OnMouseDown builds it (Src/Surtr.cpp:178-200): the direction is expected to be of unit length.
+struct Ray { Vector3 position, direction; Ray() = default; Ray(const Vector3& p, const Vector3& d) : position(p), direction(d) {} };
+// Surtr::ConvexRayIntersection (Src/Surtr.cpp:2460-2497), on the host from the definition of include/surtr_hip.h: the ray's
+// interval [0, inf) clipped by the half-space of every face plane (FacePlane; built from the first three vertices where it was
+// never constructed).  True when something is left; dist = the entry parameter (0 from inside).
+bool ConvexRayIntersection(const VMACH::Polygon3D& convex, const Ray ray, float& dist);
 
 struct FragmentRender { std::vector<VertexNormalColor> vertexData; std::vector<uint32_t> indexData; };
 
@@ -238,6 +247,16 @@ public:
     // (surtr_event_mass; definition in include/surtr_hip.h).  PieceMassProperties: the same for the resident pieces.
     std::vector<surtr_mass> MassProperties(int set, float density = 10.f);
     std::vector<surtr_mass> PieceMassProperties(int set, float density = 10.f);
+    // OnMouseDown's scene queries (Src/Surtr.cpp:207-240) on the Convex solids of the resident pieces, on the device
+    // (surtr_pieces_raycast / surtr_pieces_overlap; definition in include/surtr_hip.h).  OverlapSphere: one value per resident
+    // piece, 0 not touched, 1 touched, 2 touched but of mass <= minMass (density 10, as InitCompound; minMass < 0: no gate).
+    surtr_ray_hit Raycast(const Vector3& origin, const Vector3& dir, float maxDist = 1000.f);
+    std::vector<uint8_t> OverlapSphere(const Vector3& centre, float radius, float minMass = 1e-4f);
+    // What OnMouseDown does with them: a hit sets args.ImpactPosition = hit + dir * args.TargetAdder and returns the compounds
+    // affected, ascending -- with args.RadialMode those of the pieces a sphere of radius args.ImpactRadius / 2 about the impact
+    // touches and whose mass is above 1e-4 (Src/Surtr.cpp:228), else the compound of the piece hit.  pieceCompound[p] = compound of
+    // resident piece p.  No hit: nothing is returned and args is left as it was.
+    std::vector<int> PickImpact(const Vector3& origin, const Vector3& dir, FractureArgs& args, const std::vector<int>& pieceCompound);
     surtr_counts LastCounts() const { return counts_; }
     // The degenerate policy at this level (include/surtr_hip.h, surtr_counts::n_failed): where the reference leaves its own
     // arrays the engine flags the unit instead of emulating what the reference's memory happens to hold -- a flagged (cell,
