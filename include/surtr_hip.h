@@ -270,7 +270,7 @@ int surtr_pieces_from_event(surtr_ctx* ctx, const uint8_t* keep, uint32_t* n_pie
  * Poly::Transform of a single host polyhedron; the event path never needs it. */
 int surtr_download_piece(surtr_ctx* ctx, uint32_t piece, int set, uint32_t* out_nv, uint32_t* out_nh, float* out_pos,
                          uint32_t* out_nbr_off, int32_t* out_nbr);
-/* Host time of the last surtr_upload_pieces / surtr_pieces_from_event / surtr_transform_pieces call, in milliseconds,
+/* Host time of the last surtr_upload_pieces / surtr_pieces_from_event / surtr_transform_pieces / surtr_scene_commit call, in milliseconds,
  * and how many device allocations it made (0 in steady state: the piece buffers are pooled). */
 int surtr_upload_stats(surtr_ctx* ctx, float* ms, uint32_t* n_alloc);
 /* Diagnostic: the hand-over words of the last event's split Mesh clip (k_clip_pairs_main hands the pairs it cannot finish to
@@ -368,7 +368,9 @@ int surtr_regroup(uint32_t n_pieces, uint32_t n_outside, const int32_t* piece_ce
  * State: the skipped pieces are read from the resident pieces, so they must still be the ones the event ran over.  After
  * surtr_load_fragments there is no mask (see there).  After surtr_pieces_from_event the fragments are still the event's but its
  * pieces are gone: if the event's mask kept any piece out, the call returns SURTR_E_STATE (regroup before handing the fragments
- * on); an event without a mask, or with a mask of zeros, regroups as before. */
+ * on); an event without a mask, or with a mask of zeros, regroups as before.
+ * After surtr_scene_fracture_event only the skipped pieces of the event's compound are numbered (ascending), then the fragments:
+ * pieces of other bodies are in no bind set. */
 int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
                         uint32_t* n_pieces, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece);
 
@@ -484,6 +486,54 @@ int surtr_pieces_overlap(surtr_ctx* ctx, uint32_t n_spheres, const float* sphere
 /* The SURTR_QUERY_* bits of every piece as the last query found them (n >= the pieces of that query; synchronises).
  * SURTR_E_STATE before the first query. */
 int surtr_pieces_query_status(surtr_ctx* ctx, uint32_t n, uint32_t* status);
+
+/* ---- the scene: several bodies in the resident set (scene_dev.hip) ---- */
+/* FractureStorage::CompoundVec on the device, and the bookkeeping of ExecuteFractureRoutine (Src/Surtr.cpp:1829-1883): pick ->
+ * fracture -> commit -> pick without a download.  A compound is a contiguous range of resident pieces, the order of
+ * m_structuredBufferData (:1840-1843): compound c owns pieces [compound_off[c], compound_off[c + 1]).  After surtr_upload_pieces
+ * and surtr_pieces_from_event the scene is ONE compound holding every piece, so every other call behaves as it does without these.
+ *
+ * surtr_scene_set_compounds: n_compounds + 1 offsets, ascending from 0 to the number of resident pieces, no empty compound;
+ * anything else is SURTR_E_INVALID.  SURTR_E_STATE without resident pieces.
+ * surtr_scene_get_compounds: count-then-fill -- compound_off == NULL returns *n_compounds only; with it, cap is the entries it
+ * has room for (n_compounds + 1 are written; SURTR_E_CAPACITY when too small). */
+int surtr_scene_set_compounds(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* compound_off);
+int surtr_scene_get_compounds(surtr_ctx* ctx, uint32_t cap, uint32_t* n_compounds, uint32_t* compound_off);
+/* Poly::Transform of the pieces of one compound only (:1846-1851): n = its number of pieces, world = one matrix per piece of the
+ * compound as for surtr_transform_pieces.  The other pieces keep their bits; the derived data is rebuilt.  Like
+ * surtr_transform_pieces it forgets the last event. */
+int surtr_scene_transform_compound(surtr_ctx* ctx, uint32_t compound, uint32_t n, const float* world);
+/* surtr_fracture_event over the pieces of `compound` only: `outside` (may be NULL) has one byte per piece of that compound, in
+ * resident order; pieces of other compounds produce no pair; frag_ids carry RESIDENT piece numbers; fragments come in the same
+ * cell-major order.  surtr_event_regroup after it numbers that compound's skipped pieces (ascending), then the fragments: pieces
+ * of other bodies are in no bind set.  surtr_event_refit, surtr_event_mass(_dev) and surtr_event_download work as after any event. */
+int surtr_scene_fracture_event(surtr_ctx* ctx, uint32_t compound, uint32_t cell_begin, uint32_t cell_end, const uint8_t* outside,
+                               uint32_t flags, surtr_counts* counts);
+int surtr_scene_fracture_event_async(surtr_ctx* ctx, uint32_t compound, uint32_t cell_begin, uint32_t cell_end, const uint8_t* outside,
+                                     uint32_t flags);
+/* Makes the resident set what :1856-1875 make CompoundVec: the event's compound is erased, the compounds it broke into are pushed
+ * to the back.  (n_compounds, compound_off, compound_piece) are the compounds exactly as surtr_event_regroup returned them for the
+ * last scene event (compound 0, the pieces out of the impact, included).
+ *   New order: the pieces of every other compound first, in their old order (the compounds above the target move down by one);
+ *   then, for each returned compound in order, its members: skipped resident pieces are copied as they stand, fragments come from
+ *   the event arena with the Convex the context holds (refitted if surtr_event_refit ran).  The new compounds get the numbers
+ *   *first_new_compound .. + *n_new_compounds - 1.
+ *   Left out: a fragment that is no solid (Mesh or Convex of fewer than four vertices, as surtr_pieces_from_event) or that is
+ *   flagged (frag_status != 0); a compound left without pieces is not created.
+ *   src (may be NULL; room for the resident pieces + the event's fragments): one value per new piece, >= 0 the old resident piece,
+ *   -(f + 1) fragment f.  *n_pieces = the new number of resident pieces.
+ * The layout is made on the host from the small tables; one kernel gathers both sets from the old pieces and the arena into spare
+ * buffers kept in the context, which are then swapped in; the derived data of the whole scene is rebuilt.  From the second commit
+ * of a scene of steady size on, surtr_upload_stats reports 0 allocations.
+ * SURTR_E_STATE: no scene event; the event failed; the event was committed already; the resident pieces were replaced or
+ * transformed, or the compound table set, since the event.  SURTR_E_INVALID: the compounds do not cover pieces 0 .. n-1 exactly once
+ * (or nothing would be left).  On any error the scene is unchanged. */
+int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* compound_off, const int32_t* compound_piece,
+                       uint32_t* n_pieces, uint32_t* first_new_compound, uint32_t* n_new_compounds, int32_t* src);
+/* Diagnostic: host time of the last surtr_scene_commit in milliseconds, in two parts that both end in a stream synchronisation --
+ * checks, layout, tables and the gather kernel; then the swap, the derived data of the whole scene (derive_set) and the piece
+ * statistics. */
+int surtr_scene_commit_times(surtr_ctx* ctx, float* gather_ms, float* derive_ms);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,8 @@
 //                            (ExecuteFractureRoutine, Src/Surtr.cpp:1846-1851), then the derived data again
 //   surtr_pieces_from_event  the fragments of the last event become the pieces of the next one without leaving HBM
 //                            (recursive refracture, BASELINE configs[4])
+// The host routines (namespace pieces, declared in surtr_ctx.h) are shared with scene_dev.hip, which keeps several bodies in the
+// resident set and commits an event into it.
 // All piece buffers come from a grow-only pool: in steady state (same or smaller pieces) no call allocates or frees.
 #include <chrono>
 #include <cstring>
@@ -271,11 +273,13 @@ __global__ void k_piece_row_s(uint32_t V, uint32_t n, const uint32_t* __restrict
 // Poly::Transform (Src/Poly.cpp:580-585): Position = XMVector3TransformCoord(Position, XMMatrixTranspose(matrix)).
 // XMVector3TransformCoord (DirectXMath, not in the reference tree): r = z*M.r[2] + M.r[3]; r = y*M.r[1] + r;
 // r = x*M.r[0] + r; result = r.xyz / r.w -- with M = the transpose, M.r[k][c] = world[4*c + k].
-__global__ void k_transform(uint32_t V, uint32_t n, const uint32_t* __restrict__ vo, const float* __restrict__ world, float* __restrict__ pos)
+// Vertices [v0, V) of pieces p0 ..: world holds the matrix of piece p0 first.
+__global__ void k_transform(uint32_t V, uint32_t n, const uint32_t* __restrict__ vo, const float* __restrict__ world, float* __restrict__ pos,
+                            uint32_t v0, uint32_t p0)
 {
-    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t v = v0 + blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= V) return;
-    const float* W = world + 16 * (size_t)piece_of(vo, n, v);
+    const float* W = world + 16 * (size_t)(piece_of(vo, n, v) - p0);
     const float x = pos[3 * (size_t)v], y = pos[3 * (size_t)v + 1], z = pos[3 * (size_t)v + 2];
     float r[4];
     for (int c = 0; c < 4; ++c)
@@ -304,18 +308,12 @@ __global__ __launch_bounds__(SURTR_WG) void k_pieces_from_frags(uint32_t n, From
     if (p + 1u == n && threadIdx.x == 0) loff[dv + nv] = dh + nh;
 }
 
-// ------------------------------------------------------------------- host
-// The buffers of the pieces keep a little room, so that slightly larger pieces fit too; surtr_upload_stats counts their allocations.
-template <class T>
-int grow_pieces(surtr_ctx* ctx, DevBuf<T>& b, size_t need)
-{
-    const size_t cap0 = b.cap;
-    const int rc = b.grow(ctx, need, std::max<size_t>(need + need / 4, 64));
-    if (rc == SURTR_OK && b.cap != cap0) ++ctx->upload_allocs;
-    return rc;
-}
-
 static inline uint32_t up_count(uint32_t m) { return (m + SURTR_SPH_FAN - 1u) / SURTR_SPH_FAN; }
+
+} // namespace
+
+// ------------------------------------------------------------------- host
+namespace pieces {
 
 int reserve_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, uint32_t H, uint32_t NB)
 {
@@ -391,6 +389,10 @@ void set_piece_stats(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const uint
     ctx->half_on = 4ull * small >= 3ull * n;
     if (const char* e = getenv("SURTR_HALF")) ctx->half_on = atoi(e) != 0;      // tests: force either way
     ctx->have_event = false; ctx->frags_of_pieces = false;
+    // the scene: one compound holding every piece, until surtr_scene_set_compounds / surtr_scene_commit say otherwise
+    ctx->scene_off.assign({0u, n}); ctx->scene_event_compound = -1;
+    ctx->h_vo[0].assign(mvo, mvo + n + 1); ctx->h_ho[0].assign(mho, mho + n + 1);
+    ctx->h_vo[1].assign(cvo, cvo + n + 1); ctx->h_ho[1].assign(cho, cho + n + 1);
 }
 
 int finish_upload(surtr_ctx* ctx, uint32_t n, bool check)
@@ -404,14 +406,34 @@ int finish_upload(surtr_ctx* ctx, uint32_t n, bool check)
     return SURTR_OK;
 }
 
-struct Timer
+int transform_range(surtr_ctx* ctx, uint32_t p0, uint32_t n, const float* world)
 {
-    surtr_ctx* ctx; std::chrono::steady_clock::time_point t0;
-    explicit Timer(surtr_ctx* c) : ctx(c), t0(std::chrono::steady_clock::now()) { c->upload_allocs = 0; }
-    ~Timer() { ctx->upload_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
+    const uint32_t np = ctx->n_pieces;
+    (void)hipSetDevice(ctx->device);
+    Timer timer(ctx);
+    hipStream_t st = ctx->stream;
+    int rc = grow_pieces(ctx, ctx->d_world, (size_t)16 * n);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(ctx->d_world, world, (size_t)64 * n, hipMemcpyHostToDevice, st));
+    std::vector<uint32_t> vo(np + 1);
+    for (int set = 0; set < 2; ++set)
+    {
+        PieceSet& S = set ? ctx->cset : ctx->mset;
+        HIPCHK(hipMemcpyAsync(vo.data(), S.vo, (size_t)(np + 1) * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const uint32_t V = vo[np], v0 = vo[p0], v1 = vo[p0 + n];
+        hipLaunchKernelGGL(k_transform, dim3((v1 - v0 + 255) / 256), dim3(256), 0, st, v1, np, S.vo, ctx->d_world, S.pos, v0, p0);
+        rc = derive_set(ctx, S, np, V, sphere_offsets(np, vo.data()), false);
+        if (rc) return rc;
+    }
+    ctx->have_event = false; ctx->frags_of_pieces = false; ctx->scene_event_compound = -1;
+    HIPCHK(hipStreamSynchronize(st));
+    return SURTR_OK;
+}
 
-} // namespace
+} // namespace pieces
+using namespace pieces;
 
 extern "C" {
 
@@ -462,27 +484,7 @@ int surtr_transform_pieces(surtr_ctx* ctx, uint32_t n, const float* world)
 {
     if (!ctx || !world) return SURTR_E_INVALID;
     if (!ctx->n_pieces || n != ctx->n_pieces) return ctx && ctx->n_pieces ? SURTR_E_INVALID : SURTR_E_STATE;
-    (void)hipSetDevice(ctx->device);
-    Timer timer(ctx);
-    hipStream_t st = ctx->stream;
-    int rc = grow_pieces(ctx, ctx->d_world, (size_t)16 * n);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpyAsync(ctx->d_world, world, (size_t)64 * n, hipMemcpyHostToDevice, st));
-    std::vector<uint32_t> vo(n + 1);
-    for (int set = 0; set < 2; ++set)
-    {
-        PieceSet& S = set ? ctx->cset : ctx->mset;
-        HIPCHK(hipMemcpyAsync(vo.data(), S.vo, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        const uint32_t V = vo[n];
-        hipLaunchKernelGGL(k_transform, dim3((V + 255) / 256), dim3(256), 0, st, V, n, S.vo, ctx->d_world, S.pos);
-        rc = derive_set(ctx, S, n, V, sphere_offsets(n, vo.data()), false);
-        if (rc) return rc;
-    }
-    ctx->have_event = false; ctx->frags_of_pieces = false;
-    HIPCHK(hipStreamSynchronize(st));
-    return SURTR_OK;
+    return transform_range(ctx, 0, n, world);
 }
 
 int surtr_pieces_from_event(surtr_ctx* ctx, const uint8_t* keep, uint32_t* n_out)

@@ -308,24 +308,40 @@ extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_spher
     if (!ctx || !n_compounds) return SURTR_E_INVALID;
     if (!ctx->have_event) return SURTR_E_STATE;
     if (partial && (!origin || (n_sphere && !sphere_points))) return SURTR_E_INVALID;
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    surtr_counts c;
-    int rc = surtr_event_counts(ctx, &c);
-    if (rc) return rc;
+    {
+        surtr_counts c;
+        const int rc = surtr_event_counts(ctx, &c);
+        if (rc) return rc;
+    }
     // pieces: the resident pieces the event skipped, then its fragments; bind sets as ApplyFracture leaves them.  The `outside`
     // mask belongs to the event that took it and to the pieces it ran over: surtr_load_fragments drops it (its fragments are
     // nobody's event), and once surtr_pieces_from_event has replaced the pieces a mask that kept any of them out names solids
     // that are gone -- the compounds of that event can no longer be formed (include/surtr_hip.h)
-    std::vector<uint32_t> kind, index, set_of;
     const bool masked = std::find_if(ctx->last_outside.begin(), ctx->last_outside.end(), [](uint8_t o) { return o != 0; }) != ctx->last_outside.end();
     if (masked && (!ctx->frags_of_pieces || ctx->last_outside.size() != ctx->n_pieces))
     {
         ctx->err = "surtr_event_regroup: the event kept pieces out of the impact, and the resident pieces have been replaced since";
         return SURTR_E_STATE;
     }
+    // (after surtr_scene_fracture_event the mask is zero outside the event's compound: the pieces of other bodies are in no bind set)
+    std::vector<uint32_t> skipped;
     for (uint32_t p = 0; masked && p < ctx->n_pieces; ++p)
-        if (ctx->last_outside[p]) { kind.push_back(0u); index.push_back(p); }
+        if (ctx->last_outside[p]) skipped.push_back(p);
+    return surtr_event_regroup_skipped(ctx, skipped, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece);
+}
+
+int surtr_event_regroup_skipped(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, int partial, uint32_t n_sphere, const float* sphere_points,
+                                const float origin[3], float radius, uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece)
+{
+    if (!ctx || !n_compounds) return SURTR_E_INVALID;
+    if (!ctx->have_event) return SURTR_E_STATE;
+    if (partial && (!origin || (n_sphere && !sphere_points))) return SURTR_E_INVALID;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    surtr_counts c;
+    int rc = surtr_event_counts(ctx, &c);
+    if (rc) return rc;
+    std::vector<uint32_t> kind(skipped.size(), 0u), index(skipped), set_of;
     const uint32_t n_outside = (uint32_t)kind.size();
     std::vector<FragRec> fr(c.n_frag);
     if (c.n_frag) HIPCHK(hipMemcpy(fr.data(), ctx->d_frags, (size_t)c.n_frag * sizeof(FragRec), hipMemcpyDeviceToHost));

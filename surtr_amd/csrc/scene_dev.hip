@@ -1,0 +1,257 @@
+// scene_dev.hip -- the resident pieces as a scene of several bodies (FractureStorage::CompoundVec) and the bookkeeping of
+// ExecuteFractureRoutine (Src/Surtr.cpp:1829-1883) on the device, so that pick -> fracture -> commit -> pick never leaves HBM.
+//
+//   surtr_scene_set_compounds / _get_compounds   compound c = resident pieces [compound_off[c], compound_off[c + 1])
+//   surtr_scene_transform_compound                Poly::Transform of one compound's pieces (:1846-1851)
+//   surtr_scene_fracture_event(_async)            the event over the pieces of one compound
+//   surtr_scene_commit                            erase the compound, push back what it broke into (:1856-1875): one gather
+//                                                 kernel from the old pieces and the event arena into spare buffers, then a swap
+// The layout of the new pieces is laid out on the host from the small tables (piece offsets, fragment records), as
+// surtr_pieces_from_event does; no solid leaves HBM.
+#include <cstring>
+#include <utility>
+
+#include "surtr_ctx.h"
+
+using namespace pieces;
+
+namespace {
+
+// What piece p of the new scene is made from, per set s (0 = Mesh, 1 = Convex): src[p] >= 0 an old resident piece, -(f + 1)
+// fragment f; sv / sh its first vertex / ring entry in its source (the old set, or the arena), dv / dh in the new set
+// (n + 1 entries: the last is the total).
+struct GatherTab { const int32_t* src; const uint32_t* sv[2]; const uint32_t* sh[2]; const uint32_t* dv[2]; const uint32_t* dh[2]; };
+struct SolidsIn { const float* pos; const uint32_t* loff; const int32_t* nbr; };
+struct SolidsOut { float* pos; uint32_t* loff; int32_t* nbr; };
+
+// One workgroup per (new piece, set): positions and rings are copied, ring offsets rebased; the last piece writes the closing
+// sentinel.  Plain stores to disjoint ranges, no atomics.
+__global__ __launch_bounds__(SURTR_WG) void k_scene_gather(uint32_t n, GatherTab T, Arena A, SolidsIn old0, SolidsIn old1, SolidsOut new0, SolidsOut new1)
+{
+    const uint32_t p = blockIdx.x >> 1, set = blockIdx.x & 1u;
+    if (p >= n) return;
+    const bool frag = T.src[p] < 0;
+    const SolidsIn O = set ? old1 : old0; const SolidsOut D = set ? new1 : new0;
+    const float* spos = frag ? A.pos : O.pos; const uint32_t* sloff = frag ? A.loff : O.loff; const int32_t* snbr = frag ? A.nbr : O.nbr;
+    const uint32_t sv = T.sv[set][p], sh = T.sh[set][p], dv = T.dv[set][p], dh = T.dh[set][p];
+    const uint32_t nv = T.dv[set][p + 1] - dv, nh = T.dh[set][p + 1] - dh;
+    for (uint32_t i = threadIdx.x; i < 3u * nv; i += group_size()) D.pos[3 * (size_t)dv + i] = spos[3 * (size_t)sv + i];
+    for (uint32_t v = threadIdx.x; v < nv; v += group_size()) D.loff[dv + v] = dh + (sloff[sv + v] - sh);
+    for (uint32_t e = threadIdx.x; e < nh; e += group_size()) D.nbr[dh + e] = snbr[sh + e];
+    if (p + 1u == n && threadIdx.x == 0) D.loff[dv + nv] = dh + nh;
+}
+
+bool valid_table(uint32_t n_compounds, const uint32_t* off, uint32_t n_pieces)
+{
+    if (!n_compounds || !off || off[0] != 0u || off[n_compounds] != n_pieces) return false;
+    for (uint32_t c = 0; c < n_compounds; ++c) if (off[c + 1] <= off[c]) return false;
+    return true;
+}
+
+} // namespace
+
+extern "C" {
+
+int surtr_scene_set_compounds(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* compound_off)
+{
+    if (!ctx) return SURTR_E_INVALID;
+    if (!ctx->n_pieces) return SURTR_E_STATE;
+    if (!valid_table(n_compounds, compound_off, ctx->n_pieces)) return SURTR_E_INVALID;
+    ctx->scene_off.assign(compound_off, compound_off + n_compounds + 1);
+    ctx->scene_event_compound = -1;      // (an event's compound number belongs to the table it was given in)
+    return SURTR_OK;
+}
+
+int surtr_scene_get_compounds(surtr_ctx* ctx, uint32_t cap, uint32_t* n_compounds, uint32_t* compound_off)
+{
+    if (!ctx || !n_compounds) return SURTR_E_INVALID;
+    if (!ctx->n_pieces) return SURTR_E_STATE;
+    *n_compounds = (uint32_t)ctx->scene_off.size() - 1u;
+    if (!compound_off) return SURTR_OK;
+    if (cap < ctx->scene_off.size()) return SURTR_E_CAPACITY;
+    memcpy(compound_off, ctx->scene_off.data(), ctx->scene_off.size() * 4);
+    return SURTR_OK;
+}
+
+int surtr_scene_transform_compound(surtr_ctx* ctx, uint32_t compound, uint32_t n, const float* world)
+{
+    if (!ctx || !world) return SURTR_E_INVALID;
+    if (!ctx->n_pieces) return SURTR_E_STATE;
+    if (compound + 1u >= ctx->scene_off.size() || n != ctx->scene_off[compound + 1] - ctx->scene_off[compound]) return SURTR_E_INVALID;
+    return transform_range(ctx, ctx->scene_off[compound], n, world);
+}
+
+int surtr_scene_fracture_event_async(surtr_ctx* ctx, uint32_t compound, uint32_t cell_begin, uint32_t cell_end, const uint8_t* outside, uint32_t flags)
+{
+    if (!ctx) return SURTR_E_INVALID;
+    if (!ctx->n_pieces || !ctx->planes_ready) return SURTR_E_STATE;
+    if (compound + 1u >= ctx->scene_off.size() || cell_end > ctx->n_cells || cell_begin > cell_end) return SURTR_E_INVALID;
+    const uint32_t p0 = ctx->scene_off[compound], m = ctx->scene_off[compound + 1] - p0, nc = cell_end - cell_begin;
+    if ((uint64_t)nc * m > 0xFFFFFFFFull) return SURTR_E_INVALID;
+    // the pairs of this compound alone, cell-major as surtr_fracture_event takes them; the mask over all resident pieces
+    std::vector<uint32_t> cell((size_t)nc * m), piece((size_t)nc * m);
+    for (uint32_t c = 0; c < nc; ++c)
+        for (uint32_t q = 0; q < m; ++q) { cell[(size_t)c * m + q] = cell_begin + c; piece[(size_t)c * m + q] = p0 + q; }
+    std::vector<uint8_t> mask;
+    if (outside) { mask.assign(ctx->n_pieces, 0); memcpy(mask.data() + p0, outside, m); }
+    const int rc = surtr_event_pairs_masked(ctx, nc * m, cell.data(), piece.data(), outside ? mask.data() : nullptr, flags);
+    if (rc) return rc;
+    ctx->scene_event_compound = (int)compound;
+    return SURTR_OK;
+}
+
+int surtr_scene_fracture_event(surtr_ctx* ctx, uint32_t compound, uint32_t cell_begin, uint32_t cell_end, const uint8_t* outside, uint32_t flags,
+                               surtr_counts* counts)
+{
+    int rc = surtr_scene_fracture_event_async(ctx, compound, cell_begin, cell_end, outside, flags);
+    if (rc) return rc;
+    surtr_counts c;
+    rc = surtr_event_counts(ctx, &c);
+    if (counts) *counts = c;
+    return rc;
+}
+
+int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* compound_off, const int32_t* compound_piece, uint32_t* n_pieces_out,
+                       uint32_t* first_new_compound, uint32_t* n_new_compounds, int32_t* src_out)
+{
+    if (!ctx || !compound_off || (n_compounds && compound_off[n_compounds] && !compound_piece)) return SURTR_E_INVALID;
+    if (!ctx->n_pieces || !ctx->have_event || !ctx->frags_of_pieces || ctx->scene_event_compound < 0 ||
+        (size_t)ctx->scene_event_compound + 1 >= ctx->scene_off.size())
+        return SURTR_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    Timer timer(ctx);
+    const auto clock0 = std::chrono::steady_clock::now();
+    hipStream_t st = ctx->stream;
+    surtr_counts c;
+    if (surtr_event_counts(ctx, &c) != SURTR_OK) return SURTR_E_STATE;      // the event failed: nothing to commit
+    // ---- everything is checked and laid out before anything is written
+    const uint32_t np = ctx->n_pieces, target = (uint32_t)ctx->scene_event_compound, t0 = ctx->scene_off[target], t1 = ctx->scene_off[target + 1];
+    std::vector<uint32_t> skipped;
+    for (uint32_t p = t0; p < t1 && ctx->last_outside.size() == np; ++p) if (ctx->last_outside[p]) skipped.push_back(p);
+    const uint32_t n_skip = (uint32_t)skipped.size(), n_in = n_skip + c.n_frag;
+    if (compound_off[0] != 0u || compound_off[n_compounds] != n_in) return SURTR_E_INVALID;
+    {
+        std::vector<uint8_t> seen(n_in, 0);
+        for (uint32_t k = 0; k < n_compounds; ++k)
+        {
+            if (compound_off[k + 1] < compound_off[k] || compound_off[k + 1] > n_in) return SURTR_E_INVALID;
+            for (uint32_t i = compound_off[k]; i < compound_off[k + 1]; ++i)
+            {
+                const int32_t q = compound_piece[i];
+                if (q < 0 || (uint32_t)q >= n_in || seen[q]) return SURTR_E_INVALID;
+                seen[q] = 1;
+            }
+        }
+    }
+    std::vector<FragRec> fr(c.n_frag); std::vector<uint32_t> fstat(c.n_frag);
+    if (c.n_frag)
+    {
+        HIPCHK(hipMemcpy(fr.data(), ctx->d_frags, (size_t)c.n_frag * sizeof(FragRec), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(fstat.data(), ctx->d_frag_status, (size_t)c.n_frag * 4, hipMemcpyDeviceToHost));
+    }
+    std::vector<int32_t> src;
+    std::vector<uint32_t> sv[2], sh[2], dv[2] = {{0u}, {0u}}, dh[2] = {{0u}, {0u}}, table{0u};
+    auto push_old = [&](uint32_t p) {
+        src.push_back((int32_t)p);
+        for (int s = 0; s < 2; ++s)
+        {
+            sv[s].push_back(ctx->h_vo[s][p]); sh[s].push_back(ctx->h_ho[s][p]);
+            dv[s].push_back(dv[s].back() + (ctx->h_vo[s][p + 1] - ctx->h_vo[s][p])); dh[s].push_back(dh[s].back() + (ctx->h_ho[s][p + 1] - ctx->h_ho[s][p]));
+        }
+    };
+    // the pieces of every other compound first, in their old order: the compounds above the target move down by one
+    for (uint32_t k = 0; k + 1 < ctx->scene_off.size(); ++k)
+    {
+        if (k == target) continue;
+        for (uint32_t p = ctx->scene_off[k]; p < ctx->scene_off[k + 1]; ++p) push_old(p);
+        table.push_back((uint32_t)src.size());
+    }
+    const uint32_t first_new = (uint32_t)table.size() - 1u;
+    // then the members of every returned compound: skipped pieces as they stand, fragments from the arena with the Convex the
+    // context holds.  A fragment that is no solid, or a flagged one, is left out; a compound left without pieces is not created.
+    for (uint32_t k = 0; k < n_compounds; ++k)
+    {
+        for (uint32_t i = compound_off[k]; i < compound_off[k + 1]; ++i)
+        {
+            const uint32_t q = (uint32_t)compound_piece[i];
+            if (q < n_skip) { push_old(skipped[q]); continue; }
+            const uint32_t f = q - n_skip;
+            if (fr[f].mv_n < 4 || fr[f].cv_n < 4 || fstat[f] != 0u) continue;
+            src.push_back(-(int32_t)(f + 1u));
+            sv[0].push_back(fr[f].mv_off); sh[0].push_back(fr[f].mh_off); dv[0].push_back(dv[0].back() + fr[f].mv_n); dh[0].push_back(dh[0].back() + fr[f].mh_n);
+            sv[1].push_back(fr[f].cv_off); sh[1].push_back(fr[f].ch_off); dv[1].push_back(dv[1].back() + fr[f].cv_n); dh[1].push_back(dh[1].back() + fr[f].ch_n);
+        }
+        if (src.size() != table.back()) table.push_back((uint32_t)src.size());
+    }
+    const uint32_t n = (uint32_t)src.size();
+    if (n == 0) return SURTR_E_INVALID;      // (a scene without a piece: as surtr_pieces_from_event refuses to keep nothing)
+    // ---- spare buffers, tables, gather
+    for (int s = 0; s < 2; ++s)
+    {
+        auto& B = ctx->spare[s];
+        if (grow_pieces(ctx, B.pos, 3 * (size_t)dv[s][n] + 3) || grow_pieces(ctx, B.loff, (size_t)dv[s][n] + 1) || grow_pieces(ctx, B.nbr, (size_t)dh[s][n] + 1) ||
+            grow_pieces(ctx, B.vo, n + 1))
+            return SURTR_E_HIP;
+    }
+    if (grow_pieces(ctx, ctx->d_commit_src, n) || grow_pieces(ctx, ctx->d_commit_tab, (size_t)8 * (n + 1))) return SURTR_E_HIP;
+    if (!ctx->d_upload_err) { if (ctx->d_upload_err.grow(ctx, 4)) return SURTR_E_HIP; ++ctx->upload_allocs; }
+    HIPCHK(hipMemsetAsync(ctx->d_upload_err, 0, 4, st));
+    uint32_t* d = ctx->d_commit_tab; const size_t w = (size_t)n + 1;
+    GatherTab T{ctx->d_commit_src, {d, d + w}, {d + 2 * w, d + 3 * w}, {d + 4 * w, d + 5 * w}, {d + 6 * w, d + 7 * w}};
+    HIPCHK(hipMemcpyAsync(ctx->d_commit_src, src.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    for (int s = 0; s < 2; ++s)
+    {
+        HIPCHK(hipMemcpyAsync((void*)T.sv[s], sv[s].data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((void*)T.sh[s], sh[s].data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((void*)T.dv[s], dv[s].data(), w * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((void*)T.dh[s], dh[s].data(), w * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->spare[s].vo, dv[s].data(), w * 4, hipMemcpyHostToDevice, st));
+    }
+    PieceSet& M = ctx->mset; PieceSet& C = ctx->cset;
+    hipLaunchKernelGGL(k_scene_gather, dim3(2 * n), dim3(SURTR_WG), 0, st, n, T, ctx->arena, SolidsIn{M.pos, M.loff, M.nbr}, SolidsIn{C.pos, C.loff, C.nbr},
+                       SolidsOut{ctx->spare[0].pos, ctx->spare[0].loff, ctx->spare[0].nbr}, SolidsOut{ctx->spare[1].pos, ctx->spare[1].loff, ctx->spare[1].nbr});
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));      // (the old buffers may be freed below)
+    const auto clock1 = std::chrono::steady_clock::now();
+    // ---- the gathered solids become the resident ones; the buffers they came from are the next commit's spare ones and get the
+    //      same room now, so that a scene of steady size commits without an allocation from its second commit on
+    for (int s = 0; s < 2; ++s)
+    {
+        PieceSet& S = s ? C : M; auto& B = ctx->spare[s];
+        std::swap(S.pos, B.pos); std::swap(S.loff, B.loff); std::swap(S.nbr, B.nbr); std::swap(S.vo, B.vo);
+        if (grow_pieces(ctx, B.pos, 3 * (size_t)dv[s][n] + 3) || grow_pieces(ctx, B.loff, (size_t)dv[s][n] + 1) || grow_pieces(ctx, B.nbr, (size_t)dh[s][n] + 1) ||
+            grow_pieces(ctx, B.vo, n + 1))
+            return SURTR_E_HIP;
+    }
+    const std::vector<uint32_t> bo[2] = {sphere_offsets(n, dv[0].data()), sphere_offsets(n, dv[1].data())};
+    for (int s = 0; s < 2; ++s)
+    {
+        PieceSet& S = s ? C : M;
+        int rc = reserve_set(ctx, S, n, dv[s][n], dh[s][n], bo[s][n]);
+        if (rc) return rc;
+        rc = derive_set(ctx, S, n, dv[s][n], bo[s], false);
+        if (rc) return rc;
+    }
+    set_piece_stats(ctx, n, dv[0].data(), dh[0].data(), dv[1].data(), dh[1].data());
+    ctx->scene_off = table;
+    ctx->have_event = true;       // the event's fragments are still in the arena, as after surtr_pieces_from_event
+    ctx->frags_of_pieces = false; // (but the pieces they came from have moved)
+    if (n_pieces_out) *n_pieces_out = n;
+    if (first_new_compound) *first_new_compound = first_new;
+    if (n_new_compounds) *n_new_compounds = (uint32_t)table.size() - 1u - first_new;
+    if (src_out) memcpy(src_out, src.data(), (size_t)n * 4);
+    const int rc = finish_upload(ctx, n, false);      // (synchronises: the derived data is there)
+    ctx->commit_ms[0] = std::chrono::duration<float, std::milli>(clock1 - clock0).count();
+    ctx->commit_ms[1] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - clock1).count();
+    return rc;
+}
+
+int surtr_scene_commit_times(surtr_ctx* ctx, float* gather_ms, float* derive_ms)
+{
+    if (!ctx) return SURTR_E_INVALID;
+    if (gather_ms) *gather_ms = ctx->commit_ms[0];
+    if (derive_ms) *derive_ms = ctx->commit_ms[1];
+    return SURTR_OK;
+}
+
+} // extern "C"

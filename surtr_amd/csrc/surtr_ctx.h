@@ -2,6 +2,7 @@
 // (PairRec, FragRec, Arena), the resident pieces, the scratch pools, and the host-side context behind the C ABI.
 #pragma once
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
 #include <cstdlib>
 #include <string>
@@ -253,6 +254,14 @@ struct surtr_ctx
     DevBuf<uint32_t> d_from;         // surtr_pieces_from_event: fragment list and offsets
     DevBuf<uint32_t> d_qstatus; uint32_t qstatus_n = 0;   // query_dev.hip: per-piece status of the last ray cast / overlap
     float upload_ms = 0.f; uint32_t upload_allocs = 0;   // surtr_upload_stats
+    // the scene (scene_dev.hip): compound c owns resident pieces [scene_off[c], scene_off[c + 1]); every call that replaces the
+    // pieces leaves one compound holding all of them (set_piece_stats)
+    std::vector<uint32_t> scene_off;
+    std::vector<uint32_t> h_vo[2], h_ho[2];              // vertex / ring-entry offsets of the resident pieces (0 = Mesh, 1 = Convex), host copies
+    int scene_event_compound = -1;                       // compound the last event ran over (surtr_scene_fracture_event); -1: none, or committed
+    struct { DevBuf<float> pos; DevBuf<uint32_t> loff; DevBuf<int32_t> nbr; DevBuf<uint32_t> vo; } spare[2];   // surtr_scene_commit gathers into these, then swaps
+    DevBuf<int32_t> d_commit_src; DevBuf<uint32_t> d_commit_tab;      // its gather tables
+    float commit_ms[2] = {0.f, 0.f};                     // host time of the last commit up to the end of the gather / from there to its end (surtr_scene_commit_times)
     uint32_t regroup_rounds = 0;                         // label rounds of the last surtr_event_regroup (one launch)
     uint64_t tot_mv = 0, tot_mh = 0;
     // cells
@@ -332,6 +341,37 @@ int DevBuf<T>::grow(surtr_ctx* ctx, size_t need, size_t alloc)
     cap = n;
     return SURTR_OK;
 }
+
+// The resident pieces' host side (pieces_dev.hip), shared with scene_dev.hip.
+namespace pieces {
+// The buffers of the pieces keep a little room, so that slightly larger pieces fit too; surtr_upload_stats counts their allocations.
+template <class T>
+int grow_pieces(surtr_ctx* ctx, DevBuf<T>& b, size_t need)
+{
+    const size_t cap0 = b.cap;
+    const int rc = b.grow(ctx, need, std::max<size_t>(need + need / 4, 64));
+    if (rc == SURTR_OK && b.cap != cap0) ++ctx->upload_allocs;
+    return rc;
+}
+struct Timer
+{
+    surtr_ctx* ctx; std::chrono::steady_clock::time_point t0;
+    explicit Timer(surtr_ctx* c) : ctx(c), t0(std::chrono::steady_clock::now()) { c->upload_allocs = 0; }
+    ~Timer() { ctx->upload_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+int reserve_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, uint32_t H, uint32_t NB);
+int derive_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, const std::vector<uint32_t>& bo_h, bool check);
+std::vector<uint32_t> sphere_offsets(uint32_t n, const uint32_t* vo);
+void set_piece_stats(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const uint32_t* mho, const uint32_t* cvo, const uint32_t* cho);
+int finish_upload(surtr_ctx* ctx, uint32_t n, bool check);
+// Poly::Transform of resident pieces [p0, p0 + n) by world[16 * (p - p0) ..], the derived data again; the other pieces keep their bits
+int transform_range(surtr_ctx* ctx, uint32_t p0, uint32_t n, const float* world);
+}
+// an event over an explicit pair list with an `outside` mask over all resident pieces (surtr_hip.hip); NULL: no mask
+int surtr_event_pairs_masked(surtr_ctx* ctx, uint32_t n_pairs, const uint32_t* pair_cell, const uint32_t* pair_piece, const uint8_t* outside, uint32_t flags);
+// surtr_event_regroup given the resident pieces the event skipped, ascending (regroup_dev.hip)
+int surtr_event_regroup_skipped(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, int partial, uint32_t n_sphere, const float* sphere_points,
+                                const float origin[3], float radius, uint32_t* n_pieces, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece);
 
 // placement of cell groups with per-group scale / shift already in device memory (surtr_hip.hip)
 extern "C" int surtr_place_cells_groups_dev(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* group_cell_off, const float* d_scale3, const float* d_shift3);

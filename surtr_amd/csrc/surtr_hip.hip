@@ -3903,6 +3903,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     PROF_END(4);
     HIPCHK(hipGetLastError());
     ctx->have_event = true; ctx->last_flags = flags; ctx->last_current = false; ctx->frags_of_pieces = true;
+    ctx->scene_event_compound = -1;      // (surtr_scene_fracture_event sets it after this)
     return SURTR_OK;
 }
 
@@ -3915,6 +3916,14 @@ int surtr_fracture_event_async(surtr_ctx* ctx, uint32_t cell_begin, uint32_t cel
 }
 
 int surtr_fracture_pairs_async(surtr_ctx* ctx, uint32_t n_pairs, const uint32_t* pair_cell, const uint32_t* pair_piece, uint32_t flags)
+{
+    return surtr_event_pairs_masked(ctx, n_pairs, pair_cell, pair_piece, nullptr, flags);
+}
+
+} // extern "C"
+
+// The pair-list event with an `outside` mask over the resident pieces (surtr_scene_fracture_event lists the pairs of one compound).
+int surtr_event_pairs_masked(surtr_ctx* ctx, uint32_t n_pairs, const uint32_t* pair_cell, const uint32_t* pair_piece, const uint8_t* outside, uint32_t flags)
 {
     if (!ctx || (n_pairs && (!pair_cell || !pair_piece))) return SURTR_E_INVALID;
     if (!ctx->n_pieces || !ctx->planes_ready) return SURTR_E_STATE;
@@ -3943,8 +3952,10 @@ int surtr_fracture_pairs_async(surtr_ctx* ctx, uint32_t n_pairs, const uint32_t*
         if (rc2) return rc2;
         ctx->pair_order_is_list = true; ctx->pair_order_count = n_pairs;
     }
-    return launch_event(ctx, 0, n_pairs, ctx->d_pair_list, nullptr, flags);
+    return launch_event(ctx, 0, n_pairs, ctx->d_pair_list, outside, flags);
 }
+
+extern "C" {
 
 // face -> group table of the pattern (cached per pattern) and the placement kernel; scale3 / shift3 are device arrays
 int surtr_place_cells_groups_dev(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* group_cell_off, const float* d_scale3, const float* d_shift3)

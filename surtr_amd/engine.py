@@ -501,6 +501,62 @@ class Engine:
         self._ck(lib().surtr_pieces_from_event(self._h, _p(k), ctypes.byref(n)))
         return n.value
 
+    # ---- the scene: several bodies in the resident set (include/surtr_hip.h, scene_dev.hip)
+    def scene_set_compounds(self, compound_off):
+        """surtr_scene_set_compounds: compound c = resident pieces [compound_off[c], compound_off[c + 1])."""
+        co = np.ascontiguousarray(compound_off, np.uint32)
+        self._ck(lib().surtr_scene_set_compounds(self._h, ctypes.c_uint32(max(co.shape[0] - 1, 0)), _p(co)))
+
+    def scene_compounds(self):
+        """surtr_scene_get_compounds: the compound table as uint32[n_compounds + 1]."""
+        n = ctypes.c_uint32()
+        self._ck(lib().surtr_scene_get_compounds(self._h, ctypes.c_uint32(0), ctypes.byref(n), None))
+        co = np.zeros(n.value + 1, np.uint32)
+        self._ck(lib().surtr_scene_get_compounds(self._h, ctypes.c_uint32(co.shape[0]), ctypes.byref(n), _p(co)))
+        return co
+
+    def scene_transform_compound(self, compound, world):
+        """surtr_scene_transform_compound: Poly::Transform of that compound's pieces only; world: f32[n,4,4], one per piece of it."""
+        w = np.ascontiguousarray(world, np.float32).reshape(-1, 16)
+        self._ck(lib().surtr_scene_transform_compound(self._h, ctypes.c_uint32(int(compound)), ctypes.c_uint32(w.shape[0]), _p(w)))
+
+    def scene_fracture_event(self, compound, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
+        """surtr_scene_fracture_event: the event over the pieces of one compound; outside: one byte per piece of that compound."""
+        c = Counts()
+        om = None if outside is None else np.ascontiguousarray(outside, np.uint8)
+        if om is not None:
+            co = self.scene_compounds()
+            if not 0 <= int(compound) < co.shape[0] - 1 or om.shape[0] != int(co[int(compound) + 1]) - int(co[int(compound)]):
+                raise SurtrError(E_INVALID, "outside holds %d bytes" % om.shape[0])
+        self._ck(lib().surtr_scene_fracture_event(self._h, ctypes.c_uint32(int(compound)), ctypes.c_uint32(cell_begin), ctypes.c_uint32(cell_end),
+                                                  _p(om), ctypes.c_uint32(flags), ctypes.byref(c)))
+        return c
+
+    def scene_fracture_event_async(self, compound, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
+        om = None if outside is None else np.ascontiguousarray(outside, np.uint8)
+        self._ck(lib().surtr_scene_fracture_event_async(self._h, ctypes.c_uint32(int(compound)), ctypes.c_uint32(cell_begin),
+                                                        ctypes.c_uint32(cell_end), _p(om), ctypes.c_uint32(flags)))
+
+    def scene_commit(self, compound_off, compound_piece):
+        """surtr_scene_commit with the compounds event_regroup returned for the last scene event: the event's compound is erased,
+        what it broke into is pushed to the back.  Returns (n_pieces, first_new_compound, n_new_compounds, src): src[p] >= 0 the
+        old resident piece new piece p was, -(f + 1) fragment f."""
+        co = np.ascontiguousarray(compound_off, np.uint32)
+        cp = np.ascontiguousarray(compound_piece, np.int32)
+        if co.shape[0] < 1 or int(co[-1]) > cp.shape[0]:
+            raise SurtrError(E_INVALID, "compound_off does not fit compound_piece")
+        n, first, nnew = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        src = np.zeros(int(self.scene_compounds()[-1]) + int(co[-1]) + 1, np.int32)      # resident pieces + the event's pieces at most
+        self._ck(lib().surtr_scene_commit(self._h, ctypes.c_uint32(co.shape[0] - 1), _p(co), _p(cp), ctypes.byref(n), ctypes.byref(first),
+                                          ctypes.byref(nnew), _p(src)))
+        return n.value, first.value, nnew.value, src[:n.value].copy()
+
+    def scene_commit_times(self):
+        """surtr_scene_commit_times: host milliseconds of the last commit (up to the end of the gather, from there to its end)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        self._ck(lib().surtr_scene_commit_times(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return float(a.value), float(b.value)
+
     def upload_stats(self):
         ms, na = ctypes.c_float(), ctypes.c_uint32()
         self._ck(lib().surtr_upload_stats(self._h, ctypes.byref(ms), ctypes.byref(na)))

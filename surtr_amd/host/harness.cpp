@@ -3,6 +3,10 @@
 // JSON summary (optionally writes the fragments as an OBJ).  Usage:
 //   surtr_harness [--mesh cube|torus | --obj-in mesh.obj [--scale S]] [--cells N] [--nu A --nv B] [--ach] [--obj out.obj]
 //                 [--pick ox,oy,oz,dx,dy,dz [--impact-radius R]]
+//                 [--scene-clicks "ox,oy,oz,dx,dy,dz;..." [--impact-radius R]]
+// --scene-clicks: the event's fragments become a resident scene (piece k in compound k / 2) and every click runs OnMouseDown on
+//                 it (partial fracture, the compound of the piece hit, pattern and sphere of radius R at the impact); after each
+//                 click one JSON line: the compound table, the piece hit, the compounds hit and made, the mass of every compound.
 // --pick: the event's fragments become the resident pieces (piece k in compound k / 2) and the ray is cast into them as
 // OnMouseDown does (Src/Surtr.cpp:207-240): the hit, the impact position, the overlap mask and the affected compounds, as JSON.
 // --ach runs Surtr::PrepareFracture end to end (ACH convex instead of the plain 2x box).
@@ -11,6 +15,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <array>
+#include <set>
+#include <vector>
 #include <random>
 #include <string>
 
@@ -315,10 +322,52 @@ static void pick(FractureEngine& eng, const std::vector<Fragment>& frags, const 
     printf("}}\n");
 }
 
+// --scene-clicks: OnMouseDown per click on the resident scene; one JSON line per click.
+static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float, 6>>& clicks, float impact_radius)
+{
+    const uint32_t n0 = eng.CompoundFromLastEvent();
+    std::vector<uint32_t> off;
+    for (uint32_t p = 0; p < n0; p += 2) off.push_back(p);
+    off.push_back(n0);
+    const int rc = surtr_scene_set_compounds(eng.Raw(), (uint32_t)off.size() - 1u, off.data());
+    if (rc) throw Error(rc, "surtr_scene_set_compounds");
+    // the 26 directions of the 3 x 3 x 3 lattice, unit length (double arithmetic, narrowed): the sphere point cloud
+    std::vector<Vector3> cloud;
+    for (int i = -1; i <= 1; ++i) for (int j = -1; j <= 1; ++j) for (int k = -1; k <= 1; ++k)
+    {
+        if (!i && !j && !k) continue;
+        const double l = std::sqrt((double)(i * i + j * j + k * k));
+        cloud.emplace_back((float)(i / l), (float)(j / l), (float)(k / l));
+    }
+    for (size_t q = 0; q < clicks.size(); ++q)
+    {
+        const Vector3 o(clicks[q][0], clicks[q][1], clicks[q][2]), d(clicks[q][3], clicks[q][4], clicks[q][5]);
+        FractureArgs args;
+        args.PartialFracture = true; args.RadialMode = false; args.ImpactRadius = impact_radius;
+        const surtr_ray_hit hit = eng.Raycast(o, d);
+        std::vector<int> hitc;
+        const std::vector<int> made = eng.OnMouseDown(o, d, args, impact_radius, cloud, &hitc);
+        const std::vector<uint32_t> table = eng.SceneCompounds();
+        std::vector<std::set<int>> bind(table.size() - 1);
+        for (size_t c = 0; c + 1 < table.size(); ++c) for (uint32_t p = table[c]; p < table[c + 1]; ++p) bind[c].insert((int)p);
+        const std::vector<surtr_mass> cm = CompoundMass(bind, eng.PieceMassProperties(1));
+        printf("{\"click\": %zu, \"hit_piece\": %d, \"compounds_hit\": [", q, hit.piece);
+        for (size_t i = 0; i < hitc.size(); ++i) printf("%s%d", i ? ", " : "", hitc[i]);
+        printf("], \"compounds_made\": [");
+        for (size_t i = 0; i < made.size(); ++i) printf("%s%d", i ? ", " : "", made[i]);
+        printf("], \"table\": [");
+        for (size_t i = 0; i < table.size(); ++i) printf("%s%u", i ? ", " : "", table[i]);
+        printf("], \"mass\": [");
+        for (size_t i = 0; i < cm.size(); ++i) printf("%s%.17g", i ? ", " : "", cm[i].mass);
+        printf("]}\n");
+    }
+}
+
 int main(int argc, char** argv)
 {
     std::string mesh = "cube", obj, obj_in, dump;
     int cells = 8, nu = 250, nv = 200;
+    std::vector<std::array<float, 6>> clicks;
     bool ach = false, do_pick = false; float in_scale = 1.f, pick_ray[6] = {0, 0, 0, 1, 0, 0}, impact_radius = 1.f;
     for (int i = 1; i < argc; ++i)
     {
@@ -332,6 +381,19 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--ach")) ach = true;
         else if (!strcmp(argv[i], "--api-dump") && i + 1 < argc) dump = argv[++i];
         else if (!strcmp(argv[i], "--impact-radius") && i + 1 < argc) impact_radius = (float)atof(argv[++i]);
+        else if (!strcmp(argv[i], "--scene-clicks") && i + 1 < argc)
+        {
+            const char* c = argv[++i];
+            while (*c)
+            {
+                std::array<float, 6> r; int used = 0;
+                if (sscanf(c, "%f,%f,%f,%f,%f,%f%n", &r[0], &r[1], &r[2], &r[3], &r[4], &r[5], &used) != 6)
+                { fprintf(stderr, "surtr_harness: --scene-clicks takes ox,oy,oz,dx,dy,dz;...\n"); return 2; }
+                clicks.push_back(r);
+                c += used;
+                if (*c == ';') ++c;
+            }
+        }
         else if (!strcmp(argv[i], "--pick") && i + 1 < argc)
         {
             do_pick = sscanf(argv[++i], "%f,%f,%f,%f,%f,%f", pick_ray, pick_ray + 1, pick_ray + 2, pick_ray + 3, pick_ray + 4, pick_ray + 5) == 6;
@@ -376,6 +438,7 @@ int main(int argc, char** argv)
                "\"conv_verts\": %u, \"indices\": %u}\n", mesh.c_str(), verts.size(), tris.size() / 3, cells, c.n_frag, c.mesh_verts,
                c.mesh_nbrs, c.conv_verts, c.n_idx);
         if (do_pick) pick(eng, frags, pick_ray, impact_radius);
+        if (!clicks.empty()) scene_clicks(eng, clicks, impact_radius);
         if (!obj.empty())
         {
             FILE* f = fopen(obj.c_str(), "w");

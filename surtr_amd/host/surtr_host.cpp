@@ -584,6 +584,116 @@ std::vector<int> FractureEngine::PickImpact(const Vector3& origin, const Vector3
     return std::vector<int>(out.begin(), out.end());
 }
 
+void FractureEngine::SetScene(const std::vector<Compound>& compoundVec)
+{
+    Compound all;
+    std::vector<uint32_t> off(1, 0u);
+    for (const auto& c : compoundVec)
+    {
+        if (c.PieceVec.empty()) throw Error(SURTR_E_INVALID, "SetScene: a compound without pieces");
+        all.PieceVec.insert(all.PieceVec.end(), c.PieceVec.begin(), c.PieceVec.end());
+        off.push_back((uint32_t)all.PieceVec.size());
+    }
+    if (compoundVec.empty()) throw Error(SURTR_E_INVALID, "SetScene: no compound");
+    SetCompound(all);
+    check(surtr_scene_set_compounds(ctx_, (uint32_t)compoundVec.size(), off.data()), "surtr_scene_set_compounds");
+}
+
+std::vector<uint32_t> FractureEngine::SceneCompounds()
+{
+    uint32_t n = 0;
+    check(surtr_scene_get_compounds(ctx_, 0, &n, nullptr), "surtr_scene_get_compounds");
+    std::vector<uint32_t> off(n + 1);
+    check(surtr_scene_get_compounds(ctx_, n + 1, &n, off.data()), "surtr_scene_get_compounds");
+    return off;
+}
+
+std::vector<int> FractureEngine::PickImpact(const Vector3& origin, const Vector3& dir, FractureArgs& args)
+{
+    const std::vector<uint32_t> off = SceneCompounds();
+    std::vector<int> pieceCompound(off.back());
+    for (size_t c = 0; c + 1 < off.size(); ++c) for (uint32_t p = off[c]; p < off[c + 1]; ++p) pieceCompound[p] = (int)c;
+    return PickImpact(origin, dir, args, pieceCompound);
+}
+
+std::vector<int> FractureEngine::ExecuteFractureRoutine(int compound, const std::vector<Matrix>& world, float maxAxisScale, const FractureArgs& args,
+                                                        const std::vector<Vector3>& spherePointCloud)
+{
+    const std::vector<uint32_t> table = SceneCompounds();
+    if (compound < 0 || (size_t)compound + 1 >= table.size()) throw Error(SURTR_E_INVALID, "ExecuteFractureRoutine: no such compound");
+    const uint32_t p0 = table[(size_t)compound], m = table[(size_t)compound + 1] - p0;
+    // the pre-transform (:1846-1851)
+    if (!world.empty())
+    {
+        if (world.size() != m) throw Error(SURTR_E_INVALID, "ExecuteFractureRoutine: one matrix per piece of the compound");
+        std::vector<float> w; w.reserve(16 * world.size());
+        for (const auto& x : world) w.insert(w.end(), x.m, x.m + 16);
+        check(surtr_scene_transform_compound(ctx_, (uint32_t)compound, m, w.data()), "surtr_scene_transform_compound");
+    }
+    // DoFracture's placement (:1890-1915)
+    const float s2 = maxAxisScale * 2.f;
+    SetRefittingPointLimit(args.RefittingPointLimit);
+    PlacePattern(Vector3(s2, s2, s2), args.ImpactPosition);
+    std::vector<Vector3> cloud = spherePointCloud;
+    for (auto& v : cloud)
+    {
+        v.x *= args.ImpactRadius; v.y *= args.ImpactRadius; v.z *= args.ImpactRadius;
+        v.x += args.ImpactPosition.x; v.y += args.ImpactPosition.y; v.z += args.ImpactPosition.z;
+    }
+    const std::vector<float> fc = flat_points(cloud);
+    const float org[3] = {args.ImpactPosition.x, args.ImpactPosition.y, args.ImpactPosition.z};
+    // the pieces of the compound out of the sphere are kept whole
+    std::vector<uint8_t> mask(m, 0);
+    bool any = false;
+    for (uint32_t k = 0; args.PartialFracture && k < m; ++k)
+    {
+        uint32_t nv = 0, nh = 0;
+        check(surtr_download_piece(ctx_, p0 + k, 1, &nv, &nh, nullptr, nullptr, nullptr), "surtr_download_piece");
+        std::vector<float> pos(3 * (size_t)nv + 3); std::vector<uint32_t> no(nv + 1); std::vector<int32_t> nbr(nh + 1);
+        check(surtr_download_piece(ctx_, p0 + k, 1, &nv, &nh, pos.data(), no.data(), nbr.data()), "surtr_download_piece");
+        int out = 0;
+        const int rc = surtr_convex_out_of_sphere(nv, pos.data(), no.data(), nbr.data(), (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, &out);
+        if (rc) throw Error(rc, std::string("surtr_convex_out_of_sphere: ") + surtr_strerror(rc));
+        mask[k] = out ? 1 : 0; any = any || out;
+    }
+    check(surtr_scene_fracture_event(ctx_, (uint32_t)compound, 0, n_cells_, any ? mask.data() : nullptr, 0u, &counts_), "surtr_scene_fracture_event");
+    uint32_t np = 0, nc = 0;
+    check(surtr_event_regroup(ctx_, args.PartialFracture ? 1 : 0, (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, &np, &nc, nullptr, nullptr),
+          "surtr_event_regroup");
+    std::vector<uint32_t> off(np + 2);
+    std::vector<int32_t> piece(np + 1);
+    check(surtr_event_regroup(ctx_, args.PartialFracture ? 1 : 0, (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, &np, &nc, off.data(), piece.data()),
+          "surtr_event_regroup");
+    check(surtr_event_refit(ctx_), "surtr_event_refit");
+    check(surtr_event_counts(ctx_, &counts_), "surtr_event_counts");
+    flagged_ = FlaggedUnits();
+    flagged_.n_failed = counts_.n_failed;
+    if (counts_.n_failed && !allow_flagged_)
+        throw Error(SURTR_E_TOPOLOGY, "ExecuteFractureRoutine: the event flagged " + std::to_string(counts_.n_failed) + " unit(s); nothing was committed");
+    uint32_t n = 0, first = 0, n_new = 0;
+    check(surtr_scene_commit(ctx_, nc, off.data(), piece.data(), &n, &first, &n_new, nullptr), "surtr_scene_commit");
+    n_pieces_ = n;
+    std::vector<int> made(n_new);
+    for (uint32_t k = 0; k < n_new; ++k) made[k] = (int)(first + k);
+    return made;
+}
+
+std::vector<int> FractureEngine::OnMouseDown(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
+                                             const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds)
+{
+    std::vector<int> hit = PickImpact(origin, dir, args);
+    if (hitCompounds) *hitCompounds = hit;
+    std::vector<int> made;
+    // descending: a commit moves only the compounds above its target, and those have been dealt with
+    for (auto it = hit.rbegin(); it != hit.rend(); ++it)
+    {
+        for (int& c : made) --c;      // (the compounds made so far sit above every target still to come: each moves down by one)
+        const std::vector<int> more = ExecuteFractureRoutine(*it, {}, maxAxisScale, args, spherePointCloud);
+        made.insert(made.end(), more.begin(), more.end());
+    }
+    return made;
+}
+
 bool ConvexRayIntersection(const VMACH::Polygon3D& convex, const Ray ray, float& dist)
 {
     const double o[3] = {ray.position.x, ray.position.y, ray.position.z}, d[3] = {ray.direction.x, ray.direction.y, ray.direction.z};

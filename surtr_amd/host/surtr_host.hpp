@@ -257,6 +257,26 @@ public:
     // touches and whose mass is above 1e-4 (Src/Surtr.cpp:228), else the compound of the piece hit.  pieceCompound[p] = compound of
     // resident piece p.  No hit: nothing is returned and args is left as it was.
     std::vector<int> PickImpact(const Vector3& origin, const Vector3& dir, FractureArgs& args, const std::vector<int>& pieceCompound);
+    // ---- the click loop on a resident scene (OnMouseDown, Src/Surtr.cpp:178-254; ExecuteFractureRoutine, :1829-1883) ----
+    // FractureStorage::CompoundVec on the device: the pieces of all compounds become resident, compound c a contiguous range of
+    // them in the order of m_structuredBufferData (:1840-1843).  SceneCompounds: c owns pieces [off[c], off[c + 1]).
+    void SetScene(const std::vector<Compound>& compoundVec);
+    std::vector<uint32_t> SceneCompounds();
+    // ExecuteFractureRoutine for one compound of the scene, in its order: Poly::Transform of that compound's pieces by `world`
+    // (one matrix per piece; empty: the pieces stay where they were committed), the pattern scaled by 2 * maxAxisScale and moved to
+    // the impact, the event on that compound (with PartialFracture its pieces out of the sphere are skipped: their Convex solids,
+    // a few dozen vertices each, are read back for ConvexOutOfSphere -- nothing else leaves the device), the regrouping, the refit,
+    // and the commit: the compound is erased, what it broke into is pushed to the back.  Returns the numbers of the new compounds.
+    // A flagged fragment is left out of the scene: as everywhere, that throws unless AllowFlagged(true).
+    std::vector<int> ExecuteFractureRoutine(int compound, const std::vector<Matrix>& world, float maxAxisScale, const FractureArgs& args,
+                                            const std::vector<Vector3>& spherePointCloud);
+    // PickImpact with the scene's own table.
+    std::vector<int> PickImpact(const Vector3& origin, const Vector3& dir, FractureArgs& args);
+    // OnMouseDown: PickImpact, then ExecuteFractureRoutine for every compound hit in DESCENDING number, so that the numbers of
+    // the compounds still to come stay valid (the reference holds pointers there).  Returns the new compounds as numbered after
+    // the last commit; hitCompounds (may be null) receives what PickImpact returned.
+    std::vector<int> OnMouseDown(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
+                                 const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds = nullptr);
     surtr_counts LastCounts() const { return counts_; }
     // The degenerate policy at this level (include/surtr_hip.h, surtr_counts::n_failed): where the reference leaves its own
     // arrays the engine flags the unit instead of emulating what the reference's memory happens to hold -- a flagged (cell,
