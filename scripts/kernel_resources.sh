@@ -19,6 +19,6 @@ for line in sys.stdin:
     if k == "vgpr_spill_count" or len(cur) == 7:
         pass
     if set(cur) >= {"name", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_count", "vgpr_spill_count"}:
-        print("%-60s lds %6s scratch %5s vgpr %4s agpr %4s spill %s" % (cur["name"][:60], cur["group_segment_fixed_size"], cur["private_segment_fixed_size"], cur["vgpr_count"], cur.get("agpr_count", "-"), cur["vgpr_spill_count"]))
+        print("%-60s lds %6s scratch %5s vgpr %4s agpr %4s sgpr %4s spill %s" % (cur["name"][:60], cur["group_segment_fixed_size"], cur["private_segment_fixed_size"], cur["vgpr_count"], cur.get("agpr_count", "-"), cur.get("sgpr_count", "-"), cur["vgpr_spill_count"]))
         cur = {}
 '

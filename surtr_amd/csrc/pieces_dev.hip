@@ -618,9 +618,9 @@ int surtr_handover_stats(surtr_ctx* ctx, uint32_t out[8])
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (ctx->stream2) HIPCHK(hipStreamSynchronize(ctx->stream2));
     if (ctx->stream3) HIPCHK(hipStreamSynchronize(ctx->stream3));
-    uint32_t c[6] = {0, 0, 0, 0, 0, 0};
-    if (ctx->arena.cursors) HIPCHK(hipMemcpy(c, ctx->arena.cursors + 146, sizeof(c), hipMemcpyDeviceToHost));
-    for (int k = 0; k < 6; ++k) out[k] = c[k];
+    uint32_t c[CUR_HO_WORDS] = {};      // the hand-over block, in the order of the enumeration (surtr_ctx.h)
+    if (ctx->arena.cursors) HIPCHK(hipMemcpy(c, ctx->arena.cursors + CUR_HO_PUSHED, sizeof(c), hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < CUR_HO_WORDS; ++k) out[k] = c[k];
     out[6] = ctx->max_wg;
     out[7] = (uint32_t)ctx->d_hlist.cap;
     return SURTR_OK;

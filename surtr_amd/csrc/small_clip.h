@@ -280,7 +280,7 @@ __device__ inline int sc_park(const ScSolid& S, uint32_t nv, Shared& sh, uint32_
     const uint32_t wl = S.vw[nv - 1u];
     const uint32_t H = (wl & 0xFFFFu) + (wl >> 16);
     __syncthreads();
-    if (threadIdx.x == 0) { sh.misc[0] = atomicAdd(&cursors[0], nv); sh.misc[1] = atomicAdd(&cursors[1], H); }
+    if (threadIdx.x == 0) { sh.misc[0] = atomicAdd(&cursors[CUR_V], nv); sh.misc[1] = atomicAdd(&cursors[CUR_H], H); }
     __syncthreads();
     voff = sh.misc[0]; hoff = sh.misc[1];
     __syncthreads();

@@ -48,7 +48,7 @@ __host__ __device__ static inline ImgLayout img_layout(uint32_t F, uint32_t nbV,
     return L;
 }
 
-struct ImgArena { char* base; uint32_t cap16; };      // capacity in 16-byte units; cursor = Arena::cursors[10]
+struct ImgArena { char* base; uint32_t cap16; };      // capacity in 16-byte units; cursor = Arena::cursors[CUR_IMG]
 
 // Per-workgroup scratch of k_prep_pairs: work lists of the pre-pass and (for very large solids) its masks.
 struct PrepPool { char* base; size_t per_wg; uint32_t VMAX; };
@@ -76,12 +76,72 @@ struct Arena
     float* pos; uint32_t* loff; uint32_t* llen; int32_t* nbr; uint32_t* idx;
     uint2* isl;
     uint32_t capV, capH, capI, capIsl;
-    uint32_t* cursors;   // [0]=V [1]=H [2]=I [3]=Isl [4]=clip queue [5]=status [6]=refit queue [7]=faces queue [8]=convex queue
-                         // [9]=pre-pass queue [10]=image arena (16-byte units) [11]=big clip queue
-                         // [12]=half clip queue [13]=retry queue [14]=flagged fragments [15]=flagged pairs (n_failed = 14 + 15)
-                         // [16..31]=pairs per cost class (k_prep_pairs) [32..47]=fragments per size class [48..63]=pairs per
-                         // pre-pass class [64..79]=pairs per cost class of k_clip_pairs_half (64 = its retry list)
+    uint32_t* cursors;   // the event's device counters: CUR_COUNT words, slot map below
 };
+
+// The slot map of Arena::cursors: every word the kernels of an event coordinate through.  k_event_init clears all of them at the
+// start of an event ("cleared" below names only what clears a slot besides that).  surtr_queue_stats copies the first
+// CUR_STATS_WORDS out, and include/surtr_hip.h publishes some of them by number: those are pinned under the enumeration.
+enum : uint32_t
+{
+    // arena cursors (every kernel that parks a solid adds what it takes; k_out_scan and surtr_queue_stats read them)
+    CUR_V = 0,              // vertices.  W: arena_take, sc_park, wc_park.  surtr_load_fragments sets it
+    CUR_H = 1,              // ring entries.  W: the same
+    CUR_I = 2,              // triangle indices.  W: k_faces; R: k_out_scan.  Cleared by launch_faces
+    CUR_ISL = 3,            // island records.  W: arena_take, wc_park
+    // work-queue tickets (atomicAdd by lane 0 of a workgroup: the value is the ticket)
+    CUR_Q_CLIP = 4,         // k_clip_pairs / _wave / _main over the clip table's regular classes
+    CUR_STATUS = 5,         // W: atomicMax of the event's SURTR_E_* by any kernel; R: k_out_scan -> surtr_counts::status
+    CUR_Q_REFIT = 6,        // k_refit / k_refit_n over the fragment table.  Cleared by surtr_event_refit
+    CUR_Q_FACES = 7,        // k_faces (first tier) over the fragment table.  Cleared by launch_faces
+    CUR_Q_CONVEX = 8,       // k_clip_convex over the pairs
+    CUR_Q_PREP = 9,         // k_prep_pairs* over the pre-pass table (or the pairs themselves: front_par)
+    CUR_IMG = 10,           // image arena, 16-byte units.  W: k_prep_pairs*
+    CUR_Q_BIG = 11,         // k_clip_pairs_big / _wave_big over clip classes 15..14
+    CUR_Q_HALF = 12,        // k_clip_pairs_half over half classes 6..1
+    CUR_Q_RETRY = 13,       // the retry launch of k_clip_pairs over the half table's retry list
+    CUR_FLAGGED_FRAGS = 14, // W: k_refit*, k_faces; R: k_out_scan (n_failed = 14 + 15).  Cleared by launch_faces unless a refit flagged
+    CUR_FLAGGED_PAIRS = 15, // W: pair_failed; R: k_out_scan
+    // per-class counts, 16 classes each (a ticket walks them from the heaviest class down)
+    CUR_CLS_CLIP = 16,      // base.  W: k_prep_pairs* (enqueue); R: every Mesh clip kernel's take_pair
+    CUR_CLS_FRAG = 32,      // base.  W: k_frag_table, surtr_load_fragments; R: frag_of_ticket (k_refit*, k_faces)
+    CUR_CLS_PREP = 48,      // base.  W: k_clip_convex; R: k_prep_pairs*
+    CUR_CLS_HALF = 64,      // base.  W: k_prep_pairs* (enqueue_half); R: k_clip_pairs_half
+    CUR_RETRY_N = CUR_CLS_HALF,   // the half table's class 0 = retry list.  W: clip_pair_general<HALF>; R: the retry launch
+    // diagnostics of the Convex chain (W: convex_chain via ChainCaller; R: surtr_queue_stats)
+    CUR_CVX_RESUMED = 78,   // k_clip_convex: general clips resumed from a later plane
+    CUR_REFIT_RESUMED = 79, // k_refit*: the same
+    CUR_CVX_TOOK = 80,      // k_clip_convex: Convexes small_clip took; + 1 (81): handed on, or started on the literal clipper
+    CUR_REFIT_TOOK = 82,    // k_refit*: the same; + 1 (83): handed on
+    CUR_BIG_QUOTA = 84,     // W/R: k_prep_pairs*, large bands admitted to k_clip_pairs_big so far
+    CUR_FACES2_N = 85,      // second-tier faces list, fragments pushed.  W: k_faces first tier; R: second tier.  Cleared by launch_faces
+    CUR_Q_FACES2 = 86,      // ... its ticket (directly behind CUR_FACES2_N: launch_faces clears both with one fill)
+    // diagnostics (W: as said; R: surtr_queue_stats)
+    CUR_REC_TOOK = 88,      // clip_pairs_wave_body: pairs the record clipper finished
+    CUR_REC_HANDED = 89,    // ... handed on to the general clipper
+    CUR_LIT_TOO_LARGE = 90, // literal_run: solids too large for the literal clipper
+    CUR_REC_IMAGES = 91,    // k_prep_pairs*: bands left as record images
+    CUR_SORTED_SEL = 92,    // k_prep_pairs*: pairs that took the sorted selection
+    CUR_REC_SPENT = 93,     // clip_pairs_wave_body: record images given up on (redone from the piece)
+    CUR_CATCH_CLIPPED = 94, // k_clip_pairs_catch: pairs it clipped
+    CUR_UNREFITTED = 95,    // k_refit_n: fragments left un-refitted and flagged SURTR_E_CAPACITY
+    CUR_WC_WHY = 96,        // base of the record clipper's why[site] block (wave_clip.h: WC_WHY_WORDS words)
+    CUR_STATS_WORDS = 128,  // what surtr_queue_stats copies out (and surtr_load_fragments writes)
+    // hand-over from k_clip_pairs_main to k_clip_pairs_catch (surtr_handover_stats copies the CUR_HO_WORDS words out)
+    CUR_HO_PUSHED = 146,    // W: main, one per pair pushed to hlist; R: polling catcher, sweep
+    CUR_HO_STARTED = 147,   // W: main, one per workgroup on entry; R: polling catcher ("is it running beside me")
+    CUR_HO_SIGNED_OFF = 148,// W: main, one per workgroup after its last hand-over; R: polling catcher
+    CUR_HO_POLL_SLOT = 149, // W/R: catcher, hlist slot each polling workgroup waits on
+    CUR_Q_CATCH = 150,      // ticket of the catcher's own classes (clip classes 13..12)
+    CUR_Q_SWEEP = 151,      // ticket of the sweep launch over the pushed slots
+    CUR_HO_WORDS = 6,
+    CUR_COUNT = 256
+};
+static_assert(CUR_V == 0 && CUR_H == 1 && CUR_I == 2 && CUR_ISL == 3 && CUR_STATUS == 5 && CUR_CLS_CLIP == 16 && CUR_CLS_FRAG == 32 &&
+              CUR_CLS_PREP == 48 && CUR_CLS_HALF == 64 && CUR_REC_TOOK == 88 && CUR_REC_HANDED == 89 && CUR_LIT_TOO_LARGE == 90 &&
+              CUR_UNREFITTED == 95 && CUR_WC_WHY == 96, "include/surtr_hip.h publishes these slots of surtr_queue_stats by number");
+static_assert(CUR_STATS_WORDS <= CUR_COUNT && CUR_Q_SWEEP + 1 == CUR_HO_PUSHED + CUR_HO_WORDS && CUR_HO_PUSHED + CUR_HO_WORDS <= CUR_COUNT &&
+              CUR_Q_FACES2 == CUR_FACES2_N + 1, "slot map");
 
 struct alignas(16) SRow { uint32_t w[4]; };
 

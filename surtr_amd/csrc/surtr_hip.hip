@@ -281,8 +281,59 @@ __global__ void k_place_cells_groups(uint32_t nfaces, const float* __restrict__ 
 // error is the event's.
 __device__ __forceinline__ void pair_failed(const Arena& A, int err)
 {
-    // (cursor 15: pairs; cursor 14 counts flagged FRAGMENTS and is reset by a re-triangulation -- the pairs' count is the event's)
-    if (err == SURTR_E_TOPOLOGY) atomicAdd(&A.cursors[15], 1u); else atomicMax(&A.cursors[5], (uint32_t)err);
+    // (CUR_FLAGGED_FRAGS counts flagged FRAGMENTS and is reset by a re-triangulation -- the pairs' count is the event's)
+    if (err == SURTR_E_TOPOLOGY) atomicAdd(&A.cursors[CUR_FLAGGED_PAIRS], 1u); else atomicMax(&A.cursors[CUR_STATUS], (uint32_t)err);
+}
+
+// The fragments every kernel of the Mesh clip is put together from.
+// Ticket t -> pair: walks the class counts at A.cursors[class_base ..] from cls_hi down to cls_lo, heavy classes first, over
+// table[cls * n_pairs + i].  0xFFFFFFFF: t is beyond these classes, and is left reduced by their counts (a second table goes on
+// from there).
+__device__ __forceinline__ uint32_t pair_of_ticket(const Arena& A, const uint32_t* __restrict__ table, uint32_t n_pairs, uint32_t& t, uint32_t class_base,
+                                                   int cls_hi, int cls_lo)
+{
+    uint32_t p = 0xFFFFFFFFu;
+    for (int cls = cls_hi; cls >= cls_lo; --cls)
+    {
+        const uint32_t cnt = A.cursors[class_base + cls];
+        if (t < cnt) { p = table[(size_t)cls * n_pairs + t]; break; }
+        t -= cnt;
+    }
+    return p;
+}
+// ... of the next ticket of queue ticket_slot (one lane of the workgroup calls it)
+__device__ __forceinline__ uint32_t take_pair(const Arena& A, const uint32_t* __restrict__ table, uint32_t n_pairs, uint32_t ticket_slot, uint32_t class_base,
+                                              int cls_hi, int cls_lo)
+{
+    uint32_t t = atomicAdd(&A.cursors[ticket_slot], 1u);
+    return pair_of_ticket(A, table, n_pairs, t, class_base, cls_hi, cls_lo);
+}
+// Pair p -> its cell and piece: from the event's pair list, or cell-major over a cell range.
+struct PairAt { uint32_t cell, piece; };
+__device__ __forceinline__ PairAt pair_where(uint32_t p, const uint2* __restrict__ pair_list, uint32_t cell_begin, uint32_t n_pieces)
+{
+    return PairAt{pair_list ? pair_list[p].x : cell_begin + p / n_pieces, pair_list ? pair_list[p].y : p % n_pieces};
+}
+// The resident Mesh / Convex of a piece as a clipper's input.
+__device__ __forceinline__ SolidIn mesh_solid_in(const Pieces& P, uint32_t piece)
+{
+    const uint32_t m0 = P.mvo[piece];
+    return SolidIn{P.mpos + 3 * (size_t)m0, P.mloff + m0, P.mllen + m0, P.mnbr, P.mvo[piece + 1] - m0, P.mtri + m0, P.mrad + m0,
+                   P.mperm + m0, P.mposr_s + m0, P.mbsph + P.mbo[piece]};
+}
+__device__ __forceinline__ SolidIn convex_solid_in(const Pieces& P, uint32_t piece)
+{
+    const uint32_t c0 = P.cvo[piece];
+    return SolidIn{P.cpos + 3 * (size_t)c0, P.cloff + c0, P.cllen + c0, P.cnbr, P.cvo[piece + 1] - c0, P.ctri + c0, P.crad + c0,
+                   P.cperm + c0, P.cposr_s + c0, P.cbsph + P.cbo[piece]};
+}
+// The end of a pair's Mesh clip: a fragment with an invalid Convex fails the pair, a failed pair keeps no islands, the record is stored.
+__device__ __forceinline__ int finish_pair(const Arena& A, PairRec* __restrict__ pairs, uint32_t p, PairRec& rec, int err)
+{
+    if (err == 0 && rec.cv_bad != 0 && rec.ni != 0) err = SURTR_E_TOPOLOGY;
+    if (err != 0) { rec.status = (uint32_t)err; rec.ni = 0; if (threadIdx.x == 0) pair_failed(A, err); }
+    if (threadIdx.x == 0) pairs[p] = rec;
+    return err;
 }
 
 // ------------------------------------------------------------- arena output
@@ -292,9 +343,9 @@ __device__ __attribute__((always_inline)) static inline bool arena_take(const Ar
     __syncthreads();
     if (threadIdx.x == 0)
     {
-        sh.misc[0] = atomicAdd(&A.cursors[0], nv);
-        sh.misc[1] = atomicAdd(&A.cursors[1], nh);
-        sh.misc[2] = nisl ? atomicAdd(&A.cursors[3], nisl) : 0u;
+        sh.misc[0] = atomicAdd(&A.cursors[CUR_V], nv);
+        sh.misc[1] = atomicAdd(&A.cursors[CUR_H], nh);
+        sh.misc[2] = nisl ? atomicAdd(&A.cursors[CUR_ISL], nisl) : 0u;
     }
     __syncthreads();
     voff = sh.misc[0]; hoff = sh.misc[1]; ioff = sh.misc[2];
@@ -594,7 +645,7 @@ __device__ static void literal_write(const LitRun& r, float* pos, uint32_t* loff
 }
 __device__ __attribute__((noinline)) static ParkOut solid_literal(SolidIn in, uint32_t F, ScratchPool pool, uint32_t wg, Arena A, Shared* shp, bool ids_set = false)
 {
-    const LitRun r = literal_run(in, F, pool, wg, shp, ids_set, &A.cursors[90]);
+    const LitRun r = literal_run(in, F, pool, wg, shp, ids_set, &A.cursors[CUR_LIT_TOO_LARGE]);
     ParkOut o{r.err, 0u, 0u, 0u, 0u, r.stale};
     if (r.err != 0 || r.n == 0u) return o;
     uint32_t ioff;
@@ -738,15 +789,15 @@ __global__ __launch_bounds__(SURTR_LANES) __attribute__((amdgpu_waves_per_eu(SUR
     while (true)
     {
         __syncthreads();
-        if (tid == 0) sh.misc[7] = atomicAdd(&A.cursors[8], 1u);
+        if (tid == 0) sh.misc[7] = atomicAdd(&A.cursors[CUR_Q_CONVEX], 1u);
         __syncthreads();
         uint32_t p = sh.misc[7];
         if (p >= n_pairs) break;
         // pairs of cells with many planes first (pair_order: the event's pairs by plane count of their cell, descending): the
         // clip of a Convex costs about one step per plane, and the last tasks of the queue set the length of the kernel
         if (pair_order != nullptr) p = pair_order[p];
-        const uint32_t cell = pair_list ? pair_list[p].x : cell_begin + p / P.n;
-        const uint32_t piece = pair_list ? pair_list[p].y : p % P.n;
+        const PairAt at = pair_where(p, pair_list, cell_begin, P.n);
+        const uint32_t cell = at.cell, piece = at.piece;
         PairRec rec;
         memset(&rec, 0, sizeof(rec));
 #ifdef SURTR_STAMP_SMALL
@@ -765,19 +816,14 @@ __global__ __launch_bounds__(SURTR_LANES) __attribute__((amdgpu_waves_per_eu(SUR
         {
             for (uint32_t k = tid; k < F; k += group_size()) sh.planes[k] = planes[f0 + k];
             __syncthreads();
-            auto convex = [&] {
-                const uint32_t c0 = P.cvo[piece];
-                return SolidIn{P.cpos + 3 * (size_t)c0, P.cloff + c0, P.cllen + c0, P.cnbr, P.cvo[piece + 1] - c0, P.ctri + c0, P.crad + c0,
-                               P.cperm + c0, P.cposr_s + c0, P.cbsph + P.cbo[piece]};
-            };
             // a ring that lists a neighbour twice: the literal clipper from the start.  All planes come back from the cell's list
             // (the cost estimate below wants them too).
-            const ChainCaller who{80u, 78u, true, nullptr, planes + f0};
-            const ParkOut o = convex_chain(convex(), F, P.cdup[piece] != 0, who, [&] { return LiteralArg{convex(), false}; }, sh, U, S, pool, A, cst);
+            const ChainCaller who{CUR_CVX_TOOK, CUR_CVX_RESUMED, true, nullptr, planes + f0};
+            const ParkOut o = convex_chain(convex_solid_in(P, piece), F, P.cdup[piece] != 0, who, [&] { return LiteralArg{convex_solid_in(P, piece), false}; }, sh, U, S, pool, A, cst);
             err = o.err; rec.cv_off = o.voff; rec.cv_n = o.n; rec.ch_off = o.hoff; rec.ch_n = o.nh;
         }
         if (err == SURTR_E_TOPOLOGY) { rec.cv_bad = 1; rec.cv_off = 0; rec.cv_n = 1; rec.ch_off = 0; rec.ch_n = 0; err = 0; }
-        if (err != 0) { rec.status = (uint32_t)err; rec.cv_n = 0; if (tid == 0) atomicMax(&A.cursors[5], (uint32_t)err); }
+        if (err != 0) { rec.status = (uint32_t)err; rec.cv_n = 0; if (tid == 0) atomicMax(&A.cursors[CUR_STATUS], (uint32_t)err); }
         if (tid == 0)
         {
             if (!front_par) pairs[p] = rec;
@@ -829,7 +875,7 @@ __global__ __launch_bounds__(SURTR_LANES) __attribute__((amdgpu_waves_per_eu(SUR
                 uint32_t l2 = 0; while ((tot.x >> (l2 + 1u)) != 0u) ++l2;
                 uint32_t cls = 2u * l2 + (l2 ? ((tot.x >> (l2 - 1u)) & 1u) : 0u);
                 cls = cls > 4u ? cls - 4u : 0u; if (cls > 15u) cls = 15u;
-                porder[(size_t)cls * n_pairs + atomicAdd(&A.cursors[48u + cls], 1u)] = p;
+                porder[(size_t)cls * n_pairs + atomicAdd(&A.cursors[CUR_CLS_PREP + cls], 1u)] = p;
             }
         }
 #ifdef SURTR_STAMP_SMALL
@@ -880,8 +926,8 @@ __device__ __attribute__((always_inline)) static inline void prep_pairs_body(Sha
 {
     // order[c * n_pairs + i]: the pairs of cost class c (0 light .. 15 heavy); k_clip_pairs starts with the heavy
     // ones, so that a pair that takes milliseconds (one that outgrows the LDS topology) is not left for the end
-    auto enqueue = [&](uint32_t p, uint32_t cls) { order[(size_t)cls * n_pairs + atomicAdd(&A.cursors[16u + cls], 1u)] = p; };
-    auto enqueue_half = [&](uint32_t p, uint32_t cls) { horder[(size_t)cls * n_pairs + atomicAdd(&A.cursors[64u + cls], 1u)] = p; };
+    auto enqueue = [&](uint32_t p, uint32_t cls) { order[(size_t)cls * n_pairs + atomicAdd(&A.cursors[CUR_CLS_CLIP + cls], 1u)] = p; };
+    auto enqueue_half = [&](uint32_t p, uint32_t cls) { horder[(size_t)cls * n_pairs + atomicAdd(&A.cursors[CUR_CLS_HALF + cls], 1u)] = p; };
     const uint32_t tid = threadIdx.x;
     const bool front_par = (rec_on & 4u) != 0u;
     char* sp = pool.base + (size_t)blockIdx.x * pool.per_wg;
@@ -906,22 +952,15 @@ __device__ __attribute__((always_inline)) static inline void prep_pairs_body(Sha
         if (tid == 0)
         {
             // next ticket -> pair, expensive cost classes first (k_clip_convex filled porder with the pairs whose Convex survived)
-            uint32_t t = atomicAdd(&A.cursors[9], 1u), pp = 0xFFFFFFFFu;
-            if (front_par) { if (t < n_pairs) pp = t; }      // (no queue: k_clip_convex is still running, see launch_event)
-            else
-                for (int cls = 15; cls >= 0; --cls)
-                {
-                    const uint32_t cnt = A.cursors[48 + cls];
-                    if (t < cnt) { pp = porder[(size_t)cls * n_pairs + t]; break; }
-                    t -= cnt;
-                }
-            sh.misc[7] = pp;
+            uint32_t t = atomicAdd(&A.cursors[CUR_Q_PREP], 1u);
+            if (front_par) sh.misc[7] = t < n_pairs ? t : 0xFFFFFFFFu;      // (no queue: k_clip_convex is still running, see launch_event)
+            else sh.misc[7] = pair_of_ticket(A, porder, n_pairs, t, CUR_CLS_PREP, 15, 0);
         }
         __syncthreads();
         const uint32_t p = sh.misc[7];
         if (p >= n_pairs) break;
-        const uint32_t cell = pair_list ? pair_list[p].x : cell_begin + p / P.n;
-        const uint32_t piece = pair_list ? pair_list[p].y : p % P.n;
+        const PairAt at = pair_where(p, pair_list, cell_begin, P.n);
+        const uint32_t cell = at.cell, piece = at.piece;
         if (front_par)
         {
             // the Convex of this pair is being clipped beside this kernel: whether it is empty is not known yet.  The band of every pair
@@ -952,7 +991,7 @@ __device__ __attribute__((always_inline)) static inline void prep_pairs_body(Sha
         for (uint32_t k = tid; k < F; k += group_size()) sh.planes[k] = planes[f0 + k];
         __syncthreads();
         SolidIn min{P.mpos + 3 * (size_t)m0, P.mloff + m0, P.mllen + m0, P.mnbr, V, P.mtri + m0, P.mrad + m0,
-                    P.mperm + m0, P.mposr_s + m0, P.mbsph + P.mbo[piece]};
+                    P.mperm + m0, P.mposr_s + m0, P.mbsph + P.mbo[piece]};      // (mesh_solid_in, with the V read above)
         STAMP(70);
         const uint32_t nbV = (V + SURTR_LANES - 1u) >> SURTR_LSH;
         unsigned long long* bmask = nbV <= SURTR_PREP_NB ? lmask : gmask;
@@ -991,7 +1030,7 @@ __device__ __attribute__((always_inline)) static inline void prep_pairs_body(Sha
         {
             const RecLayout rl = rec_layout(F, n);
             const uint32_t need16 = rl.total / 16u;
-            if (tid == 0) sh.misc[0] = atomicAdd(&A.cursors[10], need16);
+            if (tid == 0) sh.misc[0] = atomicAdd(&A.cursors[CUR_IMG], need16);
             __syncthreads();
             off16 = sh.misc[0];
             __syncthreads();
@@ -1008,7 +1047,7 @@ __device__ __attribute__((always_inline)) static inline void prep_pairs_body(Sha
         if (fmt == IMG_NARROW && !rec_fmt)
         {
             const uint32_t need16 = lay.total / 16u;
-            if (tid == 0) sh.misc[0] = atomicAdd(&A.cursors[10], need16);
+            if (tid == 0) sh.misc[0] = atomicAdd(&A.cursors[CUR_IMG], need16);
             __syncthreads();
             off16 = sh.misc[0];
             __syncthreads();
@@ -1040,8 +1079,8 @@ __device__ __attribute__((always_inline)) static inline void prep_pairs_body(Sha
         if (tid == 0)
         {
             pairs[p].img_fmt = fmt; pairs[p].img_off = off16; pairs[p].img_n = n; pairs[p].img_h = hsum; pairs[p].img_pc = posCap;
-            if (fmt == IMG_REC) atomicAdd(&A.cursors[91], 1u);      // (diagnostic: surtr_queue_stats)
-            if (sorted_sel) atomicAdd(&A.cursors[92], 1u);
+            if (fmt == IMG_REC) atomicAdd(&A.cursors[CUR_REC_IMAGES], 1u);      // (diagnostic: surtr_queue_stats)
+            if (sorted_sel) atomicAdd(&A.cursors[CUR_SORTED_SEL], 1u);
             // classes 14 and 15 go to k_clip_pairs_big: bands that leave the regular LDS topology little room to grow
             // (the first plane alone may add a thousand vertices), and solids beyond any LDS topology
             // solids of at most half the half-size topology have their own table (k_clip_pairs_half)
@@ -1072,7 +1111,7 @@ __device__ __attribute__((always_inline)) static inline void prep_pairs_body(Sha
                 // after the loader and a plane or two) -- the whole-CU variant has the room
                 else if (cls < 12u && (fmt == IMG_NARROW || fmt == IMG_REC) && n > big_n && n < WC_MAXN) cls = 14u;
             }
-            else if (cls >= 14u && fmt != IMG_EMPTY && atomicAdd(&A.cursors[84], 1u) >= big_quota) cls = 13u;
+            else if (cls >= 14u && fmt != IMG_EMPTY && atomicAdd(&A.cursors[CUR_BIG_QUOTA], 1u) >= big_quota) cls = 13u;
             if (fmt == IMG_NARROW && to_half) enqueue_half(p, cls < 6u ? cls : 6u);      // (a record image is never to_half)
             else if (fmt != IMG_EMPTY) enqueue(p, cls);
         }
@@ -1143,9 +1182,7 @@ __device__ __attribute__((noinline)) static int pair_global(Pieces P, uint32_t p
     Shared& sh = *shp;
     Scratch S = carve(pool, wg);
     PairRec rec = pairs[p];
-    const uint32_t m0 = P.mvo[piece];
-    SolidIn min{P.mpos + 3 * (size_t)m0, P.mloff + m0, P.mllen + m0, P.mnbr, P.mvo[piece + 1] - m0, P.mtri + m0, P.mrad + m0,
-                P.mperm + m0, P.mposr_s + m0, P.mbsph + P.mbo[piece]};
+    SolidIn min = mesh_solid_in(P, piece);
     auto consume = [&](auto& T) -> int {
         if (T.nLive == 0) return 0;
         return park_mesh_islands(T, sh, A, rec);
@@ -1166,10 +1203,7 @@ __device__ __attribute__((noinline)) static int pair_global(Pieces P, uint32_t p
     }
     if (err == 0 && !gone) err = clip_global(min, F, S, sh, consume);
     __syncthreads();
-    if (err == 0 && rec.cv_bad != 0 && rec.ni != 0) err = SURTR_E_TOPOLOGY;
-    if (err != 0) { rec.status = (uint32_t)err; rec.ni = 0; if (threadIdx.x == 0) pair_failed(A, err); }
-    if (threadIdx.x == 0) pairs[p] = rec;
-    return err;
+    return finish_pair(A, pairs, p, rec, err);
 }
 
 // One pair through the general clipper: image (or pre-pass) -> plane loop -> islands -> arena, with the global-scratch and
@@ -1182,14 +1216,12 @@ __device__ __attribute__((always_inline)) static inline void clip_pair_general(S
                                        uint32_t* __restrict__ horder, const uint32_t p, PairRec rec)
 {
     const uint32_t tid = threadIdx.x;
-    const uint32_t cell = pair_list ? pair_list[p].x : cell_begin + p / P.n;
-    const uint32_t piece = pair_list ? pair_list[p].y : p % P.n;
+    const PairAt at = pair_where(p, pair_list, cell_begin, P.n);
+    const uint32_t cell = at.cell, piece = at.piece;
     const uint32_t f0 = plane_off[cell], F = plane_off[cell + 1] - f0;
     for (uint32_t k = tid; k < F; k += group_size()) sh.planes[k] = planes[f0 + k];
     __syncthreads();
-    const uint32_t m0 = P.mvo[piece];
-    SolidIn min{P.mpos + 3 * (size_t)m0, P.mloff + m0, P.mllen + m0, P.mnbr, P.mvo[piece + 1] - m0, P.mtri + m0, P.mrad + m0,
-                P.mperm + m0, P.mposr_s + m0, P.mbsph + P.mbo[piece]};
+    SolidIn min = mesh_solid_in(P, piece);
     auto consume = [&](auto& T) -> int {
         if (T.nLive == 0) return 0;
         return park_mesh_islands(T, sh, A, rec);
@@ -1199,7 +1231,7 @@ __device__ __attribute__((always_inline)) static inline void clip_pair_general(S
         // a sliver Mesh (a few vertices, a ring lists a neighbour twice): literal clipper from the start (see pair_global) --
         // on the regular kernel's scratch (the half-size kernel's has no room for it: its retry list).  A larger Mesh with
         // such a ring keeps the parallel clipper (one lane would take milliseconds for it) and falls back only on an error.
-        if (HALF) { if (tid == 0) horder[atomicAdd(&A.cursors[64], 1u)] = p; }
+        if (HALF) { if (tid == 0) horder[atomicAdd(&A.cursors[CUR_RETRY_N], 1u)] = p; }
         else pair_global(P, piece, F, pool, wg, A, &sh, pairs, p, 1u);
         return;
     }
@@ -1213,7 +1245,7 @@ __device__ __attribute__((always_inline)) static inline void clip_pair_general(S
         __syncthreads();
         if (err == SURTR_OVERFLOW)
         {
-            if (tid == 0) horder[atomicAdd(&A.cursors[64], 1u)] = p;
+            if (tid == 0) horder[atomicAdd(&A.cursors[CUR_RETRY_N], 1u)] = p;
             return;
         }
     }
@@ -1232,13 +1264,11 @@ __device__ __attribute__((always_inline)) static inline void clip_pair_general(S
     if (err == SURTR_E_TOPOLOGY && min.nv <= SURTR_LITERAL_MESH_V)
     {
         __syncthreads();
-        if (HALF) { if (tid == 0) horder[atomicAdd(&A.cursors[64], 1u)] = p; }       // (the regular kernel redoes the pair: see above)
+        if (HALF) { if (tid == 0) horder[atomicAdd(&A.cursors[CUR_RETRY_N], 1u)] = p; }       // (the regular kernel redoes the pair: see above)
         else pair_global(P, piece, F, pool, wg, A, &sh, pairs, p, 1u);
         return;
     }
-    if (err == 0 && rec.cv_bad != 0 && rec.ni != 0) err = SURTR_E_TOPOLOGY;       // a fragment with an invalid Convex
-    if (err != 0) { rec.status = (uint32_t)err; rec.ni = 0; if (tid == 0) pair_failed(A, err); }
-    if (tid == 0) pairs[p] = rec;
+    finish_pair(A, pairs, p, rec, err);
 }
 
 template <bool HALF = false, class LT>
@@ -1261,21 +1291,10 @@ __device__ __attribute__((always_inline)) static inline void clip_pairs_body(Sha
         if (tid == 0)
         {
             // next ticket -> pair (k_prep_pairs filled the tables), heavy classes first
+            // (the half table goes on with what the order table's classes left of the ticket)
             uint32_t t = atomicAdd(&A.cursors[qcur], 1u), p = 0xFFFFFFFFu;
-            if (!HALF)
-                for (int cls = cls_hi; cls >= cls_lo; --cls)
-                {
-                    const uint32_t cnt = A.cursors[16 + cls];
-                    if (t < cnt) { p = order[(size_t)cls * n_pairs + t]; break; }
-                    t -= cnt;
-                }
-            if (p == 0xFFFFFFFFu)
-                for (int cls = h_hi; cls >= h_lo; --cls)
-                {
-                    const uint32_t cnt = A.cursors[64 + cls];
-                    if (t < cnt) { p = horder[(size_t)cls * n_pairs + t]; break; }
-                    t -= cnt;
-                }
+            if (!HALF) p = pair_of_ticket(A, order, n_pairs, t, CUR_CLS_CLIP, cls_hi, cls_lo);
+            if (p == 0xFFFFFFFFu) p = pair_of_ticket(A, horder, n_pairs, t, CUR_CLS_HALF, h_hi, h_lo);
             sh.misc[7] = p;
         }
         __syncthreads();
@@ -1322,7 +1341,7 @@ __global__ __launch_bounds__(SURTR_WGS) __attribute__((amdgpu_waves_per_eu(2, 4)
 {
     __shared__ Shared sh;
     __shared__ LdsTopoHalf L;
-    clip_pairs_body<true>(sh, L, pool, blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, A, IA, pairs, pair_list, nullptr, horder, 6, 1, 12u);
+    clip_pairs_body<true>(sh, L, pool, blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, A, IA, pairs, pair_list, nullptr, horder, 6, 1, CUR_Q_HALF);
 }
 
 // The same with the double-size LDS topology (one workgroup per CU) for cost classes 14 and 15; runs beside
@@ -1336,7 +1355,7 @@ __global__ __launch_bounds__(SURTR_WG) void k_clip_pairs_big(Pieces P, const flo
 {
     __shared__ Shared sh;
     __shared__ LdsTopoBig L;
-    clip_pairs_body(sh, L, pool, wg_base + blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, A, IA, pairs, pair_list, order, nullptr, 15, 14, 11u);
+    clip_pairs_body(sh, L, pool, wg_base + blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, A, IA, pairs, pair_list, order, nullptr, 15, 14, CUR_Q_BIG);
 }
 
 // -------------------------------------------------------------- k_clip_pairs_wave
@@ -1350,7 +1369,7 @@ struct GenLds { Shared sh; LdsTopo L; };
 struct GenLdsBig { Shared sh; LdsTopoBig L; };
 // FALLBACK = false: k_clip_pairs_main -- no general clipper in the kernel (its LDS and registers are the record clipper's alone); a
 // pair it gives up on goes to the catcher beside it through the hand-over list `hlist`, which is then required.  cbase: where the
-// class counts of the table this kernel pulls from start in A.cursors (16: the table k_prep_pairs fills for the clip kernels).
+// class counts of the table this kernel pulls from start in A.cursors (CUR_CLS_CLIP: the table k_prep_pairs fills for the clip kernels).
 template <class WL, class GL, bool FALLBACK = true, bool OLD_IMAGES = FALLBACK>
 __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_body(unsigned char* lds_raw, uint32_t wg, const Pieces& P, const float4* __restrict__ planes,
                                                          const uint32_t* __restrict__ plane_off, uint32_t cell_begin,
@@ -1368,20 +1387,13 @@ __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_bod
     char* slot = pool.base + (size_t)wg * pool.per_wg;
     Scratch S{};
     if (FALLBACK) S = carve(pool, wg);
-    if (!FALLBACK && tid == 0) atomicAdd(&A.cursors[147], 1u);      // (the catcher beside this kernel: "it has started")
+    if (!FALLBACK && tid == 0) atomicAdd(&A.cursors[CUR_HO_STARTED], 1u);      // (the catcher beside this kernel: "it has started")
     while (true)
     {
         __syncthreads();
         if (tid == 0)
         {
-            uint32_t t = atomicAdd(&A.cursors[qcur], 1u), p = 0xFFFFFFFFu;
-            for (int cls = cls_hi; cls >= cls_lo; --cls)
-            {
-                const uint32_t cnt = A.cursors[cbase + cls];
-                if (t < cnt) { p = order[(size_t)cls * n_pairs + t]; break; }
-                t -= cnt;
-            }
-            W.misc[7] = p;
+            W.misc[7] = take_pair(A, order, n_pairs, qcur, cbase, cls_hi, cls_lo);
         }
         __syncthreads();
         const uint32_t p = W.misc[7];
@@ -1389,8 +1401,8 @@ __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_bod
         PairRec rec = pairs[p];
         if (rec.cv_n == 0 || rec.status != 0) continue;       // empty Convex: the Mesh is not clipped (:1467-1468)
         if (rec.img_fmt == IMG_EMPTY) continue;
-        const uint32_t cell = pair_list ? pair_list[p].x : cell_begin + p / P.n;
-        const uint32_t piece = pair_list ? pair_list[p].y : p % P.n;
+        const PairAt at = pair_where(p, pair_list, cell_begin, P.n);
+        const uint32_t cell = at.cell, piece = at.piece;
         const uint32_t f0 = plane_off[cell], F = plane_off[cell + 1] - f0;
         int err = WC_BAIL;
         if ((rec.img_fmt == IMG_NARROW || rec.img_fmt == IMG_REC) && P.mdup[piece] == 0 && F <= WC_MAXF)
@@ -1414,7 +1426,7 @@ __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_bod
                 const RecLayout rl = rec_layout(F, rec.img_n);
                 g.grec = (WcW4*)(img + rl.grec); g.gpos = (float4*)(img + rl.gpos); g.cpos = (float4*)slot;
                 fits = 16u * (size_t)(2u * WL::kNR) <= pool.per_wg;
-                if (fits) err = wc_attach(W, (const uint32_t*)(img + rl.hist), (const uint32_t*)(img + rl.zhist), (const uint32_t*)(img + rl.bst), F, rec.img_n, zmask, ctr, A.cursors + 96);
+                if (fits) err = wc_attach(W, (const uint32_t*)(img + rl.hist), (const uint32_t*)(img + rl.zhist), (const uint32_t*)(img + rl.bst), F, rec.img_n, zmask, ctr, A.cursors + CUR_WC_WHY);
             }
             else if constexpr (OLD_IMAGES)
             {
@@ -1423,10 +1435,10 @@ __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_bod
                                (const uint16_t*)(img + lay.ring), (const float*)(img + lay.pos), (const uint32_t*)(img + lay.hist),
                                (const uint32_t*)(img + lay.zhist), (const uint32_t*)(img + lay.nzero), rec.img_n, rec.img_h};
                 g = wc_glob(slot, pool.per_wg, rec.img_n, 2u * WL::kNR, fits);
-                if (fits) err = wc_load(W, im, F, g, zmask, ctr, A.cursors + 96);
+                if (fits) err = wc_load(W, im, F, g, zmask, ctr, A.cursors + CUR_WC_WHY);
             }
-            if (err == 0) err = wc_planes(W, F, rec.img_n, V - rec.img_n, zmask, g, 2u * WL::kNR, o, ctr, A.cursors + 96, walk0);
-            if (err == 0 && o.nLive != 0u) err = wc_park(W, F, rec.img_n, o, g, A, rec, ctr, A.cursors + 96);
+            if (err == 0) err = wc_planes(W, F, rec.img_n, V - rec.img_n, zmask, g, 2u * WL::kNR, o, ctr, A.cursors + CUR_WC_WHY, walk0);
+            if (err == 0 && o.nLive != 0u) err = wc_park(W, F, rec.img_n, o, g, A, rec, ctr, A.cursors + CUR_WC_WHY);
 #ifdef SURTR_STAMP
             __syncthreads();
             if (tid == 0)
@@ -1450,9 +1462,9 @@ __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_bod
 #endif
             // a record image the clipper gave up on has been patched by the planes it did (and the general clipper has no use for
             // records anyway): it starts from the piece (its own pre-pass), as for a pair that never had an image
-            if (err == WC_BAIL && rec.img_fmt == IMG_REC) { rec.img_fmt = IMG_NONE; if (tid == 0) atomicAdd(&A.cursors[93], 1u); }
+            if (err == WC_BAIL && rec.img_fmt == IMG_REC) { rec.img_fmt = IMG_NONE; if (tid == 0) atomicAdd(&A.cursors[CUR_REC_SPENT], 1u); }
         }
-        if (tid == 0) atomicAdd(&A.cursors[err == WC_BAIL ? 89 : 88], 1u);       // (diagnostic: pairs the record clipper took / handed on)
+        if (tid == 0) atomicAdd(&A.cursors[err == WC_BAIL ? CUR_REC_HANDED : CUR_REC_TOOK], 1u);       // (diagnostic: pairs the record clipper took / handed on)
         if (err == WC_BAIL)
         {
             if constexpr (FALLBACK)
@@ -1466,16 +1478,14 @@ __device__ __attribute__((always_inline)) static inline void clip_pairs_wave_bod
                 // to the catcher that runs beside this kernel (k_clip_pairs_catch): a slot of its list, filled with one atomic
                 // so that whoever polls the slot sees either nothing or the pair
                 __threadfence();
-                atomicExch(&hlist[atomicAdd(&A.cursors[146], 1u)], p);
+                atomicExch(&hlist[atomicAdd(&A.cursors[CUR_HO_PUSHED], 1u)], p);
             }
             continue;
         }
-        if (err == 0 && rec.cv_bad != 0 && rec.ni != 0) err = SURTR_E_TOPOLOGY;       // a fragment with an invalid Convex
-        if (err != 0) { rec.status = (uint32_t)err; rec.ni = 0; if (tid == 0) pair_failed(A, err); }
-        if (tid == 0) pairs[p] = rec;
+        finish_pair(A, pairs, p, rec, err);
     }
     // the catcher stops polling when every workgroup of this kernel has said so (after its last hand-over)
-    if (!FALLBACK && tid == 0) { __threadfence(); atomicAdd(&A.cursors[148], 1u); }
+    if (!FALLBACK && tid == 0) { __threadfence(); atomicAdd(&A.cursors[CUR_HO_SIGNED_OFF], 1u); }
 }
 
 __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(2, 4))) void k_clip_pairs_wave(Pieces P, const float4* __restrict__ planes,
@@ -1487,7 +1497,7 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(2, 4))
 {
     constexpr size_t kBytes = sizeof(WcLds) > sizeof(GenLds) ? sizeof(WcLds) : sizeof(GenLds);
     __shared__ alignas(16) unsigned char lds_raw[kBytes];
-    clip_pairs_wave_body<WcLds, GenLds>(lds_raw, blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, pairs, pair_list, order, horder, cls_hi, cls_lo, qcur, walk0, nullptr, 16u);
+    clip_pairs_wave_body<WcLds, GenLds>(lds_raw, blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, pairs, pair_list, order, horder, cls_hi, cls_lo, qcur, walk0, nullptr, CUR_CLS_CLIP);
 }
 
 // ---- The split arrangement (round 4): the regular pairs on a kernel that holds the record clipper ALONE, everything else beside it.
@@ -1519,7 +1529,7 @@ __global__ __launch_bounds__(SURTR_MAIN_THREADS) __attribute__((amdgpu_waves_per
                                                          uint32_t* __restrict__ hlist, uint32_t walk0)
 {
     __shared__ alignas(16) unsigned char lds_raw[sizeof(WcLdsMain)];
-    clip_pairs_wave_body<WcLdsMain, WcLdsMain, false, true>(lds_raw, blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, pairs, pair_list, order, nullptr, 11, 0, 4u, walk0, hlist, 16u);
+    clip_pairs_wave_body<WcLdsMain, WcLdsMain, false, true>(lds_raw, blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, pairs, pair_list, order, nullptr, 11, 0, CUR_Q_CLIP, walk0, hlist, CUR_CLS_CLIP);
 }
 
 // The catcher: see above.  n_main: workgroups of k_clip_pairs_main.  Its workgroups use the scratch slots from wg_base on.
@@ -1549,8 +1559,8 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(2, 4))
             if (sweep != 0u)
             {
                 // behind both kernels: the slots that were filled and never taken
-                const uint32_t pushed = A.cursors[146] < hcap ? A.cursors[146] : hcap;
-                for (uint32_t t = atomicAdd(&A.cursors[151], 1u); t < pushed; t = atomicAdd(&A.cursors[151], 1u))
+                const uint32_t pushed = A.cursors[CUR_HO_PUSHED] < hcap ? A.cursors[CUR_HO_PUSHED] : hcap;
+                for (uint32_t t = atomicAdd(&A.cursors[CUR_Q_SWEEP], 1u); t < pushed; t = atomicAdd(&A.cursors[CUR_Q_SWEEP], 1u))
                 {
                     const uint32_t v = atomicExch(&hlist[t], SURTR_H_TAKEN);
                     if (v < n_pairs) { p = v; break; }
@@ -1558,26 +1568,20 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(2, 4))
             }
             else if (own)
             {
-                uint32_t t = atomicAdd(&A.cursors[150], 1u);
-                for (int cls = 13; cls >= 12; --cls)
-                {
-                    const uint32_t cnt = A.cursors[16 + cls];
-                    if (t < cnt) { p = order[(size_t)cls * n_pairs + t]; break; }
-                    t -= cnt;
-                }
+                p = take_pair(A, order, n_pairs, CUR_Q_CATCH, CUR_CLS_CLIP, 13, 12);
             }
             if (sweep == 0u && p == 0xFFFFFFFFu && n_poll != 0u && (own ? blockIdx.x : 0u) < n_poll)
             {
                 // (only the first few workgroups stay for the hand-overs -- a handful per event; the others give their LDS back to the
                 //  main kernel as soon as the irregular pairs are done)
                 own = false;
-                const uint32_t t = atomicAdd(&A.cursors[149], 1u);          // this workgroup's slot of the hand-over list
+                const uint32_t t = atomicAdd(&A.cursors[CUR_HO_POLL_SLOT], 1u);          // this workgroup's slot of the hand-over list
                 for (uint32_t spin = 0; t < hcap; ++spin)
                 {
                     const uint32_t v = atomicAdd(&hlist[t], 0u);
                     if (v < n_pairs) { atomicExch(&hlist[t], SURTR_H_TAKEN); p = v; break; }
-                    if (atomicAdd(&A.cursors[148], 0u) >= n_main && atomicAdd(&A.cursors[146], 0u) <= t) break;      // nobody will fill it
-                    if (spin > (1u << 12) && atomicAdd(&A.cursors[147], 0u) == 0u) break;      // the main kernel is not running beside this one: the sweep's
+                    if (atomicAdd(&A.cursors[CUR_HO_SIGNED_OFF], 0u) >= n_main && atomicAdd(&A.cursors[CUR_HO_PUSHED], 0u) <= t) break;      // nobody will fill it
+                    if (spin > (1u << 12) && atomicAdd(&A.cursors[CUR_HO_STARTED], 0u) == 0u) break;      // the main kernel is not running beside this one: the sweep's
                     if (spin > (1u << 22)) break;                                              // ... or for very long: the sweep's as well
                     __builtin_amdgcn_s_sleep(32);
                 }
@@ -1593,7 +1597,7 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(2, 4))
         if (rec.cv_n == 0 || rec.status != 0) continue;
         if (rec.img_fmt == IMG_EMPTY) continue;
         if (rec.img_fmt == IMG_REC) rec.img_fmt = IMG_NONE;
-        if (tid == 0) atomicAdd(&A.cursors[94], 1u);      // (diagnostic, surtr_queue_stats: pairs the catcher clipped)
+        if (tid == 0) atomicAdd(&A.cursors[CUR_CATCH_CLIPPED], 1u);      // (diagnostic, surtr_queue_stats: pairs the catcher clipped)
         clip_pair_general(sh, L, S, pool, wg, P, planes, plane_off, cell_begin, A, IA, pairs, pair_list, (uint32_t*)nullptr, p, rec);
     }
 }
@@ -1610,7 +1614,7 @@ __global__ __launch_bounds__(SURTR_WG) void k_clip_pairs_wave_big(Pieces P, cons
 {
     constexpr size_t kBytes = sizeof(WcLdsBig) > sizeof(GenLdsBig) ? sizeof(WcLdsBig) : sizeof(GenLdsBig);
     __shared__ alignas(16) unsigned char lds_raw[kBytes];
-    clip_pairs_wave_body<WcLdsBig, GenLdsBig>(lds_raw, wg_base + blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, pairs, pair_list, order, nullptr, cls_hi, cls_lo, qcur, walk0, nullptr, 16u);
+    clip_pairs_wave_body<WcLdsBig, GenLdsBig>(lds_raw, wg_base + blockIdx.x, P, planes, plane_off, cell_begin, n_pairs, pool, A, IA, pairs, pair_list, order, nullptr, cls_hi, cls_lo, qcur, walk0, nullptr, CUR_CLS_CLIP);
 }
 
 // -------------------------------------------------------------- k_frag_table
@@ -1644,8 +1648,8 @@ __global__ __launch_bounds__(SURTR_WG_WIDE) void k_frag_table(const PairRec* __r
                 {
                     const uint2 is = A.isl[r.isl_off + t];
                     FragRec fr;
-                    fr.cell = (int32_t)(pair_list ? pair_list[p].x : cell_begin + p / n_pieces);
-                    fr.piece = (int32_t)(pair_list ? pair_list[p].y : p % n_pieces); fr.island = (int32_t)t;
+                    const PairAt at = pair_where(p, pair_list, cell_begin, n_pieces);
+                    fr.cell = (int32_t)at.cell; fr.piece = (int32_t)at.piece; fr.island = (int32_t)t;
                     fr.mv_off = vo; fr.mv_n = is.x; fr.mh_off = ho; fr.mh_n = is.y;
                     fr.cv_off = r.cv_off; fr.cv_n = r.cv_n; fr.ch_off = r.ch_off; fr.ch_n = r.ch_n;
                     fr.idx_off = 0; fr.idx_n = 0; fr.o_mv = fr.o_mh = fr.o_cv = fr.o_ch = fr.o_idx = 0;
@@ -1659,12 +1663,12 @@ __global__ __launch_bounds__(SURTR_WG_WIDE) void k_frag_table(const PairRec* __r
         }
     }
     __syncthreads();
-    for (uint32_t q = threadIdx.x; q < 16u; q += group_size()) A.cursors[32u + q] = sh.hist[q];
+    for (uint32_t q = threadIdx.x; q < 16u; q += group_size()) A.cursors[CUR_CLS_FRAG + q] = sh.hist[q];
     if (threadIdx.x == 0)
     {
         counts->n_frag = nf <= cap_frags ? nf : 0u;
         counts->n_pairs = n_pairs;
-        if (nf > cap_frags) atomicMax(&A.cursors[5], (uint32_t)SURTR_E_CAPACITY);
+        if (nf > cap_frags) atomicMax(&A.cursors[CUR_STATUS], (uint32_t)SURTR_E_CAPACITY);
     }
 }
 
@@ -1673,7 +1677,7 @@ __device__ static uint32_t frag_of_ticket(const Arena& A, const uint32_t* __rest
 {
     for (int cls = 15; cls >= 0; --cls)
     {
-        const uint32_t cnt = A.cursors[32 + cls];
+        const uint32_t cnt = A.cursors[CUR_CLS_FRAG + cls];
         if (t < cnt) return forder[(size_t)cls * cap_frags + t];
         t -= cnt;
     }
@@ -1874,7 +1878,7 @@ __device__ __forceinline__ void refit_fragments(const Hull hull, FragRec* __rest
     while (true)
     {
         __syncthreads();
-        if (tid == 0) sh.misc[7] = frag_of_ticket(A, forder, cap_frags, atomicAdd(&A.cursors[6], 1u));
+        if (tid == 0) sh.misc[7] = frag_of_ticket(A, forder, cap_frags, atomicAdd(&A.cursors[CUR_Q_REFIT], 1u));
         __syncthreads();
         const uint32_t f = sh.misc[7];
         if (f >= nf) break;
@@ -1947,7 +1951,7 @@ __device__ __forceinline__ void refit_fragments(const Hull hull, FragRec* __rest
             // takes the Convex whose planes either cut no vertex or cut with no vertex in the plane, and the general one resumes.
             float4* const keep = Hull::keep(H, S);
             const bool sliver = solid_is_sliver_inl(cin);
-            const ChainCaller who{82u, 79u, false, keep, keep};
+            const ChainCaller who{CUR_REFIT_TOOK, CUR_REFIT_RESUMED, false, keep, keep};
             o = convex_chain(cin, nP, sliver, who, [&] { return LiteralArg{cin, refit_ids_set(cin, fr, piece_cpos, piece_cvo)}; }, sh, U, S, pool, A, cst);
         }
         if (o.err == 0 && tid == 0)
@@ -1959,16 +1963,16 @@ __device__ __forceinline__ void refit_fragments(const Hull hull, FragRec* __rest
         {
             // An engine limit (refit_hull.h: a hull of more than 63 faces, a full table, a key out of range): the fragment keeps
             // its un-refitted Convex and is flagged SURTR_E_CAPACITY; counted apart (surtr_queue_stats out[95]).
-            if (tid == 0 && atomicExch(&frag_status[f], (uint32_t)SURTR_E_CAPACITY) == 0u) { atomicAdd(&A.cursors[14], 1u); atomicAdd(&A.cursors[95], 1u); }
+            if (tid == 0 && atomicExch(&frag_status[f], (uint32_t)SURTR_E_CAPACITY) == 0u) { atomicAdd(&A.cursors[CUR_FLAGGED_FRAGS], 1u); atomicAdd(&A.cursors[CUR_UNREFITTED], 1u); }
         }
         else if (o.err == SURTR_E_TOPOLOGY && frag_status != nullptr)
         {
             // Where the reference's own clip of this Convex by the slabs is no polyhedron any more (a link to a clipped vertex
             // that survives, renumbered through a stale ID), the fragment keeps the Convex it had -- a superset of the refitted
             // one -- and is flagged; the event and the other fragments stand (as for a fragment without triangles in k_faces).
-            if (tid == 0 && atomicExch(&frag_status[f], (uint32_t)SURTR_E_TOPOLOGY) == 0u) atomicAdd(&A.cursors[14], 1u);
+            if (tid == 0 && atomicExch(&frag_status[f], (uint32_t)SURTR_E_TOPOLOGY) == 0u) atomicAdd(&A.cursors[CUR_FLAGGED_FRAGS], 1u);
         }
-        else if (o.err != 0 && tid == 0) atomicMax(&A.cursors[5], (uint32_t)o.err);
+        else if (o.err != 0 && tid == 0) atomicMax(&A.cursors[CUR_STATUS], (uint32_t)o.err);
 #ifdef SURTR_STAMP
         if (tid == 0)
         {
@@ -2460,8 +2464,8 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
         __syncthreads();
         if (tid == 0)
         {
-            if (take_list == nullptr) sh.misc[7] = frag_of_ticket(A, forder, cap_frags, atomicAdd(&A.cursors[7], 1u));
-            else { const uint32_t t = atomicAdd(&A.cursors[86], 1u); sh.misc[7] = t < A.cursors[85] ? take_list[t] : 0xFFFFFFFFu; }      // second tier: the list of the first
+            if (take_list == nullptr) sh.misc[7] = frag_of_ticket(A, forder, cap_frags, atomicAdd(&A.cursors[CUR_Q_FACES], 1u));
+            else { const uint32_t t = atomicAdd(&A.cursors[CUR_Q_FACES2], 1u); sh.misc[7] = t < A.cursors[CUR_FACES2_N] ? take_list[t] : 0xFFFFFFFFu; }      // second tier: the list of the first
         }
         __syncthreads();
         const uint32_t f = sh.misc[7];
@@ -2477,8 +2481,8 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
         {
             if (tid == 0)
             {
-                if (push_list != nullptr) push_list[atomicAdd(&A.cursors[85], 1u)] = f;      // a fragment for the second tier's scratch
-                else atomicMax(&A.cursors[5], (uint32_t)SURTR_E_CAPACITY);
+                if (push_list != nullptr) push_list[atomicAdd(&A.cursors[CUR_FACES2_N], 1u)] = f;      // a fragment for the second tier's scratch
+                else atomicMax(&A.cursors[CUR_STATUS], (uint32_t)SURTR_E_CAPACITY);
             }
             continue;
         }
@@ -2845,7 +2849,7 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
             {
                 frags[f].idx_off = 0; frags[f].idx_n = 0;
                 // (k_refit, beside this kernel, may flag the same fragment: it is counted once)
-                if (frag_status == nullptr || atomicExch(&frag_status[f], (uint32_t)SURTR_E_TOPOLOGY) == 0u) atomicAdd(&A.cursors[14], 1u);
+                if (frag_status == nullptr || atomicExch(&frag_status[f], (uint32_t)SURTR_E_TOPOLOGY) == 0u) atomicAdd(&A.cursors[CUR_FLAGGED_FRAGS], 1u);
             }
             continue;
         }
@@ -2927,10 +2931,10 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
         auto cntfn = [&](uint32_t fi) -> uint2 { return make_uint2(fcnt[fi], 0u); };
         uint32_t nidx = 0, dum = 0;
         scan_blocks(nfaces, blk, sh, cntfn, nidx, dum);
-        if (tid == 0) sh.misc[0] = atomicAdd(&A.cursors[2], nidx);
+        if (tid == 0) sh.misc[0] = atomicAdd(&A.cursors[CUR_I], nidx);
         __syncthreads();
         const uint32_t ioff = sh.misc[0];
-        if ((uint64_t)ioff + nidx > A.capI) { if (tid == 0) atomicMax(&A.cursors[5], (uint32_t)SURTR_E_CAPACITY); continue; }
+        if ((uint64_t)ioff + nidx > A.capI) { if (tid == 0) atomicMax(&A.cursors[CUR_STATUS], (uint32_t)SURTR_E_CAPACITY); continue; }
         {
             const uint32_t nb = (nfaces + SURTR_LANES - 1u) >> SURTR_LSH;
             for (uint32_t b = wave_id(); b < nb; b += group_waves())
@@ -3012,7 +3016,7 @@ __global__ __launch_bounds__(SURTR_WG_WIDE) void k_out_scan(FragRec* __restrict_
     if (threadIdx.x == 0)
     {
         counts->mesh_verts = mv; counts->mesh_nbrs = mh; counts->conv_verts = cv; counts->conv_nbrs = chh;
-        counts->n_idx = t0; counts->status = A.cursors[5]; counts->n_failed = A.cursors[14] + A.cursors[15];
+        counts->n_idx = t0; counts->status = A.cursors[CUR_STATUS]; counts->n_failed = A.cursors[CUR_FLAGGED_FRAGS] + A.cursors[CUR_FLAGGED_PAIRS];
     }
 }
 
@@ -3061,7 +3065,7 @@ __global__ __launch_bounds__(SURTR_WG) void k_pack(const FragRec* __restrict__ f
         // that neither a stale nor a zero-filled blob is taken for a result
         if (blockIdx.x == 0 && threadIdx.x == 0)
         {
-            atomicMax(&A.cursors[5], (uint32_t)SURTR_E_CAPACITY);
+            atomicMax(&A.cursors[CUR_STATUS], (uint32_t)SURTR_E_CAPACITY);
             atomicMax(&counts->status, (uint32_t)SURTR_E_CAPACITY);
             if (capacity >= sizeof(surtr_counts))
             {
@@ -3205,7 +3209,7 @@ int surtr_create(int device, surtr_ctx** out)
         ctx->hw_wg = ctx->max_wg; ctx->hw_wg_faces = ctx->max_wg_faces; ctx->hw_wg_prep = ctx->max_wg_prep; ctx->hw_wg_big = ctx->n_wg_big;
     }
     // (surtr_destroy releases whatever was created so far: no leak on a failure half-way)
-    if (ctx->d_counts.grow(ctx, 1) != SURTR_OK || ctx->arena_buf.cursors.grow(ctx, 256) != SURTR_OK ||
+    if (ctx->d_counts.grow(ctx, 1) != SURTR_OK || ctx->arena_buf.cursors.grow(ctx, CUR_COUNT) != SURTR_OK ||
         hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_half, hipEventDisableTiming) != hipSuccess ||
@@ -3550,7 +3554,7 @@ __global__ void k_event_init(uint32_t* __restrict__ cursors, uint32_t* __restric
                              uint32_t n_status, uint32_t* __restrict__ hlist, uint32_t n_hlist)
 {
     const uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
-    for (uint32_t i = i0; i < 256u; i += step) cursors[i] = 0u;
+    for (uint32_t i = i0; i < CUR_COUNT; i += step) cursors[i] = 0u;
     for (uint32_t i = i0; i < n_counts; i += step) counts[i] = 0u;
     for (uint32_t i = i0; i < n_status; i += step) frag_status[i] = 0u;
     for (uint32_t i = i0; i < n_hlist; i += step) hlist[i] = 0xFFFFFFFFu;
@@ -3814,7 +3818,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     PROF_BEGIN_ON(8, pl.st_bigk);
     if (n_pairs && ctx->wave_big)
         hipLaunchKernelGGL(k_clip_pairs_wave_big, dim3(pl.n_wg_big), dim3(SURTR_WG), 0, pl.st_bigk, P, ctx->d_planes,
-                           ctx->d_plane_off, cell_begin, n_pairs, ctx->pool, max_wg, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, 15, 14, 11u, pl.walk0);
+                           ctx->d_plane_off, cell_begin, n_pairs, ctx->pool, max_wg, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, 15, 14, CUR_Q_BIG, pl.walk0);
     else if (n_pairs)
         hipLaunchKernelGGL(k_clip_pairs_big, dim3(pl.n_wg_big), dim3(SURTR_WG), 0, pl.st_bigk, P, ctx->d_planes,
                            ctx->d_plane_off, cell_begin, n_pairs, ctx->pool, max_wg, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order);
@@ -3828,7 +3832,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
                            ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, ctx->d_hlist, pl.walk0);
     else if (wave)
         hipLaunchKernelGGL(k_clip_pairs_wave, dim3(pl.n_wg), dim3(SURTR_WG), 0, pl.st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, horder, 13, 0, 4u, pl.walk0);
+                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, horder, 13, 0, CUR_Q_CLIP, pl.walk0);
     if (wave) PROF_HIST_END(11, pl.st_main);
     PROF_END_ON(11, pl.st_main);
     PROF_BEGIN_ON(0, pl.st_main);
@@ -3836,7 +3840,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     {
         PROF_HIST_BEGIN(0, pl.st_main);
         hipLaunchKernelGGL(k_clip_pairs, dim3(pl.n_wg), dim3(SURTR_WG), 0, pl.st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, horder, 13, 0, 4u);
+                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, horder, 13, 0, CUR_Q_CLIP);
         PROF_HIST_END(0, pl.st_main);
     }
     PROF_END_ON(0, pl.st_main);
@@ -3857,7 +3861,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     PROF_BEGIN_ON(10, pl.st_main);
     if (n_pairs && pl.use_half)
         hipLaunchKernelGGL(k_clip_pairs, dim3(pl.n_wg_retry), dim3(SURTR_WG), 0, pl.st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
-                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, horder, -1, 0, 13u);
+                           ctx->pool, ctx->arena, ctx->img, ctx->d_pairs, d_pair_list, order, horder, -1, 0, CUR_Q_RETRY);
     // ... and the sweep of the hand-over list (see k_clip_pairs_catch): normally nothing is left and its workgroups return at once
     if (split)
         hipLaunchKernelGGL(k_clip_pairs_catch, dim3(pl.n_wg_sweep), dim3(SURTR_WG), 0, pl.st_main, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
@@ -4003,8 +4007,7 @@ int surtr_event_refit(surtr_ctx* ctx)
     hipStream_t st = ctx->stream;
     const int rc = ensure_hull_ws(ctx);
     if (rc) return rc;
-    // k_refit pulls fragments from work queue 6
-    HIPCHK(hipMemsetAsync(ctx->arena.cursors + 6, 0, 4, st));
+    HIPCHK(hipMemsetAsync(ctx->arena.cursors + CUR_Q_REFIT, 0, 4, st));
     PROF_BEGIN(2);
     launch_refit(ctx, ctx->n_wg_small, st, ctx->frags_of_pieces);
     PROF_END(2);
@@ -4018,17 +4021,17 @@ int surtr_event_refit(surtr_ctx* ctx)
 static int launch_faces(surtr_ctx* ctx, uint32_t fan, uint32_t* d_face_n, uint32_t* d_face_off, int32_t* d_face_idx)
 {
     hipStream_t st = ctx->stream;
-    // queue 7 = fragments for k_faces, cursor 2 = index arena, 14 = flagged fragments (flagged pairs are counted in 15: they stay)
-    HIPCHK(hipMemsetAsync(ctx->arena.cursors + 7, 0, 4, st));
-    HIPCHK(hipMemsetAsync(ctx->arena.cursors + 2, 0, 4, st));
+    // (flagged pairs are counted in CUR_FLAGGED_PAIRS: they stay)
+    HIPCHK(hipMemsetAsync(ctx->arena.cursors + CUR_Q_FACES, 0, 4, st));
+    HIPCHK(hipMemsetAsync(ctx->arena.cursors + CUR_I, 0, 4, st));
     if (!(ctx->last_flags & SURTR_EVT_REFIT))      // (a refit of these fragments may have flagged some: those flags stay)
     {
-        HIPCHK(hipMemsetAsync(ctx->arena.cursors + 14, 0, 4, st));
+        HIPCHK(hipMemsetAsync(ctx->arena.cursors + CUR_FLAGGED_FRAGS, 0, 4, st));
         HIPCHK(hipMemsetAsync(ctx->d_frag_status, 0, (size_t)ctx->cap_frags * 4, st));
     }
     PROF_BEGIN(3);
     const bool tiers = ctx->n_wg_faces_big != 0;
-    if (tiers) HIPCHK(hipMemsetAsync(ctx->arena.cursors + 85, 0, 8, st));      // the second tier's list: fragments pushed (85), tickets taken (86)
+    if (tiers) HIPCHK(hipMemsetAsync(ctx->arena.cursors + CUR_FACES2_N, 0, 8, st));      // the second tier's list: + CUR_Q_FACES2 behind it
     hipLaunchKernelGGL(k_faces, dim3(std::max(1u, ctx->max_wg_faces)), dim3(SURTR_WG), 0, st, ctx->d_frags, ctx->d_counts, ctx->fs, ctx->d_blk,
                        ctx->blk_per_wg, ctx->arena, ctx->d_forder, ctx->cap_frags, fan, d_face_n, d_face_off, d_face_idx, ctx->d_frag_status,
                        (const uint32_t*)nullptr, tiers ? ctx->d_face_list : (uint32_t*)nullptr);
@@ -4092,7 +4095,7 @@ int surtr_load_fragments(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const 
     for (uint32_t v = 0; v < MV; ++v) { loff[v] = moff[v]; llen[v] = moff[v + 1] - moff[v]; }
     for (uint32_t v = 0; v < CV; ++v) { loff[MV + v] = MH + coff[v]; llen[MV + v] = coff[v + 1] - coff[v]; }
     std::vector<FragRec> fr(n);
-    std::vector<uint32_t> cursors(128, 0u), forder((size_t)16 * ctx->cap_frags, 0u);
+    std::vector<uint32_t> cursors(CUR_STATS_WORDS, 0u), forder((size_t)16 * ctx->cap_frags, 0u);
     for (uint32_t k = 0; k < n; ++k)
     {
         FragRec& r = fr[k];
@@ -4101,9 +4104,9 @@ int surtr_load_fragments(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const 
         r.mv_off = mvo[k]; r.mv_n = mvo[k + 1] - mvo[k]; r.mh_off = moff[mvo[k]]; r.mh_n = moff[mvo[k + 1]] - moff[mvo[k]];
         r.cv_off = MV + cvo[k]; r.cv_n = cvo[k + 1] - cvo[k]; r.ch_off = MH + coff[cvo[k]]; r.ch_n = coff[cvo[k + 1]] - coff[cvo[k]];
         uint32_t cls = 0; while ((r.mv_n >> (cls + 1u)) != 0u && cls < 15u) ++cls;      // size classes of k_frag_table
-        forder[(size_t)cls * ctx->cap_frags + cursors[32u + cls]++] = k;
+        forder[(size_t)cls * ctx->cap_frags + cursors[CUR_CLS_FRAG + cls]++] = k;
     }
-    cursors[0] = MV + CV; cursors[1] = MH + CH;
+    cursors[CUR_V] = MV + CV; cursors[CUR_H] = MH + CH;
     surtr_counts c; memset(&c, 0, sizeof(c)); c.n_frag = n; c.n_pairs = n;
     HIPCHK(hipMemcpyAsync(ctx->arena.pos, mpos, (size_t)MV * 12, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ctx->arena.pos + 3 * (size_t)MV, cpos, (size_t)CV * 12, hipMemcpyHostToDevice, st));
@@ -4113,7 +4116,7 @@ int surtr_load_fragments(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const 
     HIPCHK(hipMemcpyAsync(ctx->arena.nbr + MH, cnbr, (size_t)CH * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ctx->d_frags, fr.data(), (size_t)n * sizeof(FragRec), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ctx->d_forder, forder.data(), forder.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ctx->arena.cursors, cursors.data(), 512, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctx->arena.cursors, cursors.data(), CUR_STATS_WORDS * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ctx->d_counts, &c, sizeof(c), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(ctx->d_frag_status, 0, (size_t)ctx->cap_frags * 4, st));
     hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(SURTR_WG_WIDE), 0, st, ctx->d_frags, ctx->d_scanblk, ctx->d_counts, ctx->arena);
@@ -4438,7 +4441,7 @@ int surtr_queue_stats(surtr_ctx* ctx, uint32_t out[128])
     if (!ctx || !out) return SURTR_E_INVALID;
     (void)hipSetDevice(ctx->device);
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpy(out, ctx->arena.cursors, 512, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, ctx->arena.cursors, CUR_STATS_WORDS * 4, hipMemcpyDeviceToHost));
     return SURTR_OK;
 }
 

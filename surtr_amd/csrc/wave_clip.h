@@ -46,8 +46,11 @@
 #define WC_BAIL 102             // internal: not regular / does not fit -> the general clipper takes the pair
 #define WC_SENT 0xFFFEu         // ring entry: a vertex the band reduction dropped (InLds::SENT)
 #define WC_NONE 0xFFFFu
-// why[site]: pairs handed on per rule (Arena::cursors[96 + site], surtr_queue_stats); the single-lane CPU build of the tests
-// also says so on stderr
+// why[site]: pairs handed on per rule (Arena::cursors[CUR_WC_WHY + site], surtr_queue_stats); the single-lane CPU build of the
+// tests also says so on stderr.  Sites 1..17 are the rules; word 20 counts the pairs that ran out of LDS and 21..28 keep the fourth
+// such pair's numbers.
+#define WC_WHY_WORDS 29u
+static_assert(CUR_WC_WHY + WC_WHY_WORDS <= CUR_STATS_WORDS, "the why[] block ends inside what surtr_queue_stats copies out");
 #define WC_RET(site) do { if (threadIdx.x == 0u) atomicAdd(&why[site], 1u); SURTR_DBG("record clip: pair handed on at site %d\n", site); return WC_BAIL; } while (0)
 // Diagnostic build only (-DSURTR_STAMP): lane-0 cycles per phase
 #ifdef SURTR_STAMP
@@ -907,7 +910,7 @@ __device__ __attribute__((always_inline)) inline int wc_park(LT& W, const uint32
     auto rootfn = [&](uint32_t i) -> uint2 { return make_uint2(wc_ld16(B, lab + i) == i ? 1u : 0u, 0u); };
     const uint32_t ni = wc_scan(W, sc, nA, rootfn, rootfn, [&](uint32_t, uint32_t, uint32_t) {}).x;
     __syncthreads();
-    if (tid == 0u) { W.misc[0] = atomicAdd(&A.cursors[0], nA); W.misc[1] = atomicAdd(&A.cursors[1], H); W.misc[2] = atomicAdd(&A.cursors[3], ni); }
+    if (tid == 0u) { W.misc[0] = atomicAdd(&A.cursors[CUR_V], nA); W.misc[1] = atomicAdd(&A.cursors[CUR_H], H); W.misc[2] = atomicAdd(&A.cursors[CUR_ISL], ni); }
     __syncthreads();
     const uint32_t voff = W.misc[0], hoff = W.misc[1], ioff = W.misc[2];
     ctr.ac = ac; ctr.sc = sc;

@@ -218,6 +218,7 @@ class Engine:
         started, signed off, poll slots claimed, the catcher's own-class cursor, the sweep's cursor, clip workgroups, list capacity."""
         out = (ctypes.c_uint32 * 8)()
         self._ck(lib().surtr_handover_stats(self._h, out))
+        # (the first six in the order of the hand-over block CUR_HO_PUSHED .. CUR_Q_SWEEP of the slot enumeration in csrc/surtr_ctx.h)
         names = ("pushed", "main_started", "main_signed_off", "poll_claimed", "catch_own", "sweep_cursor", "max_wg", "hcap")
         return {n: int(out[i]) for i, n in enumerate(names)}
 
