@@ -535,6 +535,72 @@ int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* com
  * statistics. */
 int surtr_scene_commit_times(surtr_ctx* ctx, float* gather_ms, float* derive_ms);
 
+/* ---- per-body poses: pick, gate and break bodies that have moved (scene_dev.hip, query_dev.hip, mass_dev.hip) ---- */
+/* Every body of the reference is a rigid actor whose pose Update writes into m_structuredBufferData[i].WorldMatrix each frame
+ * (Src/Surtr.cpp:347-352); OnMouseDown queries the bodies where they are (:207-233) and ExecuteFractureRoutine bakes the pose into
+ * the pieces just before the event (:1846-1851).  Here: one pose per compound, kept on the host next to the compound table.  The
+ * resident pieces stay in the frame they were committed in (the body frame); a pose change rewrites no vertex.
+ *
+ * world: 16 floats per compound in the layout surtr_transform_pieces takes, x' = A x + b with A[c][k] = W[4c+k], b[c] = W[4c+3].
+ * A pose must be rigid -- evaluated in double from the floats: every entry finite, the last row exactly (0,0,0,1),
+ * max |A^T A - I| <= 1e-4, det A > 0.  Anything else, or an n_compounds that is not the scene's, is SURTR_E_INVALID and leaves the
+ * table as it was.  No call keeps a host pointer.  An empty table means every pose is the identity.
+ *   reset to the identity by: surtr_upload_pieces, surtr_pieces_from_event, surtr_scene_set_compounds;
+ *   left alone by:            surtr_transform_pieces, surtr_scene_transform_compound (explicit bakes);
+ *   surtr_scene_commit:       every surviving compound keeps its pose (those above the target move down by one with it), the
+ *                             compounds it makes get the identity -- the event ran on baked, world-space pieces, which is what
+ *                             InitCompound(compound, false) without a translate does (:1874-1875).  On any commit error the poses
+ *                             are unchanged, as the scene is.
+ * surtr_scene_get_poses: count-then-fill as surtr_scene_get_compounds (cap = the matrices world has room for).
+ * surtr_scene_apply_pose: a pose that is bit for bit the identity matrix does nothing and forgets nothing; any other is exactly
+ * surtr_scene_transform_compound(compound, n, that matrix n times) followed by pose := identity (the derived data is rebuilt, the
+ * last event is forgotten). */
+int surtr_scene_set_poses(surtr_ctx* ctx, uint32_t n_compounds, const float* world);
+int surtr_scene_get_poses(surtr_ctx* ctx, uint32_t cap, uint32_t* n_compounds, float* world);
+int surtr_scene_apply_pose(surtr_ctx* ctx, uint32_t compound);
+
+/* Ray cast and sphere overlap on the posed scene.  Definition: that of surtr_pieces_raycast / surtr_pieces_overlap, applied per
+ * piece in that piece's body frame.  For piece p of compound c with pose (A, b):
+ *   ray     o' = A^T (o - b), d' = A^T d, in double from the floats; the box test and Cyrus-Beck run on (o', d', max_dist) against the
+ *           piece as it is resident.  t is the same number in both frames: over all pieces the smallest t, the lowest piece on a tie.
+ *           pos = o + t d from the world ray; normal = A n' evaluated in double and rounded to float, not renormalised.  A ray that
+ *           starts inside gives t = 0, pos = o, normal = -d of the world ray and SURTR_RAY_STARTS_INSIDE.
+ *   sphere  c' = A^T (c - b), r unchanged, then the per-piece test.
+ * With every pose the identity each value equals the corresponding value of surtr_pieces_raycast / surtr_pieces_overlap (-0 against
+ * +0 in a normal apart).  Invalid rays and spheres, capacities, SURTR_E_STATE and surtr_pieces_query_status are as in those calls.
+ * The device copy of the poses (A^T and b as 12 doubles per compound, a compound number per piece) is brought up to date on the
+ * context's stream by the first query after a change. */
+typedef struct surtr_scene_ray_hit {
+    int32_t piece;         /* resident piece hit, -1: none */
+    uint32_t status;       /* SURTR_RAY_* bits */
+    float t;
+    float pos[3];          /* o + t * d, world */
+    float normal[3];       /* A n', world */
+    int32_t compound;      /* the body of that piece; -1 with piece == -1 */
+    uint32_t reserved[2];  /* zero; the record is 48 bytes */
+} surtr_scene_ray_hit;
+int surtr_scene_raycast_dev(surtr_ctx* ctx, uint32_t n_rays, const float* dev_rays, void* dev_hits, size_t capacity_bytes);
+int surtr_scene_raycast(surtr_ctx* ctx, uint32_t n_rays, const float* rays, surtr_scene_ray_hit* hits);
+/* dev_piece_mask (may be NULL; piece_cap >= n_spheres * n_pieces): [s * n_pieces + p] = 0 or 1, with no gate.
+ * dev_body_mask (body_cap >= n_spheres * n_compounds): [s * n_compounds + c] = 0 no piece of c is touched, 1 some piece is, 2 touched
+ * but body_mass[c].mass <= min_mass (Src/Surtr.cpp:228, on the actor as the reference does it); dev_body_mass_or_null: the
+ * n_compounds records surtr_scene_mass_dev wrote, NULL: no gate. */
+int surtr_scene_overlap_dev(surtr_ctx* ctx, uint32_t n_spheres, const float* dev_spheres, const void* dev_body_mass_or_null, float min_mass,
+                            uint8_t* dev_piece_mask_or_null, size_t piece_cap, uint8_t* dev_body_mask, size_t body_cap);
+/* From and to host arrays; synchronises.  body_mask == NULL returns the number of compounds in *n_compounds; with it, *n_compounds
+ * must hold the compounds a row has room for (SURTR_E_CAPACITY and the count when too small). */
+int surtr_scene_overlap(surtr_ctx* ctx, uint32_t n_spheres, const float* spheres, const surtr_mass* body_mass_or_null, float min_mass,
+                        uint32_t* n_compounds, uint8_t* body_mask);
+
+/* One surtr_mass record per compound of the scene, in the resident (body) frame: what setMass / setCMassLocalPose /
+ * setMassSpaceInertiaTensor take for a body whose pose the solver holds.  Each record is bit-identical to surtr_combine_mass applied
+ * to the surtr_pieces_mass records of that compound's pieces in resident order (the additions run in piece order; the by-volume rule
+ * and the status rule carry over).  The _dev form (capacity_bytes >= 96 * n_compounds) is enqueued on the context's stream with no
+ * host synchronisation and one temporary allocation for the per-piece records; the host form is count-then-fill as
+ * surtr_pieces_mass. */
+int surtr_scene_mass_dev(surtr_ctx* ctx, int set, float density, void* dev_out, size_t capacity_bytes);
+int surtr_scene_mass(surtr_ctx* ctx, int set, float density, uint32_t* n, surtr_mass* out);
+
 #ifdef __cplusplus
 }
 #endif

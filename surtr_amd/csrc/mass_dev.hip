@@ -14,6 +14,7 @@
 //   k_ms_long     one workgroup per solid with long faces: pointer jumping over that list (window MS_B * 2^r) until the
 //                 windows cover the loops -> every half-edge knows its loop's smallest vertex; its fan triangle
 //   k_ms_final    one lane per solid: the chunk partials in chunk order + the long-face partial -> the record
+//   k_ms_bodies   surtr_scene_mass: one wave per compound of the scene adds up its pieces' records as surtr_combine_mass does
 // Reductions are wave shuffles, then the waves in order, then chunks in order: no atomics on values, so two calls give the same
 // bits whatever the stream or the other work on the GPU.  The context keeps nothing: one temporary allocation per call, ordered
 // on the context's stream.
@@ -451,6 +452,67 @@ int ms_launch(surtr_ctx* ctx, const MsSrc& src, uint32_t nmax, uint64_t vmax, ui
     return SURTR_OK;
 }
 
+// The record of every compound of the scene from those of its pieces: surtr_combine_mass on the device, bit for bit.  The additions
+// are a chain in piece order, so one lane makes them; the wave's part is to bring the records in, MS_STAGE at a time through LDS with
+// coalesced loads (a record is twelve 8-byte words), once for the sums and once more for the inertia about the centre they give.
+#define MS_STAGE 64u
+__global__ __launch_bounds__(SURTR_LANES) void k_ms_bodies(SceneDev sc, const surtr_mass* __restrict__ rec, surtr_mass* __restrict__ out)
+{
+    __shared__ unsigned long long stage[MS_STAGE * 12u];
+    const uint32_t l = lane_id();
+    const unsigned long long* words = (const unsigned long long*)rec;
+    for (uint32_t c = blockIdx.x; c < sc.n_comp; c += gridDim.x)
+    {
+        const uint32_t p0 = sc.comp_off[c], p1 = sc.comp_off[c + 1];
+        bool heavy = false;
+        for (uint32_t p = p0 + l; p < p1; p += SURTR_LANES) heavy = heavy || rec[p].mass != 0.0;
+        const bool by_volume = __ballot(heavy) == 0ull;
+        surtr_mass r;
+        memset(&r, 0, sizeof(r));
+        double m = 0.0, w = 0.0, cx = 0.0, cy = 0.0, cz = 0.0;
+        for (int pass = 0; pass < 2; ++pass)
+        {
+            for (uint32_t k0 = p0; k0 < p1; k0 += MS_STAGE)
+            {
+                const uint32_t cnt = p1 - k0 < MS_STAGE ? p1 - k0 : MS_STAGE;
+                for (uint32_t i = l; i < 12u * cnt; i += SURTR_LANES) stage[i] = words[12 * (size_t)k0 + i];
+                __syncthreads();
+                if (l == 0u)
+                    for (uint32_t k = 0; k < cnt; ++k)
+                    {
+                        surtr_mass p;
+                        memcpy(&p, stage + 12u * k, sizeof(p));
+                        if (pass == 0)
+                        {
+                            r.volume += p.volume; m += p.mass; r.nv += p.nv;
+                            if (p.status > r.status) r.status = p.status;
+                            const double wp = by_volume ? p.volume : p.mass;
+                            w += wp; cx += wp * p.com[0]; cy += wp * p.com[1]; cz += wp * p.com[2];
+                        }
+                        else
+                        {
+                            const double dx = p.com[0] - r.com[0], dy = p.com[1] - r.com[1], dz = p.com[2] - r.com[2];
+                            r.inertia[0] += p.inertia[0] + p.mass * (dy * dy + dz * dz);
+                            r.inertia[1] += p.inertia[1] + p.mass * (dx * dx + dz * dz);
+                            r.inertia[2] += p.inertia[2] + p.mass * (dx * dx + dy * dy);
+                            r.inertia[3] += p.inertia[3] - p.mass * dx * dy;
+                            r.inertia[4] += p.inertia[4] - p.mass * dy * dz;
+                            r.inertia[5] += p.inertia[5] - p.mass * dz * dx;
+                        }
+                    }
+                __syncthreads();
+            }
+            if (pass == 0)
+            {
+                r.mass = m;
+                if (w != 0.0) { r.com[0] = cx / w; r.com[1] = cy / w; r.com[2] = cz / w; }
+            }
+        }
+        if (r.status == 0u && r.volume <= 0.0) r.status = 2u;
+        if (l == 0u) out[c] = r;
+    }
+}
+
 MsSrc ms_pieces_src(surtr_ctx* ctx, int set)
 {
     const PieceSet& P = set ? ctx->cset : ctx->mset;
@@ -492,6 +554,33 @@ extern "C" int surtr_pieces_mass_dev(surtr_ctx* ctx, int set, float density, voi
     if (ctx->n_pieces == 0) return SURTR_OK;
     (void)hipSetDevice(ctx->device);
     return ms_launch(ctx, ms_pieces_src(ctx, set), ctx->n_pieces, P.pos.cap / 3u, P.nbr.cap, density, dev_out, capacity_bytes);
+}
+
+// One record per compound of the scene, in the resident (body) frame: the pieces' records into one temporary allocation ordered on
+// the stream, then k_ms_bodies.  No host synchronisation.
+extern "C" int surtr_scene_mass_dev(surtr_ctx* ctx, int set, float density, void* dev_out, size_t capacity_bytes)
+{
+    if (!ctx || !dev_out || (set != 0 && set != 1)) return SURTR_E_INVALID;
+    const PieceSet& P = set ? ctx->cset : ctx->mset;
+    if (!P.pos || !P.vo || ctx->n_pieces == 0 || ctx->scene_off.size() < 2) return SURTR_E_STATE;
+    const uint32_t nc = (uint32_t)ctx->scene_off.size() - 1u, n = ctx->n_pieces;
+    if ((size_t)nc * sizeof(surtr_mass) > capacity_bytes) return SURTR_E_CAPACITY;
+    (void)hipSetDevice(ctx->device);
+    SceneDev sc;
+    int rc = scene_sync_device(ctx, &sc);
+    if (rc) return rc;
+    surtr_mass* rec = nullptr;
+    HIPCHK(ms_alloc((void**)&rec, (size_t)n * sizeof(surtr_mass), ctx->stream));
+    rc = ms_launch(ctx, ms_pieces_src(ctx, set), n, P.pos.cap / 3u, P.nbr.cap, density, rec, (size_t)n * sizeof(surtr_mass));
+    hipError_t e = hipSuccess;
+    if (rc == SURTR_OK)
+    {
+        hipLaunchKernelGGL(k_ms_bodies, dim3(std::min(nc, 65536u)), dim3(SURTR_LANES), 0, ctx->stream, sc, rec, (surtr_mass*)dev_out);
+        e = hipGetLastError();
+    }
+    ms_free(rec, ctx->stream);
+    if (e != hipSuccess) { ctx->err = std::string("scene mass: ") + hipGetErrorString(e); return SURTR_E_HIP; }
+    return rc;
 }
 
 namespace {
@@ -569,4 +658,15 @@ extern "C" int surtr_combine_mass(uint32_t n_compounds, const uint32_t* compound
         out[c] = r;
     }
     return SURTR_OK;
+}
+
+extern "C" int surtr_scene_mass(surtr_ctx* ctx, int set, float density, uint32_t* n, surtr_mass* out)
+{
+    if (!ctx || !n || (set != 0 && set != 1)) return SURTR_E_INVALID;
+    const PieceSet& P = set ? ctx->cset : ctx->mset;
+    if (!P.pos || !P.vo || ctx->n_pieces == 0 || ctx->scene_off.size() < 2) return SURTR_E_STATE;
+    const uint32_t nc = (uint32_t)ctx->scene_off.size() - 1u;
+    if (out && *n < nc) { *n = nc; return SURTR_E_CAPACITY; }
+    *n = nc;
+    return ms_host(ctx, nc, out, [&](void* d, size_t b) { return surtr_scene_mass_dev(ctx, set, density, d, b); });
 }

@@ -391,6 +391,7 @@ void set_piece_stats(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const uint
     ctx->have_event = false; ctx->frags_of_pieces = false;
     // the scene: one compound holding every piece, until surtr_scene_set_compounds / surtr_scene_commit say otherwise
     ctx->scene_off.assign({0u, n}); ctx->scene_event_compound = -1;
+    scene_reset_poses(ctx);      // (every pose the identity; surtr_scene_commit puts the survivors' back)
     ctx->h_vo[0].assign(mvo, mvo + n + 1); ctx->h_ho[0].assign(mho, mho + n + 1);
     ctx->h_vo[1].assign(cvo, cvo + n + 1); ctx->h_ho[1].assign(cho, cho + n + 1);
 }

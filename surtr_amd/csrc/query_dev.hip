@@ -35,7 +35,7 @@
 
 #include "surtr_ctx.h"
 
-static_assert(sizeof(surtr_ray_hit) == 48, "surtr_ray_hit is 48 bytes");
+static_assert(sizeof(surtr_ray_hit) == 48 && sizeof(surtr_scene_ray_hit) == 48, "the ray records are 48 bytes");
 
 #define QR_WG SURTR_WG          // threads per workgroup of the query kernels (256; one in the emulation)
 #define QR_B 256u               // longest face loop walked
@@ -46,7 +46,7 @@ namespace {
 struct QrSet { const float* pos; const uint32_t* loff; const int32_t* nbr; const uint32_t* vo; uint32_t n; };
 struct QrSolid { const float* pos; const uint32_t* loff; const int32_t* nbr; uint32_t nv; };
 struct QrPlane { double x, y, z, w; };
-struct QrPart { unsigned long long key; float n[3]; uint32_t flags; };
+struct QrPart { unsigned long long key; float n[3]; uint32_t flags; };      // (a QsPart of the posed ray cast is smaller)
 
 // Scratch of one call (one allocation, carved on the host) + the status the context keeps.
 struct QrWork
@@ -186,7 +186,8 @@ __device__ __forceinline__ bool qr_ray_ok(const float* q)
 }
 
 // The ray against one box: false when the slabs leave nothing of [0, max_dist].
-__device__ __forceinline__ bool qr_ray_box(const float* q, const float* box)
+template <class T>
+__device__ __forceinline__ bool qr_ray_box(const T* q, const float* box)
 {
     double t0 = 0.0, t1 = (double)q[6];
     for (int c = 0; c < 3; ++c)
@@ -201,7 +202,9 @@ __device__ __forceinline__ bool qr_ray_box(const float* q, const float* box)
 }
 
 // Cyrus-Beck of one ray against the planes of one piece (double: the same numbers as the definition evaluated in float64).
-__device__ __forceinline__ bool qr_ray_piece(const float* q, const QrPlane* pl, uint32_t np, float* t_out, float* nrm, uint32_t* flags)
+// The ray comes as float (world frame) or as double (taken into a body frame); *ent_out = the entering plane, -1 from inside.
+template <class T>
+__device__ __forceinline__ bool qr_ray_clip(const T* q, const QrPlane* pl, uint32_t np, float* t_out, int* ent_out, uint32_t* flags)
 {
     const double ox = q[0], oy = q[1], oz = q[2], dx = q[3], dy = q[4], dz = q[5];
     double t_in = 0.0, t_ex = (double)q[6];
@@ -219,9 +222,17 @@ __device__ __forceinline__ bool qr_ray_piece(const float* q, const QrPlane* pl, 
         else t_ex = fmin(t_ex, t);
     }
     if (np == 0u || !(t_in <= t_ex)) return false;
-    if (inside) { *t_out = 0.f; nrm[0] = -q[3]; nrm[1] = -q[4]; nrm[2] = -q[5]; *flags = SURTR_RAY_STARTS_INSIDE; return true; }
+    if (inside) { *t_out = 0.f; *ent_out = -1; *flags = SURTR_RAY_STARTS_INSIDE; return true; }
     if (ent < 0) return false;
-    *t_out = (float)t_in; nrm[0] = (float)pl[ent].x; nrm[1] = (float)pl[ent].y; nrm[2] = (float)pl[ent].z; *flags = 0u;
+    *t_out = (float)t_in; *ent_out = ent; *flags = 0u;
+    return true;
+}
+__device__ __forceinline__ bool qr_ray_piece(const float* q, const QrPlane* pl, uint32_t np, float* t_out, float* nrm, uint32_t* flags)
+{
+    int ent;
+    if (!qr_ray_clip(q, pl, np, t_out, &ent, flags)) return false;
+    if (ent < 0) { nrm[0] = -q[3]; nrm[1] = -q[4]; nrm[2] = -q[5]; }
+    else { nrm[0] = (float)pl[ent].x; nrm[1] = (float)pl[ent].y; nrm[2] = (float)pl[ent].z; }
     return true;
 }
 
@@ -292,7 +303,8 @@ __device__ __forceinline__ double qr_seg2(const double* c, const float* a, const
     return dx * dx + dy * dy + dz * dz;
 }
 
-__device__ bool qr_sphere_piece(const QrSolid& S, const float* sp, const QrPlane* pl, const uint2* edge, uint32_t np, const float* box)
+template <class T>
+__device__ bool qr_sphere_piece(const QrSolid& S, const T* sp, const QrPlane* pl, const uint2* edge, uint32_t np, const float* box)
 {
     const double c[3] = {sp[0], sp[1], sp[2]}, r2 = (double)sp[3] * (double)sp[3];
     double b2 = 0.0;      // the box first
@@ -358,6 +370,136 @@ __global__ __launch_bounds__(QR_WG) void k_qr_overlap(QrSet set, QrWork W, uint3
     }
 }
 
+// ---- the same queries on a scene whose bodies have poses (surtr_scene_set_poses): piece p of compound c with pose (A, b) is
+// asked in its body frame, o' = A^T (o - b), d' = A^T d, c' = A^T (c - b), in double from the floats; planes, boxes and solids stay as
+// they are resident, so a pose change costs an upload of 96 bytes per body and nothing else.  t is the same number in both frames.
+struct QsPart { unsigned long long key; uint32_t plane, flags; };      // plane: index of the entering plane in QrWork::plane
+static_assert(sizeof(QsPart) <= sizeof(QrPart), "the posed ray cast keeps its parts in the room QrWork::part has");
+
+// m = A^T row-major (9), b (3).  With the identity every product is x * 1 or x * 0: the body-frame numbers are the world's.
+__device__ __forceinline__ void qs_to_body(const double* m, const float* x, bool point, double* out)
+{
+    const double hx = point ? (double)x[0] - m[9] : (double)x[0], hy = point ? (double)x[1] - m[10] : (double)x[1],
+                 hz = point ? (double)x[2] - m[11] : (double)x[2];
+    for (int r = 0; r < 3; ++r) out[r] = m[3 * r] * hx + m[3 * r + 1] * hy + m[3 * r + 2] * hz;
+}
+
+// As k_qr_rays; a lane reads its piece's compound and that compound's 12 doubles.  The pieces of a compound are contiguous, so the
+// lanes of a wave mostly read the same 96 bytes: the loads stay per lane (lanes with one address share one request, and the table of
+// a few thousand bodies stays in L2), no wave-uniform special case.
+__global__ __launch_bounds__(QR_WG) void k_qs_rays(QrSet set, QrWork W, SceneDev sc, uint32_t n_rays, const float* __restrict__ rays, uint32_t nblk)
+{
+    __shared__ unsigned long long red[QR_WG / SURTR_LANES + 1];
+    const uint32_t total = n_rays * nblk;
+    QsPart* part = (QsPart*)W.part;
+    for (uint32_t item = blockIdx.x; item < total; item += gridDim.x)
+    {
+        const uint32_t ray = item / nblk, p = (item % nblk) * group_size() + threadIdx.x;
+        float q[7];
+        for (int c = 0; c < 7; ++c) q[c] = rays[7 * (size_t)ray + c];
+        unsigned long long key = QR_NONE;
+        float t = 0.f;
+        uint32_t flags = 0, plane = 0;
+        if (qr_ray_ok(q) && p < set.n && W.pcount[p] != 0u)
+        {
+            const double* m = sc.pose + 12 * (size_t)sc.piece_comp[p];
+            double b[7];
+            qs_to_body(m, q, true, b); qs_to_body(m, q + 3, false, b + 3); b[6] = (double)q[6];
+            int ent = -1;
+            const uint32_t base = qr_base(set, p);
+            if (qr_ray_box(b, W.box + 6 * (size_t)p) && qr_ray_clip(b, W.plane + base, W.pcount[p], &t, &ent, &flags))
+            {
+                key = ((unsigned long long)__float_as_uint(t) << 32) | p;
+                plane = ent < 0 ? 0u : base + (uint32_t)ent;
+            }
+        }
+        unsigned long long best = key;
+        for (uint32_t o = SURTR_LANES / 2u; o > 0u; o >>= 1) { const unsigned long long x = __shfl_down(best, o, SURTR_LANES); best = x < best ? x : best; }
+        if (lane_id() == 0u) red[wave_id()] = best;
+        __syncthreads();
+        best = red[0];
+        for (uint32_t w = 1; w < group_waves(); ++w) best = red[w] < best ? red[w] : best;
+        if (best == QR_NONE ? threadIdx.x == 0u : key == best)
+        {
+            QsPart r;
+            r.key = best; r.plane = plane; r.flags = flags;
+            part[item] = r;
+        }
+        __syncthreads();
+    }
+}
+
+// One lane per ray: the best key over the blocks; the normal goes back to the world, n = A n' in double, rounded, not renormalised.
+__global__ __launch_bounds__(QR_WG) void k_qs_ray_final(QrWork W, SceneDev sc, uint32_t n_rays, const float* __restrict__ rays, uint32_t nblk,
+                                                        surtr_scene_ray_hit* __restrict__ out)
+{
+    const QsPart* part = (const QsPart*)W.part;
+    for (uint32_t ray = blockIdx.x * blockDim.x + threadIdx.x; ray < n_rays; ray += gridDim.x * blockDim.x)
+    {
+        float q[7];
+        for (int c = 0; c < 7; ++c) q[c] = rays[7 * (size_t)ray + c];
+        surtr_scene_ray_hit h;
+        memset(&h, 0, sizeof(h));
+        h.piece = -1; h.compound = -1;
+        if (!qr_ray_ok(q)) { h.status = SURTR_RAY_INVALID; out[ray] = h; continue; }
+        uint32_t bb = 0;
+        unsigned long long best = QR_NONE;
+        for (uint32_t b = 0; b < nblk; ++b) { const unsigned long long k = part[(size_t)ray * nblk + b].key; if (k < best) { best = k; bb = b; } }
+        if (best != QR_NONE)
+        {
+            const QsPart r = part[(size_t)ray * nblk + bb];
+            h.piece = (int32_t)(uint32_t)best; h.t = __uint_as_float((uint32_t)(best >> 32)); h.status = r.flags;
+            h.compound = (int32_t)sc.piece_comp[(uint32_t)best];
+            for (int c = 0; c < 3; ++c) h.pos[c] = q[c] + q[3 + c] * h.t;
+            if (r.flags & SURTR_RAY_STARTS_INSIDE) { for (int c = 0; c < 3; ++c) h.normal[c] = -q[3 + c]; }
+            else
+            {
+                const double* m = sc.pose + 12 * (size_t)h.compound;      // A[c][k] = m[3 k + c]
+                const QrPlane P = W.plane[r.plane];
+                for (int c = 0; c < 3; ++c) h.normal[c] = (float)(m[c] * P.x + m[3 + c] * P.y + m[6 + c] * P.z);
+            }
+        }
+        out[ray] = h;
+    }
+}
+
+// One lane per (sphere, piece): the piece's byte, 0 or 1, with no gate.
+__global__ __launch_bounds__(QR_WG) void k_qs_overlap(QrSet set, QrWork W, SceneDev sc, uint32_t n_sph, const float* __restrict__ sph, uint8_t* __restrict__ mask)
+{
+    const size_t total = (size_t)n_sph * set.n;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+    {
+        const uint32_t s = (uint32_t)(i / set.n), p = (uint32_t)(i % set.n);
+        float sp[4];
+        for (int c = 0; c < 4; ++c) sp[c] = sph[4 * (size_t)s + c];
+        uint8_t m = 0;
+        const bool ok = qr_finite(sp[0]) && qr_finite(sp[1]) && qr_finite(sp[2]) && qr_finite(sp[3]) && sp[3] >= 0.f;
+        if (ok && W.pcount[p] != 0u)
+        {
+            double b[4];
+            qs_to_body(sc.pose + 12 * (size_t)sc.piece_comp[p], sp, true, b); b[3] = (double)sp[3];
+            if (qr_sphere_piece(qr_solid(set, p), b, W.plane + qr_base(set, p), W.edge + qr_base(set, p), W.pcount[p], W.box + 6 * (size_t)p)) m = 1;
+        }
+        mask[i] = m;
+    }
+}
+
+// One wave per (sphere, compound): the OR of its pieces' bytes by ballot, then the gate on the body's mass (Src/Surtr.cpp:228):
+// 0 untouched, 1 touched, 2 touched but mass <= min_mass.
+__global__ __launch_bounds__(QR_WG) void k_qs_bodies(SceneDev sc, uint32_t n_pieces, uint32_t n_sph, const uint8_t* __restrict__ mask,
+                                                     const surtr_mass* __restrict__ mass, double min_mass, uint8_t* __restrict__ body)
+{
+    const size_t total = (size_t)n_sph * sc.n_comp;
+    for (size_t item = (size_t)blockIdx.x * group_waves() + wave_id(); item < total; item += (size_t)gridDim.x * group_waves())
+    {
+        const uint32_t s = (uint32_t)(item / sc.n_comp), c = (uint32_t)(item % sc.n_comp);
+        bool any = false;
+        for (uint32_t p = sc.comp_off[c] + lane_id(); p < sc.comp_off[c + 1]; p += SURTR_LANES) any = any || mask[(size_t)s * n_pieces + p] != 0;
+        const bool touched = __ballot(any) != 0ull;
+        if (lane_id() == 0u) body[item] = !touched ? 0 : ((mass && mass[c].mass <= min_mass) ? 2 : 1);
+    }
+}
+
 hipError_t qr_alloc(void** p, size_t bytes, hipStream_t st)
 {
 #ifdef __HIP_PLATFORM_AMD__
@@ -378,8 +520,10 @@ void qr_free(void* p, hipStream_t st)
 }
 
 // Pass 1 + one of the two second passes.  rays != nullptr: ray cast into hits; else the spheres into mask.
-int qr_launch(surtr_ctx* ctx, uint32_t nq, const float* d_rays, surtr_ray_hit* d_hits, const float* d_sph, const surtr_mass* d_mass,
-              float min_mass, uint8_t* d_mask)
+// sc != nullptr: the posed forms -- hits are surtr_scene_ray_hit; d_mask (may be nullptr: scratch) takes the piece bytes, d_body the
+// bodies', gated by d_mass (one record per compound).
+int qr_launch(surtr_ctx* ctx, uint32_t nq, const float* d_rays, void* d_hits, const float* d_sph, const surtr_mass* d_mass,
+              float min_mass, uint8_t* d_mask, const SceneDev* sc = nullptr, uint8_t* d_body = nullptr)
 {
     const PieceSet& P = ctx->cset;
     const uint32_t n = ctx->n_pieces;
@@ -393,7 +537,8 @@ int qr_launch(surtr_ctx* ctx, uint32_t nq, const float* d_rays, surtr_ray_hit* d
     size_t bytes = 0;
     auto take = [&](size_t b) { const size_t at = bytes; bytes += (b + 15u) & ~(size_t)15u; return at; };
     const size_t o_plane = take(pcap * sizeof(QrPlane)), o_edge = take(pcap * sizeof(uint2)), o_cnt = take((size_t)n * 4),
-                 o_box = take((size_t)n * 24), o_part = take(d_rays ? (size_t)nq * nblk * sizeof(QrPart) : 0);
+                 o_box = take((size_t)n * 24), o_part = take(d_rays ? (size_t)nq * nblk * sizeof(QrPart) : 0),
+                 o_pmask = take(sc && !d_rays && !d_mask ? (size_t)nq * n : 0);
     char* base = nullptr;
     HIPCHK(qr_alloc((void**)&base, bytes, st));
     QrWork W;
@@ -401,10 +546,25 @@ int qr_launch(surtr_ctx* ctx, uint32_t nq, const float* d_rays, surtr_ray_hit* d
     W.box = (float*)(base + o_box); W.part = (QrPart*)(base + o_part); W.status = ctx->d_qstatus;
     QrSet S{P.pos, P.loff, P.nbr, P.vo, n};
     hipLaunchKernelGGL(k_qr_planes, dim3(std::min(n, 65536u)), dim3(SURTR_LANES), 0, st, S, W);
-    if (d_rays)
+    if (sc && d_rays)
+    {
+        hipLaunchKernelGGL(k_qs_rays, dim3(std::min(nq * nblk, 1u << 20)), dim3(QR_WG), 0, st, S, W, *sc, nq, d_rays, nblk);
+        hipLaunchKernelGGL(k_qs_ray_final, dim3(std::min((nq + QR_WG - 1u) / QR_WG, 4096u)), dim3(QR_WG), 0, st, W, *sc, nq, d_rays, nblk,
+                           (surtr_scene_ray_hit*)d_hits);
+    }
+    else if (sc)
+    {
+        const size_t total = (size_t)nq * n, waves = (size_t)nq * sc->n_comp, per = QR_WG / SURTR_LANES;
+        uint8_t* pm = d_mask ? d_mask : (uint8_t*)(base + o_pmask);
+        hipLaunchKernelGGL(k_qs_overlap, dim3((uint32_t)std::min<size_t>((total + QR_WG - 1u) / QR_WG, (size_t)1 << 20)), dim3(QR_WG), 0, st, S, W, *sc, nq,
+                           d_sph, pm);
+        hipLaunchKernelGGL(k_qs_bodies, dim3((uint32_t)std::min<size_t>((waves + per - 1u) / per, (size_t)1 << 20)), dim3(QR_WG), 0, st, *sc, n, nq, pm,
+                           d_mass, (double)min_mass, d_body);
+    }
+    else if (d_rays)
     {
         hipLaunchKernelGGL(k_qr_rays, dim3(std::min(nq * nblk, 1u << 20)), dim3(QR_WG), 0, st, S, W, nq, d_rays, nblk);
-        hipLaunchKernelGGL(k_qr_ray_final, dim3(std::min((nq + QR_WG - 1u) / QR_WG, 4096u)), dim3(QR_WG), 0, st, W, nq, d_rays, nblk, d_hits);
+        hipLaunchKernelGGL(k_qr_ray_final, dim3(std::min((nq + QR_WG - 1u) / QR_WG, 4096u)), dim3(QR_WG), 0, st, W, nq, d_rays, nblk, (surtr_ray_hit*)d_hits);
     }
     else
     {
@@ -503,4 +663,78 @@ extern "C" int surtr_pieces_query_status(surtr_ctx* ctx, uint32_t n, uint32_t* s
     HIPCHK(hipMemcpyAsync(status, ctx->d_qstatus.p, (size_t)ctx->qstatus_n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return SURTR_OK;
+}
+
+// ---- the posed forms (see include/surtr_hip.h)
+extern "C" int surtr_scene_raycast_dev(surtr_ctx* ctx, uint32_t n_rays, const float* dev_rays, void* dev_hits, size_t capacity_bytes)
+{
+    if (!ctx || !dev_rays || !dev_hits || n_rays == 0) return SURTR_E_INVALID;
+    if (qr_state(ctx)) return SURTR_E_STATE;
+    if ((size_t)n_rays * sizeof(surtr_scene_ray_hit) > capacity_bytes) return SURTR_E_CAPACITY;
+    (void)hipSetDevice(ctx->device);
+    SceneDev sc;
+    const int rc = scene_sync_device(ctx, &sc);
+    if (rc) return rc;
+    return qr_launch(ctx, n_rays, dev_rays, dev_hits, nullptr, nullptr, 0.f, nullptr, &sc, nullptr);
+}
+
+extern "C" int surtr_scene_overlap_dev(surtr_ctx* ctx, uint32_t n_spheres, const float* dev_spheres, const void* dev_body_mass_or_null, float min_mass,
+                                       uint8_t* dev_piece_mask_or_null, size_t piece_cap, uint8_t* dev_body_mask, size_t body_cap)
+{
+    if (!ctx || !dev_spheres || !dev_body_mask || n_spheres == 0) return SURTR_E_INVALID;
+    if (qr_state(ctx) || ctx->scene_off.size() < 2) return SURTR_E_STATE;
+    if ((dev_piece_mask_or_null && (size_t)n_spheres * ctx->n_pieces > piece_cap) || (size_t)n_spheres * (ctx->scene_off.size() - 1) > body_cap)
+        return SURTR_E_CAPACITY;
+    (void)hipSetDevice(ctx->device);
+    SceneDev sc;
+    const int rc = scene_sync_device(ctx, &sc);
+    if (rc) return rc;
+    return qr_launch(ctx, n_spheres, nullptr, nullptr, dev_spheres, (const surtr_mass*)dev_body_mass_or_null, min_mass, dev_piece_mask_or_null, &sc, dev_body_mask);
+}
+
+extern "C" int surtr_scene_raycast(surtr_ctx* ctx, uint32_t n_rays, const float* rays, surtr_scene_ray_hit* hits)
+{
+    if (!ctx || !rays || !hits || n_rays == 0) return SURTR_E_INVALID;
+    if (qr_state(ctx)) return SURTR_E_STATE;
+    for (uint32_t i = 0; i < n_rays; ++i)
+    {
+        const float* q = rays + 7 * (size_t)i;
+        for (int c = 0; c < 6; ++c) if (!qr_host_finite(q[c])) return SURTR_E_INVALID;
+        if ((q[3] == 0.f && q[4] == 0.f && q[5] == 0.f) || !(q[6] >= 0.f)) return SURTR_E_INVALID;
+    }
+    (void)hipSetDevice(ctx->device);
+    DevBuf<float> d_r; DevBuf<surtr_scene_ray_hit> d_h;
+    int rc = d_r.grow(ctx, 7 * (size_t)n_rays);
+    if (rc == SURTR_OK) rc = d_h.grow(ctx, n_rays);
+    if (rc == SURTR_OK && hipMemcpyAsync(d_r.p, rays, 28 * (size_t)n_rays, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = SURTR_E_HIP;
+    if (rc == SURTR_OK) rc = surtr_scene_raycast_dev(ctx, n_rays, d_r.p, d_h.p, (size_t)n_rays * sizeof(surtr_scene_ray_hit));
+    if (rc == SURTR_OK && hipMemcpyAsync(hits, d_h.p, (size_t)n_rays * sizeof(surtr_scene_ray_hit), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = SURTR_E_HIP;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == SURTR_OK) rc = SURTR_E_HIP;
+    return rc;
+}
+
+extern "C" int surtr_scene_overlap(surtr_ctx* ctx, uint32_t n_spheres, const float* spheres, const surtr_mass* body_mass_or_null, float min_mass,
+                                   uint32_t* n_compounds, uint8_t* body_mask)
+{
+    if (!ctx || !n_compounds) return SURTR_E_INVALID;
+    if (qr_state(ctx) || ctx->scene_off.size() < 2) return SURTR_E_STATE;
+    const uint32_t nc = (uint32_t)ctx->scene_off.size() - 1u;
+    if (!body_mask) { *n_compounds = nc; return SURTR_OK; }
+    if (!spheres || n_spheres == 0) return SURTR_E_INVALID;
+    if (*n_compounds < nc) { *n_compounds = nc; return SURTR_E_CAPACITY; }
+    *n_compounds = nc;
+    for (uint32_t i = 0; i < 4u * n_spheres; ++i) if (!qr_host_finite(spheres[i])) return SURTR_E_INVALID;
+    for (uint32_t i = 0; i < n_spheres; ++i) if (!(spheres[4 * (size_t)i + 3] >= 0.f)) return SURTR_E_INVALID;
+    (void)hipSetDevice(ctx->device);
+    const size_t total = (size_t)n_spheres * nc;
+    DevBuf<float> d_s; DevBuf<uint8_t> d_m; DevBuf<surtr_mass> d_w;
+    int rc = d_s.grow(ctx, 4 * (size_t)n_spheres);
+    if (rc == SURTR_OK) rc = d_m.grow(ctx, total);
+    if (rc == SURTR_OK && body_mass_or_null) rc = d_w.grow(ctx, nc);
+    if (rc == SURTR_OK && hipMemcpyAsync(d_s.p, spheres, 16 * (size_t)n_spheres, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = SURTR_E_HIP;
+    if (rc == SURTR_OK && body_mass_or_null && hipMemcpyAsync(d_w.p, body_mass_or_null, (size_t)nc * sizeof(surtr_mass), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = SURTR_E_HIP;
+    if (rc == SURTR_OK) rc = surtr_scene_overlap_dev(ctx, n_spheres, d_s.p, body_mass_or_null ? d_w.p : nullptr, min_mass, nullptr, 0, d_m.p, total);
+    if (rc == SURTR_OK && hipMemcpyAsync(body_mask, d_m.p, total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = SURTR_E_HIP;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == SURTR_OK) rc = SURTR_E_HIP;
+    return rc;
 }

@@ -3,11 +3,14 @@
 //
 //   surtr_scene_set_compounds / _get_compounds   compound c = resident pieces [compound_off[c], compound_off[c + 1])
 //   surtr_scene_transform_compound                Poly::Transform of one compound's pieces (:1846-1851)
+//   surtr_scene_set_poses / _get_poses / _apply_pose   a rigid pose per compound (WorldMatrix, :347-352), kept on the host next to the
+//                                                 table; the posed queries (query_dev.hip) read it, apply_pose bakes it in
 //   surtr_scene_fracture_event(_async)            the event over the pieces of one compound
 //   surtr_scene_commit                            erase the compound, push back what it broke into (:1856-1875): one gather
 //                                                 kernel from the old pieces and the event arena into spare buffers, then a swap
 // The layout of the new pieces is laid out on the host from the small tables (piece offsets, fragment records), as
 // surtr_pieces_from_event does; no solid leaves HBM.
+#include <cmath>
 #include <cstring>
 #include <utility>
 
@@ -48,9 +51,69 @@ bool valid_table(uint32_t n_compounds, const uint32_t* off, uint32_t n_pieces)
     return true;
 }
 
+const float IDENTITY[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+
+// Rigid: finite, last row exactly (0, 0, 0, 1), max |A^T A - I| <= 1e-4, det A > 0; in double from the floats.
+bool rigid_pose(const float* W)
+{
+    for (int i = 0; i < 16; ++i) if (!(std::fabs(W[i]) <= 3.4028235e38f)) return false;
+    if (W[12] != 0.f || W[13] != 0.f || W[14] != 0.f || W[15] != 1.f) return false;
+    double A[3][3];
+    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) A[r][k] = (double)W[4 * r + k];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+        {
+            const double g = A[0][i] * A[0][j] + A[1][i] * A[1][j] + A[2][i] * A[2][j] - (i == j ? 1.0 : 0.0);
+            if (!(std::fabs(g) <= 1e-4)) return false;
+        }
+    const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+                       A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+    return det > 0.0;
+}
+
 } // namespace
 
 extern "C" {
+
+int surtr_scene_set_poses(surtr_ctx* ctx, uint32_t n_compounds, const float* world)
+{
+    if (!ctx || !world) return SURTR_E_INVALID;
+    if (!ctx->n_pieces) return SURTR_E_STATE;
+    if ((size_t)n_compounds + 1 != ctx->scene_off.size()) return SURTR_E_INVALID;
+    for (uint32_t c = 0; c < n_compounds; ++c) if (!rigid_pose(world + 16 * (size_t)c)) return SURTR_E_INVALID;
+    ctx->scene_pose.assign(world, world + 16 * (size_t)n_compounds);
+    ctx->scene_dev_stale = true;
+    return SURTR_OK;
+}
+
+int surtr_scene_get_poses(surtr_ctx* ctx, uint32_t cap, uint32_t* n_compounds, float* world)
+{
+    if (!ctx || !n_compounds) return SURTR_E_INVALID;
+    if (!ctx->n_pieces) return SURTR_E_STATE;
+    const uint32_t nc = (uint32_t)ctx->scene_off.size() - 1u;
+    *n_compounds = nc;
+    if (!world) return SURTR_OK;
+    if (cap < nc) return SURTR_E_CAPACITY;
+    if (ctx->scene_pose.empty()) for (uint32_t c = 0; c < nc; ++c) memcpy(world + 16 * (size_t)c, IDENTITY, 64);
+    else memcpy(world, ctx->scene_pose.data(), (size_t)64 * nc);
+    return SURTR_OK;
+}
+
+int surtr_scene_apply_pose(surtr_ctx* ctx, uint32_t compound)
+{
+    if (!ctx) return SURTR_E_INVALID;
+    if (!ctx->n_pieces) return SURTR_E_STATE;
+    if (compound + 1u >= ctx->scene_off.size()) return SURTR_E_INVALID;
+    if (ctx->scene_pose.empty() || memcmp(ctx->scene_pose.data() + 16 * (size_t)compound, IDENTITY, 64) == 0) return SURTR_OK;
+    const uint32_t n = ctx->scene_off[compound + 1] - ctx->scene_off[compound];
+    std::vector<float> w((size_t)16 * n);
+    for (uint32_t k = 0; k < n; ++k) memcpy(w.data() + 16 * (size_t)k, ctx->scene_pose.data() + 16 * (size_t)compound, 64);
+    const int rc = transform_range(ctx, ctx->scene_off[compound], n, w.data());
+    if (rc) return rc;
+    memcpy(ctx->scene_pose.data() + 16 * (size_t)compound, IDENTITY, 64);
+    ctx->scene_dev_stale = true;
+    return SURTR_OK;
+}
 
 int surtr_scene_set_compounds(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* compound_off)
 {
@@ -59,6 +122,7 @@ int surtr_scene_set_compounds(surtr_ctx* ctx, uint32_t n_compounds, const uint32
     if (!valid_table(n_compounds, compound_off, ctx->n_pieces)) return SURTR_E_INVALID;
     ctx->scene_off.assign(compound_off, compound_off + n_compounds + 1);
     ctx->scene_event_compound = -1;      // (an event's compound number belongs to the table it was given in)
+    scene_reset_poses(ctx);              // (and so does a pose)
     return SURTR_OK;
 }
 
@@ -232,8 +296,16 @@ int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* com
         rc = derive_set(ctx, S, n, dv[s][n], bo[s], false);
         if (rc) return rc;
     }
+    // the poses of the surviving compounds move down with them; what the event made is in world space already (InitCompound(compound, false))
+    std::vector<float> pose = std::move(ctx->scene_pose);
+    if (!pose.empty())
+    {
+        pose.erase(pose.begin() + 16 * (size_t)target, pose.begin() + 16 * (size_t)(target + 1u));
+        for (size_t k = first_new; k + 1 < table.size(); ++k) pose.insert(pose.end(), IDENTITY, IDENTITY + 16);
+    }
     set_piece_stats(ctx, n, dv[0].data(), dh[0].data(), dv[1].data(), dh[1].data());
     ctx->scene_off = table;
+    ctx->scene_pose = std::move(pose); ctx->scene_dev_stale = true;
     ctx->have_event = true;       // the event's fragments are still in the arena, as after surtr_pieces_from_event
     ctx->frags_of_pieces = false; // (but the pieces they came from have moved)
     if (n_pieces_out) *n_pieces_out = n;

@@ -319,6 +319,13 @@ struct surtr_ctx
     std::vector<uint32_t> scene_off;
     std::vector<uint32_t> h_vo[2], h_ho[2];              // vertex / ring-entry offsets of the resident pieces (0 = Mesh, 1 = Convex), host copies
     int scene_event_compound = -1;                       // compound the last event ran over (surtr_scene_fracture_event); -1: none, or committed
+    // per-body poses (surtr_scene_set_poses): 16 floats per compound, x' = A x + b as surtr_transform_pieces takes them; empty: every
+    // pose is the identity.  The device copy (scene_sync_device below) is made by the first query after the poses or the table change.
+    std::vector<float> scene_pose;
+    bool scene_dev_stale = true;
+    std::vector<double> h_pose_stage; std::vector<uint32_t> h_comp_stage;      // what the last upload was made from
+    DevBuf<double> d_pose;               // per compound: A^T row-major (9), b (3)
+    DevBuf<uint32_t> d_piece_comp;       // per resident piece: its compound; then the compound table (n_compounds + 1 offsets)
     struct { DevBuf<float> pos; DevBuf<uint32_t> loff; DevBuf<int32_t> nbr; DevBuf<uint32_t> vo; } spare[2];   // surtr_scene_commit gathers into these, then swaps
     DevBuf<int32_t> d_commit_src; DevBuf<uint32_t> d_commit_tab;      // its gather tables
     float commit_ms[2] = {0.f, 0.f};                     // host time of the last commit up to the end of the gather / from there to its end (surtr_scene_commit_times)
@@ -427,6 +434,43 @@ int finish_upload(surtr_ctx* ctx, uint32_t n, bool check);
 // Poly::Transform of resident pieces [p0, p0 + n) by world[16 * (p - p0) ..], the derived data again; the other pieces keep their bits
 int transform_range(surtr_ctx* ctx, uint32_t p0, uint32_t n, const float* world);
 }
+// The scene's tables as the posed queries (query_dev.hip) and surtr_scene_mass (mass_dev.hip) read them on the device.  Fields only:
+// every translation unit that needs them brings them up to date itself, on the context's stream, when the host's have changed.
+struct SceneDev { const double* pose; const uint32_t* piece_comp; const uint32_t* comp_off; uint32_t n_comp; };
+static inline void scene_reset_poses(surtr_ctx* ctx) { ctx->scene_pose.clear(); ctx->scene_dev_stale = true; }
+static inline int scene_sync_device(surtr_ctx* ctx, SceneDev* out)
+{
+    if (ctx->scene_off.size() < 2 || ctx->scene_off.back() != ctx->n_pieces) return SURTR_E_STATE;
+    const uint32_t nc = (uint32_t)ctx->scene_off.size() - 1u, np = ctx->n_pieces;
+    if (ctx->scene_dev_stale || !ctx->d_pose || !ctx->d_piece_comp)
+    {
+        // (refilling the staging vectors is safe although the copies below are "async": they are pageable memory, and a pageable
+        //  host-to-device copy has left its source before hipMemcpyAsync returns, as for the tables of surtr_scene_commit)
+        std::vector<double>& P = ctx->h_pose_stage; std::vector<uint32_t>& C = ctx->h_comp_stage;
+        P.assign((size_t)12 * nc, 0.0); C.resize((size_t)np + nc + 1u);
+        for (uint32_t c = 0; c < nc; ++c)
+        {
+            double* m = P.data() + (size_t)12 * c;
+            if (ctx->scene_pose.empty()) { m[0] = m[4] = m[8] = 1.0; }
+            else
+            {
+                const float* W = ctx->scene_pose.data() + (size_t)16 * c;
+                for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) m[3 * r + k] = (double)W[4 * k + r]; m[9 + r] = (double)W[4 * r + 3]; }
+            }
+            for (uint32_t p = ctx->scene_off[c]; p < ctx->scene_off[c + 1]; ++p) C[p] = c;
+        }
+        for (uint32_t c = 0; c <= nc; ++c) C[(size_t)np + c] = ctx->scene_off[c];
+        int rc = ctx->d_pose.grow(ctx, P.size(), P.size() + P.size() / 4);
+        if (rc == SURTR_OK) rc = ctx->d_piece_comp.grow(ctx, C.size(), C.size() + C.size() / 4);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(ctx->d_pose.p, P.data(), P.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->d_piece_comp.p, C.data(), C.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        ctx->scene_dev_stale = false;
+    }
+    *out = SceneDev{ctx->d_pose.p, ctx->d_piece_comp.p, ctx->d_piece_comp.p + np, nc};
+    return SURTR_OK;
+}
+
 // an event over an explicit pair list with an `outside` mask over all resident pieces (surtr_hip.hip); NULL: no mask
 int surtr_event_pairs_masked(surtr_ctx* ctx, uint32_t n_pairs, const uint32_t* pair_cell, const uint32_t* pair_piece, const uint8_t* outside, uint32_t flags);
 // surtr_event_regroup given the resident pieces the event skipped, ascending (regroup_dev.hip)

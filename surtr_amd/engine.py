@@ -43,6 +43,10 @@ assert MASS_DTYPE.itemsize == ctypes.sizeof(Mass) == 96
 RAY_HIT_DTYPE = np.dtype([("piece", "<i4"), ("status", "<u4"), ("t", "<f4"), ("pos", "<f4", (3,)), ("normal", "<f4", (3,)),
                           ("reserved", "<u4", (3,))])
 assert RAY_HIT_DTYPE.itemsize == 48
+# surtr_scene_ray_hit: the same record with the body of the piece hit
+SCENE_RAY_HIT_DTYPE = np.dtype([("piece", "<i4"), ("status", "<u4"), ("t", "<f4"), ("pos", "<f4", (3,)), ("normal", "<f4", (3,)),
+                                ("compound", "<i4"), ("reserved", "<u4", (2,))])
+assert SCENE_RAY_HIT_DTYPE.itemsize == 48
 RAY_STARTS_INSIDE, RAY_INVALID = 1, 2
 QUERY_FEW, QUERY_OPEN, QUERY_FLAT, QUERY_LONG = 1, 2, 4, 8
 
@@ -557,6 +561,64 @@ class Engine:
         a, b = ctypes.c_float(), ctypes.c_float()
         self._ck(lib().surtr_scene_commit_times(self._h, ctypes.byref(a), ctypes.byref(b)))
         return float(a.value), float(b.value)
+
+    # ---- per-body poses: the scene's bodies where a solver has moved them
+    def scene_set_poses(self, world):
+        """surtr_scene_set_poses: one rigid pose per compound, f32[n_compounds, 4, 4] in transform_pieces' layout (x' = A x + b, the
+        translation in the last column)."""
+        w = np.ascontiguousarray(world, np.float32).reshape(-1, 16)
+        self._ck(lib().surtr_scene_set_poses(self._h, ctypes.c_uint32(w.shape[0]), _p(w)))
+
+    def scene_poses(self):
+        """surtr_scene_get_poses: f32[n_compounds, 4, 4]."""
+        n = ctypes.c_uint32()
+        self._ck(lib().surtr_scene_get_poses(self._h, ctypes.c_uint32(0), ctypes.byref(n), None))
+        w = np.zeros((n.value, 4, 4), np.float32)
+        self._ck(lib().surtr_scene_get_poses(self._h, ctypes.c_uint32(n.value), ctypes.byref(n), _p(w)))
+        return w
+
+    def scene_apply_pose(self, compound):
+        """surtr_scene_apply_pose: bakes the compound's pose into its pieces (nothing at all for the identity)."""
+        self._ck(lib().surtr_scene_apply_pose(self._h, ctypes.c_uint32(int(compound))))
+
+    def scene_raycast(self, rays):
+        """surtr_scene_raycast: rays f32[n, 7] against the bodies where their poses put them -> SCENE_RAY_HIT_DTYPE[n]."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 7)
+        out = np.zeros(r.shape[0], SCENE_RAY_HIT_DTYPE)
+        self._ck(lib().surtr_scene_raycast(self._h, ctypes.c_uint32(r.shape[0]), _p(r), _p(out)))
+        return out
+
+    def scene_raycast_dev(self, n_rays, dev_rays, dev_hits, capacity):
+        self._ck(lib().surtr_scene_raycast_dev(self._h, ctypes.c_uint32(int(n_rays)), ctypes.c_void_p(dev_rays), ctypes.c_void_p(dev_hits),
+                                               ctypes.c_size_t(capacity)))
+
+    def scene_overlap(self, spheres, body_mass=None, min_mass=1e-4):
+        """surtr_scene_overlap: spheres f32[n, 4] -> uint8[n, n_compounds]: 0 no piece of the body is touched, 1 touched, 2 touched
+        but the body's mass <= min_mass (body_mass: the records of scene_mass; None: no gate)."""
+        sp = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+        m = None if body_mass is None else np.ascontiguousarray(body_mass, MASS_DTYPE)
+        n = ctypes.c_uint32()
+        args = [self._h, ctypes.c_uint32(sp.shape[0]), _p(sp), _p(m), ctypes.c_float(min_mass)]
+        self._ck(lib().surtr_scene_overlap(*args, ctypes.byref(n), None))
+        if m is not None and m.shape[0] != n.value:
+            raise SurtrError(E_INVALID, "body_mass holds %d records for %d compounds" % (m.shape[0], n.value))
+        out = np.zeros((sp.shape[0], n.value), np.uint8)
+        self._ck(lib().surtr_scene_overlap(*args, ctypes.byref(n), _p(out)))
+        return out
+
+    def scene_overlap_dev(self, n_spheres, dev_spheres, dev_body_mask, body_capacity, dev_piece_mask=None, piece_capacity=0, dev_body_mass=None,
+                          min_mass=1e-4):
+        self._ck(lib().surtr_scene_overlap_dev(self._h, ctypes.c_uint32(int(n_spheres)), ctypes.c_void_p(dev_spheres), ctypes.c_void_p(dev_body_mass),
+                                               ctypes.c_float(min_mass), ctypes.c_void_p(dev_piece_mask), ctypes.c_size_t(piece_capacity),
+                                               ctypes.c_void_p(dev_body_mask), ctypes.c_size_t(body_capacity)))
+
+    def scene_mass(self, set=1, density=10.0):
+        """surtr_scene_mass: one MASS_DTYPE record per compound, in the body frame, added up on the device."""
+        return self._mass(lib().surtr_scene_mass, set, density)
+
+    def scene_mass_dev(self, dev_ptr, capacity, set=1, density=10.0):
+        self._ck(lib().surtr_scene_mass_dev(self._h, ctypes.c_int(int(set)), ctypes.c_float(density), ctypes.c_void_p(dev_ptr),
+                                            ctypes.c_size_t(capacity)))
 
     def upload_stats(self):
         ms, na = ctypes.c_float(), ctypes.c_uint32()

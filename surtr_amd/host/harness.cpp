@@ -7,6 +7,12 @@
 // --scene-clicks: the event's fragments become a resident scene (piece k in compound k / 2) and every click runs OnMouseDown on
 //                 it (partial fracture, the compound of the piece hit, pattern and sphere of radius R at the impact); after each
 //                 click one JSON line: the compound table, the piece hit, the compounds hit and made, the mass of every compound.
+// --body-clicks "ox,oy,oz,dx,dy,dz;..." [--scene-poses "c:16 floats;..."] [--radial]: the same scene, with the poses given set
+//                 before the clicks (compound c: a row-major matrix, the translation in the last column); every click runs
+//                 OnMouseDownBodies -- the ray and the impact sphere see the bodies where their poses put them, the body hit (with
+//                 --radial: every body the sphere of radius R / 2 touches and whose mass is above 1e-4) has its pose baked in and is
+//                 broken.  After each click one JSON line: the piece and compound hit, the body mask of the impact sphere, the
+//                 compounds hit and made, the table, the poses and the body masses after the click.
 // --pick: the event's fragments become the resident pieces (piece k in compound k / 2) and the ray is cast into them as
 // OnMouseDown does (Src/Surtr.cpp:207-240): the hit, the impact position, the overlap mask and the affected compounds, as JSON.
 // --ach runs Surtr::PrepareFracture end to end (ACH convex instead of the plain 2x box).
@@ -363,11 +369,80 @@ static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float
     }
 }
 
+static std::vector<Vector3> lattice_cloud()
+{
+    // the 26 directions of the 3 x 3 x 3 lattice, unit length (double arithmetic, narrowed): the sphere point cloud
+    std::vector<Vector3> cloud;
+    for (int i = -1; i <= 1; ++i) for (int j = -1; j <= 1; ++j) for (int k = -1; k <= 1; ++k)
+    {
+        if (!i && !j && !k) continue;
+        const double l = std::sqrt((double)(i * i + j * j + k * k));
+        cloud.emplace_back((float)(i / l), (float)(j / l), (float)(k / l));
+    }
+    return cloud;
+}
+
+// --body-clicks: OnMouseDownBodies per click on the posed scene; one JSON line per click.
+static void body_clicks(FractureEngine& eng, const std::vector<std::array<float, 6>>& clicks, const std::vector<std::pair<int, Matrix>>& poses,
+                        float impact_radius, bool radial)
+{
+    const uint32_t n0 = eng.CompoundFromLastEvent();
+    std::vector<uint32_t> off;
+    for (uint32_t p = 0; p < n0; p += 2) off.push_back(p);
+    off.push_back(n0);
+    const int rc = surtr_scene_set_compounds(eng.Raw(), (uint32_t)off.size() - 1u, off.data());
+    if (rc) throw Error(rc, "surtr_scene_set_compounds");
+    if (!poses.empty())
+    {
+        std::vector<Matrix> world(off.size() - 1);
+        for (const auto& p : poses)
+        {
+            if (p.first < 0 || (size_t)p.first >= world.size()) throw Error(SURTR_E_INVALID, "--scene-poses: no such compound");
+            world[(size_t)p.first] = p.second;
+        }
+        eng.SetPoses(world);
+    }
+    const std::vector<Vector3> cloud = lattice_cloud();
+    for (size_t q = 0; q < clicks.size(); ++q)
+    {
+        const Vector3 o(clicks[q][0], clicks[q][1], clicks[q][2]), d(clicks[q][3], clicks[q][4], clicks[q][5]);
+        FractureArgs args;
+        args.PartialFracture = true; args.RadialMode = radial; args.ImpactRadius = impact_radius;
+        surtr_scene_ray_hit hit;
+        std::vector<uint8_t> body;
+        std::vector<int> hitc;
+        const std::vector<int> made = eng.OnMouseDownBodies(o, d, args, impact_radius, cloud, &hitc, &hit, &body);      // (what the click acted on)
+        const std::vector<uint32_t> table = eng.SceneCompounds();
+        const std::vector<Matrix> world = eng.Poses();
+        const std::vector<surtr_mass> bm = eng.BodyMassProperties(1);
+        printf("{\"body_click\": %zu, \"hit_piece\": %d, \"hit_compound\": %d, \"body_mask\": [", q, hit.piece, hit.compound);
+        for (size_t i = 0; i < body.size(); ++i) printf("%s%d", i ? ", " : "", (int)body[i]);
+        printf("], \"compounds_hit\": [");
+        for (size_t i = 0; i < hitc.size(); ++i) printf("%s%d", i ? ", " : "", hitc[i]);
+        printf("], \"compounds_made\": [");
+        for (size_t i = 0; i < made.size(); ++i) printf("%s%d", i ? ", " : "", made[i]);
+        printf("], \"table\": [");
+        for (size_t i = 0; i < table.size(); ++i) printf("%s%u", i ? ", " : "", table[i]);
+        printf("], \"poses\": [");
+        for (size_t c = 0; c < world.size(); ++c)
+        {
+            printf("%s[", c ? ", " : "");
+            for (int k = 0; k < 16; ++k) printf("%s%.9g", k ? ", " : "", world[c].m[k]);
+            printf("]");
+        }
+        printf("], \"mass\": [");
+        for (size_t i = 0; i < bm.size(); ++i) printf("%s%.17g", i ? ", " : "", bm[i].mass);
+        printf("]}\n");
+    }
+}
+
 int main(int argc, char** argv)
 {
     std::string mesh = "cube", obj, obj_in, dump;
     int cells = 8, nu = 250, nv = 200;
-    std::vector<std::array<float, 6>> clicks;
+    std::vector<std::array<float, 6>> clicks, bclicks;
+    std::vector<std::pair<int, Matrix>> poses;
+    bool radial = false;
     bool ach = false, do_pick = false; float in_scale = 1.f, pick_ray[6] = {0, 0, 0, 1, 0, 0}, impact_radius = 1.f;
     for (int i = 1; i < argc; ++i)
     {
@@ -381,15 +456,36 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--ach")) ach = true;
         else if (!strcmp(argv[i], "--api-dump") && i + 1 < argc) dump = argv[++i];
         else if (!strcmp(argv[i], "--impact-radius") && i + 1 < argc) impact_radius = (float)atof(argv[++i]);
-        else if (!strcmp(argv[i], "--scene-clicks") && i + 1 < argc)
+        else if (!strcmp(argv[i], "--radial")) radial = true;
+        else if (!strcmp(argv[i], "--scene-poses") && i + 1 < argc)
         {
+            const char* c = argv[++i];
+            while (*c)
+            {
+                int comp = 0, used = 0;
+                Matrix w;
+                if (sscanf(c, "%d:%n", &comp, &used) != 1 || used == 0) { fprintf(stderr, "surtr_harness: --scene-poses takes c:16 floats;...\n"); return 2; }
+                c += used;
+                for (int k = 0; k < 16; ++k)
+                {
+                    if (sscanf(c, "%f%n", &w.m[k], &used) != 1) { fprintf(stderr, "surtr_harness: --scene-poses takes c:16 floats;...\n"); return 2; }
+                    c += used;
+                    if (*c == ',') ++c;
+                }
+                poses.emplace_back(comp, w);
+                if (*c == ';') ++c;
+            }
+        }
+        else if ((!strcmp(argv[i], "--scene-clicks") || !strcmp(argv[i], "--body-clicks")) && i + 1 < argc)
+        {
+            std::vector<std::array<float, 6>>& into = !strcmp(argv[i], "--body-clicks") ? bclicks : clicks;
             const char* c = argv[++i];
             while (*c)
             {
                 std::array<float, 6> r; int used = 0;
                 if (sscanf(c, "%f,%f,%f,%f,%f,%f%n", &r[0], &r[1], &r[2], &r[3], &r[4], &r[5], &used) != 6)
-                { fprintf(stderr, "surtr_harness: --scene-clicks takes ox,oy,oz,dx,dy,dz;...\n"); return 2; }
-                clicks.push_back(r);
+                { fprintf(stderr, "surtr_harness: --scene-clicks and --body-clicks take ox,oy,oz,dx,dy,dz;...\n"); return 2; }
+                into.push_back(r);
                 c += used;
                 if (*c == ';') ++c;
             }
@@ -439,6 +535,7 @@ int main(int argc, char** argv)
                c.mesh_nbrs, c.conv_verts, c.n_idx);
         if (do_pick) pick(eng, frags, pick_ray, impact_radius);
         if (!clicks.empty()) scene_clicks(eng, clicks, impact_radius);
+        else if (!bclicks.empty()) body_clicks(eng, bclicks, poses, impact_radius, radial);
         if (!obj.empty())
         {
             FILE* f = fopen(obj.c_str(), "w");

@@ -630,6 +630,7 @@ std::vector<int> FractureEngine::ExecuteFractureRoutine(int compound, const std:
         for (const auto& x : world) w.insert(w.end(), x.m, x.m + 16);
         check(surtr_scene_transform_compound(ctx_, (uint32_t)compound, m, w.data()), "surtr_scene_transform_compound");
     }
+    else ApplyPose(compound);      // the pose the scene holds for this body (the identity: nothing)
     // DoFracture's placement (:1890-1915)
     const float s2 = maxAxisScale * 2.f;
     SetRefittingPointLimit(args.RefittingPointLimit);
@@ -688,6 +689,92 @@ std::vector<int> FractureEngine::OnMouseDown(const Vector3& origin, const Vector
     for (auto it = hit.rbegin(); it != hit.rend(); ++it)
     {
         for (int& c : made) --c;      // (the compounds made so far sit above every target still to come: each moves down by one)
+        const std::vector<int> more = ExecuteFractureRoutine(*it, {}, maxAxisScale, args, spherePointCloud);
+        made.insert(made.end(), more.begin(), more.end());
+    }
+    return made;
+}
+
+void FractureEngine::SetPoses(const std::vector<Matrix>& world)
+{
+    std::vector<float> w; w.reserve(16 * world.size());
+    for (const auto& x : world) w.insert(w.end(), x.m, x.m + 16);
+    check(surtr_scene_set_poses(ctx_, (uint32_t)world.size(), w.data()), "surtr_scene_set_poses");
+}
+
+std::vector<Matrix> FractureEngine::Poses()
+{
+    uint32_t n = 0;
+    check(surtr_scene_get_poses(ctx_, 0, &n, nullptr), "surtr_scene_get_poses");
+    std::vector<float> w(16 * (size_t)n + 16);
+    check(surtr_scene_get_poses(ctx_, n, &n, w.data()), "surtr_scene_get_poses");
+    std::vector<Matrix> out(n);
+    for (uint32_t c = 0; c < n; ++c) std::copy(w.begin() + 16 * (size_t)c, w.begin() + 16 * (size_t)(c + 1), out[c].m);
+    return out;
+}
+
+void FractureEngine::ApplyPose(int compound)
+{
+    if (compound < 0) throw Error(SURTR_E_INVALID, "ApplyPose: no such compound");
+    check(surtr_scene_apply_pose(ctx_, (uint32_t)compound), "surtr_scene_apply_pose");
+}
+
+surtr_scene_ray_hit FractureEngine::RaycastScene(const Vector3& origin, const Vector3& dir, float maxDist)
+{
+    const float ray[7] = {origin.x, origin.y, origin.z, dir.x, dir.y, dir.z, maxDist};
+    surtr_scene_ray_hit hit;
+    check(surtr_scene_raycast(ctx_, 1, ray, &hit), "surtr_scene_raycast");
+    return hit;
+}
+
+std::vector<surtr_mass> FractureEngine::BodyMassProperties(int set, float density)
+{
+    uint32_t n = 0;
+    check(surtr_scene_mass(ctx_, set, density, &n, nullptr), "surtr_scene_mass");
+    std::vector<surtr_mass> out(n);
+    if (n) check(surtr_scene_mass(ctx_, set, density, &n, out.data()), "surtr_scene_mass");
+    return out;
+}
+
+std::vector<uint8_t> FractureEngine::OverlapBodies(const Vector3& centre, float radius, float minMass)
+{
+    const float sphere[4] = {centre.x, centre.y, centre.z, radius};
+    uint32_t n = 0;
+    check(surtr_scene_overlap(ctx_, 1, sphere, nullptr, 0.f, &n, nullptr), "surtr_scene_overlap");
+    std::vector<uint8_t> mask(n);
+    std::vector<surtr_mass> mass;
+    if (minMass >= 0.f) mass = BodyMassProperties(1);
+    check(surtr_scene_overlap(ctx_, 1, sphere, mass.empty() ? nullptr : mass.data(), minMass, &n, mask.data()), "surtr_scene_overlap");
+    return mask;
+}
+
+std::vector<int> FractureEngine::PickBodies(const Vector3& origin, const Vector3& dir, FractureArgs& args, surtr_scene_ray_hit* hitOut,
+                                            std::vector<uint8_t>* bodyMask)
+{
+    const surtr_scene_ray_hit hit = RaycastScene(origin, dir);
+    if (hitOut) *hitOut = hit;
+    if (bodyMask) bodyMask->clear();
+    if (hit.piece < 0) return {};
+    args.ImpactPosition = Vector3(hit.pos[0] + dir.x * args.TargetAdder, hit.pos[1] + dir.y * args.TargetAdder, hit.pos[2] + dir.z * args.TargetAdder);
+    if (!args.RadialMode && !bodyMask) return {hit.compound};
+    const std::vector<uint8_t> mask = OverlapBodies(args.ImpactPosition, args.ImpactRadius / 2.f, 1e-4f);
+    if (bodyMask) *bodyMask = mask;
+    if (!args.RadialMode) return {hit.compound};
+    std::vector<int> out;
+    for (size_t c = 0; c < mask.size(); ++c) if (mask[c] == 1) out.push_back((int)c);
+    return out;
+}
+
+std::vector<int> FractureEngine::OnMouseDownBodies(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
+                                                   const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds,
+                                                   surtr_scene_ray_hit* hitOut, std::vector<uint8_t>* bodyMask)
+{
+    std::vector<int> hit = PickBodies(origin, dir, args, hitOut, bodyMask);
+    if (hitCompounds) *hitCompounds = hit;
+    std::vector<int> made;
+    for (auto it = hit.rbegin(); it != hit.rend(); ++it)
+    {
+        for (int& c : made) --c;      // (as in OnMouseDown)
         const std::vector<int> more = ExecuteFractureRoutine(*it, {}, maxAxisScale, args, spherePointCloud);
         made.insert(made.end(), more.begin(), more.end());
     }

@@ -263,7 +263,7 @@ public:
     void SetScene(const std::vector<Compound>& compoundVec);
     std::vector<uint32_t> SceneCompounds();
     // ExecuteFractureRoutine for one compound of the scene, in its order: Poly::Transform of that compound's pieces by `world`
-    // (one matrix per piece; empty: the pieces stay where they were committed), the pattern scaled by 2 * maxAxisScale and moved to
+    // (one matrix per piece; empty: the compound's stored pose is baked in, ApplyPose -- nothing with the identity), the pattern scaled by 2 * maxAxisScale and moved to
     // the impact, the event on that compound (with PartialFracture its pieces out of the sphere are skipped: their Convex solids,
     // a few dozen vertices each, are read back for ConvexOutOfSphere -- nothing else leaves the device), the regrouping, the refit,
     // and the commit: the compound is erased, what it broke into is pushed to the back.  Returns the numbers of the new compounds.
@@ -277,6 +277,31 @@ public:
     // the last commit; hitCompounds (may be null) receives what PickImpact returned.
     std::vector<int> OnMouseDown(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
                                  const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds = nullptr);
+    // ---- bodies that move (Update writes each body's pose into m_structuredBufferData[i].WorldMatrix, Src/Surtr.cpp:347-352) ----
+    // One rigid pose per compound of the scene (surtr_scene_set_poses: Matrix::m in the layout TransformCompound takes); the resident
+    // pieces stay in the frame they were committed in.  ApplyPose bakes a compound's pose into its pieces (:1846-1851) and makes the
+    // pose the identity; with the identity it does nothing at all.
+    void SetPoses(const std::vector<Matrix>& world);
+    std::vector<Matrix> Poses();
+    void ApplyPose(int compound);
+    // OnMouseDown's queries on the bodies where their poses put them (surtr_scene_raycast / surtr_scene_overlap).  OverlapBodies: one
+    // value per COMPOUND, 0 no piece of it is touched, 1 touched, 2 touched but the body's mass <= minMass (density 10; < 0: no gate).
+    surtr_scene_ray_hit RaycastScene(const Vector3& origin, const Vector3& dir, float maxDist = 1000.f);
+    std::vector<uint8_t> OverlapBodies(const Vector3& centre, float radius, float minMass = 1e-4f);
+    // One record per compound in its body frame, added up on the device (surtr_scene_mass): what setMass / setCMassLocalPose /
+    // setMassSpaceInertiaTensor take for a body whose pose the solver holds.
+    std::vector<surtr_mass> BodyMassProperties(int set, float density = 10.f);
+    // OnMouseDown's picking with the reference's semantics (:207-233): the ray is cast on the posed scene; a hit sets
+    // args.ImpactPosition = hit + dir * args.TargetAdder; with args.RadialMode the compounds whose body mask is 1 for the sphere of
+    // radius args.ImpactRadius / 2 are returned (the gate is on the mass of the BODY), else the compound hit.  Ascending.
+    // hit / bodyMask (may be null) receive the ray's record and the sphere's body mask (asked for, it is taken without RadialMode too).
+    std::vector<int> PickBodies(const Vector3& origin, const Vector3& dir, FractureArgs& args, surtr_scene_ray_hit* hit = nullptr,
+                                std::vector<uint8_t>* bodyMask = nullptr);
+    // PickBodies, then ExecuteFractureRoutine (which bakes the stored pose first) in descending compound number.  hit / bodyMask:
+    // what the pick it acted on found.
+    std::vector<int> OnMouseDownBodies(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
+                                       const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds = nullptr,
+                                       surtr_scene_ray_hit* hit = nullptr, std::vector<uint8_t>* bodyMask = nullptr);
     surtr_counts LastCounts() const { return counts_; }
     // The degenerate policy at this level (include/surtr_hip.h, surtr_counts::n_failed): where the reference leaves its own
     // arrays the engine flags the unit instead of emulating what the reference's memory happens to hold -- a flagged (cell,
