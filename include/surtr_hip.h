@@ -148,7 +148,11 @@ int surtr_event_pair_costs(surtr_ctx* ctx, uint32_t n_pairs, uint32_t* cost);
 /* ---- inputs ------------------------------------------------------------ */
 /* Replaces compound.PieceVec (Inc/Surtr.h:113-134): n pieces, each a (Convex, Mesh)
  * pair of solids.  Copies host -> device once; validates neighbour symmetry
- * and degree >= 3 (SURTR_E_TOPOLOGY). */
+ * and degree >= 3 (SURTR_E_TOPOLOGY).  Ring offsets that decrease or point past the last ring entry are SURTR_E_INVALID, a ring
+ * shorter than three or a link that names no vertex of its piece is SURTR_E_TOPOLOGY (the larger code when both occur), whatever
+ * the values: the first kernel of the upload vets every offset before it reads a ring and every link before it follows it, and
+ * the kernels that walk through links do nothing once it has found a fault.  A refused upload leaves no resident pieces and the
+ * context usable. */
 int surtr_upload_pieces(surtr_ctx* ctx, uint32_t n_pieces,
                         const uint32_t* mesh_vert_off, const float* mesh_pos,
                         const uint32_t* mesh_nbr_off, const int32_t* mesh_nbr,
@@ -270,6 +274,32 @@ int surtr_pieces_from_event(surtr_ctx* ctx, const uint8_t* keep, uint32_t* n_pie
  * Poly::Transform of a single host polyhedron; the event path never needs it. */
 int surtr_download_piece(surtr_ctx* ctx, uint32_t piece, int set, uint32_t* out_nv, uint32_t* out_nh, float* out_pos,
                          uint32_t* out_nbr_off, int32_t* out_nbr);
+/* Diagnostic: one array of the data every upload, transform, surtr_pieces_from_event and surtr_scene_commit derives from the
+ * resident pieces for the pre-pass (pieces_dev.hip: derive_set), read back as it stands (set 0 = Mesh, 1 = Convex).  V = vertices of
+ * the set, n = pieces; arrays over vertices are in piece order, sorted ones (perm, posr_s, row_s) in Morton order inside each piece.
+ * Count-then-fill: *bytes is the size of the array; out == NULL returns it only; SURTR_E_CAPACITY when capacity_bytes is smaller.
+ * SURTR_E_STATE without resident pieces (SURTR_DERIVED_BUILD needs none).  Synchronises the context's stream; launches nothing and
+ * changes nothing.  For tests: the event path never calls it. */
+enum {
+    SURTR_DERIVED_LLEN = 0,    /* uint32[V]   ring length */
+    SURTR_DERIVED_TRI = 1,     /* uint8[V]    1: every face through the vertex is a triangle */
+    SURTR_DERIVED_RAD = 2,     /* float[V]    radius of a ball around the vertex that holds every vertex of its faces */
+    SURTR_DERIVED_BOX = 3,     /* float[6n]   lo xyz, hi xyz of every piece */
+    SURTR_DERIVED_PERM = 4,    /* uint32[V]   piece-local vertex of sorted slot i */
+    SURTR_DERIVED_POSR_S = 5,  /* float[4V]   position and ball radius of sorted slot i */
+    SURTR_DERIVED_BSPH = 6,    /* float[4 * spheres]  centre, radius: one per build[0] sorted vertices of a piece */
+    SURTR_DERIVED_BSPH2 = 7,   /*             one per build[1] spheres of the level below, per piece */
+    SURTR_DERIVED_BSPH3 = 8,
+    SURTR_DERIVED_IPERM = 9,   /* uint32[V]   sorted slot of piece-local vertex v */
+    SURTR_DERIVED_ROW_S = 10,  /* uint16[8V]  header, then up to seven ring entries as sorted slots, 0xFFFF padding */
+    SURTR_DERIVED_DUP = 11,    /* uint8[n]    1: some ring of the piece lists a vertex twice */
+    SURTR_DERIVED_BO = 12,     /* uint32[n+1] first sphere of every piece at level 1 */
+    SURTR_DERIVED_BO2 = 13,    /*             ... level 2 */
+    SURTR_DERIVED_BO3 = 14,    /*             ... level 3 */
+    SURTR_DERIVED_BUILD = 15,  /* uint32[2]   what the library was built with: vertices per level-1 sphere, spheres per coarser sphere */
+    SURTR_DERIVED_COUNT = 16
+};
+int surtr_pieces_derived(surtr_ctx* ctx, int set, int which, void* out, size_t capacity_bytes, size_t* bytes);
 /* Host time of the last surtr_upload_pieces / surtr_pieces_from_event / surtr_transform_pieces / surtr_scene_commit call, in milliseconds,
  * and how many device allocations it made (0 in steady state: the piece buffers are pooled). */
 int surtr_upload_stats(surtr_ctx* ctx, float* ms, uint32_t* n_alloc);

@@ -36,14 +36,17 @@ __device__ __forceinline__ uint32_t piece_of(const uint32_t* __restrict__ vo, ui
 
 // llen + the checks of Poly::ExtractNeighborFromMesh's postcondition (Src/Poly.cpp:253-260): indices in range, no self
 // link, every link has its back link; degree >= 3.  err = max SURTR_E_* seen.
+// It is also the gate of a host upload, whose offsets and links may be anything: H = entries of nbr (0xFFFFFFFF where the rings
+// were made on the device); this kernel reads no ring that does not lie inside [0, H) and follows no link before it has compared
+// it with the piece's size, and the kernels after it that walk through links (k_piece_tri_rad) do nothing once err is set.
 __global__ void k_piece_check(uint32_t V, uint32_t n, const uint32_t* __restrict__ vo, const uint32_t* __restrict__ loff,
                               const int32_t* __restrict__ nbr, uint32_t* __restrict__ llen, uint32_t check, uint32_t* __restrict__ err,
-                              uint8_t* __restrict__ dup)
+                              uint8_t* __restrict__ dup, uint32_t H)
 {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= V) return;
     const uint32_t lo = loff[v], hi = loff[v + 1];
-    if (hi < lo) { atomicMax(err, (uint32_t)SURTR_E_INVALID); llen[v] = 0; return; }
+    if (hi < lo || hi > H) { atomicMax(err, (uint32_t)SURTR_E_INVALID); llen[v] = 0; return; }
     const uint32_t deg = hi - lo;
     llen[v] = deg;
     const uint32_t p = piece_of(vo, n, v), a = vo[p], m = vo[p + 1] - a;
@@ -59,6 +62,7 @@ __global__ void k_piece_check(uint32_t V, uint32_t n, const uint32_t* __restrict
         const int32_t u = nbr[j];
         if (u < 0 || (uint32_t)u >= m || u == lv) { atomicMax(err, (uint32_t)SURTR_E_TOPOLOGY); return; }
         const uint32_t ulo = loff[a + (uint32_t)u], uhi = loff[a + (uint32_t)u + 1];
+        if (uhi > H) { atomicMax(err, (uint32_t)SURTR_E_INVALID); return; }      // (u's own thread says so too)
         bool back = false;
         for (uint32_t q = ulo; q < uhi && q >= ulo; ++q) if (nbr[q] == lv) { back = true; break; }
         if (!back) { atomicMax(err, (uint32_t)SURTR_E_TOPOLOGY); return; }
@@ -69,10 +73,13 @@ __global__ void k_piece_check(uint32_t V, uint32_t n, const uint32_t* __restrict
 // rad[v] = radius of a ball around v that holds every vertex of every face incident to v (rounded up).
 __global__ void k_piece_tri_rad(uint32_t V, uint32_t n, const uint32_t* __restrict__ vo, const float* __restrict__ pos,
                                 const uint32_t* __restrict__ loff, const int32_t* __restrict__ nbr, uint8_t* __restrict__ tri,
-                                float* __restrict__ rad)
+                                float* __restrict__ rad, const uint32_t* __restrict__ gate)
 {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= V) return;
+    // gate: k_piece_check's error word when the links come from the host (null otherwise).  Set: some link or offset of the
+    // upload names nothing, the upload is refused, and no ring is walked (tri / rad keep whatever they held).
+    if (gate && *gate) return;
     const uint32_t p = piece_of(vo, n, v), a = vo[p], m = vo[p + 1] - a;
     const int32_t lv = (int32_t)(v - a);
     auto ring = [&](int32_t x) { return nbr + loff[a + (uint32_t)x]; };
@@ -330,15 +337,17 @@ int reserve_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, uint32_t H,
 }
 
 // Derived data of one set whose pos / loff / nbr / vo are in place.  `check`: validate the links (host uploads).
-int derive_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, const std::vector<uint32_t>& bo_h, bool check)
+// H: entries of nbr, known and passed for a host upload only -- what k_piece_check vets the ring offsets against.
+int derive_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, const std::vector<uint32_t>& bo_h, bool check, uint32_t H)
 {
     hipStream_t st = ctx->stream;
     const uint32_t NB = bo_h[n];
     HIPCHK(hipMemcpyAsync(S.bo, bo_h.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
     const dim3 blk(256), gridV((V + 255) / 256);
     HIPCHK(hipMemsetAsync(S.dup, 0, (size_t)n + 1, st));
-    hipLaunchKernelGGL(k_piece_check, gridV, blk, 0, st, V, n, S.vo, S.loff, S.nbr, S.llen, check ? 1u : 0u, ctx->d_upload_err, S.dup);
-    hipLaunchKernelGGL(k_piece_tri_rad, gridV, blk, 0, st, V, n, S.vo, S.pos, S.loff, S.nbr, S.tri, S.rad);
+    hipLaunchKernelGGL(k_piece_check, gridV, blk, 0, st, V, n, S.vo, S.loff, S.nbr, S.llen, check ? 1u : 0u, ctx->d_upload_err, S.dup, check ? H : 0xFFFFFFFFu);
+    hipLaunchKernelGGL(k_piece_tri_rad, gridV, blk, 0, st, V, n, S.vo, S.pos, S.loff, S.nbr, S.tri, S.rad,
+                       check ? (const uint32_t*)ctx->d_upload_err.p : (const uint32_t*)nullptr);
     hipLaunchKernelGGL(k_piece_box, dim3(n), dim3(SURTR_WG), 0, st, n, S.vo, S.pos, S.box);
     hipLaunchKernelGGL(k_piece_keys, gridV, blk, 0, st, V, n, S.vo, S.pos, S.box, S.key, S.val);
     // stable sort of (piece, Morton code) -> piece-local vertex: per piece the host order std::sort gave pairs (code, vertex)
@@ -474,7 +483,7 @@ int surtr_upload_pieces(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const f
         HIPCHK(hipMemcpyAsync(S.loff, off, (size_t)(V + 1) * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(S.nbr, nbr, (size_t)H * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(S.vo, vo, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
-        rc = derive_set(ctx, S, n, V, bo, true);
+        rc = derive_set(ctx, S, n, V, bo, true, H);
         if (rc) return rc;
     }
     set_piece_stats(ctx, n, mvo, mho.data(), cvo, cho.data());
@@ -636,6 +645,50 @@ int surtr_pair_order(surtr_ctx* ctx, uint32_t cap, uint32_t* n, uint32_t* order)
     if (cap < *n) return SURTR_E_CAPACITY;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipMemcpy(order, ctx->d_pair_order, (size_t)*n * 4, hipMemcpyDeviceToHost));
+    return SURTR_OK;
+}
+
+int surtr_pieces_derived(surtr_ctx* ctx, int set, int which, void* out, size_t capacity_bytes, size_t* bytes)
+{
+    if (!ctx || set < 0 || set > 1 || !bytes || which < 0 || which >= SURTR_DERIVED_COUNT) return SURTR_E_INVALID;
+    const uint32_t build[2] = {SURTR_SB, SURTR_SPH_FAN};
+    const void* src = nullptr; size_t b = 0;
+    if (which == SURTR_DERIVED_BUILD) b = sizeof(build);
+    else
+    {
+        if (!ctx->n_pieces) return SURTR_E_STATE;
+        const PieceSet& S = set ? ctx->cset : ctx->mset;
+        const uint32_t n = ctx->n_pieces; const size_t V = ctx->h_vo[set][n];
+        // the sphere counts of the three levels, as derive_set lays them out
+        const std::vector<uint32_t> bo = sphere_offsets(n, ctx->h_vo[set].data());
+        size_t nb2 = 0, nb3 = 0;
+        for (uint32_t p = 0; p < n; ++p) { const uint32_t a = up_count(bo[p + 1] - bo[p]); nb2 += a; nb3 += up_count(a); }
+        switch (which)
+        {
+        case SURTR_DERIVED_LLEN:   src = S.llen.p;   b = V * 4; break;
+        case SURTR_DERIVED_TRI:    src = S.tri.p;    b = V; break;
+        case SURTR_DERIVED_RAD:    src = S.rad.p;    b = V * 4; break;
+        case SURTR_DERIVED_BOX:    src = S.box.p;    b = (size_t)n * 24; break;
+        case SURTR_DERIVED_PERM:   src = S.perm.p;   b = V * 4; break;
+        case SURTR_DERIVED_POSR_S: src = S.posr_s.p; b = V * 16; break;
+        case SURTR_DERIVED_BSPH:   src = S.bsph.p;   b = (size_t)bo[n] * 16; break;
+        case SURTR_DERIVED_BSPH2:  src = S.bsph2.p;  b = nb2 * 16; break;
+        case SURTR_DERIVED_BSPH3:  src = S.bsph3.p;  b = nb3 * 16; break;
+        case SURTR_DERIVED_IPERM:  src = S.iperm.p;  b = V * 4; break;
+        case SURTR_DERIVED_ROW_S:  src = S.row_s.p;  b = V * 16; break;
+        case SURTR_DERIVED_DUP:    src = S.dup.p;    b = n; break;
+        case SURTR_DERIVED_BO:     src = S.bo.p;     b = ((size_t)n + 1) * 4; break;
+        case SURTR_DERIVED_BO2:    src = S.bo2.p;    b = ((size_t)n + 1) * 4; break;
+        default:                   src = S.bo3.p;    b = ((size_t)n + 1) * 4; break;
+        }
+    }
+    *bytes = b;
+    if (!out) return SURTR_OK;
+    if (capacity_bytes < b) return SURTR_E_CAPACITY;
+    if (!src) { memcpy(out, build, b); return SURTR_OK; }
+    (void)hipSetDevice(ctx->device);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (b) HIPCHK(hipMemcpy(out, src, b, hipMemcpyDeviceToHost));
     return SURTR_OK;
 }
 

@@ -427,7 +427,7 @@ struct Timer
     ~Timer() { ctx->upload_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
 int reserve_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, uint32_t H, uint32_t NB);
-int derive_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, const std::vector<uint32_t>& bo_h, bool check);
+int derive_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, const std::vector<uint32_t>& bo_h, bool check, uint32_t H = 0xFFFFFFFFu);
 std::vector<uint32_t> sphere_offsets(uint32_t n, const uint32_t* vo);
 void set_piece_stats(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const uint32_t* mho, const uint32_t* cvo, const uint32_t* cho);
 int finish_upload(surtr_ctx* ctx, uint32_t n, bool check);

@@ -51,6 +51,12 @@ RAY_STARTS_INSIDE, RAY_INVALID = 1, 2
 QUERY_FEW, QUERY_OPEN, QUERY_FLAT, QUERY_LONG = 1, 2, 4, 8
 
 
+# the arrays of surtr_pieces_derived, in the order of the SURTR_DERIVED_* enumeration (include/surtr_hip.h)
+_DERIVED = (("llen", np.uint32), ("tri", np.uint8), ("rad", np.float32), ("box", np.float32), ("perm", np.uint32),
+            ("posr_s", np.float32), ("bsph", np.float32), ("bsph2", np.float32), ("bsph3", np.float32), ("iperm", np.uint32),
+            ("row_s", np.uint16), ("dup", np.uint8), ("bo", np.uint32), ("bo2", np.uint32), ("bo3", np.uint32), ("build", np.uint32))
+
+
 class Fragments(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in
                 ("frag_ids", "mesh_vert_off", "mesh_pos", "mesh_nbr_off", "mesh_nbr", "conv_vert_off", "conv_pos",
@@ -413,6 +419,25 @@ class Engine:
         pos = np.zeros((nv.value, 3), np.float32); off = np.zeros(nv.value + 1, np.uint32); nbr = np.zeros(nh.value, np.int32)
         self._ck(lib().surtr_download_piece(*args, ctypes.byref(nv), ctypes.byref(nh), _p(pos), _p(off), _p(nbr)))
         return {"pos": pos, "off": off, "nbr": nbr}
+
+    def pieces_derived(self, set=0):
+        """surtr_pieces_derived: what the pre-pass derives from the resident pieces of one set (0 = Mesh, 1 = Convex), read back
+        as a dict of numpy arrays: llen, tri, rad, box [n, 6], perm, posr_s [V, 4], bsph / bsph2 / bsph3 [., 4], iperm,
+        row_s [V, 8], dup, bo / bo2 / bo3, and the library's 'SB' and 'FAN' (vertices per level-1 sphere, spheres per coarser
+        sphere).  A diagnostic for tests."""
+        def get(which, dtype):
+            b = ctypes.c_size_t()
+            args = [self._h, ctypes.c_int(int(set)), ctypes.c_int(which)]
+            self._ck(lib().surtr_pieces_derived(*args, None, ctypes.c_size_t(0), ctypes.byref(b)))
+            buf = np.zeros(b.value, np.uint8)
+            self._ck(lib().surtr_pieces_derived(*args, _p(buf), ctypes.c_size_t(b.value), ctypes.byref(b)))
+            return buf.view(dtype)
+        out = {name: get(which, dt) for which, (name, dt) in enumerate(_DERIVED)}
+        for name, width in (("box", 6), ("posr_s", 4), ("bsph", 4), ("bsph2", 4), ("bsph3", 4), ("row_s", 8)):
+            out[name] = out[name].reshape(-1, width)
+        build = out.pop("build")
+        out["SB"], out["FAN"] = int(build[0]), int(build[1])
+        return out
 
     def event_refit(self):
         self._ck(lib().surtr_event_refit(self._h))

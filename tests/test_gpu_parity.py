@@ -318,6 +318,10 @@ def test_outside_mask_skips_pieces_gpu(gpu_engine, oracle):
 
 
 def test_errors_are_reported_on_the_gpu(gpu_engine):
+    """The wrong link tried here names a vertex of the piece.  Links and ring offsets that name nothing (-1, 1 << 30, an offset of
+    1 << 28, ...) are refused too, but that is pinned on the emulation only (tests/test_pieces_derived.py): were the guard
+    incomplete, the same case on the device would fault a GPU that others share, and the device code is the very source the
+    emulation compiles."""
     sc = scenes.blob_scene(64)
     # bad topology: refused by the device-side link check of the upload
     bad = dict(sc["mesh"], nbr=sc["mesh"]["nbr"].copy())
