@@ -134,7 +134,9 @@ int surtr_kernel_history(surtr_ctx* ctx, float ms[16], int slot[16], uint32_t* n
  * general clipper ([96+r]: by rule r), [90] solids that were too large for the literal last-resort clipper (more than 32 ring
  * entries at a vertex, or more vertices than its scratch): their pair / fragment is flagged like one without a valid result in
  * the reference -- this counter is how to tell the engine's limit from the reference's undefined behaviour; [95] fragments a
- * refit at a RefittingPointLimit above 4 left un-refitted and flagged SURTR_E_CAPACITY (see n_failed). */
+ * refit at a RefittingPointLimit above 4 left un-refitted and flagged SURTR_E_CAPACITY (see n_failed); [80] / [81] Convexes of the
+ * pairs the regular one-wave clipper took / handed on (or that started on the literal clipper), [87] pairs k_clip_convex_lean left
+ * to k_clip_convex as its second tier (0 after an event that took the one-kernel arrangement). */
 int surtr_queue_stats(surtr_ctx* ctx, uint32_t out[128]);
 /* Diagnostic: the status of every pair of the last event (0, or the SURTR_E_* code that pair raised), in pair order
  * (cell-major for surtr_fracture_event, list order for surtr_fracture_pairs).  Works after an event that failed. */

@@ -24,38 +24,57 @@
 namespace surtr {
 
 // The solid in LDS.  A ring entry carries, beside the neighbour's id, the slot of the reverse entry in the neighbour's ring (its
-// "twin"), so that a face walk and the renumbering of the compaction never search a ring: entry = id | twin << 16.  The twins
+// "twin"), so that a face walk and the renumbering of the compaction never search a ring: entry = id | twin << 16 (or << 8, see ScSolidT).  The twins
 // are found once, when the solid is loaded; a regular plane keeps them up to date for free -- the ring of a kept vertex keeps
 // its length and order (:350-354 patch entries in place), and a new vertex [pred, succ, kept end] is entry 1 of its predecessor,
 // entry 0 of its successor, and takes the place of its clipped end in the kept end's ring.
-struct ScSolid
+// (the capacities are parameters: k_clip_convex_lean sizes its LDS for more workgroups per CU than SC_V / SC_H admit; what a smaller
+//  solid cannot hold is handed on like any other SC_FALLBACK)
+// WORD: uint32_t, or uint16_t for half the bytes of the rings: a ring has at most 15 entries (4 bits for a length or a twin slot), so a
+// solid of up to 256 vertices and 4 096 ring entries packs into 8 + 4 and 12 + 4 bits.  Same solid, same decisions.
+template <uint32_t CAPV, uint32_t CAPH, class WORD = uint32_t>
+struct ScSolidT
 {
-    float pos[3 * SC_V];
-    uint32_t vw[SC_V];                    // ring offset | ring length << 16
-    uint32_t re[SC_H];                    // neighbour | twin slot << 16
+    typedef WORD Word;
+    static constexpr uint32_t kVwSh = sizeof(WORD) == 4 ? 16u : 12u, kReSh = sizeof(WORD) == 4 ? 16u : 8u;
+    static_assert(CAPV <= (1u << kReSh) && CAPH <= (1u << kVwSh), "a vertex id / a ring offset fits its field");
+    float pos[3 * CAPV];
+    WORD vw[CAPV];                        // ring offset | ring length << kVwSh
+    WORD re[CAPH];                        // neighbour | twin slot << kReSh
 };
+typedef ScSolidT<SC_V, SC_H> ScSolid;
 
-struct ScLds
+template <uint32_t CAPV, uint32_t CAPH, class WORD = uint32_t>
+struct ScLdsT
 {
-    ScSolid buf[2];
-    int8_t c[SC_V];                       // comp of the plane in progress
-    uint16_t km[SC_V];                    // clipped vertex: bit j = ring slot j holds a kept neighbour
-    uint16_t mp[SC_V];                    // kept vertex: its index after the compaction; clipped: 0x8000 | number of its first new vertex
-    uint16_t noff[SC_V];                  // kept vertex: its ring offset after the compaction
-    uint16_t succ[SC_V], pred[SC_V];      // per new vertex
+    static_assert(CAPV % 4u == 0 && CAPV <= 0x7FFFu && CAPH <= 0xFFFFu, "16-bit indices, 4-byte arrays");
+    static constexpr uint32_t kV = CAPV, kH = CAPH;
+    typedef ScSolidT<CAPV, CAPH, WORD> Solid;
+    Solid buf[2];
+    int8_t c[CAPV];                       // comp of the plane in progress
+    uint16_t km[CAPV];                    // clipped vertex: bit j = ring slot j holds a kept neighbour
+    uint16_t mp[CAPV];                    // kept vertex: its index after the compaction; clipped: 0x8000 | number of its first new vertex
+    uint16_t noff[CAPV];                  // kept vertex: its ring offset after the compaction
+    uint16_t succ[CAPV], pred[CAPV];      // per new vertex
     uint32_t nv[2], flag;
 #ifdef SURTR_STAMP
     unsigned long long tph[8];            // lane 0's cycles: load, classify, numbering, relink, check, compaction; cutting planes
 #endif
 };
+typedef ScLdsT<SC_V, SC_H> ScLds;
 
 // Clips `in` by sh.planes[0..F).  0: done, the result is L.buf[*which] with L.nv[*which] vertices (0 = empty);
 // SC_FALLBACK: use the general clipper.  One wave; every lane must call it.
 // stop (optional): with SC_FALLBACK, the plane it stopped at when the solid before that plane -- L.buf[*which], L.nv[*which]
 // vertices, exactly the reference's compacted solid after the planes before (:464-495) -- is there for the general clipper to go
 // on from (sc_stage); 0xFFFFFFFF when there is none (the input itself is not regular).
-__device__ inline int small_clip(const SolidIn in, const uint32_t F, const Shared& sh, ScLds& L, uint32_t* which, uint32_t* stop = nullptr)
+// (SH: Shared, or any type with its planes[]; LDS: an ScLdsT)
+template <class SH, class LDS>
+__device__ inline int small_clip(const SolidIn in, const uint32_t F, const SH& sh, LDS& L, uint32_t* which, uint32_t* stop = nullptr)
 {
+    typedef typename LDS::Solid ScSolid;
+    constexpr uint32_t CAPV = LDS::kV, CAPH = LDS::kH;
+    constexpr uint32_t VS = ScSolid::kVwSh, VM = (1u << VS) - 1u, RS = ScSolid::kReSh, RM = (1u << RS) - 1u;      // the fields of vw / re
     const uint32_t lane = lane_id();
     const uint32_t V = in.nv;
 #ifdef SURTR_STAMP
@@ -66,9 +85,9 @@ __device__ inline int small_clip(const SolidIn in, const uint32_t F, const Share
 #define SC_STAMP(i) do { } while (0)
 #endif
     if (stop != nullptr) *stop = 0xFFFFFFFFu;
-    if (V == 0 || V > SC_V) return SC_FALLBACK;
+    if (V == 0 || V > CAPV) return SC_FALLBACK;
     const uint32_t hbase = in.loff[0], H = in.loff[V - 1u] + in.llen[V - 1u] - hbase;
-    if (H > SC_H) return SC_FALLBACK;
+    if (H > CAPH) return SC_FALLBACK;
     bool odd = false;
     for (uint32_t v = lane; v < V; v += SURTR_LANES)
     {
@@ -77,12 +96,12 @@ __device__ inline int small_clip(const SolidIn in, const uint32_t F, const Share
         const uint32_t lo = in.loff[v] - hbase, deg = in.llen[v];
         if (deg > 15u || deg < 3u) odd = true;
         const uint32_t dl = deg > 15u ? 15u : deg;
-        S.vw[v] = lo | (dl << 16);
+        S.vw[v] = lo | (dl << VS);
         const int32_t* r = in.nbr + in.loff[v];
-        for (uint32_t j = 0; j < dl && lo + j < SC_H; ++j)
+        for (uint32_t j = 0; j < dl && lo + j < CAPH; ++j)
         {
             if ((uint32_t)r[j] >= V) odd = true;
-            S.re[lo + j] = (uint32_t)r[j] & 0xFFFFu;
+            S.re[lo + j] = (uint32_t)r[j] & RM;
             // A ring that lists a vertex twice (slivers) makes the reference's first-occurrence patches and walks order
             // dependent: the general clipper reproduces that, this one does not try.  Checked once, here: a regular plane
             // cannot create such a ring in a kept vertex (its clipped neighbours become the distinct new vertices of distinct
@@ -96,15 +115,15 @@ __device__ inline int small_clip(const SolidIn in, const uint32_t F, const Share
     for (uint32_t v = lane; v < V; v += SURTR_LANES)
     {
         ScSolid& S = L.buf[0];
-        const uint32_t w = S.vw[v], lo = w & 0xFFFFu, deg = w >> 16;
+        const uint32_t w = S.vw[v], lo = w & VM, deg = w >> VS;
         for (uint32_t j = 0; j < deg; ++j)
         {
-            const uint32_t e = S.re[lo + j] & 0xFFFFu;
-            const uint32_t we = S.vw[e], elo = we & 0xFFFFu, edeg = we >> 16;
+            const uint32_t e = S.re[lo + j] & RM;
+            const uint32_t we = S.vw[e], elo = we & VM, edeg = we >> VS;
             uint32_t q = 0;
-            while (q < edeg && (S.re[elo + q] & 0xFFFFu) != v) ++q;
+            while (q < edeg && (S.re[elo + q] & RM) != v) ++q;
             if (q >= edeg) odd = true;
-            S.re[lo + j] = e | (q << 16);      // (only this lane writes the high half of its own entries; the others read the low half)
+            S.re[lo + j] = e | (q << RS);      // (only this lane writes the high part of its own entries; the others read the low part)
         }
     }
     if (__ballot(odd) != 0ull) return SC_FALLBACK;
@@ -143,11 +162,11 @@ __device__ inline int small_clip(const SolidIn in, const uint32_t F, const Share
             uint32_t mask = 0, isKept = 0, deg = 0;
             if (v < nv)
             {
-                const uint32_t w = S.vw[v], lo = w & 0xFFFFu;
-                deg = w >> 16;
+                const uint32_t w = S.vw[v], lo = w & VM;
+                deg = w >> VS;
                 if (L.c[v] > 0) isKept = 1u;
                 else
-                    for (uint32_t j = 0; j < deg; ++j) if (L.c[S.re[lo + j] & 0xFFFFu] > 0) mask |= 1u << j;
+                    for (uint32_t j = 0; j < deg; ++j) if (L.c[S.re[lo + j] & RM] > 0) mask |= 1u << j;
             }
             const uint32_t cnt = (uint32_t)__builtin_popcount(mask);
             // one scan for the three running sums: new vertices | kept vertices << 16, kept ring entries
@@ -162,7 +181,7 @@ __device__ inline int small_clip(const SolidIn in, const uint32_t F, const Share
             carryM += tx & 0xFFFFu; carryK += tx >> 16; carryH += ty;
         }
         const uint32_t M = carryM, nKeep = carryK, HK = carryH;
-        if (nKeep + M > SC_V || HK + 3u * M > SC_H) SC_GIVE_UP;
+        if (nKeep + M > CAPV || HK + 3u * M > CAPH) SC_GIVE_UP;
         if (nKeep + M < 4u) { nv = 0; break; }                        // (:497-499)
         for (uint32_t t = lane; t < M; t += SURTR_LANES) L.pred[t] = 0xFFFFu;
         __syncthreads();
@@ -181,12 +200,12 @@ __device__ inline int small_clip(const SolidIn in, const uint32_t F, const Share
                 uint32_t cv = v, w = wv, slot = (uint32_t)__builtin_ctz(mask), steps = 0, end = 0xFFFFu;
                 while (steps++ <= nv)
                 {
-                    const uint32_t len = w >> 16;
+                    const uint32_t len = w >> VS;
                     const uint32_t p = slot == 0u ? len - 1u : slot - 1u;
-                    const uint32_t rw = S.re[(w & 0xFFFFu) + p];
-                    const uint32_t e = rw & 0xFFFFu;
+                    const uint32_t rw = S.re[(w & VM) + p];
+                    const uint32_t e = rw & RM;
                     if (L.c[e] > 0) { end = (L.mp[cv] & 0x7FFFu) + (uint32_t)__builtin_popcount(L.km[cv] & ((1u << p) - 1u)); break; }
-                    cv = e; slot = rw >> 16; w = S.vw[e];              // the walk arrives at clipped e from cv: the twin is the slot
+                    cv = e; slot = rw >> RS; w = S.vw[e];              // the walk arrives at clipped e from cv: the twin is the slot
                 }
                 if (end == 0xFFFFu || end == t) { bad = true; continue; }
                 L.succ[t] = (uint16_t)end;
@@ -203,20 +222,20 @@ __device__ inline int small_clip(const SolidIn in, const uint32_t F, const Share
         // ---- the solid after this plane, compacted (:464-495): kept vertices in order, then the new ones ----
         for (uint32_t v = lane; v < nv; v += SURTR_LANES)
         {
-            const uint32_t w = S.vw[v], lo0 = w & 0xFFFFu, deg = w >> 16;
+            const uint32_t w = S.vw[v], lo0 = w & VM, deg = w >> VS;
             if (L.c[v] > 0)
             {
                 const uint32_t id = L.mp[v], lo = L.noff[v];
                 N.pos[3 * id] = S.pos[3 * v]; N.pos[3 * id + 1] = S.pos[3 * v + 1]; N.pos[3 * id + 2] = S.pos[3 * v + 2];
-                N.vw[id] = lo | (deg << 16);
+                N.vw[id] = lo | (deg << VS);
                 for (uint32_t j = 0; j < deg; ++j)
                 {
-                    const uint32_t rw = S.re[lo0 + j], e = rw & 0xFFFFu, q = rw >> 16;
+                    const uint32_t rw = S.re[lo0 + j], e = rw & RM, q = rw >> RS;
                     const uint32_t m = L.mp[e], kme = L.km[e];
                     // a kept neighbour under its new number, same twin; the link to a clipped neighbour now holds the new vertex on
                     // that edge (:350-354), whose third entry this vertex is
-                    N.re[lo + j] = (m & 0x8000u) ? (nKeep + (m & 0x7FFFu) + (uint32_t)__builtin_popcount(kme & ((1u << q) - 1u))) | (2u << 16)
-                                                 : m | (q << 16);
+                    N.re[lo + j] = (m & 0x8000u) ? (nKeep + (m & 0x7FFFu) + (uint32_t)__builtin_popcount(kme & ((1u << q) - 1u))) | (2u << RS)
+                                                 : m | (q << RS);
                 }
             }
             else
@@ -226,7 +245,7 @@ __device__ inline int small_clip(const SolidIn in, const uint32_t F, const Share
                 uint32_t t = L.mp[v] & 0x7FFFu;
                 for (uint32_t mask = L.km[v]; mask; mask &= mask - 1u, ++t)
                 {
-                    const uint32_t rw = S.re[lo0 + (uint32_t)__builtin_ctz(mask)], u = rw & 0xFFFFu;
+                    const uint32_t rw = S.re[lo0 + (uint32_t)__builtin_ctz(mask)], u = rw & RM;
                     const float bx = S.pos[3 * u], by = S.pos[3 * u + 1], bz = S.pos[3 * u + 2];
                     const float sb = plane_dist(pl, bx, by, bz);
                     // PlaneLineIntersection (:746-751): (a*sb - b*sa) * (1/(sb-sa))
@@ -235,9 +254,9 @@ __device__ inline int small_clip(const SolidIn in, const uint32_t F, const Share
                     N.pos[3 * id] = (ax * sb - bx * sa) * inv;
                     N.pos[3 * id + 1] = (ay * sb - by * sa) * inv;
                     N.pos[3 * id + 2] = (az * sb - bz * sa) * inv;
-                    N.vw[id] = lo | (3u << 16);
-                    N.re[lo] = (nKeep + L.pred[t]) | (1u << 16); N.re[lo + 1] = (nKeep + L.succ[t]) | (0u << 16);
-                    N.re[lo + 2] = (uint32_t)L.mp[u] | (rw & 0xFFFF0000u);      // (the kept end lists this vertex where it listed v)
+                    N.vw[id] = lo | (3u << VS);
+                    N.re[lo] = (nKeep + L.pred[t]) | (1u << RS); N.re[lo + 1] = (nKeep + L.succ[t]) | (0u << RS);
+                    N.re[lo + 2] = (uint32_t)L.mp[u] | (rw & ~RM);      // (the kept end lists this vertex where it listed v)
                 }
             }
         }
@@ -259,14 +278,16 @@ __device__ inline int small_clip(const SolidIn in, const uint32_t F, const Share
 
 // The solid small_clip stopped with, as an input of the general clipper: positions and rings into global staging arrays
 // (`ring` is indexed by the offsets written to `loff`).  One wave; ends with a barrier.
-__device__ inline SolidIn sc_stage(const ScSolid& S, uint32_t nv, float* pos, uint32_t* loff, uint32_t* llen, uint32_t* ring)
+template <class SOLID>
+__device__ inline SolidIn sc_stage(const SOLID& S, uint32_t nv, float* pos, uint32_t* loff, uint32_t* llen, uint32_t* ring)
 {
+    constexpr uint32_t VS = SOLID::kVwSh, VM = (1u << VS) - 1u, RM = (1u << SOLID::kReSh) - 1u;
     for (uint32_t v = lane_id(); v < nv; v += SURTR_LANES)
     {
         pos[3 * v] = S.pos[3 * v]; pos[3 * v + 1] = S.pos[3 * v + 1]; pos[3 * v + 2] = S.pos[3 * v + 2];
-        const uint32_t w = S.vw[v], lo = w & 0xFFFFu, len = w >> 16;
+        const uint32_t w = S.vw[v], lo = w & VM, len = w >> VS;
         loff[v] = lo; llen[v] = len;
-        for (uint32_t q = 0; q < len; ++q) ring[lo + q] = S.re[lo + q] & 0xFFFFu;
+        for (uint32_t q = 0; q < len; ++q) ring[lo + q] = S.re[lo + q] & RM;
     }
     __threadfence_block();
     __syncthreads();
@@ -274,11 +295,13 @@ __device__ inline SolidIn sc_stage(const ScSolid& S, uint32_t nv, float* pos, ui
 }
 
 // Writes the result of small_clip to the arena as one packed solid (the layout park_topo writes).  One wave.
-__device__ inline int sc_park(const ScSolid& S, uint32_t nv, Shared& sh, uint32_t* cursors, float* apos, uint32_t* aloff, uint32_t* allen, int32_t* anbr,
+template <class SOLID, class SH>
+__device__ inline int sc_park(const SOLID& S, uint32_t nv, SH& sh, uint32_t* cursors, float* apos, uint32_t* aloff, uint32_t* allen, int32_t* anbr,
                               uint32_t capV, uint32_t capH, uint32_t& voff, uint32_t& n, uint32_t& hoff, uint32_t& nh)
 {
+    constexpr uint32_t VS = SOLID::kVwSh, VM = (1u << VS) - 1u, RM = (1u << SOLID::kReSh) - 1u;
     const uint32_t wl = S.vw[nv - 1u];
-    const uint32_t H = (wl & 0xFFFFu) + (wl >> 16);
+    const uint32_t H = (wl & VM) + (wl >> VS);
     __syncthreads();
     if (threadIdx.x == 0) { sh.misc[0] = atomicAdd(&cursors[CUR_V], nv); sh.misc[1] = atomicAdd(&cursors[CUR_H], H); }
     __syncthreads();
@@ -290,10 +313,10 @@ __device__ inline int sc_park(const ScSolid& S, uint32_t nv, Shared& sh, uint32_
         const size_t id = (size_t)voff + v;
         apos[3 * id] = S.pos[3 * v]; apos[3 * id + 1] = S.pos[3 * v + 1]; apos[3 * id + 2] = S.pos[3 * v + 2];
         const uint32_t w = S.vw[v];
-        const uint32_t lo = hoff + (w & 0xFFFFu), len = w >> 16;
+        const uint32_t lo = hoff + (w & VM), len = w >> VS;
         aloff[id] = lo; allen[id] = len;
-        const uint32_t* r = S.re + (w & 0xFFFFu);
-        for (uint32_t q = 0; q < len; ++q) anbr[lo + q] = (int32_t)(r[q] & 0xFFFFu);
+        const typename SOLID::Word* r = S.re + (w & VM);
+        for (uint32_t q = 0; q < len; ++q) anbr[lo + q] = (int32_t)(r[q] & RM);
     }
     n = nv; nh = H;
     __syncthreads();

@@ -116,6 +116,7 @@ enum : uint32_t
     CUR_BIG_QUOTA = 84,     // W/R: k_prep_pairs*, large bands admitted to k_clip_pairs_big so far
     CUR_FACES2_N = 85,      // second-tier faces list, fragments pushed.  W: k_faces first tier; R: second tier.  Cleared by launch_faces
     CUR_Q_FACES2 = 86,      // ... its ticket (directly behind CUR_FACES2_N: launch_faces clears both with one fill)
+    CUR_CVX_GAVE_UP = 87,   // give-up list of k_clip_convex_lean, pairs pushed.  W: the lean kernel; R: k_clip_convex as its second tier
     // diagnostics (W: as said; R: surtr_queue_stats)
     CUR_REC_TOOK = 88,      // clip_pairs_wave_body: pairs the record clipper finished
     CUR_REC_HANDED = 89,    // ... handed on to the general clipper
@@ -126,6 +127,7 @@ enum : uint32_t
     CUR_CATCH_CLIPPED = 94, // k_clip_pairs_catch: pairs it clipped
     CUR_UNREFITTED = 95,    // k_refit_n: fragments left un-refitted and flagged SURTR_E_CAPACITY
     CUR_WC_WHY = 96,        // base of the record clipper's why[site] block (wave_clip.h: WC_WHY_WORDS words)
+    CUR_Q_CONVEX2 = 125,    // ticket of k_clip_convex as second tier, over the give-up list
     CUR_STATS_WORDS = 128,  // what surtr_queue_stats copies out (and surtr_load_fragments writes)
     // hand-over from k_clip_pairs_main to k_clip_pairs_catch (surtr_handover_stats copies the CUR_HO_WORDS words out)
     CUR_HO_PUSHED = 146,    // W: main, one per pair pushed to hlist; R: polling catcher, sweep
@@ -283,7 +285,7 @@ struct surtr_ctx
     bool frags_of_pieces = false;      // the current fragments are an event's over the resident pieces (k_refit may look at the piece a Convex came from)
     // what the CUs can hold (surtr_create); max_wg* below are those, cut down to what the scratch of the current pieces leaves room for
     uint32_t hw_wg = 512, hw_wg_faces = 1024, hw_wg_prep = 1792, hw_wg_big = 48, budget_vmax = 0xFFFFFFFFu, budget_hmax = 0xFFFFFFFFu;
-    uint32_t max_wg = 512, max_wg_faces = 1024, max_wg_small = 2048, max_wg_prep = 1792, max_wg_half = 1024;
+    uint32_t max_wg = 512, max_wg_faces = 1024, max_wg_small = 2048, max_wg_lean = 3072, max_wg_prep = 1792, max_wg_half = 1024;
     DevBuf<uint32_t> d_hlist;                               // hand-over list of the split arrangement (k_clip_pairs_main -> k_clip_pairs_catch)
     uint32_t vmin = 0;                                      // smallest Mesh of the resident pieces
     ScratchPool pool_half{}; uint32_t n_wg_half = 0; DevBuf<char> pool_half_buf;     // k_clip_pairs_half: scratch for the half-size LDS topology only
@@ -333,6 +335,7 @@ struct surtr_ctx
     uint64_t tot_mv = 0, tot_mh = 0;
     // cells
     uint32_t n_cells = 0, n_faces = 0;
+    DevBuf<uint32_t> d_cvx_giveup;      // k_clip_convex_lean: the pairs it left to k_clip_convex (one word per pair of the event)
     DevBuf<uint32_t> d_pair_order; uint32_t pair_order_begin = 0, pair_order_count = 0;   // k_clip_convex: pairs by plane count
     bool pair_order_is_list = false;
     DevBuf<float> d_v012; DevBuf<float4> d_planes; DevBuf<uint32_t> d_plane_off;

@@ -774,12 +774,75 @@ __device__ __forceinline__ ParkOut convex_chain(const SolidIn cin, const uint32_
 #ifndef SURTR_SMALL_WAVES
 #define SURTR_SMALL_WAVES 2
 #endif
+// What the two Convex kernels do with a pair once its Convex is clipped and parked.
+// The pair's record: whole, or beside a running pre-pass (front_par) everything but the img_* words, which k_prep_pairs writes.
+__device__ __forceinline__ static void convex_publish(PairRec* __restrict__ pairs, uint32_t p, const PairRec& rec, uint32_t front_par)
+{
+    if (threadIdx.x != 0) return;
+    if (!front_par) pairs[p] = rec;
+    else
+    {
+        PairRec& o = pairs[p];
+        o.cv_off = rec.cv_off; o.cv_n = rec.cv_n; o.ch_off = rec.ch_off; o.ch_n = rec.ch_n;
+        o.mv_off = 0; o.mv_n = 0; o.mh_off = 0; o.mh_n = 0; o.ni = 0; o.isl_off = 0; o.status = rec.status; o.cv_bad = rec.cv_bad;
+    }
+}
+// Cost class of the Mesh pre-pass of a pair whose Convex survived, so that k_prep_pairs can start with the expensive ones: the
+// sphere test of its pass A0 on every eighth group of the piece's sorted vertices.  planes: the cell's F planes in LDS; pmar: F
+// words of LDS for their margins.  An estimate only: it orders work, it decides nothing.  One wave; starts with a barrier.
+__device__ __forceinline__ static void convex_enqueue_prep(const Pieces& P, uint32_t piece, uint32_t p, uint32_t F, const float4* planes, float4* pmar,
+                                                           const Arena& A, uint32_t* __restrict__ porder, uint32_t n_pairs)
+{
+    const uint32_t tid = threadIdx.x;
+    const uint32_t m0 = P.mvo[piece], V = P.mvo[piece + 1] - m0;
+    const float4* bs = P.mbsph + P.mbo[piece];
+    const uint32_t nsb = (V + SURTR_SB - 1u) / SURTR_SB;
+    __syncthreads();
+    for (uint32_t k = tid; k < F; k += group_size())      // the margins of prepass_select (the Convex itself was loaded whole)
+    {
+        const float4 pk = planes[k];
+        const float n1 = fabsf(pk.x) + fabsf(pk.y) + fabsf(pk.z);
+        const float n2 = sqrtf(pk.x * pk.x + pk.y * pk.y + pk.z * pk.z) * 1.0001f;
+        pmar[k] = make_float4(n2 * 1.00101f, 1.0e-5f * fabsf(pk.w), 1.0e-5f * n1, 0.f);
+    }
+    __syncthreads();
+    uint32_t und = 0;
+    for (uint32_t sb = tid * 8u; sb < nsb; sb += group_size() * 8u)
+    {
+        const float4 sp = bs[sb];
+        const float mag = fabsf(sp.x) + fabsf(sp.y) + fabsf(sp.z) + sp.w;
+        bool decided = false;
+        for (uint32_t k = 0; k < F; ++k)
+        {
+            const float4 mk = pmar[k];
+            const float sk = plane_dist(planes[k], sp.x, sp.y, sp.z);
+            const float margin = sp.w * mk.x + mk.y + mk.z * mag;
+            if (sk > margin) { decided = true; break; }
+            if (!(sk < -margin)) break;
+        }
+        if (!decided) ++und;
+    }
+    const uint2 tot = wave_incl_scan2(make_uint2(und, 0u));
+    if (tid == group_size() - 1u)
+    {
+        // half-octave classes of the sampled count (1 .. ~V/64)
+        uint32_t l2 = 0; while ((tot.x >> (l2 + 1u)) != 0u) ++l2;
+        uint32_t cls = 2u * l2 + (l2 ? ((tot.x >> (l2 - 1u)) & 1u) : 0u);
+        cls = cls > 4u ? cls - 4u : 0u; if (cls > 15u) cls = 15u;
+        porder[(size_t)cls * n_pairs + atomicAdd(&A.cursors[CUR_CLS_PREP + cls], 1u)] = p;
+    }
+}
+
+// giveup != nullptr: the launch behind k_clip_convex_lean (its second tier).  The pairs are those of the lean kernel's give-up list,
+// taken by a ticket against the list's count and restarted from the piece's Convex with all planes; an empty list costs every
+// workgroup one counter read.
 __global__ __launch_bounds__(SURTR_LANES) __attribute__((amdgpu_waves_per_eu(SURTR_SMALL_WAVES, 8))) void k_clip_convex(Pieces P, const float4* __restrict__ planes,
                                                     const uint32_t* __restrict__ plane_off, uint32_t cell_begin,
                                                     uint32_t n_pairs, const uint8_t* __restrict__ outside,
                                                     ScratchPool pool, Arena A, PairRec* __restrict__ pairs,
                                                     const uint2* __restrict__ pair_list, uint32_t* __restrict__ porder,
-                                                    const uint32_t* __restrict__ pair_order, uint32_t front_par)
+                                                    const uint32_t* __restrict__ pair_order, uint32_t front_par,
+                                                    const uint32_t* __restrict__ giveup)
 {
     __shared__ Shared sh;
     __shared__ OneWaveLds U;
@@ -789,13 +852,21 @@ __global__ __launch_bounds__(SURTR_LANES) __attribute__((amdgpu_waves_per_eu(SUR
     while (true)
     {
         __syncthreads();
-        if (tid == 0) sh.misc[7] = atomicAdd(&A.cursors[CUR_Q_CONVEX], 1u);
+        if (tid == 0)
+        {
+            if (giveup == nullptr) sh.misc[7] = atomicAdd(&A.cursors[CUR_Q_CONVEX], 1u);
+            else
+            {
+                const uint32_t t = atomicAdd(&A.cursors[CUR_Q_CONVEX2], 1u);
+                sh.misc[7] = t < A.cursors[CUR_CVX_GAVE_UP] ? giveup[t] : 0xFFFFFFFFu;
+            }
+        }
         __syncthreads();
         uint32_t p = sh.misc[7];
         if (p >= n_pairs) break;
         // pairs of cells with many planes first (pair_order: the event's pairs by plane count of their cell, descending): the
         // clip of a Convex costs about one step per plane, and the last tasks of the queue set the length of the kernel
-        if (pair_order != nullptr) p = pair_order[p];
+        if (giveup == nullptr && pair_order != nullptr) p = pair_order[p];
         const PairAt at = pair_where(p, pair_list, cell_begin, P.n);
         const uint32_t cell = at.cell, piece = at.piece;
         PairRec rec;
@@ -824,60 +895,9 @@ __global__ __launch_bounds__(SURTR_LANES) __attribute__((amdgpu_waves_per_eu(SUR
         }
         if (err == SURTR_E_TOPOLOGY) { rec.cv_bad = 1; rec.cv_off = 0; rec.cv_n = 1; rec.ch_off = 0; rec.ch_n = 0; err = 0; }
         if (err != 0) { rec.status = (uint32_t)err; rec.cv_n = 0; if (tid == 0) atomicMax(&A.cursors[CUR_STATUS], (uint32_t)err); }
-        if (tid == 0)
-        {
-            if (!front_par) pairs[p] = rec;
-            else
-            {
-                // k_prep_pairs runs beside this kernel and writes the img_* words of the same record: everything but those
-                PairRec& o = pairs[p];
-                o.cv_off = rec.cv_off; o.cv_n = rec.cv_n; o.ch_off = rec.ch_off; o.ch_n = rec.ch_n;
-                o.mv_off = 0; o.mv_n = 0; o.mh_off = 0; o.mh_n = 0; o.ni = 0; o.isl_off = 0; o.status = rec.status; o.cv_bad = rec.cv_bad;
-            }
-        }
-        if (rec.cv_n != 0 && porder != nullptr)
-        {
-            // Cost class of the Mesh pre-pass of this pair, so that k_prep_pairs can start with the expensive ones: the
-            // sphere test of its pass A0 on every eighth group of the piece's sorted vertices (sh.planes / sh.pmar still
-            // hold this cell's planes and margins).  An estimate only: it orders work, it decides nothing.
-            const uint32_t m0 = P.mvo[piece], V = P.mvo[piece + 1] - m0;
-            const float4* bs = P.mbsph + P.mbo[piece];
-            const uint32_t nsb = (V + SURTR_SB - 1u) / SURTR_SB;
-            __syncthreads();
-            for (uint32_t k = tid; k < F; k += group_size())      // the margins of prepass_select (the Convex itself was loaded whole)
-            {
-                const float4 pk = sh.planes[k];
-                const float n1 = fabsf(pk.x) + fabsf(pk.y) + fabsf(pk.z);
-                const float n2 = sqrtf(pk.x * pk.x + pk.y * pk.y + pk.z * pk.z) * 1.0001f;
-                sh.pmar[k] = make_float4(n2 * 1.00101f, 1.0e-5f * fabsf(pk.w), 1.0e-5f * n1, 0.f);
-            }
-            __syncthreads();
-            uint32_t und = 0;
-            for (uint32_t sb = tid * 8u; sb < nsb; sb += group_size() * 8u)
-            {
-                const float4 sp = bs[sb];
-                const float mag = fabsf(sp.x) + fabsf(sp.y) + fabsf(sp.z) + sp.w;
-                bool decided = false;
-                for (uint32_t k = 0; k < F; ++k)
-                {
-                    const float4 mk = sh.pmar[k];
-                    const float sk = plane_dist(sh.planes[k], sp.x, sp.y, sp.z);
-                    const float margin = sp.w * mk.x + mk.y + mk.z * mag;
-                    if (sk > margin) { decided = true; break; }
-                    if (!(sk < -margin)) break;
-                }
-                if (!decided) ++und;
-            }
-            const uint2 tot = wave_incl_scan2(make_uint2(und, 0u));
-            if (tid == group_size() - 1u)
-            {
-                // half-octave classes of the sampled count (1 .. ~V/64)
-                uint32_t l2 = 0; while ((tot.x >> (l2 + 1u)) != 0u) ++l2;
-                uint32_t cls = 2u * l2 + (l2 ? ((tot.x >> (l2 - 1u)) & 1u) : 0u);
-                cls = cls > 4u ? cls - 4u : 0u; if (cls > 15u) cls = 15u;
-                porder[(size_t)cls * n_pairs + atomicAdd(&A.cursors[CUR_CLS_PREP + cls], 1u)] = p;
-            }
-        }
+        convex_publish(pairs, p, rec, front_par);
+        // (sh.planes still holds this cell's planes; pmar is free while a Convex is clipped)
+        if (rec.cv_n != 0 && porder != nullptr) convex_enqueue_prep(P, piece, p, F, sh.planes, sh.pmar, A, porder, n_pairs);
 #ifdef SURTR_STAMP_SMALL
         if (tid == 0) for (int q = 0; q < 16; ++q) if (sh.ph[q]) atomicAdd(&g_stamp[q], sh.ph[q]);
 #endif
@@ -896,6 +916,101 @@ __global__ __launch_bounds__(SURTR_LANES) __attribute__((amdgpu_waves_per_eu(SUR
             }
         }
 #endif
+    }
+}
+
+// ------------------------------------------------------- k_clip_convex_lean
+// The same pairs, records and queue as k_clip_convex with the first clipper of its chain alone: small_clip, parked by sc_park.  The
+// three other clippers of convex_chain cost k_clip_convex its registers, its private scratch and a scratch slot per workgroup, and
+// hold it at two waves per SIMD; the Convexes of an event seldom enter them.  Without them, and with an LDS solid sized for it, this
+// kernel runs SURTR_LEAN_WAVES waves per SIMD.  A pair it cannot finish -- a Convex whose ring lists a neighbour twice (cdup: literal
+// first), one beyond the LDS solid, a plane small_clip does not take, a park that fails -- goes to the give-up list and is
+// k_clip_convex's (launched right behind this kernel): nothing of it is published here, no record, no porder entry.
+// Measured at configs[3] (profiles/convex_lean_bench.txt): per launch, both tiers, 252 / 260 / 229 us at 2 / 3 / 4 against k_clip_convex's
+// 245 -- the tasks slow down as more of them share a SIMD, so occupancy buys little -- but with six events in flight 2 and 3 take
+// 0.15 ms off a step and 4 none: at 2 the grid leaves a fifth of every CU's LDS and most of its registers to the other events' kernels.
+#ifndef SURTR_LEAN_WAVES
+#define SURTR_LEAN_WAVES 2
+#endif
+// The LDS solid per occupancy (with LeanShared, against a CU's 160 KiB; the kernel needs ~50 VGPRs, so the LDS alone decides):
+//   2 waves per SIMD   small_clip's own solid, 32-bit ring words              15 472 B (the register budget asked for is two waves)
+//   3                  the same capacities with 16-bit ring words             12 144 B: twelve workgroups per CU
+//   4                  156 vertices / 480 ring entries, 16-bit ring words     10 096 B: sixteen
+#ifndef SURTR_LEAN_V
+#if SURTR_LEAN_WAVES <= 2
+#define SURTR_LEAN_V SC_V
+#define SURTR_LEAN_H SC_H
+#define SURTR_LEAN_WORD uint32_t
+#elif SURTR_LEAN_WAVES == 3
+#define SURTR_LEAN_V SC_V
+#define SURTR_LEAN_H SC_H
+#define SURTR_LEAN_WORD uint16_t
+#else
+#define SURTR_LEAN_V 156u
+#define SURTR_LEAN_H 480u
+#define SURTR_LEAN_WORD uint16_t
+#endif
+#endif
+struct LeanShared { float4 planes[SURTR_MAXF + 1]; uint32_t misc[8]; };
+typedef ScLdsT<SURTR_LEAN_V, SURTR_LEAN_H, SURTR_LEAN_WORD> LeanSolidLds;
+// (the margins of the cost estimate take the bytes of the solid, which is parked by then)
+union alignas(16) LeanLds { LeanSolidLds f; float4 pmar[SURTR_MAXF + 1]; };
+#if SURTR_LANES != 1
+static_assert((sizeof(LeanShared) + sizeof(LeanLds)) * 4u * SURTR_LEAN_WAVES <= 160u * 1024u, "LDS admits fewer workgroups per CU than the register budget");
+#endif
+__global__ __launch_bounds__(SURTR_LANES) __attribute__((amdgpu_waves_per_eu(SURTR_LEAN_WAVES, 8))) void k_clip_convex_lean(Pieces P, const float4* __restrict__ planes,
+                                                    const uint32_t* __restrict__ plane_off, uint32_t cell_begin,
+                                                    uint32_t n_pairs, const uint8_t* __restrict__ outside,
+                                                    Arena A, PairRec* __restrict__ pairs,
+                                                    const uint2* __restrict__ pair_list, uint32_t* __restrict__ porder,
+                                                    const uint32_t* __restrict__ pair_order, uint32_t front_par,
+                                                    uint32_t* __restrict__ giveup)
+{
+    __shared__ LeanShared sh;
+    __shared__ LeanLds U;
+    const uint32_t tid = threadIdx.x;
+    while (true)
+    {
+        __syncthreads();
+        if (tid == 0) sh.misc[7] = atomicAdd(&A.cursors[CUR_Q_CONVEX], 1u);
+        __syncthreads();
+        uint32_t p = sh.misc[7];
+        if (p >= n_pairs) break;
+        if (pair_order != nullptr) p = pair_order[p];      // (cells of many planes first, see k_clip_convex)
+        const PairAt at = pair_where(p, pair_list, cell_begin, P.n);
+        const uint32_t cell = at.cell, piece = at.piece;
+        PairRec rec;
+        memset(&rec, 0, sizeof(rec));
+        bool skip = outside != nullptr && outside[piece] != 0;
+        const uint32_t f0 = plane_off[cell], F = plane_off[cell + 1] - f0;
+        if (F > SURTR_MAXF) { rec.status = SURTR_E_INVALID; skip = true; }
+        if (!skip)
+        {
+            int err = SC_FALLBACK;
+            uint32_t voff = 0, n = 0, hoff = 0, nh = 0;
+            if (P.cdup[piece] == 0)
+            {
+                for (uint32_t k = tid; k < F; k += group_size()) sh.planes[k] = planes[f0 + k];
+                __syncthreads();
+                uint32_t which = 0;
+                err = small_clip(convex_solid_in(P, piece), F, sh, U.f, &which);
+                if (err == 0)
+                {
+                    const uint32_t nv = U.f.nv[which];
+                    if (nv != 0u) err = sc_park(U.f.buf[which], nv, sh, A.cursors, A.pos, A.loff, A.llen, A.nbr, A.capV, A.capH, voff, n, hoff, nh);
+                }
+                __syncthreads();
+            }
+            if (err != 0)      // (uniform over the wave)
+            {
+                if (tid == 0) giveup[atomicAdd(&A.cursors[CUR_CVX_GAVE_UP], 1u)] = p;
+                continue;
+            }
+            if (tid == 0) atomicAdd(&A.cursors[CUR_CVX_TOOK], 1u);
+            rec.cv_off = voff; rec.cv_n = n; rec.ch_off = hoff; rec.ch_n = nh;
+        }
+        convex_publish(pairs, p, rec, front_par);
+        if (rec.cv_n != 0 && porder != nullptr) convex_enqueue_prep(P, piece, p, F, sh.planes, U.pmar, A, porder, n_pairs);
     }
 }
 
@@ -3202,6 +3317,7 @@ int surtr_create(int device, surtr_ctx** out)
             uint32_t small_per_cu = 8u;
             if (const char* e = getenv("SURTR_SMALL_PER_CU")) { const int v = atoi(e); if (v > 0 && v <= 32) small_per_cu = (uint32_t)v; }
             ctx->max_wg_small = (uint32_t)prop.multiProcessorCount * small_per_cu;
+            ctx->max_wg_lean = (uint32_t)prop.multiProcessorCount * 4u * SURTR_LEAN_WAVES;      // one wave a workgroup, four SIMDs a CU
             uint32_t prep_per_cu = SURTR_PREP_WAVES;
             if (const char* e = getenv("SURTR_PREP_PER_CU")) { const int v = atoi(e); if (v > 0 && v <= 32) prep_per_cu = (uint32_t)v; }
             ctx->max_wg_prep = (uint32_t)prop.multiProcessorCount * prep_per_cu;
@@ -3544,7 +3660,8 @@ static int ensure_arena(surtr_ctx* ctx, uint32_t n_pairs, uint64_t min_v = 0, ui
         ctx->arena = Arena{B.pos, B.loff, B.llen, B.nbr, B.idx, B.isl, (uint32_t)av, (uint32_t)ah, (uint32_t)ai, capIsl, B.cursors};
         ctx->cap_frags = capIsl;
     }
-    const int rc = ctx->d_pairs.grow(ctx, n_pairs);
+    int rc = ctx->d_pairs.grow(ctx, n_pairs);
+    if (rc == SURTR_OK) rc = ctx->d_cvx_giveup.grow(ctx, n_pairs);
     if (rc) return rc;
     return ctx->d_scanblk.grow(ctx, std::max(n_pairs, ctx->cap_frags) / SURTR_LANES + 4);
 }
@@ -3584,9 +3701,10 @@ struct EventPlan
     decltype(&k_prep_pairs) prep;         // the pre-pass kernel (k_prep_pairs, _sorted or _wide; nullptr: no pairs)
     uint32_t prep_threads;
     bool wave_on, split_on, use_half, front_par, both;
+    bool cvx_lean;                        // the Convexes on k_clip_convex_lean, with k_clip_convex as its second tier behind it
     uint32_t rec_on;                      // k_prep_pairs' mode word: 1 record images, 2 round 3's selection, 4 front_par, rec_maxn << 8
     uint32_t big_quota, big_n, walk0, n_catch, n_poll;
-    uint32_t n_wg, n_wg_cvx, n_wg_prep, n_wg_big, n_wg_half, n_wg_retry, n_wg_sweep;      // grids
+    uint32_t n_wg, n_wg_cvx, n_wg_lean, n_wg_cvx2, n_wg_prep, n_wg_big, n_wg_half, n_wg_retry, n_wg_sweep;      // grids
     uint32_t g_refit, g_faces, t_faces;
     hipStream_t st_cvx, st_main, st_bigk, st_refit;
 };
@@ -3600,6 +3718,8 @@ static EventPlan plan_event(const surtr_ctx* ctx, uint32_t n_pairs, bool pair_li
     pl.cell_order = !pair_list && n_pairs && ctx->n_pieces && n_pairs % ctx->n_pieces == 0 && !getenv("SURTR_NO_CELL_ORDER");
     pl.n_wg = std::max(1u, std::min(n1, max_wg));
     pl.n_wg_cvx = std::max(1u, std::min(n1, ctx->max_wg_small));
+    pl.n_wg_lean = std::max(1u, std::min(n1, ctx->max_wg_lean));
+    pl.n_wg_cvx2 = std::min(n1, 64u);      // (what the lean kernel gives up on is rare: a grid that costs nothing when its list is empty)
     pl.n_wg_half = std::max(1u, std::min(n1, ctx->max_wg_half));
     pl.n_wg_prep = std::max(1u, std::min(n1, ctx->max_wg_prep));
     pl.n_wg_big = std::min(ctx->n_wg_big, n1);
@@ -3669,6 +3789,11 @@ static EventPlan plan_event(const surtr_ctx* ctx, uint32_t n_pairs, bool pair_li
     pl.front_par = n_pairs != 0 && n_pairs <= SURTR_FRONT_PAR_MAX && !prep_wide;
     if (const char* e = getenv("SURTR_FRONT_PAR")) pl.front_par = n_pairs != 0 && atoi(e) != 0;
     if (pl.front_par) pl.rec_on |= 4u;
+    // The lean Convex kernel where the pairs outnumber k_clip_convex's workgroups: there the Convex clip runs in rounds of latency-bound
+    // one-wave tasks, and the lean kernel's higher occupancy shortens them.  An event whose every pair finds a workgroup at once gains
+    // nothing from it and would pay the second tier's launch.
+    pl.cvx_lean = n_pairs > ctx->max_wg_small;
+    if (const char* e = getenv("SURTR_CVX_LEAN")) pl.cvx_lean = n_pairs != 0 && atoi(e) != 0;      // (tests / A-B)
     pl.prep = nullptr; pl.prep_threads = SURTR_WG;
     if (n_pairs && prep_wide) { pl.prep = k_prep_pairs_wide; pl.prep_threads = SURTR_WG_WIDE; }
     else if (n_pairs && !(pl.rec_on & 2u) && ctx->vmax < 0xFFFFu && ctx->vmin >= SURTR_PREP_MINV && (ctx->vmax + SURTR_LANES - 1u) / SURTR_LANES <= SURTR_PREP_NB)
@@ -3795,10 +3920,20 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
         HIPCHK(hipStreamWaitEvent(pl.st_cvx, ctx->ev_prep, 0));
     }
     PROF_BEGIN_ON(6, pl.st_cvx);
-    if (n_pairs)
+    if (n_pairs && pl.cvx_lean)
+    {
+        // (both tiers in order on one stream: the pre-pass and the clip kernels wait for the second as they waited for the one kernel)
+        uint32_t* const cvx_porder = pl.front_par ? (uint32_t*)nullptr : porder;
+        hipLaunchKernelGGL(k_clip_convex_lean, dim3(pl.n_wg_lean), dim3(SURTR_LANES), 0, pl.st_cvx, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
+                           d_out, ctx->arena, ctx->d_pairs, d_pair_list, cvx_porder, d_pair_order, pl.front_par ? 1u : 0u, (uint32_t*)ctx->d_cvx_giveup);
+        hipLaunchKernelGGL(k_clip_convex, dim3(pl.n_wg_cvx2), dim3(SURTR_LANES), 0, pl.st_cvx, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
+                           d_out, ctx->pool_small, ctx->arena, ctx->d_pairs, d_pair_list, cvx_porder, (const uint32_t*)nullptr,
+                           pl.front_par ? 1u : 0u, (const uint32_t*)ctx->d_cvx_giveup);
+    }
+    else if (n_pairs)
         hipLaunchKernelGGL(k_clip_convex, dim3(pl.n_wg_cvx), dim3(SURTR_LANES), 0, pl.st_cvx, P, ctx->d_planes, ctx->d_plane_off, cell_begin, n_pairs,
                            d_out, ctx->pool_small, ctx->arena, ctx->d_pairs, d_pair_list, pl.front_par ? (uint32_t*)nullptr : porder, d_pair_order,
-                           pl.front_par ? 1u : 0u);
+                           pl.front_par ? 1u : 0u, (const uint32_t*)nullptr);
     PROF_END_ON(6, pl.st_cvx);
     if (pl.front_par) HIPCHK(hipEventRecord(ctx->ev_cvx, pl.st_cvx));
     PROF_BEGIN(7);
