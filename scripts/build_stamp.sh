@@ -3,6 +3,7 @@
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p build_tmp
+# every .hip and .cpp directly under csrc is a translation unit of the library (tests/test_source_list.py holds the build to that)
 S=surtr_amd/csrc
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -std=c++17 -fPIC -shared -DSURTR_STAMP "$@" -o build_tmp/libsurtr_hip_stamp.so \
-    $S/surtr_hip.hip $S/pieces_dev.hip $S/cells_dev.hip $S/mesh_dev.hip $S/regroup_dev.hip $S/host_geom.cpp $S/host_regroup.cpp
+    $S/*.hip $S/*.cpp

@@ -1,5 +1,11 @@
-import numpy as np
+import os
+import subprocess
+import sys
 
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOPOLOGY_KEYS = ("frag_ids", "mesh_vert_off", "mesh_nbr_off", "mesh_nbr", "conv_vert_off", "conv_nbr_off", "conv_nbr",
                  "idx_off", "idx")
 COORD_KEYS = ("mesh_pos", "conv_pos", "vnc")
@@ -35,6 +41,20 @@ def run_event(engine_mod, oracle, sc, flags=3, cells=None, threads=4):
     ref = oracle.event([sc["mesh"]], [sc["convex"]], sc["face_off"], planes, refit=bool(flags & 1), render=bool(flags & 2),
                        threads=threads, cell_end=n)
     return c, got, ref
+
+
+def run_gpu_child(template, case, seconds):
+    """One case of a module's GPU tier in a child process of its own, under a time limit: template is the child's program with
+    %(root)r and %(tests)r for the two import paths, and it prints "ok <case>" when the case has passed."""
+    code = template % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}
+    try:
+        p = subprocess.run(["timeout", "-k", "10", str(seconds), sys.executable, "-c", code, case], cwd=ROOT, capture_output=True, text=True,
+                           timeout=seconds + 30)
+    except subprocess.TimeoutExpired:
+        pytest.fail("%s: no result within %d s" % (case, seconds))
+    print(p.stdout[-3000:])
+    assert p.returncode == 0, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
+    assert ("ok " + case) in p.stdout
 
 
 def fragment(ev, k, which="mesh"):

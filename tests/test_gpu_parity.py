@@ -16,6 +16,14 @@ HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 TOPO = ("frag_ids", "mesh_vert_off", "mesh_nbr_off", "mesh_nbr", "conv_vert_off", "conv_nbr_off", "conv_nbr", "idx_off", "idx")
 
 
+def host_program(name):
+    """A program of the C++ host layer (surtr_amd/host), brought up to date."""
+    import subprocess
+    host = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "surtr_amd", "host")
+    subprocess.check_call(["make", "-s", "-C", host])
+    return os.path.join(host, name)
+
+
 @pytest.fixture(scope="module")
 def torus_run():
     from surtr_amd import engine
@@ -199,9 +207,7 @@ def test_cpp_host_layer_and_harness(gpu_engine, oracle):
     """The C++ host layer (reference API names over the C ABI) through the headless harness binary."""
     import json as js
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(root, "surtr_amd", "host")])
-    exe = os.path.join(root, "surtr_amd", "host", "surtr_harness")
+    exe = host_program("surtr_harness")
     out = js.loads(subprocess.check_output([exe, "--mesh", "cube", "--cells", "8"]).decode().strip().splitlines()[-1])
     sc = scenes.cube_scene(8)
     planes = oracle.place_cells(sc["v012"], sc["scale"], sc["translate"])
@@ -398,9 +404,7 @@ def test_cpp_api_surface(gpu_engine, oracle):
     import json as js
     import subprocess
     import tempfile
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(root, "surtr_amd", "host")])
-    exe = os.path.join(root, "surtr_amd", "host", "surtr_harness")
+    exe = host_program("surtr_harness")
     with tempfile.TemporaryDirectory() as d:
         dump = os.path.join(d, "api.json")
         subprocess.check_output([exe, "--mesh", "torus", "--cells", "64", "--nu", "60", "--nv", "36", "--api-dump", dump])
@@ -605,9 +609,7 @@ def test_cpp_rccl_harness_single_rank(oracle):
     what one GPU can rehearse; the N-rank run forks one process per GPU (surtr_harness_mgpu --ranks N)."""
     import json as js
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.check_call(["make", "-s", "-C", os.path.join(root, "surtr_amd", "host")])
-    exe = os.path.join(root, "surtr_amd", "host", "surtr_harness_mgpu")
+    exe = host_program("surtr_harness_mgpu")
     out = js.loads(subprocess.check_output([exe, "--ranks", "1", "--cells", "256", "--nu", "100", "--nv", "60", "--steps", "2"], timeout=300).decode().strip().splitlines()[-1])
     sc = scenes.make_scene(*meshgen.bumpy_torus(100, 60), 256)
     v = sc["mesh"]["pos"]; lo, hi = v.min(0), v.max(0)

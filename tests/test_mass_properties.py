@@ -2,39 +2,18 @@
 (surtr_combine_mass), against a numpy float64 reference built from Engine.extract_faces: every face fanned around its lowest
 vertex, every term relative to the solid's vertex 0 (Poly::Moments' origin shift).
 
-The CPU tier builds its own emulation library (the product sources + mass_dev.hip, tests/emul stand-ins) into a temporary
-directory; the GPU tier runs the bench scene on the MI355X in child processes under a time limit."""
+The CPU tier runs on the one emulation library of tests/emul (conftest's emul_engine); the GPU tier runs the bench scene on the
+MI355X in child processes under a time limit (helpers.run_gpu_child)."""
 import ctypes
-import os
-import subprocess
-import sys
 import textwrap
 
 import numpy as np
 import pytest
 
+from helpers import run_gpu_child
 from surtr_amd import engine, scenes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "surtr_amd", "csrc")
-EMUL_SOURCES = ["surtr_hip.hip", "pieces_dev.hip", "cells_dev.hip", "mesh_dev.hip", "regroup_dev.hip", "mass_dev.hip",
-                "host_geom.cpp", "host_regroup.cpp"]
-# the flags of tests/emul/Makefile
-CXXFLAGS = ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-Wall", "-Wno-unused-function",
-            "-Wno-sign-compare", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 RHO = 10.0
-
-
-@pytest.fixture(scope="module")
-def mass_emul(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mass_emul") / "libsurtr_emul_mass.so")
-    cmd = [os.environ.get("CXX", "g++")] + CXXFLAGS + ["-I", os.path.join(ROOT, "tests", "emul"), "-shared", "-o", out, "-x", "c++"]
-    subprocess.check_call(cmd + [os.path.join(CSRC, f) for f in EMUL_SOURCES])
-    engine._use_library_for_tests(out)
-    try:
-        yield engine
-    finally:
-        engine._use_library_for_tests(None)
 
 
 # ------------------------------------------------------------------ numpy reference
@@ -147,11 +126,11 @@ ROT = np.array([[0.36, 0.48, -0.8], [-0.8, 0.6, 0.0], [0.48, 0.64, 0.6]])       
 
 
 # ------------------------------------------------------------------ CPU tier (emulation)
-def test_known_answers(mass_emul):
+def test_known_answers(emul_engine):
     box = scenes.box_solid((1, 1, 1), (0, 0, 0), factor=1.0)
     rot = dict(box, pos=(box["pos"].astype(np.float64) @ ROT.T).astype(np.float32))
     tet = regular_tetrahedron()
-    eng = mass_emul.Engine(0)
+    eng = emul_engine.Engine(0)
     eng.load_fragments([box, rot, tet], [box, rot, tet])
     for s in (0, 1):
         rec = eng.event_mass(set=s, density=RHO)
@@ -171,9 +150,9 @@ def test_known_answers(mass_emul):
 
 
 @pytest.mark.parametrize("scene", ["cube", "torus"])
-def test_event_against_reference(mass_emul, scene):
+def test_event_against_reference(emul_engine, scene):
     sc = scenes.cube_scene(8) if scene == "cube" else scenes.torus_scene(24)
-    eng, ref = mass_emul.Engine(0), mass_emul.Engine(0)
+    eng, ref = emul_engine.Engine(0), emul_engine.Engine(0)
     ev = run_scene(eng, sc)
     recs = {s: eng.event_mass(set=s) for s in (0, 1)}
     for s, pre in ((0, "mesh"), (1, "conv")):
@@ -186,9 +165,9 @@ def test_event_against_reference(mass_emul, scene):
 
 
 @pytest.mark.parametrize("partial", [False, True])
-def test_compounds(mass_emul, partial):
+def test_compounds(emul_engine, partial):
     sc = scenes.cube_scene(8)
-    eng, ref = mass_emul.Engine(0), mass_emul.Engine(0)
+    eng, ref = emul_engine.Engine(0), emul_engine.Engine(0)
     eng.upload_pieces([sc["mesh"]], [sc["convex"]])
     eng.upload_pattern(sc["face_off"], sc["v012"])
     eng.place_cells(sc["scale"], sc["translate"])
@@ -227,9 +206,9 @@ def test_compounds(mass_emul, partial):
     eng.close(); ref.close()
 
 
-def test_resident_pieces(mass_emul):
+def test_resident_pieces(emul_engine):
     sc = scenes.cube_scene(8)
-    eng, ref = mass_emul.Engine(0), mass_emul.Engine(0)
+    eng, ref = emul_engine.Engine(0), emul_engine.Engine(0)
     with pytest.raises(engine.SurtrError) as e:
         eng.pieces_mass()
     assert e.value.code == engine.E_STATE
@@ -243,9 +222,9 @@ def test_resident_pieces(mass_emul):
     eng.close(); ref.close()
 
 
-def test_edge_cases(mass_emul):
-    eng = mass_emul.Engine(0)
-    L = mass_emul.lib()
+def test_edge_cases(emul_engine):
+    eng = emul_engine.Engine(0)
+    L = emul_engine.lib()
     # before any event
     with pytest.raises(engine.SurtrError) as e:
         eng.event_mass()
@@ -273,7 +252,7 @@ def test_edge_cases(mass_emul):
     eng.close()
 
 
-def test_long_faces(mass_emul):
+def test_long_faces(emul_engine):
     """A prism over a 300-gon: its two caps are far longer than the walk bound and go through pointer jumping."""
     n = 300
     t = np.arange(n) * (2 * np.pi / n)
@@ -290,7 +269,7 @@ def test_long_faces(mass_emul):
     if engine.moments(s)[0] < 0:
         s = engine.neighbors_from_mesh(pos, tris[:, ::-1].copy())
     capped = _drop_cap_diagonals(s, n)
-    eng, ref = mass_emul.Engine(0), mass_emul.Engine(0)
+    eng, ref = emul_engine.Engine(0), emul_engine.Engine(0)
     eng.load_fragments([capped], [capped])
     fo, _ = ref.extract_faces(capped)
     assert np.diff(fo).max() == n           # the caps are single faces
@@ -367,22 +346,11 @@ GPU_CHILD = textwrap.dedent("""
 """)
 
 
-def _run_gpu_child(case, seconds):
-    code = GPU_CHILD % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}
-    try:
-        p = subprocess.run([sys.executable, "-c", code, case], cwd=ROOT, capture_output=True, text=True, timeout=seconds)
-    except subprocess.TimeoutExpired:
-        pytest.fail("%s: no result within %d s" % (case, seconds))
-    print(p.stdout[-3000:])
-    assert p.returncode == 0, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
-    assert ("ok " + case) in p.stdout
-
-
 @pytest.mark.gpu
 def test_gpu_torus_event_and_pieces():
-    _run_gpu_child("torus", 900)
+    run_gpu_child(GPU_CHILD, "torus", 900)
 
 
 @pytest.mark.gpu
 def test_gpu_determinism_across_contexts():
-    _run_gpu_child("contexts", 300)
+    run_gpu_child(GPU_CHILD, "contexts", 300)

@@ -17,41 +17,23 @@ flagged solid that can be resident is a flat one (faces of zero normal).  The Co
 entry, and its clip has no valid answer: SURTR_E_TOPOLOGY); the sliver Convex whose rings do list a neighbour twice is the one of
 tests/golden/sliver_convex_walk_bound.npz, which is used.
 
-The CPU tier builds its own emulation library with query_dev.hip added; the GPU tier runs the same scenes on the MI355X in child
-processes under a time limit."""
+The CPU tier runs on the one emulation library of tests/emul (conftest's emul_engine); the GPU tier runs the same scenes on the
+MI355X in child processes under a time limit (helpers.run_gpu_child)."""
 import ctypes
 import json
 import os
 import subprocess
-import sys
 import textwrap
 
 import numpy as np
 import pytest
 
+from helpers import run_gpu_child
 from surtr_amd import engine, scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "surtr_amd", "csrc")
-EMUL_SOURCES = ["surtr_hip.hip", "pieces_dev.hip", "cells_dev.hip", "mesh_dev.hip", "regroup_dev.hip", "mass_dev.hip", "query_dev.hip",
-                "host_geom.cpp", "host_regroup.cpp"]
-# the flags of tests/emul/Makefile
-CXXFLAGS = ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-Wall", "-Wno-unused-function",
-            "-Wno-sign-compare", "-Wno-unused-variable", "-Wno-unused-but-set-variable", "-Wno-unknown-pragmas"]
 CAP = 0.05          # undecided rays / pairs
 ANGLE = 1e-3        # rad
-
-
-@pytest.fixture(scope="module")
-def pick_emul(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("pick_emul") / "libsurtr_emul_pick.so")
-    cmd = [os.environ.get("CXX", "g++")] + CXXFLAGS + ["-I", os.path.join(ROOT, "tests", "emul"), "-shared", "-o", out, "-x", "c++"]
-    subprocess.check_call(cmd + [os.path.join(CSRC, f) for f in EMUL_SOURCES])
-    engine._use_library_for_tests(out)
-    try:
-        yield engine
-    finally:
-        engine._use_library_for_tests(None)
 
 
 # ------------------------------------------------------------------ numpy float64 reference
@@ -467,13 +449,13 @@ def run_scene_checks(E, name, dev_forms=None):
 
 # ------------------------------------------------------------------ CPU tier (emulation)
 @pytest.mark.parametrize("name", ["a", "b", "c", "d"])
-def test_scene_against_reference(pick_emul, name):
-    run_scene_checks(pick_emul, name)
+def test_scene_against_reference(emul_engine, name):
+    run_scene_checks(emul_engine, name)
 
 
-def test_flagged_solids_and_their_neighbours(pick_emul):
+def test_flagged_solids_and_their_neighbours(emul_engine):
     """Scene (c) in detail: status per solid; the sound tetrahedra answer as they do alone."""
-    eng, n = scene_c(pick_emul)
+    eng, n = scene_c(emul_engine)
     solids = hand_made()
     rays = np.asarray([[-10, 0.1, 0.05, 1, 0, 0, 100], [0.3, 0.1, 0, 0, 0, 1, 100], [0.1, 0.05, 20, 0, 0, -1, 100], [6.2, 0.1, -20, 0, 0, 1, 100]], np.float32)
     got = eng.pieces_raycast(rays)
@@ -482,7 +464,7 @@ def test_flagged_solids_and_their_neighbours(pick_emul):
     # through the far tetrahedron first; from inside the first, past the flat solid at z = 6 without a hit
     assert got[0]["piece"] == 3 and got[1]["piece"] == 0 and got[1]["status"] == engine.RAY_STARTS_INSIDE and got[2]["piece"] == 0, got
     assert not eng.pieces_overlap([[0, 0, 6, 3]])[0][2] and eng.pieces_overlap([[0, 0, 6, 30]])[0].tolist() == [1, 1, 0, 1]
-    alone = pick_emul.Engine(0)
+    alone = emul_engine.Engine(0)
     alone.load_fragments([solids[0], solids[3]], [solids[0], solids[3]])
     alone.pieces_from_event(keep=np.ones(2, np.uint8))
     ga = alone.pieces_raycast(rays)
@@ -507,11 +489,11 @@ def test_flagged_solids_and_their_neighbours(pick_emul):
     eng.close(); alone.close()
 
 
-def test_known_answers(pick_emul):
+def test_known_answers(emul_engine):
     """A unit box about the origin: hit distances, normals, positions and the sphere distances are known exactly."""
     box = scenes.box_solid((1, 1, 1), (0, 0, 0), factor=1.0)
     far = scenes.box_solid((1, 1, 1), (4, 0, 0), factor=1.0)
-    eng = pick_emul.Engine(0)
+    eng = emul_engine.Engine(0)
     eng.upload_pieces([box, far], [box, far])
     rays = np.asarray([[-3, 0.1, 0.2, 1, 0, 0, 100], [8, 0.1, 0.2, -1, 0, 0, 100], [0.1, 0.2, 5, 0, 0, -1, 100], [0, 0, 0, 0, 1, 0, 100],
                        [-3, 0.1, 0.2, 1, 0, 0, 2.4], [-3, 0.1, 0.2, 1, 0, 0, 2.5], [-3, 0.5, 0, 1, 0, 0, 100], [-3, 0.75, 0, 1, 0, 0, 100],
@@ -531,9 +513,9 @@ def test_known_answers(pick_emul):
     eng.close()
 
 
-def test_errors_and_dev_forms(pick_emul):
-    L_ = pick_emul.lib()
-    eng = pick_emul.Engine(0)
+def test_errors_and_dev_forms(emul_engine):
+    L_ = emul_engine.lib()
+    eng = emul_engine.Engine(0)
     ray = np.asarray([[-3, 0, 0, 1, 0, 0, 100]], np.float32)
     for call in (lambda: eng.pieces_raycast(ray), lambda: eng.pieces_overlap([[0, 0, 0, 1]]), lambda: eng.pieces_query_status(1)):
         with pytest.raises(engine.SurtrError) as e:
@@ -631,24 +613,12 @@ def check_harness(E, root):
     eng.close()
 
 
-def _run_gpu_child(case, seconds):
-    code = GPU_CHILD % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}
-    try:
-        p = subprocess.run(["timeout", "-k", "10", str(seconds), sys.executable, "-c", code, case], cwd=ROOT, capture_output=True, text=True,
-                           timeout=seconds + 30)
-    except subprocess.TimeoutExpired:
-        pytest.fail("%s: no result within %d s" % (case, seconds))
-    print(p.stdout[-3000:])
-    assert p.returncode == 0, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
-    assert ("ok " + case) in p.stdout
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["a", "b", "c", "d"])
 def test_gpu_scene_against_reference(name):
-    _run_gpu_child(name, 120)
+    run_gpu_child(GPU_CHILD, name, 120)
 
 
 @pytest.mark.gpu
 def test_gpu_harness_pick():
-    _run_gpu_child("harness", 150)
+    run_gpu_child(GPU_CHILD, "harness", 150)

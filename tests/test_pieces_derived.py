@@ -31,7 +31,6 @@ import test_scene as TS
 from helpers import assert_event_equal, solid_has_doubled_neighbour, solid_is_polyhedron
 from surtr_amd import engine, meshgen, scenes
 from test_record_clipper import _event
-from test_scene import scene_emul      # noqa: F401  (the emulation with scene_dev.hip: one recipe, test_scene's)
 from test_sorted_prepass import _quad_torus
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -421,20 +420,6 @@ def run_far_from_origin(E, O, shift):
 
 
 # ------------------------------------------------------------------ CPU tier (emulation, one vertex per level-1 sphere)
-_SCENE_LIB = {}
-
-
-@pytest.fixture()
-def scene_engine(scene_emul):
-    """test_scene's library, bound again for every test (the function-scoped emulation fixtures unbind theirs when they finish)."""
-    path = _SCENE_LIB.setdefault("path", scene_emul.lib()._name)
-    engine._use_library_for_tests(path)
-    try:
-        yield engine
-    finally:
-        engine._use_library_for_tests(None)
-
-
 def test_accessor_contract_emulation(emul_engine):
     run_accessor_contract(emul_engine)
     box = scenes.box_solid((1, 1, 1), (0, 0, 0))
@@ -458,8 +443,8 @@ def test_ladder_each_piece_alone_emulation(emul_engine, oracle):
 
 
 @pytest.mark.parametrize("path", REBUILDS)
-def test_rebuilt_data_equals_a_fresh_upload_emulation(scene_engine, oracle, path):
-    run_rebuild(scene_engine, oracle, path)
+def test_rebuilt_data_equals_a_fresh_upload_emulation(emul_engine, oracle, path):
+    run_rebuild(emul_engine, oracle, path)
 
 
 @pytest.mark.parametrize("shift", [512, 4096])

@@ -21,43 +21,25 @@ test commits such compounds), and the fragment of tests/golden/nonterminating_fa
 is flagged by a render event; committed with every piece in a compound of its own, that fragment's compound is not created.  The
 expectation is built from reference (a)'s download, and that something was left out is asserted.
 
-The CPU tier builds its own emulation library with scene_dev.hip added (the flags of tests/emul/Makefile); the GPU tier runs the
-same scenes on the MI355X in child processes under a time limit."""
+The CPU tier runs on the one emulation library of tests/emul (conftest's emul_engine); the GPU tier runs the same scenes on the
+MI355X in child processes under a time limit (helpers.run_gpu_child)."""
 import hashlib
 import json
 import os
 import subprocess
-import sys
 import textwrap
 
 import numpy as np
 import pytest
 
+from helpers import run_gpu_child
 from surtr_amd import engine, scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "surtr_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-EMUL_SOURCES = ["surtr_hip.hip", "pieces_dev.hip", "cells_dev.hip", "mesh_dev.hip", "regroup_dev.hip", "mass_dev.hip", "query_dev.hip",
-                "scene_dev.hip", "host_geom.cpp", "host_regroup.cpp"]
-# the flags of tests/emul/Makefile
-CXXFLAGS = ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-Wall", "-Wno-unused-function",
-            "-Wno-sign-compare", "-Wno-unused-variable", "-Wno-unused-but-set-variable", "-Wno-unknown-pragmas"]
 EVENT_KEYS = ("mesh_vert_off", "mesh_pos", "mesh_nbr_off", "mesh_nbr", "conv_vert_off", "conv_pos", "conv_nbr_off", "conv_nbr", "frag_status")
 SHIFT_B = np.float32([10, 0, 0])
 SHIFT_BLOB = np.float32([0, 300, 0])
-
-
-@pytest.fixture(scope="module")
-def scene_emul(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("scene_emul") / "libsurtr_emul_scene.so")
-    cmd = [os.environ.get("CXX", "g++")] + CXXFLAGS + ["-I", os.path.join(ROOT, "tests", "emul"), "-shared", "-o", out, "-x", "c++"]
-    subprocess.check_call(cmd + [os.path.join(CSRC, f) for f in EMUL_SOURCES])
-    engine._use_library_for_tests(out)
-    try:
-        yield engine
-    finally:
-        engine._use_library_for_tests(None)
 
 
 # ------------------------------------------------------------------ helpers
@@ -465,29 +447,29 @@ def run_steady_allocations(E):
 
 
 # ------------------------------------------------------------------ CPU tier (emulation)
-def test_two_clicks_against_both_references(scene_emul):
-    n, n2 = run_two_clicks(scene_emul)
+def test_two_clicks_against_both_references(emul_engine):
+    n, n2 = run_two_clicks(emul_engine)
     print("resident pieces after click 1:", n, "after click 2:", n2)
 
 
-def test_untouched_bodies_keep_their_bits(scene_emul):
-    run_transform(scene_emul)
+def test_untouched_bodies_keep_their_bits(emul_engine):
+    run_transform(emul_engine)
 
 
-def test_existing_behaviour_without_a_scene_call(scene_emul):
-    run_existing_behaviour(scene_emul)
+def test_existing_behaviour_without_a_scene_call(emul_engine):
+    run_existing_behaviour(emul_engine)
 
 
-def test_errors_leave_the_scene_unchanged(scene_emul):
-    run_errors(scene_emul)
+def test_errors_leave_the_scene_unchanged(emul_engine):
+    run_errors(emul_engine)
 
 
-def test_flagged_fragment_and_its_compound_are_left_out(scene_emul):
-    run_unsolid(scene_emul)
+def test_flagged_fragment_and_its_compound_are_left_out(emul_engine):
+    run_unsolid(emul_engine)
 
 
-def test_steady_commits_do_not_allocate(scene_emul):
-    run_steady_allocations(scene_emul)
+def test_steady_commits_do_not_allocate(emul_engine):
+    run_steady_allocations(emul_engine)
 
 
 # ------------------------------------------------------------------ GPU tier
@@ -573,24 +555,12 @@ def check_harness(E, root):
     eng.close()
 
 
-def _run_gpu_child(case, seconds):
-    code = GPU_CHILD % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}
-    try:
-        p = subprocess.run(["timeout", "-k", "10", str(seconds), sys.executable, "-c", code, case], cwd=ROOT, capture_output=True, text=True,
-                           timeout=seconds + 30)
-    except subprocess.TimeoutExpired:
-        pytest.fail("%s: no result within %d s" % (case, seconds))
-    print(p.stdout[-3000:])
-    assert p.returncode == 0, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
-    assert ("ok " + case) in p.stdout
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["clicks", "transform", "existing_behaviour", "errors", "unsolid", "steady_allocations", "async"])
 def test_gpu_scene(case):
-    _run_gpu_child(case, 120)
+    run_gpu_child(GPU_CHILD, case, 120)
 
 
 @pytest.mark.gpu
 def test_gpu_harness_scene_clicks():
-    _run_gpu_child("harness", 150)
+    run_gpu_child(GPU_CHILD, "harness", 150)

@@ -16,25 +16,23 @@ The lattice is test_pick_queries.scene_d's 306 boxes in compounds of 1, 2, 61, 6
 (64, 128) and one short of / past one, a compound that straddles piece 256 (the second workgroup of the ray kernel).  Every compound
 but one is turned about an axis of its own through its centre and moved 24 units away from the one left at the identity.
 
-The CPU tier builds its own emulation library from test_scene.py's source list; the GPU tier runs the same functions on the MI355X
-in child processes under a time limit, plus the _dev forms, two contexts and the harness."""
+The CPU tier runs on the one emulation library of tests/emul (conftest's emul_engine); the GPU tier runs the same functions on the
+MI355X in child processes under a time limit (helpers.run_gpu_child), plus the _dev forms, two contexts and the harness."""
 import ctypes
 import json
 import os
 import subprocess
-import sys
 import textwrap
 
 import numpy as np
 import pytest
 
+from helpers import run_gpu_child
 from surtr_amd import engine, scenes
 
 import test_pick_queries as PQ
 import test_scene as TS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "surtr_amd", "csrc")
 SIZES = [1, 2, 61, 64, 65, 70, 43]
 TABLE = np.cumsum([0] + SIZES).astype(np.uint32)
 AT_REST = 3                                   # the compound left at the identity
@@ -42,18 +40,6 @@ OFFSETS = [(-24, 0, 0), (24, 0, 0), (0, -24, 0), (0, 0, 0), (0, 24, 0), (0, 0, -
 AXES = [(1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1), (1, 1, 0), (0, 1, 1), (1, 0, 1)]
 ANGLES = [0.4, -0.7, 1.1, 0.0, 2.0, -1.3, 0.25]
 CAP = PQ.CAP
-
-
-@pytest.fixture(scope="module")
-def poses_emul(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("poses_emul") / "libsurtr_emul_poses.so")
-    cmd = [os.environ.get("CXX", "g++")] + TS.CXXFLAGS + ["-I", os.path.join(ROOT, "tests", "emul"), "-shared", "-o", out, "-x", "c++"]
-    subprocess.check_call(cmd + [os.path.join(CSRC, f) for f in TS.EMUL_SOURCES])
-    engine._use_library_for_tests(out)
-    try:
-        yield engine
-    finally:
-        engine._use_library_for_tests(None)
 
 
 # ------------------------------------------------------------------ poses and the posed reference
@@ -585,34 +571,34 @@ def run_invalid_ray_dev(E, mem):
 
 
 # ------------------------------------------------------------------ CPU tier (emulation)
-def test_posed_lattice_against_reference(poses_emul):
-    run_posed_lattice(poses_emul, HostMem())
+def test_posed_lattice_against_reference(emul_engine):
+    run_posed_lattice(emul_engine, HostMem())
 
 
-def test_identity_poses_equal_the_unposed_queries(poses_emul):
-    run_identity(poses_emul, HostMem())
+def test_identity_poses_equal_the_unposed_queries(emul_engine):
+    run_identity(emul_engine, HostMem())
 
 
-def test_posed_queries_equal_baked_pieces(poses_emul):
-    run_baked(poses_emul)
+def test_posed_queries_equal_baked_pieces(emul_engine):
+    run_baked(emul_engine)
 
 
-def test_body_mass_is_the_hosts_sum_bit_for_bit(poses_emul):
-    run_body_mass(poses_emul)
+def test_body_mass_is_the_hosts_sum_bit_for_bit(emul_engine):
+    run_body_mass(emul_engine)
 
 
-def test_apply_pose_is_the_transform(poses_emul):
-    run_apply_pose(poses_emul)
+def test_apply_pose_is_the_transform(emul_engine):
+    run_apply_pose(emul_engine)
 
 
-def test_click_loop_with_motion(poses_emul):
-    n, n2 = run_click_loop(poses_emul)
+def test_click_loop_with_motion(emul_engine):
+    n, n2 = run_click_loop(emul_engine)
     print("resident pieces after click 1:", n, "after click 2:", n2)
 
 
-def test_errors_leave_table_poses_and_pieces_unchanged(poses_emul):
-    run_errors(poses_emul)
-    run_invalid_ray_dev(poses_emul, HostMem())
+def test_errors_leave_table_poses_and_pieces_unchanged(emul_engine):
+    run_errors(emul_engine)
+    run_invalid_ray_dev(emul_engine, HostMem())
 
 
 # ------------------------------------------------------------------ GPU tier
@@ -738,24 +724,12 @@ def check_harness(E, root):
         eng.close()
 
 
-def _run_gpu_child(case, seconds):
-    code = GPU_CHILD % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}
-    try:
-        p = subprocess.run(["timeout", "-k", "10", str(seconds), sys.executable, "-c", code, case], cwd=ROOT, capture_output=True, text=True,
-                           timeout=seconds + 30)
-    except subprocess.TimeoutExpired:
-        pytest.fail("%s: no result within %d s" % (case, seconds))
-    print(p.stdout[-3000:])
-    assert p.returncode == 0, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
-    assert ("ok " + case) in p.stdout
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["posed_lattice", "identity", "baked", "body_mass", "apply_pose", "click_loop", "errors", "invalid_ray_dev", "dev_forms"])
 def test_gpu_scene_poses(case):
-    _run_gpu_child(case, 120)
+    run_gpu_child(GPU_CHILD, case, 120)
 
 
 @pytest.mark.gpu
 def test_gpu_harness_body_clicks():
-    _run_gpu_child("harness", 150)
+    run_gpu_child(GPU_CHILD, "harness", 150)
