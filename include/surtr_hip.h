@@ -402,9 +402,27 @@ int surtr_regroup(uint32_t n_pieces, uint32_t n_outside, const int32_t* piece_ce
  * pieces are gone: if the event's mask kept any piece out, the call returns SURTR_E_STATE (regroup before handing the fragments
  * on); an event without a mask, or with a mask of zeros, regroups as before.
  * After surtr_scene_fracture_event only the skipped pieces of the event's compound are numbered (ascending), then the fragments:
- * pieces of other bodies are in no bind set. */
+ * pieces of other bodies are in no bind set.
+ * CAPACITY AFTER A BODIES EVENT: after surtr_scene_fracture_bodies with n_targets > 1 every body has a bind 0 of its own, and this
+ * call (which takes no capacity) writes up to *n_pieces + n_targets + 1 offsets: size compound_off for that, not n_pieces + 2, or
+ * use surtr_event_regroup_bodies, whose sizes-only call returns the number of bodies. */
 int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
                         uint32_t* n_pieces, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece);
+/* The same with one more output: which compounds belong to which body of the event.  After surtr_scene_fracture_bodies a body is a
+ * target of the click, in the order the targets were given; after any other event there is one body.  *n_bodies is set by every
+ * call (the one with NULL arrays included); body_compound_off (may be NULL) gets *n_bodies + 1 entries: body b's compounds are
+ * compounds [body_compound_off[b], body_compound_off[b + 1]), the first of them its bind 0 (the pieces out of the impact, possibly
+ * none).  compound_off needs *n_pieces + *n_bodies + 1 entries.
+ *   Pieces are numbered as above: the skipped resident pieces of every target, ascending, then the fragments in output order.
+ *   A bind set belongs to one body: bind 0 is made per body; the cell binds are cut where the cell or the body changes (the last cell
+ *   of one body and the first of the next may carry the same number); MergeOutOfImpact moves a fragment to its own body's bind 0;
+ *   the groups HandleConvexIsland splits off follow their own body's binds.  The kernels run once over all the pieces.
+ *   Each body's compounds are, in order and in membership, what surtr_event_regroup returns for that body's own event.
+ * surtr_event_regroup after a bodies event returns the same compounds without the extra array (its compound_off then needs
+ * *n_pieces + n_targets + 1 entries as well: every body has a bind 0 of its own). */
+int surtr_event_regroup_bodies(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
+                               uint32_t* n_pieces, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece,
+                               uint32_t* n_bodies, uint32_t* body_compound_off);
 
 /* Runs m_refittingTask (and the output scan) on the fragments of the last event: the reference regroups on the
  * un-refitted Convex solids and refits afterwards (Src/Surtr.cpp:1921-1939). */
@@ -543,6 +561,34 @@ int surtr_scene_fracture_event(surtr_ctx* ctx, uint32_t compound, uint32_t cell_
                                uint32_t flags, surtr_counts* counts);
 int surtr_scene_fracture_event_async(surtr_ctx* ctx, uint32_t compound, uint32_t cell_begin, uint32_t cell_end, const uint8_t* outside,
                                      uint32_t flags);
+/* One event over the pieces of several compounds: every body a click's impact sphere touches (OnMouseDown, Src/Surtr.cpp:213-253) in
+ * one pass instead of one event, regroup and commit per body.  compounds: n_targets >= 1 compound numbers, STRICTLY DESCENDING (so
+ * that the committed scene is the one n_targets commits in that order leave), no duplicate, in range; anything else is
+ * SURTR_E_INVALID and changes nothing.  outside (may be NULL): one byte per piece of the listed compounds, concatenated in the order
+ * given, each compound in resident order -- the layout surtr_scene_outside returns.  The pair list is target-major in the given
+ * order and cell-major over the target's pieces within a target; frag_ids carry resident piece numbers.  With one target every
+ * result equals surtr_scene_fracture_event's bit for bit.  Follow with surtr_event_regroup_bodies (or surtr_event_regroup),
+ * surtr_event_refit and ONE surtr_scene_commit. */
+int surtr_scene_fracture_bodies(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t cell_begin, uint32_t cell_end,
+                                const uint8_t* outside, uint32_t flags, surtr_counts* counts);
+int surtr_scene_fracture_bodies_async(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t cell_begin, uint32_t cell_end,
+                                      const uint8_t* outside, uint32_t flags);
+/* Surtr::ConvexOutOfSphere (Src/Surtr.cpp:2415-2458) of the resident Convex solids of the listed compounds (any order, in range), on
+ * the device: one byte per piece, concatenated in the order the compounds are given, each compound in resident order; 1 where every
+ * vertex is at least `radius` from `origin` and no point of the cloud lies inside all face planes -- the answer of
+ * surtr_convex_out_of_sphere on the downloaded solid, bit for bit, for every solid that is a regular polyhedron (no ring lists a
+ * neighbour twice, no face loop passes through a vertex twice: every convex hull and every unflagged fragment).  The kernel finds
+ * the faces in parallel, not in ExtractFaces' visiting order; on a solid that breaks the precondition the byte is defined and
+ * deterministic but may differ from the host's.  One launch, one wave per piece (k_scene_outside).
+ * surtr_scene_outside: count-then-fill -- outside == NULL returns *n only; with it, cap is the bytes it has room for
+ * (SURTR_E_CAPACITY when too small).  surtr_scene_outside_dev: cloud and mask in device memory, enqueued on the context's stream,
+ * nothing is read back; the piece list goes through a buffer of the context that is reallocated (which waits for the device) only
+ * when a call lists more pieces than any before it.  A Convex of more than 4096 half-edges (or vertices) gives SURTR_E_CAPACITY before anything is enqueued;
+ * the context stays usable.  Poses are not applied: bake them first (surtr_scene_apply_poses). */
+int surtr_scene_outside(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t n_sphere, const float* sphere_points,
+                        const float origin[3], float radius, uint32_t cap, uint32_t* n, uint8_t* outside);
+int surtr_scene_outside_dev(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t n_sphere, const float* dev_sphere_points,
+                            const float origin[3], float radius, uint8_t* dev_outside, size_t capacity_bytes);
 /* Makes the resident set what :1856-1875 make CompoundVec: the event's compound is erased, the compounds it broke into are pushed
  * to the back.  (n_compounds, compound_off, compound_piece) are the compounds exactly as surtr_event_regroup returned them for the
  * last scene event (compound 0, the pieces out of the impact, included).
@@ -559,7 +605,11 @@ int surtr_scene_fracture_event_async(surtr_ctx* ctx, uint32_t compound, uint32_t
  * of a scene of steady size on, surtr_upload_stats reports 0 allocations.
  * SURTR_E_STATE: no scene event; the event failed; the event was committed already; the resident pieces were replaced or
  * transformed, or the compound table set, since the event.  SURTR_E_INVALID: the compounds do not cover pieces 0 .. n-1 exactly once
- * (or nothing would be left).  On any error the scene is unchanged. */
+ * (or nothing would be left).  On any error the scene is unchanged.
+ * After surtr_scene_fracture_bodies: every target is erased, with its pose; the other compounds stay first, in their old order;
+ * the returned compounds (all bodies', as surtr_event_regroup_bodies gave them) are appended in order, the skipped pieces of any
+ * target as they stand; one gather and one rebuild of the derived data.  Because the targets descend, the scene is the one that
+ * one commit per target, in that order, leaves. */
 int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* compound_off, const int32_t* compound_piece,
                        uint32_t* n_pieces, uint32_t* first_new_compound, uint32_t* n_new_compounds, int32_t* src);
 /* Diagnostic: host time of the last surtr_scene_commit in milliseconds, in two parts that both end in a stream synchronisation --
@@ -590,6 +640,10 @@ int surtr_scene_commit_times(surtr_ctx* ctx, float* gather_ms, float* derive_ms)
 int surtr_scene_set_poses(surtr_ctx* ctx, uint32_t n_compounds, const float* world);
 int surtr_scene_get_poses(surtr_ctx* ctx, uint32_t cap, uint32_t* n_compounds, float* world);
 int surtr_scene_apply_pose(surtr_ctx* ctx, uint32_t compound);
+/* surtr_scene_apply_pose for several compounds (any order, in range; one named twice is baked once): one transform launch per
+ * compound whose pose is not bit for bit the identity, the derived data rebuilt ONCE, those poses set to the identity.  The resident
+ * bits are those surtr_scene_apply_pose per compound leaves.  When every pose is the identity nothing happens at all. */
+int surtr_scene_apply_poses(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds);
 
 /* Ray cast and sphere overlap on the posed scene.  Definition: that of surtr_pieces_raycast / surtr_pieces_overlap, applied per
  * piece in that piece's body frame.  For piece p of compound c with pose (A, b):

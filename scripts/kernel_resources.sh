@@ -1,10 +1,11 @@
 #!/bin/bash
-# Per-kernel LDS / VGPR / scratch usage of the device code (compiles surtr_hip.hip to an object with the build's flags).
+# Per-kernel LDS / VGPR / scratch usage of the device code (compiles one unit to an object with the build's flags): surtr_hip.hip, or
+# the unit named in SRC, e.g. SRC=surtr_amd/csrc/regroup_dev.hip.
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p build_tmp/res
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -std=c++17 -fPIC --cuda-device-only -c "$@" \
-    -o build_tmp/res/dev.o surtr_amd/csrc/surtr_hip.hip
+    -o build_tmp/res/dev.o "${SRC:-surtr_amd/csrc/surtr_hip.hip}"
 /opt/rocm/lib/llvm/bin/clang-offload-bundler --unbundle --type=o --input=build_tmp/res/dev.o \
     --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=build_tmp/res/dev.co
 /opt/rocm/lib/llvm/bin/llvm-readelf --notes build_tmp/res/dev.co | python3 -c '

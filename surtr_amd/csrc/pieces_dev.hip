@@ -399,7 +399,7 @@ void set_piece_stats(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const uint
     if (const char* e = getenv("SURTR_HALF")) ctx->half_on = atoi(e) != 0;      // tests: force either way
     ctx->have_event = false; ctx->frags_of_pieces = false;
     // the scene: one compound holding every piece, until surtr_scene_set_compounds / surtr_scene_commit say otherwise
-    ctx->scene_off.assign({0u, n}); ctx->scene_event_compound = -1;
+    ctx->scene_off.assign({0u, n}); ctx->scene_event_compound.clear();
     scene_reset_poses(ctx);      // (every pose the identity; surtr_scene_commit puts the survivors' back)
     ctx->h_vo[0].assign(mvo, mvo + n + 1); ctx->h_ho[0].assign(mho, mho + n + 1);
     ctx->h_vo[1].assign(cvo, cvo + n + 1); ctx->h_ho[1].assign(cho, cho + n + 1);
@@ -418,26 +418,38 @@ int finish_upload(surtr_ctx* ctx, uint32_t n, bool check)
 
 int transform_range(surtr_ctx* ctx, uint32_t p0, uint32_t n, const float* world)
 {
+    return transform_ranges(ctx, 1, &p0, &n, world);
+}
+
+int transform_ranges(surtr_ctx* ctx, uint32_t n_ranges, const uint32_t* p0, const uint32_t* n, const float* world)
+{
     const uint32_t np = ctx->n_pieces;
     (void)hipSetDevice(ctx->device);
     Timer timer(ctx);
     hipStream_t st = ctx->stream;
-    int rc = grow_pieces(ctx, ctx->d_world, (size_t)16 * n);
+    size_t total = 0;
+    for (uint32_t r = 0; r < n_ranges; ++r) total += n[r];
+    int rc = grow_pieces(ctx, ctx->d_world, (size_t)16 * total);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpyAsync(ctx->d_world, world, (size_t)64 * n, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctx->d_world, world, (size_t)64 * total, hipMemcpyHostToDevice, st));
     std::vector<uint32_t> vo(np + 1);
     for (int set = 0; set < 2; ++set)
     {
         PieceSet& S = set ? ctx->cset : ctx->mset;
         HIPCHK(hipMemcpyAsync(vo.data(), S.vo, (size_t)(np + 1) * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        const uint32_t V = vo[np], v0 = vo[p0], v1 = vo[p0 + n];
-        hipLaunchKernelGGL(k_transform, dim3((v1 - v0 + 255) / 256), dim3(256), 0, st, v1, np, S.vo, ctx->d_world, S.pos, v0, p0);
+        const uint32_t V = vo[np];
+        size_t at = 0;
+        for (uint32_t r = 0; r < n_ranges; at += n[r], ++r)
+        {
+            const uint32_t v0 = vo[p0[r]], v1 = vo[p0[r] + n[r]];
+            hipLaunchKernelGGL(k_transform, dim3((v1 - v0 + 255) / 256), dim3(256), 0, st, v1, np, S.vo, ctx->d_world.p + 16 * at, S.pos, v0, p0[r]);
+        }
         rc = derive_set(ctx, S, np, V, sphere_offsets(np, vo.data()), false);
         if (rc) return rc;
     }
-    ctx->have_event = false; ctx->frags_of_pieces = false; ctx->scene_event_compound = -1;
+    ctx->have_event = false; ctx->frags_of_pieces = false; ctx->scene_event_compound.clear();
     HIPCHK(hipStreamSynchronize(st));
     return SURTR_OK;
 }

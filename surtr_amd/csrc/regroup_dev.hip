@@ -8,9 +8,11 @@
 //   k_rg_pairs                one lane per face: the faces of its compound within 1e-3 of its |d| -> opposite normals ->
 //                             point-in-polygon both ways (VMACH::OnYourRight) -> an edge between the two pieces
 //   k_rg_labels               min-label propagation over the pieces until nothing changes
+//   k_scene_outside           ConvexOutOfSphere of resident pieces before an event (surtr_scene_outside): one wave per piece
 // Only per-piece flags and labels (a few bytes per piece) cross the bus; the host turns them into the reference's bind sets
 // (first group of a compound stays, the others are appended in discovery order).  Pieces are numbered as in
-// surtr_regroup: the resident pieces the event skipped (its `outside` mask), ascending, then the event's fragments.
+// surtr_regroup: the resident pieces the event skipped (its `outside` mask), ascending, then the event's fragments.  After an event
+// over several bodies (surtr_scene_fracture_bodies) a bind set belongs to one body (surtr_event_regroup_bodies).
 #include <array>
 #include <cstring>
 #include <mutex>
@@ -175,6 +177,102 @@ __global__ __launch_bounds__(SURTR_LANES) void k_rg_faces(uint32_t n_pieces, RgS
     }
 }
 
+// Surtr::ConvexOutOfSphere (Src/Surtr.cpp:2415-2458) of resident Convex solids, one wave per listed piece, in one launch: what
+// k_rg_faces' second pass answers for the pieces of an event, here for the pieces a click is about to break (the `outside` mask of
+// surtr_scene_fracture_bodies), without a count pass, a face list in memory or a host round trip.
+//   1. every vertex at least `radius` from the origin, across the lanes; a piece with a vertex inside ends here (byte 0);
+//   2. the faces, one lane per half-edge: Poly::ExtractFaces starts every face at its smallest vertex, so the half-edge (v, adj) leads
+//      a face when v is the least vertex of the loop it walks (and adj's first slot in v's ring: the reference's visited set is keyed
+//      by (vertex, neighbour)).  A leader forms the plane from v and the two vertices after it -- the float expressions of
+//      k_rg_faces' second part and of surtr_convex_out_of_sphere -- and puts it into LDS at a slot counted with a ballot; loops of
+//      fewer than three points are skipped.  Leaders are distinct half-edges: at most RG_MAXH planes;
+//   3. the cloud, a lane per point, against the planes in LDS (every lane reads the same plane: a broadcast); one store of the byte.
+// PRECONDITION for the host's answer bit for bit: the solid is a regular polyhedron -- no ring lists a neighbour twice (PieceSet::dup
+// is 0) and no face loop passes through a vertex twice, so that "next half-edge" is a permutation of the half-edges and its orbits
+// are the faces.  That is every convex hull and every unflagged fragment.  On any other solid the leaders need not be the faces
+// ExtractFaces' visited set yields (a plane may be formed that the host never forms, or one skipped), the byte is still defined and
+// deterministic, and nothing is read or written out of bounds: walks are bounded as the host's are and there is room for a plane
+// per half-edge.
+// LDS: static, RG_MAXH planes = 64 KiB, two one-wave blocks per CU.  The grid is the handful of pieces a click touches; a size
+// taken from the largest piece of the list would need dynamic LDS, which the one-lane emulation build does not have.
+__global__ __launch_bounds__(SURTR_LANES) void k_scene_outside(uint32_t n, const uint32_t* __restrict__ list, const float* __restrict__ cpos,
+                                                               const uint32_t* __restrict__ cloff, const int32_t* __restrict__ cnbr,
+                                                               const uint32_t* __restrict__ cvo, uint32_t n_sphere, const float* __restrict__ sphere,
+                                                               float ox, float oy, float oz, float radius, uint8_t* __restrict__ out)
+{
+    __shared__ float4 plane[RG_MAXH];
+    const uint32_t i = blockIdx.x;
+    if (i >= n) return;
+    const uint32_t lane = threadIdx.x, G = group_size();
+    const uint32_t p = list[i], a0 = cvo[p];
+    const RgSolid S{cpos + 3 * (size_t)a0, cloff + a0, nullptr, cnbr, cvo[p + 1] - a0};
+    bool near = false;
+    for (uint32_t v = lane; v < S.nv && !near; v += G)
+    {
+        const P3 d = sub3(P3{ox, oy, oz}, rg_pos(S, (int)v));
+        if (sqrtf(dotp(d, d)) < radius) near = true;
+    }
+    const bool inside = __ballot(near) != 0ull;
+    if (inside || n_sphere == 0u)
+    {
+        if (lane == 0u) out[i] = inside ? 0 : 1;
+        return;
+    }
+    const uint32_t h0 = S.loff[0], H = S.loff[S.nv] - h0;      // (the host has checked H and nv against RG_MAXH)
+    uint32_t nf = 0;
+    for (uint32_t e0 = 0; e0 < H; e0 += G)
+    {
+        const uint32_t e = e0 + lane;
+        bool lead = false; float4 pl = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (e < H)
+        {
+            uint32_t lo = 0, hi = S.nv;                         // the vertex of half-edge e: loff[lo] <= h0 + e < loff[hi]
+            while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (S.loff[mid] <= h0 + e) lo = mid; else hi = mid; }
+            const int v = (int)lo;
+            const int32_t* ring = S.nbr + S.loff[v]; const uint32_t s = h0 + e - S.loff[v];
+            const int adj = ring[s];
+            bool first = true;
+            for (uint32_t k = 0; k < s; ++k) if (ring[k] == adj) first = false;
+            if (first)
+            {
+                int prev = v, cur = adj, third = -1; uint32_t len = 1; bool least = true;
+                while (cur != v && len <= S.nv * 8u + 8u)
+                {
+                    if (cur < v) { least = false; break; }
+                    if (len == 2u) third = cur;
+                    const int nx = rg_before(S, cur, prev);
+                    prev = cur; cur = nx; ++len;
+                }
+                if (least && len >= 3u)
+                {
+                    const P3 a = rg_pos(S, v), b = rg_pos(S, adj), c = rg_pos(S, third);
+                    const P3 nn = unit3(cross3(sub3(b, a), sub3(c, a)));
+                    pl = make_float4(nn.x, nn.y, nn.z, -dotp(a, nn));
+                    lead = true;
+                }
+            }
+        }
+        const unsigned long long m = __ballot(lead);
+        if (lead) plane[nf + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = pl;
+        nf += (uint32_t)__builtin_popcountll(m);
+    }
+    __syncthreads();
+    bool hit = false;
+    for (uint32_t q = lane; q < n_sphere && !hit; q += G)
+    {
+        const P3 po{sphere[3 * q], sphere[3 * q + 1], sphere[3 * q + 2]};
+        bool contain = true;
+        for (uint32_t f = 0; f < nf && contain; ++f)
+        {
+            const float4 w = plane[f];
+            if (dotp(P3{w.x, w.y, w.z}, po) + w.w > 0.f) contain = false;
+        }
+        if (contain) hit = true;
+    }
+    const bool any = __ballot(hit) != 0ull;
+    if (lane == 0u) out[i] = any ? 0 : 1;
+}
+
 __global__ void k_rg_keys(uint32_t nf, const FaceNode* __restrict__ nodes, const uint32_t* __restrict__ set_of, unsigned long long* __restrict__ key,
                           uint32_t* __restrict__ val)
 {
@@ -302,8 +400,12 @@ extern "C" void surtr_regroup_forget(const surtr_ctx* ctx)
     g_stats.erase(ctx);
 }
 
-extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
-                                   uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece)
+static int regroup_bodies(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, int partial, uint32_t n_sphere, const float* sphere_points,
+                          const float origin[3], float radius, uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece,
+                          uint32_t* body_compound_off);
+
+static int regroup_event(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
+                         uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece, uint32_t* body_compound_off)
 {
     if (!ctx || !n_compounds) return SURTR_E_INVALID;
     if (!ctx->have_event) return SURTR_E_STATE;
@@ -327,11 +429,29 @@ extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_spher
     std::vector<uint32_t> skipped;
     for (uint32_t p = 0; masked && p < ctx->n_pieces; ++p)
         if (ctx->last_outside[p]) skipped.push_back(p);
-    return surtr_event_regroup_skipped(ctx, skipped, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece);
+    return regroup_bodies(ctx, skipped, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off);
 }
 
-int surtr_event_regroup_skipped(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, int partial, uint32_t n_sphere, const float* sphere_points,
-                                const float origin[3], float radius, uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece)
+extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
+                                   uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece)
+{
+    return regroup_event(ctx, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece, nullptr);
+}
+
+extern "C" int surtr_event_regroup_bodies(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
+                                          uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece,
+                                          uint32_t* n_bodies, uint32_t* body_compound_off)
+{
+    if (!ctx || !n_bodies) return SURTR_E_INVALID;
+    *n_bodies = (uint32_t)std::max<size_t>(ctx->scene_event_compound.size(), 1);
+    return regroup_event(ctx, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off);
+}
+
+// The bodies of the event: after surtr_scene_fracture_bodies one per target, in the order the targets were given (a bind set belongs
+// to one body); after any other event one body holding everything, which is the regrouping as it was before there were bodies.
+static int regroup_bodies(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, int partial, uint32_t n_sphere, const float* sphere_points,
+                          const float origin[3], float radius, uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece,
+                          uint32_t* body_compound_off)
 {
     if (!ctx || !n_compounds) return SURTR_E_INVALID;
     if (!ctx->have_event) return SURTR_E_STATE;
@@ -348,17 +468,36 @@ int surtr_event_regroup_skipped(surtr_ctx* ctx, const std::vector<uint32_t>& ski
     for (uint32_t f = 0; f < c.n_frag; ++f) { kind.push_back(1u); index.push_back(f); }
     const uint32_t n = (uint32_t)kind.size();
     if (n_pieces_out) *n_pieces_out = n;
-    if (!compound_off || !compound_piece) { *n_compounds = 0; return SURTR_OK; }      // sizes only: n + 2 / n entries are enough
+    if (!compound_off || !compound_piece) { *n_compounds = 0; return SURTR_OK; }      // sizes only: n + bodies + 1 / n entries are enough
     StatsScope stats(ctx);
     stats.v[RGS_PIECES] = n;
-    std::vector<std::set<int>> bind(1);
-    for (uint32_t p = 0; p < n_outside; ++p) bind[0].insert((int)p);
+    // body of every piece: the target whose compound holds the resident piece (a fragment's: the piece it was cut from)
+    const std::vector<uint32_t>& targets = ctx->scene_event_compound;
+    const uint32_t nb = (uint32_t)std::max<size_t>(targets.size(), 1);
+    auto body_of = [&](uint32_t resident) -> uint32_t {
+        if (nb == 1u) return 0u;
+        const uint32_t comp = (uint32_t)(std::upper_bound(ctx->scene_off.begin(), ctx->scene_off.end(), resident) - ctx->scene_off.begin()) - 1u;
+        for (uint32_t b = 0; b < nb; ++b) if (targets[b] == comp) return b;
+        return 0u;
+    };
+    // bind[b], b < nb: bind 0 of body b (its pieces out of the impact); then the cell binds, cut where the cell OR the body changes
+    // (two bodies' fragments of equal cell number are two binds); owner[i]: the body of bind i
+    std::vector<std::set<int>> bind(nb);
+    std::vector<uint32_t> owner(nb), frag_body(c.n_frag);
+    for (uint32_t b = 0; b < nb; ++b) owner[b] = b;
+    for (uint32_t p = 0; p < n_outside; ++p) bind[body_of(skipped[p])].insert((int)p);
     for (uint32_t f = 0; f < c.n_frag; ++f)
     {
-        if (f == 0 || fr[f].cell != fr[f - 1].cell) bind.emplace_back();
+        frag_body[f] = body_of((uint32_t)fr[f].piece);
+        if (f == 0 || fr[f].cell != fr[f - 1].cell || frag_body[f] != frag_body[f - 1]) { bind.emplace_back(); owner.push_back(frag_body[f]); }
         bind.back().insert((int)(n_outside + f));
     }
-    if (n == 0) { *n_compounds = 1; compound_off[0] = compound_off[1] = 0; return SURTR_OK; }
+    if (n == 0)
+    {
+        *n_compounds = nb;
+        for (uint32_t b = 0; b <= nb; ++b) { compound_off[b] = 0; if (body_compound_off) body_compound_off[b] = b; }
+        return SURTR_OK;
+    }
     // (the call's temporaries: at least 4 elements each)
     auto alloc = [&](auto& b, size_t k) { return b.grow(ctx, std::max<size_t>(k, 4)) == SURTR_OK; };
     DevBuf<uint32_t> d_kind, d_index, d_cnt, d_foff, d_poff, d_set, d_val, d_order, d_lab, d_flag32; DevBuf<uint8_t> d_out; DevBuf<float> d_sph;
@@ -400,14 +539,17 @@ int surtr_event_regroup_skipped(surtr_ctx* ctx, const std::vector<uint32_t>& ski
         std::vector<uint8_t> flag(n);
         HIPCHK(hipMemcpyAsync(flag.data(), d_out.p, n, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        for (size_t i = 1; i < bind.size(); ++i)
+        for (size_t i = nb; i < bind.size(); ++i)
         {
             std::set<int> outside;
             for (int cpi : bind[i]) if (flag[cpi]) outside.insert(cpi);
-            for (int cpi : outside) { bind[i].erase(cpi); bind[0].insert(cpi); }
+            for (int cpi : outside) { bind[i].erase(cpi); bind[owner[i]].insert(cpi); }      // (to its own body's bind 0)
             stats.v[RGS_OUT] += (uint32_t)outside.size();
         }
-        bind.erase(std::remove_if(bind.begin() + 1, bind.end(), [](const std::set<int>& s) { return s.empty(); }), bind.end());
+        size_t kept = nb;
+        for (size_t i = nb; i < bind.size(); ++i)
+            if (!bind[i].empty()) { if (kept != i) { bind[kept] = std::move(bind[i]); owner[kept] = owner[i]; } ++kept; }
+        bind.resize(kept); owner.resize(kept);
     }
     set_of.assign(n, 0u);
     for (size_t i = 0; i < bind.size(); ++i) for (int p : bind[i]) set_of[p] = (uint32_t)i;
@@ -449,9 +591,10 @@ int surtr_event_regroup_skipped(surtr_ctx* ctx, const std::vector<uint32_t>& ski
         stats.v[RGS_ROUNDS] = rounds;
     }
     // HandleConvexIsland's outcome: per compound, groups = label classes in order of their lowest piece; the first stays
-    std::vector<std::set<int>> extra;
-    for (auto& local : bind)
+    std::vector<std::set<int>> extra; std::vector<uint32_t> extra_owner;
+    for (size_t i = 0; i < bind.size(); ++i)
     {
+        std::set<int>& local = bind[i];
         if (local.size() <= 1) continue;
         std::vector<std::pair<uint32_t, std::set<int>>> groups;      // (label = lowest piece, members)
         for (int p : local)
@@ -464,17 +607,96 @@ int surtr_event_regroup_skipped(surtr_ctx* ctx, const std::vector<uint32_t>& ski
         if (groups.size() >= 2)
         {
             local = groups[0].second;
-            for (size_t g = 1; g < groups.size(); ++g) extra.push_back(groups[g].second);
+            for (size_t g = 1; g < groups.size(); ++g) { extra.push_back(groups[g].second); extra_owner.push_back(owner[i]); }
         }
     }
-    bind.insert(bind.end(), extra.begin(), extra.end());
-    uint32_t at = 0;
+    // per body: its bind 0, its cell binds, then the groups HandleConvexIsland split off them -- the order of the one-body call
+    uint32_t at = 0, nc = 0;
     compound_off[0] = 0;
-    for (size_t i = 0; i < bind.size(); ++i)
+    auto emit = [&](const std::set<int>& s) { for (int p : s) compound_piece[at++] = p; compound_off[++nc] = at; };
+    for (uint32_t b = 0; b < nb; ++b)
     {
-        for (int p : bind[i]) compound_piece[at++] = p;
-        compound_off[i + 1] = at;
+        if (body_compound_off) body_compound_off[b] = nc;
+        for (size_t i = 0; i < bind.size(); ++i) if (owner[i] == b) emit(bind[i]);
+        for (size_t i = 0; i < extra.size(); ++i) if (extra_owner[i] == b) emit(extra[i]);
     }
-    *n_compounds = (uint32_t)bind.size();
+    if (body_compound_off) body_compound_off[nb] = nc;
+    *n_compounds = nc;
+    return SURTR_OK;
+}
+
+// ---- the out-of-sphere mask of the pieces a click is about to break (k_scene_outside) ----
+// The listed compounds' pieces, in the order given, each compound in resident order; SURTR_E_CAPACITY for a Convex k_scene_outside
+// has no room for.  Nothing has been enqueued when an error is returned.
+static int outside_list(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, std::vector<uint32_t>& list)
+{
+    if (!ctx || !n_targets || !compounds) return SURTR_E_INVALID;
+    if (!ctx->n_pieces || ctx->scene_off.size() < 2 || ctx->scene_off.back() != ctx->n_pieces) return SURTR_E_STATE;
+    list.clear();
+    for (uint32_t t = 0; t < n_targets; ++t)
+    {
+        if ((size_t)compounds[t] + 1 >= ctx->scene_off.size()) return SURTR_E_INVALID;
+        for (uint32_t p = ctx->scene_off[compounds[t]]; p < ctx->scene_off[compounds[t] + 1]; ++p)
+        {
+            if (ctx->h_vo[1][p + 1] - ctx->h_vo[1][p] > RG_MAXH || ctx->h_ho[1][p + 1] - ctx->h_ho[1][p] > RG_MAXH)
+            {
+                ctx->err = "surtr_scene_outside: a Convex of more than " + std::to_string(RG_MAXH) + " half-edges";
+                return SURTR_E_CAPACITY;
+            }
+            list.push_back(p);
+        }
+    }
+    return SURTR_OK;
+}
+
+// Enqueues the list's upload and the kernel on the context's stream.  The list goes through a buffer the context keeps, which grows
+// (an allocation, and a free of the smaller one, which waits for the device) only when a call lists more pieces than any before it.
+// Its source is pageable host memory: the runtime has staged such a copy when hipMemcpyAsync returns, as for the tables of
+// surtr_scene_commit and scene_sync_device, so the caller's vector may go at once.
+static int outside_enqueue(surtr_ctx* ctx, const std::vector<uint32_t>& list, uint32_t n_sphere, const float* dev_sphere_points, const float origin[3],
+                           float radius, uint8_t* dev_outside)
+{
+    const uint32_t n = (uint32_t)list.size();
+    (void)hipSetDevice(ctx->device);
+    const int rc = ctx->d_outside_list.grow(ctx, n, (size_t)n + n / 4 + 64);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_outside_list.p, list.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    const PieceSet& C = ctx->cset;
+    hipLaunchKernelGGL(k_scene_outside, dim3(n), dim3(SURTR_LANES), 0, ctx->stream, n, (const uint32_t*)ctx->d_outside_list.p, (const float*)C.pos.p,
+                       (const uint32_t*)C.loff.p, (const int32_t*)C.nbr.p, (const uint32_t*)C.vo.p, n_sphere, dev_sphere_points, origin[0], origin[1], origin[2],
+                       radius, dev_outside);
+    HIPCHK(hipGetLastError());
+    return SURTR_OK;
+}
+
+extern "C" int surtr_scene_outside_dev(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t n_sphere, const float* dev_sphere_points,
+                                       const float origin[3], float radius, uint8_t* dev_outside, size_t capacity_bytes)
+{
+    if (!ctx || !origin || !dev_outside || (n_sphere && !dev_sphere_points)) return SURTR_E_INVALID;
+    std::vector<uint32_t> list;
+    const int rc = outside_list(ctx, n_targets, compounds, list);
+    if (rc) return rc;
+    if (capacity_bytes < list.size()) return SURTR_E_CAPACITY;
+    return outside_enqueue(ctx, list, n_sphere, dev_sphere_points, origin, radius, dev_outside);
+}
+
+extern "C" int surtr_scene_outside(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t n_sphere, const float* sphere_points,
+                                   const float origin[3], float radius, uint32_t cap, uint32_t* n, uint8_t* outside)
+{
+    if (!ctx || !n || !origin || (n_sphere && !sphere_points)) return SURTR_E_INVALID;
+    std::vector<uint32_t> list;
+    int rc = outside_list(ctx, n_targets, compounds, list);
+    if (rc) return rc;
+    *n = (uint32_t)list.size();
+    if (!outside) return SURTR_OK;
+    if (cap < *n) return SURTR_E_CAPACITY;
+    (void)hipSetDevice(ctx->device);
+    DevBuf<float> d_sph; DevBuf<uint8_t> d_out;
+    if (d_sph.grow(ctx, 3 * (size_t)n_sphere + 3) || d_out.grow(ctx, std::max<size_t>(*n, 4))) return SURTR_E_HIP;
+    if (n_sphere) HIPCHK(hipMemcpyAsync(d_sph.p, sphere_points, (size_t)n_sphere * 12, hipMemcpyHostToDevice, ctx->stream));
+    rc = outside_enqueue(ctx, list, n_sphere, d_sph.p, origin, radius, d_out.p);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(outside, d_out.p, *n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));      // (also: the temporaries are freed below)
     return SURTR_OK;
 }

@@ -6,8 +6,10 @@
 //   surtr_scene_set_poses / _get_poses / _apply_pose   a rigid pose per compound (WorldMatrix, :347-352), kept on the host next to the
 //                                                 table; the posed queries (query_dev.hip) read it, apply_pose bakes it in
 //   surtr_scene_fracture_event(_async)            the event over the pieces of one compound
-//   surtr_scene_commit                            erase the compound, push back what it broke into (:1856-1875): one gather
-//                                                 kernel from the old pieces and the event arena into spare buffers, then a swap
+//   surtr_scene_apply_poses / _fracture_bodies(_async)   the same for every body a click hits at once: one bake, one event whose pair
+//                                                 list is target-major (the mask of surtr_scene_outside, regroup_dev.hip)
+//   surtr_scene_commit                            erase the event's compound(s), push back what they broke into (:1856-1875): one
+//                                                 gather kernel from the old pieces and the event arena into spare buffers, then a swap
 // The layout of the new pieces is laid out on the host from the small tables (piece offsets, fragment records), as
 // surtr_pieces_from_event does; no solid leaves HBM.
 #include <cmath>
@@ -115,13 +117,37 @@ int surtr_scene_apply_pose(surtr_ctx* ctx, uint32_t compound)
     return SURTR_OK;
 }
 
+int surtr_scene_apply_poses(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds)
+{
+    if (!ctx || (n_targets && !compounds)) return SURTR_E_INVALID;
+    if (!ctx->n_pieces) return SURTR_E_STATE;
+    for (uint32_t t = 0; t < n_targets; ++t) if ((size_t)compounds[t] + 1 >= ctx->scene_off.size()) return SURTR_E_INVALID;
+    // the compounds whose pose is not bit for bit the identity, each once (a compound named twice is baked once, as two calls of
+    // surtr_scene_apply_pose would)
+    std::vector<uint32_t> moved, p0, np; std::vector<float> w;
+    for (uint32_t t = 0; t < n_targets && !ctx->scene_pose.empty(); ++t)
+    {
+        const uint32_t c = compounds[t];
+        const float* W = ctx->scene_pose.data() + 16 * (size_t)c;
+        if (memcmp(W, IDENTITY, 64) == 0 || std::find(moved.begin(), moved.end(), c) != moved.end()) continue;
+        moved.push_back(c); p0.push_back(ctx->scene_off[c]); np.push_back(ctx->scene_off[c + 1] - ctx->scene_off[c]);
+        for (uint32_t k = 0; k < np.back(); ++k) w.insert(w.end(), W, W + 16);
+    }
+    if (moved.empty()) return SURTR_OK;      // (nothing at all: a pending event stays committable)
+    const int rc = transform_ranges(ctx, (uint32_t)moved.size(), p0.data(), np.data(), w.data());
+    if (rc) return rc;
+    for (uint32_t c : moved) memcpy(ctx->scene_pose.data() + 16 * (size_t)c, IDENTITY, 64);
+    ctx->scene_dev_stale = true;
+    return SURTR_OK;
+}
+
 int surtr_scene_set_compounds(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* compound_off)
 {
     if (!ctx) return SURTR_E_INVALID;
     if (!ctx->n_pieces) return SURTR_E_STATE;
     if (!valid_table(n_compounds, compound_off, ctx->n_pieces)) return SURTR_E_INVALID;
     ctx->scene_off.assign(compound_off, compound_off + n_compounds + 1);
-    ctx->scene_event_compound = -1;      // (an event's compound number belongs to the table it was given in)
+    ctx->scene_event_compound.clear();   // (an event's compound numbers belong to the table they were given in)
     scene_reset_poses(ctx);              // (and so does a pose)
     return SURTR_OK;
 }
@@ -160,7 +186,7 @@ int surtr_scene_fracture_event_async(surtr_ctx* ctx, uint32_t compound, uint32_t
     if (outside) { mask.assign(ctx->n_pieces, 0); memcpy(mask.data() + p0, outside, m); }
     const int rc = surtr_event_pairs_masked(ctx, nc * m, cell.data(), piece.data(), outside ? mask.data() : nullptr, flags);
     if (rc) return rc;
-    ctx->scene_event_compound = (int)compound;
+    ctx->scene_event_compound.assign(1, compound);
     return SURTR_OK;
 }
 
@@ -175,12 +201,59 @@ int surtr_scene_fracture_event(surtr_ctx* ctx, uint32_t compound, uint32_t cell_
     return rc;
 }
 
+int surtr_scene_fracture_bodies_async(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t cell_begin, uint32_t cell_end,
+                                      const uint8_t* outside, uint32_t flags)
+{
+    if (!ctx) return SURTR_E_INVALID;
+    if (!ctx->n_pieces || !ctx->planes_ready) return SURTR_E_STATE;
+    if (!n_targets || !compounds || cell_end > ctx->n_cells || cell_begin > cell_end) return SURTR_E_INVALID;
+    uint64_t total = 0;
+    for (uint32_t t = 0; t < n_targets; ++t)
+    {
+        if ((size_t)compounds[t] + 1 >= ctx->scene_off.size() || (t && compounds[t] >= compounds[t - 1])) return SURTR_E_INVALID;      // strictly descending
+        total += ctx->scene_off[compounds[t] + 1] - ctx->scene_off[compounds[t]];
+    }
+    const uint32_t nc = cell_end - cell_begin;
+    if ((uint64_t)nc * total > 0xFFFFFFFFull) return SURTR_E_INVALID;
+    // the pairs target-major in the order given, cell-major over the target's pieces within a target: every target's fragments come
+    // out as its own surtr_scene_fracture_event gives them; the mask is spread over all resident pieces
+    std::vector<uint32_t> cell, piece;
+    cell.reserve((size_t)nc * total); piece.reserve((size_t)nc * total);
+    std::vector<uint8_t> mask;
+    if (outside) mask.assign(ctx->n_pieces, 0);
+    size_t at = 0;
+    for (uint32_t t = 0; t < n_targets; ++t)
+    {
+        const uint32_t p0 = ctx->scene_off[compounds[t]], m = ctx->scene_off[compounds[t] + 1] - p0;
+        for (uint32_t c = 0; c < nc; ++c)
+            for (uint32_t q = 0; q < m; ++q) { cell.push_back(cell_begin + c); piece.push_back(p0 + q); }
+        if (outside) memcpy(mask.data() + p0, outside + at, m);
+        at += m;
+    }
+    const std::vector<uint32_t> targets(compounds, compounds + n_targets);      // (launch_event clears the context's list)
+    const int rc = surtr_event_pairs_masked(ctx, (uint32_t)cell.size(), cell.data(), piece.data(), outside ? mask.data() : nullptr, flags);
+    if (rc) return rc;
+    ctx->scene_event_compound = targets;
+    return SURTR_OK;
+}
+
+int surtr_scene_fracture_bodies(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t cell_begin, uint32_t cell_end,
+                                const uint8_t* outside, uint32_t flags, surtr_counts* counts)
+{
+    int rc = surtr_scene_fracture_bodies_async(ctx, n_targets, compounds, cell_begin, cell_end, outside, flags);
+    if (rc) return rc;
+    surtr_counts c;
+    rc = surtr_event_counts(ctx, &c);
+    if (counts) *counts = c;
+    return rc;
+}
+
 int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* compound_off, const int32_t* compound_piece, uint32_t* n_pieces_out,
                        uint32_t* first_new_compound, uint32_t* n_new_compounds, int32_t* src_out)
 {
     if (!ctx || !compound_off || (n_compounds && compound_off[n_compounds] && !compound_piece)) return SURTR_E_INVALID;
-    if (!ctx->n_pieces || !ctx->have_event || !ctx->frags_of_pieces || ctx->scene_event_compound < 0 ||
-        (size_t)ctx->scene_event_compound + 1 >= ctx->scene_off.size())
+    if (!ctx->n_pieces || !ctx->have_event || !ctx->frags_of_pieces || ctx->scene_event_compound.empty() ||
+        (size_t)ctx->scene_event_compound[0] + 1 >= ctx->scene_off.size())      // (descending: the first is the highest)
         return SURTR_E_STATE;
     (void)hipSetDevice(ctx->device);
     Timer timer(ctx);
@@ -189,9 +262,13 @@ int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* com
     surtr_counts c;
     if (surtr_event_counts(ctx, &c) != SURTR_OK) return SURTR_E_STATE;      // the event failed: nothing to commit
     // ---- everything is checked and laid out before anything is written
-    const uint32_t np = ctx->n_pieces, target = (uint32_t)ctx->scene_event_compound, t0 = ctx->scene_off[target], t1 = ctx->scene_off[target + 1];
-    std::vector<uint32_t> skipped;
-    for (uint32_t p = t0; p < t1 && ctx->last_outside.size() == np; ++p) if (ctx->last_outside[p]) skipped.push_back(p);
+    const uint32_t np = ctx->n_pieces;
+    const std::vector<uint32_t> targets = ctx->scene_event_compound;      // strictly descending
+    std::vector<uint8_t> is_target(ctx->scene_off.size() - 1, 0);
+    for (uint32_t t : targets) is_target[t] = 1;
+    std::vector<uint32_t> skipped;      // of every target, ascending: surtr_event_regroup's numbers
+    for (uint32_t k = 0; k + 1 < ctx->scene_off.size() && ctx->last_outside.size() == np; ++k)
+        for (uint32_t p = ctx->scene_off[k]; is_target[k] && p < ctx->scene_off[k + 1]; ++p) if (ctx->last_outside[p]) skipped.push_back(p);
     const uint32_t n_skip = (uint32_t)skipped.size(), n_in = n_skip + c.n_frag;
     if (compound_off[0] != 0u || compound_off[n_compounds] != n_in) return SURTR_E_INVALID;
     {
@@ -223,10 +300,10 @@ int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* com
             dv[s].push_back(dv[s].back() + (ctx->h_vo[s][p + 1] - ctx->h_vo[s][p])); dh[s].push_back(dh[s].back() + (ctx->h_ho[s][p + 1] - ctx->h_ho[s][p]));
         }
     };
-    // the pieces of every other compound first, in their old order: the compounds above the target move down by one
+    // the pieces of every other compound first, in their old order: a compound moves down by the number of targets below it
     for (uint32_t k = 0; k + 1 < ctx->scene_off.size(); ++k)
     {
-        if (k == target) continue;
+        if (is_target[k]) continue;
         for (uint32_t p = ctx->scene_off[k]; p < ctx->scene_off[k + 1]; ++p) push_old(p);
         table.push_back((uint32_t)src.size());
     }
@@ -300,7 +377,7 @@ int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* com
     std::vector<float> pose = std::move(ctx->scene_pose);
     if (!pose.empty())
     {
-        pose.erase(pose.begin() + 16 * (size_t)target, pose.begin() + 16 * (size_t)(target + 1u));
+        for (uint32_t target : targets) pose.erase(pose.begin() + 16 * (size_t)target, pose.begin() + 16 * (size_t)(target + 1u));      // (highest first)
         for (size_t k = first_new; k + 1 < table.size(); ++k) pose.insert(pose.end(), IDENTITY, IDENTITY + 16);
     }
     set_piece_stats(ctx, n, dv[0].data(), dh[0].data(), dv[1].data(), dh[1].data());

@@ -320,7 +320,10 @@ struct surtr_ctx
     // pieces leaves one compound holding all of them (set_piece_stats)
     std::vector<uint32_t> scene_off;
     std::vector<uint32_t> h_vo[2], h_ho[2];              // vertex / ring-entry offsets of the resident pieces (0 = Mesh, 1 = Convex), host copies
-    int scene_event_compound = -1;                       // compound the last event ran over (surtr_scene_fracture_event); -1: none, or committed
+    // the compounds the last event ran over, strictly descending (surtr_scene_fracture_event: one; surtr_scene_fracture_bodies: the
+    // click's targets); empty: none, or committed
+    std::vector<uint32_t> scene_event_compound;
+    DevBuf<uint32_t> d_outside_list;                     // surtr_scene_outside(_dev): the pieces it was asked about
     // per-body poses (surtr_scene_set_poses): 16 floats per compound, x' = A x + b as surtr_transform_pieces takes them; empty: every
     // pose is the identity.  The device copy (scene_sync_device below) is made by the first query after the poses or the table change.
     std::vector<float> scene_pose;
@@ -436,6 +439,9 @@ void set_piece_stats(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const uint
 int finish_upload(surtr_ctx* ctx, uint32_t n, bool check);
 // Poly::Transform of resident pieces [p0, p0 + n) by world[16 * (p - p0) ..], the derived data again; the other pieces keep their bits
 int transform_range(surtr_ctx* ctx, uint32_t p0, uint32_t n, const float* world);
+// the same for several disjoint ranges [p0[r], p0[r] + n[r]), world holding the matrices of range 0's pieces, then range 1's, ...:
+// one k_transform per range and set, the derived data once per set
+int transform_ranges(surtr_ctx* ctx, uint32_t n_ranges, const uint32_t* p0, const uint32_t* n, const float* world);
 }
 // The scene's tables as the posed queries (query_dev.hip) and surtr_scene_mass (mass_dev.hip) read them on the device.  Fields only:
 // every translation unit that needs them brings them up to date itself, on the context's stream, when the host's have changed.
@@ -476,9 +482,6 @@ static inline int scene_sync_device(surtr_ctx* ctx, SceneDev* out)
 
 // an event over an explicit pair list with an `outside` mask over all resident pieces (surtr_hip.hip); NULL: no mask
 int surtr_event_pairs_masked(surtr_ctx* ctx, uint32_t n_pairs, const uint32_t* pair_cell, const uint32_t* pair_piece, const uint8_t* outside, uint32_t flags);
-// surtr_event_regroup given the resident pieces the event skipped, ascending (regroup_dev.hip)
-int surtr_event_regroup_skipped(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, int partial, uint32_t n_sphere, const float* sphere_points,
-                                const float origin[3], float radius, uint32_t* n_pieces, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece);
 
 // placement of cell groups with per-group scale / shift already in device memory (surtr_hip.hip)
 extern "C" int surtr_place_cells_groups_dev(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* group_cell_off, const float* d_scale3, const float* d_shift3);

@@ -4042,7 +4042,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     PROF_END(4);
     HIPCHK(hipGetLastError());
     ctx->have_event = true; ctx->last_flags = flags; ctx->last_current = false; ctx->frags_of_pieces = true;
-    ctx->scene_event_compound = -1;      // (surtr_scene_fracture_event sets it after this)
+    ctx->scene_event_compound.clear();      // (surtr_scene_fracture_event / _bodies set it after this)
     return SURTR_OK;
 }
 

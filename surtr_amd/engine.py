@@ -332,12 +332,25 @@ class Engine:
         """surtr_event_regroup: bind sets + MergeOutOfImpact + HandleConvexIsland of the last event, on the device."""
         sp = np.zeros((0, 3), np.float32) if sphere_points is None else np.ascontiguousarray(sphere_points, np.float32).reshape(-1, 3)
         org = np.ascontiguousarray(origin, np.float32)
-        n, nc = ctypes.c_uint32(), ctypes.c_uint32()
+        n, nc, nb = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
         args = [self._h, ctypes.c_int(int(partial)), ctypes.c_uint32(sp.shape[0]), _p(sp), _p(org), ctypes.c_float(radius)]
-        self._ck(lib().surtr_event_regroup(*args, ctypes.byref(n), ctypes.byref(nc), None, None))
-        co = np.zeros(n.value + 2, np.uint32); cp = np.zeros(max(n.value, 1), np.int32)
+        # (the sizes: after scene_fracture_bodies every body has a bind 0 of its own, so n_pieces + n_bodies + 1 offsets)
+        self._ck(lib().surtr_event_regroup_bodies(*args, ctypes.byref(n), ctypes.byref(nc), None, None, ctypes.byref(nb), None))
+        co = np.zeros(n.value + nb.value + 1, np.uint32); cp = np.zeros(max(n.value, 1), np.int32)
         self._ck(lib().surtr_event_regroup(*args, ctypes.byref(n), ctypes.byref(nc), _p(co), _p(cp)))
         return co[:nc.value + 1].copy(), cp[:co[nc.value]].copy()
+
+    def event_regroup_bodies(self, partial=False, sphere_points=None, origin=(0, 0, 0), radius=1.0):
+        """surtr_event_regroup_bodies: event_regroup with the compounds of every body of the event -> (compound_off, compound_piece,
+        body_compound_off): body b (target b of scene_fracture_bodies) owns compounds [body_off[b], body_off[b + 1])."""
+        sp = np.zeros((0, 3), np.float32) if sphere_points is None else np.ascontiguousarray(sphere_points, np.float32).reshape(-1, 3)
+        org = np.ascontiguousarray(origin, np.float32)
+        n, nc, nb = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        args = [self._h, ctypes.c_int(int(partial)), ctypes.c_uint32(sp.shape[0]), _p(sp), _p(org), ctypes.c_float(radius)]
+        self._ck(lib().surtr_event_regroup_bodies(*args, ctypes.byref(n), ctypes.byref(nc), None, None, ctypes.byref(nb), None))
+        co = np.zeros(n.value + nb.value + 1, np.uint32); cp = np.zeros(max(n.value, 1), np.int32); bo = np.zeros(nb.value + 1, np.uint32)
+        self._ck(lib().surtr_event_regroup_bodies(*args, ctypes.byref(n), ctypes.byref(nc), _p(co), _p(cp), ctypes.byref(nb), _p(bo)))
+        return co[:nc.value + 1].copy(), cp[:co[nc.value]].copy(), bo
 
     def regroup_stats(self):
         """What the last event_regroup counted (include/surtr_hip.h: surtr_regroup_stats); no synchronisation."""
@@ -566,6 +579,55 @@ class Engine:
         om = None if outside is None else np.ascontiguousarray(outside, np.uint8)
         self._ck(lib().surtr_scene_fracture_event_async(self._h, ctypes.c_uint32(int(compound)), ctypes.c_uint32(cell_begin),
                                                         ctypes.c_uint32(cell_end), _p(om), ctypes.c_uint32(flags)))
+
+    def _bodies_mask(self, compounds, outside):
+        t = np.ascontiguousarray(compounds, np.uint32).reshape(-1)
+        om = None if outside is None else np.ascontiguousarray(outside, np.uint8).reshape(-1)
+        if om is not None:
+            co = self.scene_compounds()
+            if any(int(c) >= co.shape[0] - 1 for c in t) or om.shape[0] != sum(int(co[int(c) + 1]) - int(co[int(c)]) for c in t):
+                raise SurtrError(E_INVALID, "outside holds %d bytes" % om.shape[0])
+        return t, om
+
+    def scene_fracture_bodies(self, compounds, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
+        """surtr_scene_fracture_bodies: one event over the pieces of several compounds (strictly descending); outside: one byte per
+        piece of the listed compounds, concatenated in the order given (what scene_outside returns)."""
+        t, om = self._bodies_mask(compounds, outside)
+        c = Counts()
+        self._ck(lib().surtr_scene_fracture_bodies(self._h, ctypes.c_uint32(t.shape[0]), _p(t), ctypes.c_uint32(cell_begin), ctypes.c_uint32(cell_end),
+                                                   _p(om), ctypes.c_uint32(flags), ctypes.byref(c)))
+        return c
+
+    def scene_fracture_bodies_async(self, compounds, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
+        t, om = self._bodies_mask(compounds, outside)
+        self._ck(lib().surtr_scene_fracture_bodies_async(self._h, ctypes.c_uint32(t.shape[0]), _p(t), ctypes.c_uint32(cell_begin),
+                                                         ctypes.c_uint32(cell_end), _p(om), ctypes.c_uint32(flags)))
+
+    def scene_outside(self, compounds, sphere_points, origin, radius, capacity=None):
+        """surtr_scene_outside: Surtr::ConvexOutOfSphere of every resident Convex of the listed compounds, on the device -> uint8, one
+        per piece, compound after compound in the order given.  capacity: the bytes to offer (None: what the call asks for)."""
+        t = np.ascontiguousarray(compounds, np.uint32).reshape(-1)
+        sp = np.zeros((0, 3), np.float32) if sphere_points is None else np.ascontiguousarray(sphere_points, np.float32).reshape(-1, 3)
+        org = np.ascontiguousarray(origin, np.float32)
+        n = ctypes.c_uint32()
+        args = [self._h, ctypes.c_uint32(t.shape[0]), _p(t), ctypes.c_uint32(sp.shape[0]), _p(sp), _p(org), ctypes.c_float(radius)]
+        self._ck(lib().surtr_scene_outside(*args, ctypes.c_uint32(0), ctypes.byref(n), None))
+        cap = n.value if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 1), np.uint8)
+        self._ck(lib().surtr_scene_outside(*args, ctypes.c_uint32(cap), ctypes.byref(n), _p(out)))
+        return out[:n.value].copy()
+
+    def scene_outside_dev(self, compounds, n_sphere, dev_sphere_points, origin, radius, dev_outside, capacity):
+        """surtr_scene_outside_dev: cloud and mask in device memory, on the context's stream; nothing is read back."""
+        t = np.ascontiguousarray(compounds, np.uint32).reshape(-1)
+        org = np.ascontiguousarray(origin, np.float32)
+        self._ck(lib().surtr_scene_outside_dev(self._h, ctypes.c_uint32(t.shape[0]), _p(t), ctypes.c_uint32(int(n_sphere)), ctypes.c_void_p(dev_sphere_points),
+                                               _p(org), ctypes.c_float(radius), ctypes.c_void_p(dev_outside), ctypes.c_size_t(capacity)))
+
+    def scene_apply_poses(self, compounds):
+        """surtr_scene_apply_poses: scene_apply_pose for several compounds with the derived data rebuilt once."""
+        t = np.ascontiguousarray(compounds, np.uint32).reshape(-1)
+        self._ck(lib().surtr_scene_apply_poses(self._h, ctypes.c_uint32(t.shape[0]), _p(t)))
 
     def scene_commit(self, compound_off, compound_piece):
         """surtr_scene_commit with the compounds event_regroup returned for the last scene event: the event's compound is erased,

@@ -13,6 +13,8 @@
 //                 --radial: every body the sphere of radius R / 2 touches and whose mass is above 1e-4) has its pose baked in and is
 //                 broken.  After each click one JSON line: the piece and compound hit, the body mask of the impact sphere, the
 //                 compounds hit and made, the table, the poses and the body masses after the click.
+// --one-event (with --scene-clicks or --body-clicks): every compound a click hits goes through ONE event, one regrouping and one
+//                 commit (ExecuteFractureRoutine over several compounds) instead of one of each per compound; the JSON is the same.
 // --pick: the event's fragments become the resident pieces (piece k in compound k / 2) and the ray is cast into them as
 // OnMouseDown does (Src/Surtr.cpp:207-240): the hit, the impact position, the overlap mask and the affected compounds, as JSON.
 // --ach runs Surtr::PrepareFracture end to end (ACH convex instead of the plain 2x box).
@@ -329,7 +331,7 @@ static void pick(FractureEngine& eng, const std::vector<Fragment>& frags, const 
 }
 
 // --scene-clicks: OnMouseDown per click on the resident scene; one JSON line per click.
-static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float, 6>>& clicks, float impact_radius)
+static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float, 6>>& clicks, float impact_radius, bool one_event)
 {
     const uint32_t n0 = eng.CompoundFromLastEvent();
     std::vector<uint32_t> off;
@@ -352,7 +354,7 @@ static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float
         args.PartialFracture = true; args.RadialMode = false; args.ImpactRadius = impact_radius;
         const surtr_ray_hit hit = eng.Raycast(o, d);
         std::vector<int> hitc;
-        const std::vector<int> made = eng.OnMouseDown(o, d, args, impact_radius, cloud, &hitc);
+        const std::vector<int> made = eng.OnMouseDown(o, d, args, impact_radius, cloud, &hitc, one_event);
         const std::vector<uint32_t> table = eng.SceneCompounds();
         std::vector<std::set<int>> bind(table.size() - 1);
         for (size_t c = 0; c + 1 < table.size(); ++c) for (uint32_t p = table[c]; p < table[c + 1]; ++p) bind[c].insert((int)p);
@@ -384,7 +386,7 @@ static std::vector<Vector3> lattice_cloud()
 
 // --body-clicks: OnMouseDownBodies per click on the posed scene; one JSON line per click.
 static void body_clicks(FractureEngine& eng, const std::vector<std::array<float, 6>>& clicks, const std::vector<std::pair<int, Matrix>>& poses,
-                        float impact_radius, bool radial)
+                        float impact_radius, bool radial, bool one_event)
 {
     const uint32_t n0 = eng.CompoundFromLastEvent();
     std::vector<uint32_t> off;
@@ -411,7 +413,7 @@ static void body_clicks(FractureEngine& eng, const std::vector<std::array<float,
         surtr_scene_ray_hit hit;
         std::vector<uint8_t> body;
         std::vector<int> hitc;
-        const std::vector<int> made = eng.OnMouseDownBodies(o, d, args, impact_radius, cloud, &hitc, &hit, &body);      // (what the click acted on)
+        const std::vector<int> made = eng.OnMouseDownBodies(o, d, args, impact_radius, cloud, &hitc, &hit, &body, one_event);      // (what the click acted on)
         const std::vector<uint32_t> table = eng.SceneCompounds();
         const std::vector<Matrix> world = eng.Poses();
         const std::vector<surtr_mass> bm = eng.BodyMassProperties(1);
@@ -442,7 +444,7 @@ int main(int argc, char** argv)
     int cells = 8, nu = 250, nv = 200;
     std::vector<std::array<float, 6>> clicks, bclicks;
     std::vector<std::pair<int, Matrix>> poses;
-    bool radial = false;
+    bool radial = false, one_event = false;
     bool ach = false, do_pick = false; float in_scale = 1.f, pick_ray[6] = {0, 0, 0, 1, 0, 0}, impact_radius = 1.f;
     for (int i = 1; i < argc; ++i)
     {
@@ -457,6 +459,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--api-dump") && i + 1 < argc) dump = argv[++i];
         else if (!strcmp(argv[i], "--impact-radius") && i + 1 < argc) impact_radius = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--radial")) radial = true;
+        else if (!strcmp(argv[i], "--one-event")) one_event = true;
         else if (!strcmp(argv[i], "--scene-poses") && i + 1 < argc)
         {
             const char* c = argv[++i];
@@ -534,8 +537,8 @@ int main(int argc, char** argv)
                "\"conv_verts\": %u, \"indices\": %u}\n", mesh.c_str(), verts.size(), tris.size() / 3, cells, c.n_frag, c.mesh_verts,
                c.mesh_nbrs, c.conv_verts, c.n_idx);
         if (do_pick) pick(eng, frags, pick_ray, impact_radius);
-        if (!clicks.empty()) scene_clicks(eng, clicks, impact_radius);
-        else if (!bclicks.empty()) body_clicks(eng, bclicks, poses, impact_radius, radial);
+        if (!clicks.empty()) scene_clicks(eng, clicks, impact_radius, one_event);
+        else if (!bclicks.empty()) body_clicks(eng, bclicks, poses, impact_radius, radial, one_event);
         if (!obj.empty())
         {
             FILE* f = fopen(obj.c_str(), "w");

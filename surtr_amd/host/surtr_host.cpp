@@ -679,11 +679,83 @@ std::vector<int> FractureEngine::ExecuteFractureRoutine(int compound, const std:
     return made;
 }
 
+static std::vector<uint32_t> compound_numbers(const std::vector<int>& compounds, const char* who)
+{
+    std::vector<uint32_t> out;
+    for (int c : compounds)
+    {
+        if (c < 0) throw Error(SURTR_E_INVALID, std::string(who) + ": no such compound");
+        out.push_back((uint32_t)c);
+    }
+    return out;
+}
+
+std::vector<uint8_t> FractureEngine::OutsideMask(const std::vector<int>& compounds, const FractureArgs& args, const std::vector<Vector3>& cloud)
+{
+    const std::vector<uint32_t> t = compound_numbers(compounds, "OutsideMask");
+    const std::vector<float> fc = flat_points(cloud);
+    const float org[3] = {args.ImpactPosition.x, args.ImpactPosition.y, args.ImpactPosition.z};
+    uint32_t n = 0;
+    check(surtr_scene_outside(ctx_, (uint32_t)t.size(), t.data(), (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, 0, &n, nullptr), "surtr_scene_outside");
+    std::vector<uint8_t> mask(n + 1);
+    check(surtr_scene_outside(ctx_, (uint32_t)t.size(), t.data(), (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, n, &n, mask.data()), "surtr_scene_outside");
+    mask.resize(n);
+    return mask;
+}
+
+std::vector<int> FractureEngine::ExecuteFractureRoutine(const std::vector<int>& compounds, float maxAxisScale, const FractureArgs& args,
+                                                        const std::vector<Vector3>& spherePointCloud)
+{
+    std::vector<int> sorted(compounds);
+    std::sort(sorted.begin(), sorted.end(), [](int a, int b) { return a > b; });
+    if (sorted.empty()) throw Error(SURTR_E_INVALID, "ExecuteFractureRoutine: no compound");
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw Error(SURTR_E_INVALID, "ExecuteFractureRoutine: a compound is named twice");
+    const std::vector<uint32_t> t = compound_numbers(sorted, "ExecuteFractureRoutine");
+    ApplyPoses(sorted);
+    // DoFracture's placement (:1890-1915)
+    const float s2 = maxAxisScale * 2.f;
+    SetRefittingPointLimit(args.RefittingPointLimit);
+    PlacePattern(Vector3(s2, s2, s2), args.ImpactPosition);
+    std::vector<Vector3> cloud = spherePointCloud;
+    for (auto& v : cloud)
+    {
+        v.x *= args.ImpactRadius; v.y *= args.ImpactRadius; v.z *= args.ImpactRadius;
+        v.x += args.ImpactPosition.x; v.y += args.ImpactPosition.y; v.z += args.ImpactPosition.z;
+    }
+    const std::vector<float> fc = flat_points(cloud);
+    const float org[3] = {args.ImpactPosition.x, args.ImpactPosition.y, args.ImpactPosition.z};
+    std::vector<uint8_t> mask;
+    if (args.PartialFracture) mask = OutsideMask(sorted, args, cloud);
+    const bool any = std::find_if(mask.begin(), mask.end(), [](uint8_t o) { return o != 0; }) != mask.end();
+    check(surtr_scene_fracture_bodies(ctx_, (uint32_t)t.size(), t.data(), 0, n_cells_, any ? mask.data() : nullptr, 0u, &counts_), "surtr_scene_fracture_bodies");
+    const int partial = args.PartialFracture ? 1 : 0;
+    uint32_t np = 0, nc = 0, nb = 0;
+    check(surtr_event_regroup_bodies(ctx_, partial, (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, &np, &nc, nullptr, nullptr, &nb, nullptr),
+          "surtr_event_regroup_bodies");
+    std::vector<uint32_t> off((size_t)np + nb + 1), body(nb + 1);
+    std::vector<int32_t> piece(np + 1);
+    check(surtr_event_regroup_bodies(ctx_, partial, (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, &np, &nc, off.data(), piece.data(), &nb, body.data()),
+          "surtr_event_regroup_bodies");
+    check(surtr_event_refit(ctx_), "surtr_event_refit");
+    check(surtr_event_counts(ctx_, &counts_), "surtr_event_counts");
+    flagged_ = FlaggedUnits();
+    flagged_.n_failed = counts_.n_failed;
+    if (counts_.n_failed && !allow_flagged_)
+        throw Error(SURTR_E_TOPOLOGY, "ExecuteFractureRoutine: the event flagged " + std::to_string(counts_.n_failed) + " unit(s); nothing was committed");
+    uint32_t n = 0, first = 0, n_new = 0;
+    check(surtr_scene_commit(ctx_, nc, off.data(), piece.data(), &n, &first, &n_new, nullptr), "surtr_scene_commit");
+    n_pieces_ = n;
+    std::vector<int> made(n_new);
+    for (uint32_t k = 0; k < n_new; ++k) made[k] = (int)(first + k);
+    return made;
+}
+
 std::vector<int> FractureEngine::OnMouseDown(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
-                                             const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds)
+                                             const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds, bool oneEvent)
 {
     std::vector<int> hit = PickImpact(origin, dir, args);
     if (hitCompounds) *hitCompounds = hit;
+    if (oneEvent) return hit.empty() ? std::vector<int>() : ExecuteFractureRoutine(hit, maxAxisScale, args, spherePointCloud);
     std::vector<int> made;
     // descending: a commit moves only the compounds above its target, and those have been dealt with
     for (auto it = hit.rbegin(); it != hit.rend(); ++it)
@@ -717,6 +789,12 @@ void FractureEngine::ApplyPose(int compound)
 {
     if (compound < 0) throw Error(SURTR_E_INVALID, "ApplyPose: no such compound");
     check(surtr_scene_apply_pose(ctx_, (uint32_t)compound), "surtr_scene_apply_pose");
+}
+
+void FractureEngine::ApplyPoses(const std::vector<int>& compounds)
+{
+    const std::vector<uint32_t> t = compound_numbers(compounds, "ApplyPoses");
+    check(surtr_scene_apply_poses(ctx_, (uint32_t)t.size(), t.data()), "surtr_scene_apply_poses");
 }
 
 surtr_scene_ray_hit FractureEngine::RaycastScene(const Vector3& origin, const Vector3& dir, float maxDist)
@@ -767,10 +845,11 @@ std::vector<int> FractureEngine::PickBodies(const Vector3& origin, const Vector3
 
 std::vector<int> FractureEngine::OnMouseDownBodies(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
                                                    const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds,
-                                                   surtr_scene_ray_hit* hitOut, std::vector<uint8_t>* bodyMask)
+                                                   surtr_scene_ray_hit* hitOut, std::vector<uint8_t>* bodyMask, bool oneEvent)
 {
     std::vector<int> hit = PickBodies(origin, dir, args, hitOut, bodyMask);
     if (hitCompounds) *hitCompounds = hit;
+    if (oneEvent) return hit.empty() ? std::vector<int>() : ExecuteFractureRoutine(hit, maxAxisScale, args, spherePointCloud);
     std::vector<int> made;
     for (auto it = hit.rbegin(); it != hit.rend(); ++it)
     {

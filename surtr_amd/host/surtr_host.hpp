@@ -270,13 +270,25 @@ public:
     // A flagged fragment is left out of the scene: as everywhere, that throws unless AllowFlagged(true).
     std::vector<int> ExecuteFractureRoutine(int compound, const std::vector<Matrix>& world, float maxAxisScale, const FractureArgs& args,
                                             const std::vector<Vector3>& spherePointCloud);
+    // ExecuteFractureRoutine for every compound a click hit, in ONE pass (surtr_scene_fracture_bodies): the compounds may come in any
+    // order; they are sorted descending, a duplicate throws Error(SURTR_E_INVALID).  In order: ApplyPoses, the placement, the device
+    // out-of-sphere mask when PartialFracture (OutsideMask: nothing is read back but the bytes), one event over all of them, one
+    // regrouping, one refit, one commit.  Returns the compounds made: the scene is the one the one-compound routine called per
+    // compound in descending number leaves.  One difference: when the event flagged a unit and AllowFlagged is off, NOTHING of the
+    // click is committed, where the one-compound route has committed the compounds it had dealt with before it threw.
+    std::vector<int> ExecuteFractureRoutine(const std::vector<int>& compounds, float maxAxisScale, const FractureArgs& args,
+                                            const std::vector<Vector3>& spherePointCloud);
+    // Surtr::ConvexOutOfSphere of every piece of the listed compounds, on the device (surtr_scene_outside): one byte per piece,
+    // compound after compound in the order given.  cloud: the sphere's points as placed (scaled by the radius, moved to the impact).
+    std::vector<uint8_t> OutsideMask(const std::vector<int>& compounds, const FractureArgs& args, const std::vector<Vector3>& cloud);
     // PickImpact with the scene's own table.
     std::vector<int> PickImpact(const Vector3& origin, const Vector3& dir, FractureArgs& args);
     // OnMouseDown: PickImpact, then ExecuteFractureRoutine for every compound hit in DESCENDING number, so that the numbers of
     // the compounds still to come stay valid (the reference holds pointers there).  Returns the new compounds as numbered after
     // the last commit; hitCompounds (may be null) receives what PickImpact returned.
+    // oneEvent: every compound hit goes through the several-compound ExecuteFractureRoutine instead (one event, one regrouping, one commit).
     std::vector<int> OnMouseDown(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
-                                 const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds = nullptr);
+                                 const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds = nullptr, bool oneEvent = false);
     // ---- bodies that move (Update writes each body's pose into m_structuredBufferData[i].WorldMatrix, Src/Surtr.cpp:347-352) ----
     // One rigid pose per compound of the scene (surtr_scene_set_poses: Matrix::m in the layout TransformCompound takes); the resident
     // pieces stay in the frame they were committed in.  ApplyPose bakes a compound's pose into its pieces (:1846-1851) and makes the
@@ -284,6 +296,7 @@ public:
     void SetPoses(const std::vector<Matrix>& world);
     std::vector<Matrix> Poses();
     void ApplyPose(int compound);
+    void ApplyPoses(const std::vector<int>& compounds);      // the same for several, the derived data rebuilt once (surtr_scene_apply_poses)
     // OnMouseDown's queries on the bodies where their poses put them (surtr_scene_raycast / surtr_scene_overlap).  OverlapBodies: one
     // value per COMPOUND, 0 no piece of it is touched, 1 touched, 2 touched but the body's mass <= minMass (density 10; < 0: no gate).
     surtr_scene_ray_hit RaycastScene(const Vector3& origin, const Vector3& dir, float maxDist = 1000.f);
@@ -298,10 +311,10 @@ public:
     std::vector<int> PickBodies(const Vector3& origin, const Vector3& dir, FractureArgs& args, surtr_scene_ray_hit* hit = nullptr,
                                 std::vector<uint8_t>* bodyMask = nullptr);
     // PickBodies, then ExecuteFractureRoutine (which bakes the stored pose first) in descending compound number.  hit / bodyMask:
-    // what the pick it acted on found.
+    // what the pick it acted on found.  oneEvent: as for OnMouseDown.
     std::vector<int> OnMouseDownBodies(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
                                        const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds = nullptr,
-                                       surtr_scene_ray_hit* hit = nullptr, std::vector<uint8_t>* bodyMask = nullptr);
+                                       surtr_scene_ray_hit* hit = nullptr, std::vector<uint8_t>* bodyMask = nullptr, bool oneEvent = false);
     surtr_counts LastCounts() const { return counts_; }
     // The degenerate policy at this level (include/surtr_hip.h, surtr_counts::n_failed): where the reference leaves its own
     // arrays the engine flags the unit instead of emulating what the reference's memory happens to hold -- a flagged (cell,
