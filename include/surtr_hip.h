@@ -120,7 +120,7 @@ int surtr_set_arena(surtr_ctx* ctx, uint64_t verts, uint64_t nbrs, uint64_t idx)
  * 0 clip_pairs (Mesh), 1 frag_table, 2 refit, 3 faces, 4 out_scan, 5 pack, 6 clip_convex, 7 prep_pairs,
  * 8 clip_pairs_big (or _wave_big), 9 clip_pairs_half, 10 clip_pairs retry launch + the catcher's sweep,
  * 11 clip_pairs_wave (or _main), 13 clip_pairs_catch (the Mesh clip's kernels run side by side on the caller's and
- * two internal streams); -1 where not run (slots 12, 14 and 15 never are). */
+ * two internal streams), 12 frags_from_pieces (surtr_scene_fragments); -1 where not run (slots 14 and 15 never are). */
 int surtr_set_profiling(surtr_ctx* ctx, int on);
 int surtr_kernel_times(surtr_ctx* ctx, float ms[16]);
 /* The durations of the Mesh clip kernel (slot[k] = 0: k_clip_pairs, 11: k_clip_pairs_wave) over the last *n <= 16 events since
@@ -254,7 +254,8 @@ int surtr_triangulate(surtr_ctx* ctx, uint32_t nv, const float* pos, const uint3
 /* Presents n host pieces as the fragments of an event (fragment k = Mesh k + Convex k, ids = frag_ids[3k..] or
  * (k, 0, 0) when NULL), so that surtr_event_refit / surtr_event_triangulate / surtr_event_download /
  * surtr_pieces_from_event work on solids that did not come out of surtr_fracture_event.  The `outside` mask of an earlier
- * event is dropped: surtr_event_regroup after this call regroups these n fragments alone (bind 0 starts empty). */
+ * event is dropped: surtr_event_regroup after this call regroups these n fragments alone (bind 0 starts empty).
+ * Its device twin, for pieces that are resident already, is surtr_scene_fragments (below): nothing leaves HBM there. */
 int surtr_load_fragments(surtr_ctx* ctx, uint32_t n,
                          const uint32_t* mesh_vert_off, const float* mesh_pos, const uint32_t* mesh_nbr_off, const int32_t* mesh_nbr,
                          const uint32_t* conv_vert_off, const float* conv_pos, const uint32_t* conv_nbr_off, const int32_t* conv_nbr,
@@ -612,6 +613,21 @@ int surtr_scene_outside_dev(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* 
  * one commit per target, in that order, leaves. */
 int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* compound_off, const int32_t* compound_piece,
                        uint32_t* n_pieces, uint32_t* first_new_compound, uint32_t* n_new_compounds, int32_t* src);
+/* InitCompound on the scene (Src/Surtr.cpp:2499-2529, m_initCompoundTask :1436-1447): the resident pieces of the listed compounds become
+ * the current fragments, device to device.  `compounds == NULL` means every compound, ascending.  Fragments come in list order, and
+ * inside a compound in piece order.  frag_ids = (compound, resident piece number, 0).  Convex slot = the piece's Convex.  Mesh slot =
+ * the piece's Mesh, or with render_convex != 0 a second copy of the Convex.  flags: 0 or SURTR_EVT_RENDER.  With SURTR_EVT_RENDER the
+ * Mesh slot is triangulated at once (EarClipping, or the fan when render_convex), as by surtr_event_triangulate(ctx, render_convex).
+ * The scene, its table and its poses are not touched, and positions are those of the resident frame (no pose applied).  Like the
+ * single-solid operators it uses the event arena: the fragments of the last event are gone, and a surtr_scene_commit after it is
+ * SURTR_E_STATE.  Everything that reads the current fragments works on them: surtr_event_triangulate, surtr_event_refit,
+ * surtr_event_mass(_dev), surtr_event_pack_dev, surtr_event_download.  Synchronises once to return the counts; the _async form does not.
+ * Errors, each leaving the scene and any current event as they were: SURTR_E_STATE without resident pieces; SURTR_E_INVALID for a
+ * compound out of range or listed twice, n_targets == 0 with a list, or any other flag (SURTR_EVT_REFIT included: call
+ * surtr_event_refit next); SURTR_E_CAPACITY for more fragments than the fragment table can hold; a failed growth of the arena or the
+ * scratch is reported as by surtr_load_fragments.  With surtr_set_profiling the copy kernel's time is slot 12 of surtr_kernel_times. */
+int surtr_scene_fragments(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, int render_convex, uint32_t flags, surtr_counts* counts);
+int surtr_scene_fragments_async(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, int render_convex, uint32_t flags);
 /* Diagnostic: host time of the last surtr_scene_commit in milliseconds, in two parts that both end in a stream synchronisation --
  * checks, layout, tables and the gather kernel; then the swap, the derived data of the whole scene (derive_set) and the piece
  * statistics. */

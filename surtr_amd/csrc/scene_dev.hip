@@ -8,6 +8,8 @@
 //   surtr_scene_fracture_event(_async)            the event over the pieces of one compound
 //   surtr_scene_apply_poses / _fracture_bodies(_async)   the same for every body a click hits at once: one bake, one event whose pair
 //                                                 list is target-major (the mask of surtr_scene_outside, regroup_dev.hip)
+//   surtr_scene_fragments(_async)                 the resident pieces of some compounds as the current fragments (InitCompound, :2499-2529):
+//                                                 the device twin of surtr_load_fragments, one chunked copy kernel into the event arena
 //   surtr_scene_commit                            erase the event's compound(s), push back what they broke into (:1856-1875): one
 //                                                 gather kernel from the old pieces and the event arena into spare buffers, then a swap
 // The layout of the new pieces is laid out on the host from the small tables (piece offsets, fragment records), as
@@ -44,6 +46,53 @@ __global__ __launch_bounds__(SURTR_WG) void k_scene_gather(uint32_t n, GatherTab
     for (uint32_t v = threadIdx.x; v < nv; v += group_size()) D.loff[dv + v] = dh + (sloff[sv + v] - sh);
     for (uint32_t e = threadIdx.x; e < nh; e += group_size()) D.nbr[dh + e] = snbr[sh + e];
     if (p + 1u == n && threadIdx.x == 0) D.loff[dv + nv] = dh + nh;
+}
+
+// ---- surtr_scene_fragments: resident pieces -> event arena.  The host cuts the copy into chunks of at most FRAG_SPAN words, so that a
+// body of 50 000 vertices is spread over as many workgroups as thousands of small pieces beside it.  Pieces that follow each other in
+// the resident set follow each other in the arena too, so a run of them is ONE range per array whatever the pieces' sizes: the chunks
+// know nothing of pieces.  Every array is copied as 32-bit words (positions keep their bits); `add` rebases the ring offsets.  The
+// host starts every run at an arena slot congruent to its source modulo 4, and every chunk but a run's first at a source multiple of
+// 4: source and destination are 16-byte aligned together, and all but a head and a tail of up to 3 words moves as 128-bit words.
+enum : uint32_t { FC_POS = 0, FC_NBR = 1, FC_LOFF = 2, FC_LLEN = 3, FC_ORDER = 4, FC_SET1 = 16 };
+#define FRAG_SPAN 4096u
+struct alignas(16) FragChunk { uint32_t kind, n, add, pad; unsigned long long src, dst; };      // kind = FC_* (| FC_SET1: from the Convex set)
+struct alignas(16) Words4 { uint32_t w[4]; };
+struct PieceWords { const uint32_t* pos; const uint32_t* nbr; const uint32_t* loff; const uint32_t* llen; };
+
+// One workgroup per chunk.  FC_ORDER chunks fill the size-class lists of the fragment table: fragment dst + i goes to slot[src + i].
+// Plain stores to disjoint ranges; no atomics, no LDS.
+__global__ __launch_bounds__(SURTR_WG) void k_frags_from_pieces(uint32_t n_chunks, const FragChunk* __restrict__ chunks, const uint32_t* __restrict__ slot,
+                                                                PieceWords S0, PieceWords S1, Arena A, uint32_t* __restrict__ forder)
+{
+    if (blockIdx.x >= n_chunks) return;
+    const FragChunk C = chunks[blockIdx.x];
+    const uint32_t kind = C.kind & 15u, n = C.n;
+    if (kind == FC_ORDER)
+    {
+        for (uint32_t i = threadIdx.x; i < n; i += group_size()) forder[slot[C.src + i]] = (uint32_t)C.dst + i;
+        return;
+    }
+    const PieceWords S = (C.kind & FC_SET1) ? S1 : S0;
+    const uint32_t* s = kind == FC_POS ? S.pos : kind == FC_NBR ? S.nbr : kind == FC_LOFF ? S.loff : S.llen;
+    uint32_t* d = kind == FC_POS ? (uint32_t*)A.pos : kind == FC_NBR ? (uint32_t*)A.nbr : kind == FC_LOFF ? A.loff : A.llen;
+    s += C.src; d += C.dst;
+    const uint32_t add = C.add;
+    if ((C.src ^ C.dst) & 3ull)      // (never with the host's layout: the two are not aligned together, word by word)
+    {
+        for (uint32_t i = threadIdx.x; i < n; i += group_size()) d[i] = s[i] + add;
+        return;
+    }
+    const uint32_t lead = (4u - (uint32_t)(C.src & 3ull)) & 3u, head = lead < n ? lead : n, n4 = (n - head) >> 2, tail = head + 4u * n4;
+    for (uint32_t i = threadIdx.x; i < head; i += group_size()) d[i] = s[i] + add;
+    const Words4* s4 = (const Words4*)(s + head); Words4* d4 = (Words4*)(d + head);
+    for (uint32_t i = threadIdx.x; i < n4; i += group_size())
+    {
+        Words4 w = s4[i];
+        w.w[0] += add; w.w[1] += add; w.w[2] += add; w.w[3] += add;
+        d4[i] = w;
+    }
+    for (uint32_t i = tail + threadIdx.x; i < n; i += group_size()) d[i] = s[i] + add;
 }
 
 bool valid_table(uint32_t n_compounds, const uint32_t* off, uint32_t n_pieces)
@@ -241,6 +290,143 @@ int surtr_scene_fracture_bodies(surtr_ctx* ctx, uint32_t n_targets, const uint32
                                 const uint8_t* outside, uint32_t flags, surtr_counts* counts)
 {
     int rc = surtr_scene_fracture_bodies_async(ctx, n_targets, compounds, cell_begin, cell_end, outside, flags);
+    if (rc) return rc;
+    surtr_counts c;
+    rc = surtr_event_counts(ctx, &c);
+    if (counts) *counts = c;
+    return rc;
+}
+
+int surtr_scene_fragments_async(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, int render_convex, uint32_t flags)
+{
+    if (!ctx) return SURTR_E_INVALID;
+    if (!ctx->n_pieces || ctx->scene_off.size() < 2) return SURTR_E_STATE;
+    if ((flags & ~(uint32_t)SURTR_EVT_RENDER) || (compounds && !n_targets)) return SURTR_E_INVALID;
+    const uint32_t nc = (uint32_t)ctx->scene_off.size() - 1u;
+    if (!compounds) n_targets = nc;
+    // ---- everything is checked, laid out and grown before anything is enqueued
+    uint64_t n64 = 0;
+    {
+        std::vector<uint8_t> seen(nc, 0);
+        for (uint32_t t = 0; t < n_targets; ++t)
+        {
+            const uint32_t c = compounds ? compounds[t] : t;
+            if (c >= nc || seen[c]) return SURTR_E_INVALID;
+            seen[c] = 1; n64 += ctx->scene_off[c + 1] - ctx->scene_off[c];
+        }
+    }
+    if (n64 == 0) return SURTR_E_INVALID;
+    if (n64 > 0x7FFFFFFFull) return SURTR_E_CAPACITY;      // (more than any fragment table holds: ensure_arena)
+    const uint32_t n = (uint32_t)n64;
+    (void)hipSetDevice(ctx->device);
+    // The staged words: FragRec[n] | cursors[CUR_STATS_WORDS] | surtr_counts (padded to 12 words) | slot[n] | chunks.  The first three go
+    // to d_frags, the arena's cursors and d_counts; the last two are the kernel's own tables.
+    constexpr size_t FR_W = sizeof(FragRec) / 4, CH_W = sizeof(FragChunk) / 4, CNT_W = 12;
+    static_assert(sizeof(FragRec) % 4 == 0 && sizeof(surtr_counts) <= CNT_W * 4 && sizeof(FragChunk) == 32, "staging layout");
+    const size_t at_cur = FR_W * n, at_cnt = at_cur + CUR_STATS_WORDS, at_slot = (at_cnt + CNT_W + 3) & ~(size_t)3, at_chunk = (at_slot + n + 3) & ~(size_t)3;
+    std::vector<uint32_t>& H = ctx->h_frag_stage;
+    H.assign(at_chunk, 0u);
+    std::vector<FragChunk> chunks;
+    auto cut = [&](uint32_t kind, uint64_t src, uint64_t dst, uint64_t count, uint32_t add) {
+        while (count)
+        {
+            const uint32_t take = (uint32_t)std::min<uint64_t>(count, FRAG_SPAN - (src & 3u));      // the next chunk starts at a multiple of 4
+            chunks.push_back(FragChunk{kind, take, add, 0u, src, dst});
+            src += take; dst += take; count -= take;
+        }
+    };
+    uint32_t vmax = 0, hmax = 0, cvmax = 0, chmax = 0;
+    uint64_t vcur = 0, hcur = 0, slotV[2] = {0, 0}, slotH[2] = {0, 0};
+    for (int slot = 0; slot < 2; ++slot)      // the Mesh slots of all fragments first, then the Convex slots, as surtr_load_fragments lays them out
+    {
+        const int set = (slot || render_convex) ? 1 : 0;
+        const std::vector<uint32_t>& vo = ctx->h_vo[set]; const std::vector<uint32_t>& ho = ctx->h_ho[set];
+        const uint32_t from = set ? FC_SET1 : 0u;
+        const uint64_t v0 = vcur, h0 = hcur;
+        uint32_t k = 0, prev = 0xFFFFFFFFu;
+        uint64_t run_sv = 0, run_sh = 0, run_dv = 0, run_dh = 0, run_nv = 0, run_nh = 0;
+        auto close_run = [&]() {
+            if (!run_nv) return;
+            cut(FC_POS | from, 3 * run_sv, 3 * run_dv, 3 * run_nv, 0u); cut(FC_NBR | from, run_sh, run_dh, run_nh, 0u);
+            cut(FC_LOFF | from, run_sv, run_dv, run_nv, (uint32_t)(run_dh - run_sh)); cut(FC_LLEN | from, run_sv, run_dv, run_nv, 0u);
+            run_nv = run_nh = 0;
+        };
+        for (uint32_t t = 0; t < n_targets; ++t)
+        {
+            const uint32_t c = compounds ? compounds[t] : t;
+            for (uint32_t p = ctx->scene_off[c]; p < ctx->scene_off[c + 1]; ++p, ++k)
+            {
+                const uint32_t sv = vo[p], nv = vo[p + 1] - sv, sh = ho[p], nh = ho[p + 1] - sh;
+                if (p != prev + 1u || prev == 0xFFFFFFFFu)      // a new run: its arena slots congruent to the source's modulo 4
+                {
+                    close_run();
+                    vcur += (sv - vcur) & 3u; hcur += (sh - hcur) & 3u;
+                    run_sv = sv; run_sh = sh; run_dv = vcur; run_dh = hcur;
+                }
+                prev = p;
+                FragRec r; memset(&r, 0, sizeof(r));
+                memcpy(&r, H.data() + FR_W * k, sizeof(r));
+                if (slot == 0)
+                {
+                    r.cell = (int32_t)c; r.piece = (int32_t)p; r.island = 0;
+                    r.mv_off = (uint32_t)vcur; r.mv_n = nv; r.mh_off = (uint32_t)hcur; r.mh_n = nh;
+                    vmax = std::max(vmax, nv); hmax = std::max(hmax, nh);
+                    uint32_t cls = 0; while ((nv >> (cls + 1u)) != 0u && cls < 15u) ++cls;      // size classes of k_frag_table
+                    H[at_slot + k] = cls;      // (the slot itself once the arena, and with it the lists' stride, is known)
+                }
+                else
+                {
+                    r.cv_off = (uint32_t)vcur; r.cv_n = nv; r.ch_off = (uint32_t)hcur; r.ch_n = nh;
+                    cvmax = std::max(cvmax, nv); chmax = std::max(chmax, nh);
+                }
+                memcpy(H.data() + FR_W * k, &r, sizeof(r));
+                vcur += nv; hcur += nh; run_nv += nv; run_nh += nh;
+            }
+        }
+        close_run();
+        slotV[slot] = vcur - v0; slotH[slot] = hcur - h0;
+    }
+    if (vcur > 0xFFFFFFF0ull || hcur > 0xFFFFFFF0ull) return SURTR_E_CAPACITY;
+    cut(FC_ORDER, 0, 0, n, 0u);
+    int rc = frags_reserve(ctx, n, vmax, hmax, cvmax, chmax, slotV[0], slotV[1], slotH[0], slotH[1]);
+    if (rc) return rc;
+    if (n > ctx->cap_frags || vcur > ctx->arena.capV || hcur > ctx->arena.capH) return SURTR_E_CAPACITY;
+    if ((rc = ctx->d_frag_tab.grow(ctx, (size_t)n + CH_W * chunks.size() + 4, ((size_t)n + CH_W * chunks.size()) * 5 / 4 + 64)) != SURTR_OK) return rc;
+    for (uint32_t k = 0; k < n; ++k)
+    {
+        const uint32_t cls = H[at_slot + k];
+        H[at_slot + k] = cls * ctx->cap_frags + H[at_cur + CUR_CLS_FRAG + cls]++;
+    }
+    H[at_cur + CUR_V] = (uint32_t)vcur; H[at_cur + CUR_H] = (uint32_t)hcur;
+    surtr_counts c; memset(&c, 0, sizeof(c)); c.n_frag = n; c.n_pairs = n;
+    memcpy(H.data() + at_cnt, &c, sizeof(c));
+    H.resize(at_chunk + CH_W * chunks.size());
+    memcpy(H.data() + at_chunk, chunks.data(), chunks.size() * sizeof(FragChunk));
+    // ---- enqueue.  (The staging vector is the context's: pageable memory has left its source when hipMemcpyAsync returns, and the
+    //      vector lives until the next call refills it, as the tables of scene_sync_device do.)
+    hipStream_t st = ctx->stream;
+    ctx->have_event = false; ctx->scene_event_compound.clear();
+    uint32_t* d_slot = ctx->d_frag_tab; const size_t dev_chunk = ((size_t)n + 3) & ~(size_t)3;      // (16-byte aligned chunk records)
+    HIPCHK(hipMemcpyAsync(ctx->d_frags, H.data(), (size_t)n * sizeof(FragRec), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctx->arena.cursors, H.data() + at_cur, CUR_STATS_WORDS * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctx->d_counts, H.data() + at_cnt, sizeof(c), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_slot, H.data() + at_slot, (H.size() - at_slot) * 4, hipMemcpyHostToDevice, st));
+    static_assert(sizeof(float) == 4 && sizeof(int32_t) == 4, "the solids are copied as 32-bit words");
+    PieceSet& M = ctx->mset; PieceSet& C = ctx->cset;
+    const PieceWords S0{(const uint32_t*)M.pos.p, (const uint32_t*)M.nbr.p, M.loff.p, M.llen.p}, S1{(const uint32_t*)C.pos.p, (const uint32_t*)C.nbr.p, C.loff.p, C.llen.p};
+    PROF_BEGIN(12);
+    hipLaunchKernelGGL(k_frags_from_pieces, dim3((uint32_t)chunks.size()), dim3(SURTR_WG), 0, st, (uint32_t)chunks.size(),
+                       (const FragChunk*)(d_slot + dev_chunk), (const uint32_t*)d_slot, S0, S1, ctx->arena, ctx->d_forder.p);
+    PROF_END(12);
+    HIPCHK(hipGetLastError());
+    rc = frags_present(ctx, (flags & SURTR_EVT_RENDER) != 0u, render_convex);
+    if (rc) ctx->have_event = false;
+    return rc;
+}
+
+int surtr_scene_fragments(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, int render_convex, uint32_t flags, surtr_counts* counts)
+{
+    int rc = surtr_scene_fragments_async(ctx, n_targets, compounds, render_convex, flags);
     if (rc) return rc;
     surtr_counts c;
     rc = surtr_event_counts(ctx, &c);

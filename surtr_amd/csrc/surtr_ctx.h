@@ -333,6 +333,9 @@ struct surtr_ctx
     DevBuf<uint32_t> d_piece_comp;       // per resident piece: its compound; then the compound table (n_compounds + 1 offsets)
     struct { DevBuf<float> pos; DevBuf<uint32_t> loff; DevBuf<int32_t> nbr; DevBuf<uint32_t> vo; } spare[2];   // surtr_scene_commit gathers into these, then swaps
     DevBuf<int32_t> d_commit_src; DevBuf<uint32_t> d_commit_tab;      // its gather tables
+    // surtr_scene_fragments: the tables it lays out on the host (fragment records, cursors, counts, size-class slots, chunk table), kept
+    // between calls so that the _async form leaves nothing behind that goes out of scope; the device copy of the last two
+    std::vector<uint32_t> h_frag_stage; DevBuf<uint32_t> d_frag_tab;
     float commit_ms[2] = {0.f, 0.f};                     // host time of the last commit up to the end of the gather / from there to its end (surtr_scene_commit_times)
     uint32_t regroup_rounds = 0;                         // label rounds of the last surtr_event_regroup (one launch)
     uint64_t tot_mv = 0, tot_mh = 0;
@@ -482,6 +485,14 @@ static inline int scene_sync_device(surtr_ctx* ctx, SceneDev* out)
 
 // an event over an explicit pair list with an `outside` mask over all resident pieces (surtr_hip.hip); NULL: no mask
 int surtr_event_pairs_masked(surtr_ctx* ctx, uint32_t n_pairs, const uint32_t* pair_cell, const uint32_t* pair_piece, const uint8_t* outside, uint32_t flags);
+
+// Room for n loaded fragments of MV + CV vertices and MH + CH ring entries (Mesh + Convex slots), the largest of them vmax / hmax
+// (Mesh slot) and cvmax / chmax (Convex slot): the context's maxima are raised, then scratch, one-wave scratch and arena get the bounds
+// of surtr_load_fragments (room for a refit and a triangulation of them).  Nothing is enqueued.  (surtr_hip.hip)
+int frags_reserve(surtr_ctx* ctx, uint32_t n, uint32_t vmax, uint32_t hmax, uint32_t cvmax, uint32_t chmax, uint64_t MV, uint64_t CV, uint64_t MH, uint64_t CH);
+// The fragments whose records, solids, cursors and counts have been enqueued on the context's stream become the current ones: status
+// words cleared, k_faces when `render` (the fan when is_convex), k_out_scan.  No synchronisation.  (surtr_hip.hip)
+int frags_present(surtr_ctx* ctx, bool render, int is_convex);
 
 // placement of cell groups with per-group scale / shift already in device memory (surtr_hip.hip)
 extern "C" int surtr_place_cells_groups_dev(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* group_cell_off, const float* d_scale3, const float* d_shift3);

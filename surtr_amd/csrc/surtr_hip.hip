@@ -4181,6 +4181,34 @@ static int launch_faces(surtr_ctx* ctx, uint32_t fan, uint32_t* d_face_n, uint32
     return SURTR_OK;
 }
 
+extern "C++" {      // (shared with scene_dev.hip through surtr_ctx.h, not part of the C ABI)
+int frags_reserve(surtr_ctx* ctx, uint32_t n, uint32_t vmax, uint32_t hmax, uint32_t cvmax, uint32_t chmax, uint64_t MV, uint64_t CV, uint64_t MH, uint64_t CH)
+{
+    ctx->cvmax = std::max(ctx->cvmax, cvmax); ctx->chmax = std::max(ctx->chmax, chmax);
+    ctx->vmax = std::max(ctx->vmax, std::max(vmax, cvmax)); ctx->hmax = std::max(ctx->hmax, std::max(hmax, chmax));
+    int rc = ensure_scratch(ctx, ctx->vmax, ctx->hmax, std::max(1u, ctx->n_wg));
+    if (rc) return rc;
+    rc = ensure_scratch_small(ctx, std::max(ctx->max_wg_small, ctx->n_wg_small));
+    if (rc) return rc;
+    // the solids, the refitted Convex solids (a clip by 8 planes -- 2F at a RefittingPointLimit above 4, refit_planes -- adds a
+    // few vertices per plane), 3 indices per half-edge at most
+    const uint64_t rp = refit_planes(ctx);
+    return ensure_arena(ctx, n, MV + 3ull * CV + 8ull * rp * n, MH + 4ull * CH + 32ull * rp * n, 3ull * MH + 64);
+}
+
+int frags_present(surtr_ctx* ctx, bool render, int is_convex)
+{
+    hipStream_t st = ctx->stream;
+    ctx->have_event = true; ctx->last_flags = 0; ctx->last_current = false; ctx->frags_of_pieces = false;
+    ctx->last_outside.clear();      // (the mask of an earlier event says nothing about these fragments: surtr_event_regroup)
+    if (render) return launch_faces(ctx, is_convex ? 1u : 0u, nullptr, nullptr, nullptr);      // (clears the status words itself)
+    HIPCHK(hipMemsetAsync(ctx->d_frag_status, 0, (size_t)ctx->cap_frags * 4, st));
+    hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(SURTR_WG_WIDE), 0, st, ctx->d_frags, ctx->d_scanblk, ctx->d_counts, ctx->arena);
+    HIPCHK(hipGetLastError());
+    return SURTR_OK;
+}
+} // extern "C++"
+
 int surtr_event_triangulate(surtr_ctx* ctx, int is_convex)
 {
     if (!ctx) return SURTR_E_INVALID;
@@ -4212,16 +4240,7 @@ int surtr_load_fragments(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const 
             else { vmax = std::max(vmax, b - a); hmax = std::max(hmax, off[b] - off[a]); }
         }
     }
-    ctx->cvmax = std::max(ctx->cvmax, cvmax); ctx->chmax = std::max(ctx->chmax, chmax);
-    ctx->vmax = std::max(ctx->vmax, std::max(vmax, cvmax)); ctx->hmax = std::max(ctx->hmax, std::max(hmax, chmax));
-    int rc = ensure_scratch(ctx, ctx->vmax, ctx->hmax, std::max(1u, ctx->n_wg));
-    if (rc) return rc;
-    rc = ensure_scratch_small(ctx, std::max(ctx->max_wg_small, ctx->n_wg_small));
-    if (rc) return rc;
-    // the solids, the refitted Convex solids (a clip by 8 planes -- 2F at a RefittingPointLimit above 4, refit_planes -- adds a
-    // few vertices per plane), 3 indices per half-edge at most
-    const uint64_t rp = refit_planes(ctx);
-    rc = ensure_arena(ctx, n, (uint64_t)MV + 3ull * CV + 8ull * rp * n, (uint64_t)MH + 4ull * CH + 32ull * rp * n, 3ull * MH + 64);
+    int rc = frags_reserve(ctx, n, vmax, hmax, cvmax, chmax, MV, CV, MH, CH);
     if (rc) return rc;
     if (n > ctx->cap_frags) return SURTR_E_CAPACITY;
     hipStream_t st = ctx->stream;

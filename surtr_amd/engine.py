@@ -643,6 +643,30 @@ class Engine:
                                           ctypes.byref(nnew), _p(src)))
         return n.value, first.value, nnew.value, src[:n.value].copy()
 
+    def _compound_list(self, compounds):
+        if compounds is None:
+            return None, 0
+        t = np.ascontiguousarray(compounds, np.uint32).reshape(-1)
+        return (t if t.shape[0] else np.zeros(1, np.uint32)), t.shape[0]      # (an empty list is a list: SURTR_E_INVALID, not "all")
+
+    def scene_fragments(self, compounds=None, render_convex=False, flags=EVT_RENDER):
+        """surtr_scene_fragments: the resident pieces of the listed compounds (None: all) become the current fragments on the device,
+        triangulated with EVT_RENDER; read them with download() / pack_dev() / event_mass().  -> Counts."""
+        t, n = self._compound_list(compounds)
+        c = Counts()
+        self._ck(lib().surtr_scene_fragments(self._h, ctypes.c_uint32(n), _p(t), ctypes.c_int(int(render_convex)), ctypes.c_uint32(flags), ctypes.byref(c)))
+        return c
+
+    def scene_fragments_async(self, compounds=None, render_convex=False, flags=EVT_RENDER):
+        t, n = self._compound_list(compounds)
+        self._ck(lib().surtr_scene_fragments_async(self._h, ctypes.c_uint32(n), _p(t), ctypes.c_int(int(render_convex)), ctypes.c_uint32(flags)))
+
+    def scene_fragments_ms(self):
+        """Milliseconds of the last scene_fragments' copy kernel (slot 12 of surtr_kernel_times; -1 without set_profiling)."""
+        ms = (ctypes.c_float * 16)()
+        self._ck(lib().surtr_kernel_times(self._h, ms))
+        return float(ms[12])
+
     def scene_commit_times(self):
         """surtr_scene_commit_times: host milliseconds of the last commit (up to the end of the gather, from there to its end)."""
         a, b = ctypes.c_float(), ctypes.c_float()

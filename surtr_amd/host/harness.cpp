@@ -15,6 +15,8 @@
 //                 compounds hit and made, the table, the poses and the body masses after the click.
 // --one-event (with --scene-clicks or --body-clicks): every compound a click hits goes through ONE event, one regrouping and one
 //                 commit (ExecuteFractureRoutine over several compounds) instead of one of each per compound; the JSON is the same.
+// --init-compounds [--init-compounds-obj DIR] (with --scene-clicks or --body-clicks): after each click, InitCompounds on the compounds it
+//                 made -- their render buffers straight from the resident scene (surtr_scene_fragments) --, one JSON line per compound.
 // --pick: the event's fragments become the resident pieces (piece k in compound k / 2) and the ray is cast into them as
 // OnMouseDown does (Src/Surtr.cpp:207-240): the hit, the impact position, the overlap mask and the affected compounds, as JSON.
 // --ach runs Surtr::PrepareFracture end to end (ACH convex instead of the plain 2x box).
@@ -330,6 +332,42 @@ static void pick(FractureEngine& eng, const std::vector<Fragment>& frags, const 
     printf("}}\n");
 }
 
+// --init-compounds (with --scene-clicks or --body-clicks): InitCompounds on the compounds a click made; one JSON line per compound
+// with the totals of its render buffers and an FNV-1a of their bytes (vnc, then idx, piece after piece).  --init-compounds-obj DIR
+// writes them as DIR/click<q>_compound<c>.obj, one object per piece.
+static bool g_init_compounds = false;
+static std::string g_init_obj;
+static void init_compounds(FractureEngine& eng, size_t click, const std::vector<int>& made)
+{
+    if (!g_init_compounds || made.empty()) return;
+    const std::vector<std::vector<InitCompoundResult>> res = eng.InitCompounds(made, false);
+    const std::vector<uint32_t> table = eng.SceneCompounds();
+    for (size_t k = 0; k < made.size(); ++k)
+    {
+        unsigned long long h = 0xCBF29CE484222325ull;
+        auto eat = [&](const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 0x100000001B3ull; } };
+        size_t nv = 0, ni = 0;
+        for (const auto& r : res[k]) eat(r.Mesh.vertexData.data(), r.Mesh.vertexData.size() * sizeof(VertexNormalColor));
+        for (const auto& r : res[k]) { eat(r.Mesh.indexData.data(), r.Mesh.indexData.size() * 4); nv += r.Mesh.vertexData.size(); ni += r.Mesh.indexData.size(); }
+        printf("{\"init_compound\": %d, \"click\": %zu, \"pieces\": %zu, \"vertices\": %zu, \"indices\": %zu, \"fnv\": \"%016llx\"}\n", made[k], click,
+               res[k].size(), nv, ni, h);
+        if (g_init_obj.empty()) continue;
+        std::vector<int32_t> ids; std::vector<uint32_t> vo{0u}, io{0u}, idx; std::vector<float> vnc;
+        for (size_t j = 0; j < res[k].size(); ++j)
+        {
+            const FragmentRender& m = res[k][j].Mesh;
+            ids.push_back(made[k]); ids.push_back((int32_t)(table[(size_t)made[k]] + j)); ids.push_back(0);
+            const float* v = (const float*)m.vertexData.data();
+            vnc.insert(vnc.end(), v, v + 9 * m.vertexData.size());
+            idx.insert(idx.end(), m.indexData.begin(), m.indexData.end());
+            vo.push_back(vo.back() + (uint32_t)m.vertexData.size()); io.push_back(io.back() + (uint32_t)m.indexData.size());
+        }
+        const std::string path = g_init_obj + "/click" + std::to_string(click) + "_compound" + std::to_string(made[k]) + ".obj";
+        const int rc = surtr_write_obj(path.c_str(), (uint32_t)res[k].size(), ids.data(), vo.data(), vnc.data(), io.data(), idx.data());
+        if (rc) throw Error(rc, "surtr_write_obj " + path);
+    }
+}
+
 // --scene-clicks: OnMouseDown per click on the resident scene; one JSON line per click.
 static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float, 6>>& clicks, float impact_radius, bool one_event)
 {
@@ -368,6 +406,7 @@ static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float
         printf("], \"mass\": [");
         for (size_t i = 0; i < cm.size(); ++i) printf("%s%.17g", i ? ", " : "", cm[i].mass);
         printf("]}\n");
+        init_compounds(eng, q, made);
     }
 }
 
@@ -435,6 +474,7 @@ static void body_clicks(FractureEngine& eng, const std::vector<std::array<float,
         printf("], \"mass\": [");
         for (size_t i = 0; i < bm.size(); ++i) printf("%s%.17g", i ? ", " : "", bm[i].mass);
         printf("]}\n");
+        init_compounds(eng, q, made);
     }
 }
 
@@ -460,6 +500,8 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--impact-radius") && i + 1 < argc) impact_radius = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--radial")) radial = true;
         else if (!strcmp(argv[i], "--one-event")) one_event = true;
+        else if (!strcmp(argv[i], "--init-compounds")) g_init_compounds = true;
+        else if (!strcmp(argv[i], "--init-compounds-obj") && i + 1 < argc) { g_init_compounds = true; g_init_obj = argv[++i]; }
         else if (!strcmp(argv[i], "--scene-poses") && i + 1 < argc)
         {
             const char* c = argv[++i];

@@ -843,6 +843,50 @@ std::vector<int> FractureEngine::PickBodies(const Vector3& origin, const Vector3
     return out;
 }
 
+std::vector<std::vector<InitCompoundResult>> FractureEngine::InitCompounds(const std::vector<int>& compounds, bool renderConvex)
+{
+    std::vector<std::vector<InitCompoundResult>> out;
+    if (compounds.empty()) return out;
+    std::vector<uint32_t> list;
+    for (int c : compounds) { if (c < 0) throw Error(SURTR_E_INVALID, "InitCompounds: no such compound"); list.push_back((uint32_t)c); }
+    const std::vector<uint32_t> table = SceneCompounds();
+    check(surtr_scene_fragments(ctx_, (uint32_t)list.size(), list.data(), renderConvex ? 1 : 0, SURTR_EVT_RENDER, &counts_), "surtr_scene_fragments");
+    const surtr_counts& c = counts_;
+    // only what the two consumers take: the Convex points, the render buffers, the status words
+    std::vector<uint32_t> mvo(c.n_frag + 1), cvo(c.n_frag + 1), ioff(c.n_frag + 1), idx(c.n_idx), fstat(c.n_frag);
+    std::vector<float> cpos(3 * (size_t)c.conv_verts), vnc(9 * (size_t)c.mesh_verts);
+    surtr_fragments fr{};
+    fr.mesh_vert_off = mvo.data(); fr.conv_vert_off = cvo.data(); fr.conv_pos = cpos.data(); fr.vnc = vnc.data(); fr.idx_off = ioff.data(); fr.idx = idx.data();
+    fr.frag_status = fstat.data();
+    check(surtr_event_download(ctx_, &fr), "surtr_event_download");
+    flagged_ = FlaggedUnits();
+    flagged_.n_failed = c.n_failed;
+    for (uint32_t f = 0; f < c.n_frag; ++f) if (fstat[f] != 0) flagged_.fragments.push_back(f);
+    if (c.n_failed != 0 && !allow_flagged_)
+        throw Error(SURTR_E_TOPOLOGY, "InitCompounds: " + std::to_string(flagged_.fragments.size()) +
+                    " piece(s) flagged (their faces cannot be extracted; AllowFlagged(true) returns the rest)");
+    uint32_t f = 0;
+    for (uint32_t comp : list)
+    {
+        out.emplace_back();
+        for (uint32_t p = table[comp]; p < table[comp + 1]; ++p, ++f)
+        {
+            InitCompoundResult r;
+            for (uint32_t v = cvo[f]; v < cvo[f + 1]; ++v) r.ConvexPoints.emplace_back(cpos[3 * (size_t)v], cpos[3 * (size_t)v + 1], cpos[3 * (size_t)v + 2]);
+            r.Mesh.vertexData.resize(mvo[f + 1] - mvo[f]);
+            if (!r.Mesh.vertexData.empty()) std::memcpy(r.Mesh.vertexData.data(), vnc.data() + 9 * (size_t)mvo[f], sizeof(VertexNormalColor) * r.Mesh.vertexData.size());
+            r.Mesh.indexData.assign(idx.begin() + ioff[f], idx.begin() + ioff[f + 1]);
+            out.back().push_back(std::move(r));
+        }
+    }
+    return out;
+}
+
+std::vector<InitCompoundResult> FractureEngine::InitCompound(int compound, bool renderConvex)
+{
+    return std::move(InitCompounds(std::vector<int>{compound}, renderConvex).front());
+}
+
 std::vector<int> FractureEngine::OnMouseDownBodies(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
                                                    const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds,
                                                    surtr_scene_ray_hit* hitOut, std::vector<uint8_t>* bodyMask, bool oneEvent)

@@ -289,6 +289,16 @@ public:
     // oneEvent: every compound hit goes through the several-compound ExecuteFractureRoutine instead (one event, one regrouping, one commit).
     std::vector<int> OnMouseDown(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
                                  const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds = nullptr, bool oneEvent = false);
+    // InitCompound (Src/Surtr.cpp:2499-2529) for bodies of the resident scene: per piece of the body, in piece order, what
+    // m_initCompoundTask (:1436-1447) hands to PxCreateConvexMesh (ConvexPoints) and to DynamicMesh (Mesh = RenderPolyhedron of the Mesh,
+    // or of the Convex as convex with renderConvex), in the resident frame.  One device call (surtr_scene_fragments: nothing is read
+    // back to triangulate) and one download for the whole list -- what a caller does with the compounds OnMouseDown /
+    // OnMouseDownBodies / ExecuteFractureRoutine return.  The compounds come back in the order given; a compound named twice or out of
+    // range throws Error(SURTR_E_INVALID).  The current event is replaced (LastCounts() are this call's).  A piece whose faces cannot
+    // be extracted is flagged: as everywhere, that throws unless AllowFlagged(true); then it comes back without triangles and
+    // LastFlagged().fragments names it by its position in the call's piece order.
+    std::vector<std::vector<InitCompoundResult>> InitCompounds(const std::vector<int>& compounds, bool renderConvex);
+    std::vector<InitCompoundResult> InitCompound(int compound, bool renderConvex);
     // ---- bodies that move (Update writes each body's pose into m_structuredBufferData[i].WorldMatrix, Src/Surtr.cpp:347-352) ----
     // One rigid pose per compound of the scene (surtr_scene_set_poses: Matrix::m in the layout TransformCompound takes); the resident
     // pieces stay in the frame they were committed in.  ApplyPose bakes a compound's pose into its pieces (:1846-1851) and makes the
