@@ -120,7 +120,8 @@ int surtr_set_arena(surtr_ctx* ctx, uint64_t verts, uint64_t nbrs, uint64_t idx)
  * 0 clip_pairs (Mesh), 1 frag_table, 2 refit, 3 faces, 4 out_scan, 5 pack, 6 clip_convex, 7 prep_pairs,
  * 8 clip_pairs_big (or _wave_big), 9 clip_pairs_half, 10 clip_pairs retry launch + the catcher's sweep,
  * 11 clip_pairs_wave (or _main), 13 clip_pairs_catch (the Mesh clip's kernels run side by side on the caller's and
- * two internal streams), 12 frags_from_pieces (surtr_scene_fragments); -1 where not run (slots 14 and 15 never are). */
+ * two internal streams), 12 frags_from_pieces (surtr_scene_fragments), 14 hulls count + scan, 15 hulls emit + errors
+ * (surtr_event_hulls_dev / surtr_pieces_hulls_dev); -1 where not run. */
 int surtr_set_profiling(surtr_ctx* ctx, int on);
 int surtr_kernel_times(surtr_ctx* ctx, float ms[16]);
 /* The durations of the Mesh clip kernel (slot[k] = 0: k_clip_pairs, 11: k_clip_pairs_wave) over the last *n <= 16 events since
@@ -702,6 +703,70 @@ int surtr_scene_overlap(surtr_ctx* ctx, uint32_t n_spheres, const float* spheres
  * surtr_pieces_mass. */
 int surtr_scene_mass_dev(surtr_ctx* ctx, int set, float density, void* dev_out, size_t capacity_bytes);
 int surtr_scene_mass(surtr_ctx* ctx, int set, float density, uint32_t* n, surtr_mass* out);
+
+/* ---- collision hulls: face loops and planes of every Convex (hull_dev.hip) ---- */
+/* What Compound::PieceExtractedConvex holds for CookingConvexManual (Src/Surtr.cpp:2151-2155, 2555-2614), for every Convex of the
+ * current fragments or of the resident pieces, as the arrays PxConvexMeshDesc::polygons / indices take -- with planes that hold
+ * (PxPlane(f[0], f[1], f[2]) in float does not where a loop starts on three nearly collinear vertices) and a verdict per solid.
+ *
+ * FACES.  The faces of a solid are the loops Poly::ExtractFaces yields, in its order: loops come by (start vertex, ring slot), each
+ * starts at its smallest vertex, and a later slot that repeats a neighbour starts no face of its own.
+ * PLANE of a loop q_0 .. q_(k-1), positions converted to double, every product and sum a separate double operation:
+ *     N = sum_{i=1}^{k-2} (q_i - q_0) x (q_{i+1} - q_0), summed in loop order
+ *     n = N / sqrt(N.N),  N.N = (Nx Nx + Ny Ny) + Nz Nz
+ *     t_i = (n.x q_i.x + n.y q_i.y) + n.z q_i.z,   d = -(max t_i + min t_i) / 2
+ *     plane = (n, d) rounded to float.  N exactly zero: plane = 0 and SURTR_HULL_FLAT; the polygon and its indices are still
+ *     written, and the face takes no part in the two errors.
+ * ERRORS, in double from the FLOAT plane as written, ((n.x x + n.y y) + n.z z) + d, then rounded to float:
+ *     convexity = max over (vertex, non-flat face) of that value (0 when every face is flat): how far a vertex stands in front of a
+ *                 face plane -- a sliver face whose normal is noise shows here;
+ *     planarity = max over the non-flat faces and their OWN vertices of its magnitude.
+ *   A maximum is order-independent and nothing is accumulated with atomics: the same bits whatever the stream, the
+ *   events-in-flight hint or the other work on the GPU.
+ * STATUS.  FEW: fewer than four vertices.  LARGE: more than 65 535 vertices or ring entries (decided from the counts, before any
+ * walk; a solid with FEW or LARGE gets no other withholding bit).  OPEN: a ring entry names no vertex, a position is not finite, a
+ * link lacks its way back, or a walk does not close within the solid's ring entries.  IRREGULAR: a ring lists a neighbour twice; the
+ * walk of a half-edge comes back to its start vertex, on another half-edge, before it closes or meets a smaller vertex (ExtractFaces
+ * ends a loop at its start vertex); the number of ring entries H is odd; or V - H / 2 + F != 2.  OVER_255: more than 255 vertices or
+ * written faces (PhysX's hull limit): information only, it withholds nothing.
+ * FEW, OPEN, IRREGULAR and LARGE WITHHOLD the output: n_faces = n_idx = max_loop = 0 and convexity = planarity = extent = 0.  A solid
+ * with none of them carries exactly ExtractFaces' loops. */
+typedef struct surtr_hull_polygon {     /* 20 bytes: PxHullPolygon's layout */
+    float plane[4];        /* (n, d): inside is n.x + d <= 0 */
+    uint16_t n_verts;      /* vertices of the loop */
+    uint16_t index_base;   /* first index of the loop, counted from the solid's idx_off */
+} surtr_hull_polygon;
+typedef struct surtr_hull {             /* 48 bytes per solid */
+    uint32_t nv, n_faces, n_idx, status;   /* n_faces / n_idx: what was WRITTEN for this solid; status: SURTR_HULL_* bits */
+    uint32_t face_off, idx_off;            /* first polygon / first index: exclusive sums over the solids before it */
+    uint32_t max_loop, reserved0;          /* vertices of the longest loop */
+    float convexity;                       /* max over (vertex, non-flat face) of n.x + d */
+    float planarity;                       /* max over non-flat faces and their OWN vertices of |n.x + d| */
+    float extent;                          /* largest edge of the box of the vertices (float): the scale the two errors are read against */
+    uint32_t reserved1;
+} surtr_hull;
+enum { SURTR_HULL_FEW = 1, SURTR_HULL_OPEN = 2, SURTR_HULL_FLAT = 4, SURTR_HULL_IRREGULAR = 8, SURTR_HULL_LARGE = 16, SURTR_HULL_OVER_255 = 32 };
+/* The Convex of every current fragment (the one the context holds: refitted or not, whatever frag_status says), in fragment order.
+ * dev_records (device memory) takes one 48-byte header, then one surtr_hull per fragment; the header's nv = the solids, n_faces /
+ * n_idx = the totals, status = SURTR_OK or SURTR_E_CAPACITY.  dev_polys has room for polys_cap polygons, dev_idx for idx_cap
+ * indices (16-bit, solid-local: PxConvexFlag::e16_BIT_INDICES); surtr_counts::conv_nbrs / 3 polygons and conv_nbrs indices are always
+ * enough for solids that are written.  Enqueued on the context's stream with no host synchronisation; one temporary device allocation
+ * ordered on that stream; with surtr_set_profiling, slot 14 of surtr_kernel_times is count + scan and slot 15 emit + errors.
+ * SURTR_E_STATE with no event or after an event that failed.  SURTR_E_CAPACITY, before anything is enqueued, when records_bytes
+ * cannot hold the header or -- where the host holds the event's counts -- the records.  Everything else is checked on the device (the
+ * totals are known only there): when something does not fit, the header is written with status SURTR_E_CAPACITY and the totals
+ * needed, and nothing else is. */
+int surtr_event_hulls_dev(surtr_ctx* ctx, void* dev_records, size_t records_bytes, surtr_hull_polygon* dev_polys, size_t polys_cap,
+                          uint16_t* dev_idx, size_t idx_cap);
+/* The same for the Convex solids of the resident pieces, in piece order.  SURTR_E_STATE before any upload.  Bodies of the scene go
+ * through surtr_scene_fragments(compounds, ...) and then surtr_event_hulls. */
+int surtr_pieces_hulls_dev(surtr_ctx* ctx, void* dev_records, size_t records_bytes, surtr_hull_polygon* dev_polys, size_t polys_cap,
+                           uint16_t* dev_idx, size_t idx_cap);
+/* Host forms, synchronous, count-then-fill: with the three arrays NULL, *n / *n_polys / *n_idx return the records (without the
+ * header), polygons and indices; with all three given they must hold the capacities (SURTR_E_CAPACITY and the counts when one is too
+ * small; some but not all arrays NULL is SURTR_E_INVALID). */
+int surtr_event_hulls(surtr_ctx* ctx, uint32_t* n, surtr_hull* records, uint32_t* n_polys, surtr_hull_polygon* polys, uint32_t* n_idx, uint16_t* idx);
+int surtr_pieces_hulls(surtr_ctx* ctx, uint32_t* n, surtr_hull* records, uint32_t* n_polys, surtr_hull_polygon* polys, uint32_t* n_idx, uint16_t* idx);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,24 @@ MASS_DTYPE = np.dtype([("volume", "<f8"), ("mass", "<f8"), ("com", "<f8", (3,)),
                        ("nv", "<u4"), ("status", "<u4")])
 assert MASS_DTYPE.itemsize == ctypes.sizeof(Mass) == 96
 
+# surtr_hull / surtr_hull_polygon (include/surtr_hip.h): one record per solid, one polygon per face (PxHullPolygon's layout)
+HULL_DTYPE = np.dtype([("nv", "<u4"), ("n_faces", "<u4"), ("n_idx", "<u4"), ("status", "<u4"), ("face_off", "<u4"), ("idx_off", "<u4"),
+                       ("max_loop", "<u4"), ("reserved0", "<u4"), ("convexity", "<f4"), ("planarity", "<f4"), ("extent", "<f4"),
+                       ("reserved1", "<u4")])
+POLY_DTYPE = np.dtype([("plane", "<f4", (4,)), ("n_verts", "<u2"), ("index_base", "<u2")])
+assert HULL_DTYPE.itemsize == 48 and POLY_DTYPE.itemsize == 20
+HULL_FEW, HULL_OPEN, HULL_FLAT, HULL_IRREGULAR, HULL_LARGE, HULL_OVER_255 = 1, 2, 4, 8, 16, 32
+HULL_WITHHELD = HULL_FEW | HULL_OPEN | HULL_IRREGULAR | HULL_LARGE
+
+
+def hull_usable(record, rel_tol=1e-5):
+    """surtr::HullUsable: no withholding bit, no flat face, and both errors within rel_tol of the solid's extent; a hull that fails
+    falls back to ConvexPoints (a quickhull of the points)."""
+    if int(record["status"]) & (HULL_WITHHELD | HULL_FLAT):
+        return False
+    tol = np.float32(rel_tol) * np.float32(record["extent"])
+    return bool(record["convexity"] <= tol and record["planarity"] <= tol)
+
 
 # surtr_ray_hit (include/surtr_hip.h), 48 bytes; status bits and the per-piece status bits of a query
 RAY_HIT_DTYPE = np.dtype([("piece", "<i4"), ("status", "<u4"), ("t", "<f4"), ("pos", "<f4", (3,)), ("normal", "<f4", (3,)),
@@ -385,6 +403,33 @@ class Engine:
     def pieces_mass_dev(self, dev_ptr, capacity, set=1, density=10.0):
         self._ck(lib().surtr_pieces_mass_dev(self._h, ctypes.c_int(int(set)), ctypes.c_float(density), ctypes.c_void_p(dev_ptr),
                                              ctypes.c_size_t(capacity)))
+
+    def _hulls(self, fn):
+        n, nf, ni = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        self._ck(fn(self._h, ctypes.byref(n), None, ctypes.byref(nf), None, ctypes.byref(ni), None))
+        rec, poly, idx = np.zeros(n.value, HULL_DTYPE), np.zeros(nf.value, POLY_DTYPE), np.zeros(ni.value, np.uint16)
+        # (zero-length arrays still pass as non-NULL: numpy gives them an address)
+        self._ck(fn(self._h, ctypes.byref(n), _p(rec), ctypes.byref(nf), _p(poly), ctypes.byref(ni), _p(idx)))
+        return {"records": rec, "polygons": poly, "idx": idx}
+
+    def event_hulls(self):
+        """surtr_event_hulls: face loops and planes of the Convex of every current fragment, computed on the device ->
+        {records (HULL_DTYPE), polygons (POLY_DTYPE), idx (uint16, solid-local)}."""
+        return self._hulls(lib().surtr_event_hulls)
+
+    def pieces_hulls(self):
+        """surtr_pieces_hulls: the same for the Convex solids of the resident pieces."""
+        return self._hulls(lib().surtr_pieces_hulls)
+
+    def event_hulls_dev(self, dev_records, records_bytes, dev_polys, polys_cap, dev_idx, idx_cap):
+        """surtr_event_hulls_dev: header + records, polygons and indices into device buffers, on the context's stream, without a
+        synchronisation (capacities in bytes, polygons, indices)."""
+        self._ck(lib().surtr_event_hulls_dev(self._h, ctypes.c_void_p(dev_records), ctypes.c_size_t(records_bytes), ctypes.c_void_p(dev_polys),
+                                             ctypes.c_size_t(polys_cap), ctypes.c_void_p(dev_idx), ctypes.c_size_t(idx_cap)))
+
+    def pieces_hulls_dev(self, dev_records, records_bytes, dev_polys, polys_cap, dev_idx, idx_cap):
+        self._ck(lib().surtr_pieces_hulls_dev(self._h, ctypes.c_void_p(dev_records), ctypes.c_size_t(records_bytes), ctypes.c_void_p(dev_polys),
+                                              ctypes.c_size_t(polys_cap), ctypes.c_void_p(dev_idx), ctypes.c_size_t(idx_cap)))
 
     def pieces_raycast(self, rays):
         """surtr_pieces_raycast: rays f32[n, 7] (origin, direction, max_dist) against the Convex solids of the resident pieces,

@@ -17,6 +17,9 @@
 //                 commit (ExecuteFractureRoutine over several compounds) instead of one of each per compound; the JSON is the same.
 // --init-compounds [--init-compounds-obj DIR] (with --scene-clicks or --body-clicks): after each click, InitCompounds on the compounds it
 //                 made -- their render buffers straight from the resident scene (surtr_scene_fragments) --, one JSON line per compound.
+// --hulls (with --init-compounds): InitCompounds with the collision hulls (InitCompoundResult::Hull); every line also carries the
+//                 compound's hull polygons and indices, the number of its hulls HullUsable accepts, and an FNV-1a of polygons + indices;
+//                 SetExtract of the same fragments is checked against the loops (a difference ends the run with status 3).
 // --pick: the event's fragments become the resident pieces (piece k in compound k / 2) and the ray is cast into them as
 // OnMouseDown does (Src/Surtr.cpp:207-240): the hit, the impact position, the overlap mask and the affected compounds, as JSON.
 // --ach runs Surtr::PrepareFracture end to end (ACH convex instead of the plain 2x box).
@@ -336,12 +339,33 @@ static void pick(FractureEngine& eng, const std::vector<Fragment>& frags, const 
 // with the totals of its render buffers and an FNV-1a of their bytes (vnc, then idx, piece after piece).  --init-compounds-obj DIR
 // writes them as DIR/click<q>_compound<c>.obj, one object per piece.
 static bool g_init_compounds = false;
+static bool g_hulls = false;
 static std::string g_init_obj;
 static void init_compounds(FractureEngine& eng, size_t click, const std::vector<int>& made)
 {
     if (!g_init_compounds || made.empty()) return;
-    const std::vector<std::vector<InitCompoundResult>> res = eng.InitCompounds(made, false);
+    const std::vector<std::vector<InitCompoundResult>> res = eng.InitCompounds(made, false, g_hulls);
     const std::vector<uint32_t> table = eng.SceneCompounds();
+    if (g_hulls)
+    {
+        // SetExtract reads the same fragments: its loops are the polygons' indices, piece after piece in the order of the call
+        const std::vector<Poly::Extract> ex = eng.SetExtract();
+        size_t f = 0;
+        for (const auto& body : res)
+            for (const auto& r : body)
+            {
+                bool same = f < ex.size() && ex[f].size() == r.Hull.Polygons.size();
+                for (size_t j = 0; same && j < ex[f].size(); ++j)
+                {
+                    const surtr_hull_polygon& p = r.Hull.Polygons[j];
+                    same = ex[f][j].size() == p.n_verts;
+                    for (size_t i = 0; same && i < ex[f][j].size(); ++i) same = ex[f][j][i] == (int)r.Hull.Indices[p.index_base + i];
+                }
+                if (!same) { fprintf(stderr, "SetExtract differs from InitCompounds' hull at piece %zu of the call\n", f); exit(3); }
+                ++f;
+            }
+        if (f != ex.size()) { fprintf(stderr, "SetExtract returned %zu pieces for %zu\n", ex.size(), f); exit(3); }
+    }
     for (size_t k = 0; k < made.size(); ++k)
     {
         unsigned long long h = 0xCBF29CE484222325ull;
@@ -349,8 +373,18 @@ static void init_compounds(FractureEngine& eng, size_t click, const std::vector<
         size_t nv = 0, ni = 0;
         for (const auto& r : res[k]) eat(r.Mesh.vertexData.data(), r.Mesh.vertexData.size() * sizeof(VertexNormalColor));
         for (const auto& r : res[k]) { eat(r.Mesh.indexData.data(), r.Mesh.indexData.size() * 4); nv += r.Mesh.vertexData.size(); ni += r.Mesh.indexData.size(); }
-        printf("{\"init_compound\": %d, \"click\": %zu, \"pieces\": %zu, \"vertices\": %zu, \"indices\": %zu, \"fnv\": \"%016llx\"}\n", made[k], click,
+        printf("{\"init_compound\": %d, \"click\": %zu, \"pieces\": %zu, \"vertices\": %zu, \"indices\": %zu, \"fnv\": \"%016llx\"", made[k], click,
                res[k].size(), nv, ni, h);
+        if (g_hulls)
+        {
+            // polygons of every piece, then indices of every piece: what the device wrote for this compound, in its order
+            size_t np = 0, nx = 0, usable = 0;
+            h = 0xCBF29CE484222325ull;
+            for (const auto& r : res[k]) { eat(r.Hull.Polygons.data(), r.Hull.Polygons.size() * sizeof(surtr_hull_polygon)); np += r.Hull.Polygons.size(); }
+            for (const auto& r : res[k]) { eat(r.Hull.Indices.data(), r.Hull.Indices.size() * 2); nx += r.Hull.Indices.size(); usable += HullUsable(r.Hull.Record) ? 1 : 0; }
+            printf(", \"hull_polygons\": %zu, \"hull_indices\": %zu, \"hulls_usable\": %zu, \"hull_fnv\": \"%016llx\"", np, nx, usable, h);
+        }
+        printf("}\n");
         if (g_init_obj.empty()) continue;
         std::vector<int32_t> ids; std::vector<uint32_t> vo{0u}, io{0u}, idx; std::vector<float> vnc;
         for (size_t j = 0; j < res[k].size(); ++j)
@@ -501,6 +535,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--radial")) radial = true;
         else if (!strcmp(argv[i], "--one-event")) one_event = true;
         else if (!strcmp(argv[i], "--init-compounds")) g_init_compounds = true;
+        else if (!strcmp(argv[i], "--hulls")) g_hulls = true;
         else if (!strcmp(argv[i], "--init-compounds-obj") && i + 1 < argc) { g_init_compounds = true; g_init_obj = argv[++i]; }
         else if (!strcmp(argv[i], "--scene-poses") && i + 1 < argc)
         {

@@ -541,6 +541,52 @@ std::vector<surtr_mass> FractureEngine::MassProperties(int set, float density)
     return out;
 }
 
+namespace {
+template <class F>
+HullSet hulls_of(F call, const char* what)
+{
+    HullSet h;
+    uint32_t n = 0, np = 0, ni = 0;
+    int rc = call(&n, nullptr, &np, nullptr, &ni, nullptr);
+    if (rc) throw Error(rc, what);
+    h.Records.resize(n); h.Polygons.resize(np); h.Indices.resize(ni);
+    // (the fill form wants three arrays: empty vectors lend it a place to stand)
+    surtr_hull r0; surtr_hull_polygon p0; uint16_t i0;
+    rc = call(&n, n ? h.Records.data() : &r0, &np, np ? h.Polygons.data() : &p0, &ni, ni ? h.Indices.data() : &i0);
+    if (rc) throw Error(rc, what);
+    return h;
+}
+}
+
+HullSet FractureEngine::Hulls()
+{
+    return hulls_of([&](uint32_t* n, surtr_hull* r, uint32_t* np, surtr_hull_polygon* p, uint32_t* ni, uint16_t* i) { return surtr_event_hulls(ctx_, n, r, np, p, ni, i); },
+                    "surtr_event_hulls");
+}
+
+HullSet FractureEngine::PieceHulls()
+{
+    return hulls_of([&](uint32_t* n, surtr_hull* r, uint32_t* np, surtr_hull_polygon* p, uint32_t* ni, uint16_t* i) { return surtr_pieces_hulls(ctx_, n, r, np, p, ni, i); },
+                    "surtr_pieces_hulls");
+}
+
+std::vector<Poly::Extract> FractureEngine::SetExtract()
+{
+    const HullSet h = Hulls();
+    std::vector<Poly::Extract> out(h.Records.size());
+    for (size_t k = 0; k < h.Records.size(); ++k)
+    {
+        const surtr_hull& r = h.Records[k];
+        for (uint32_t f = 0; f < r.n_faces; ++f)
+        {
+            const surtr_hull_polygon& p = h.Polygons[r.face_off + f];
+            const uint16_t* q = h.Indices.data() + r.idx_off + p.index_base;
+            out[k].emplace_back(q, q + p.n_verts);
+        }
+    }
+    return out;
+}
+
 std::vector<surtr_mass> FractureEngine::PieceMassProperties(int set, float density)
 {
     uint32_t n = 0;
@@ -843,7 +889,7 @@ std::vector<int> FractureEngine::PickBodies(const Vector3& origin, const Vector3
     return out;
 }
 
-std::vector<std::vector<InitCompoundResult>> FractureEngine::InitCompounds(const std::vector<int>& compounds, bool renderConvex)
+std::vector<std::vector<InitCompoundResult>> FractureEngine::InitCompounds(const std::vector<int>& compounds, bool renderConvex, bool withHulls)
 {
     std::vector<std::vector<InitCompoundResult>> out;
     if (compounds.empty()) return out;
@@ -865,6 +911,8 @@ std::vector<std::vector<InitCompoundResult>> FractureEngine::InitCompounds(const
     if (c.n_failed != 0 && !allow_flagged_)
         throw Error(SURTR_E_TOPOLOGY, "InitCompounds: " + std::to_string(flagged_.fragments.size()) +
                     " piece(s) flagged (their faces cannot be extracted; AllowFlagged(true) returns the rest)");
+    HullSet hulls;
+    if (withHulls) hulls = Hulls();
     uint32_t f = 0;
     for (uint32_t comp : list)
     {
@@ -876,15 +924,22 @@ std::vector<std::vector<InitCompoundResult>> FractureEngine::InitCompounds(const
             r.Mesh.vertexData.resize(mvo[f + 1] - mvo[f]);
             if (!r.Mesh.vertexData.empty()) std::memcpy(r.Mesh.vertexData.data(), vnc.data() + 9 * (size_t)mvo[f], sizeof(VertexNormalColor) * r.Mesh.vertexData.size());
             r.Mesh.indexData.assign(idx.begin() + ioff[f], idx.begin() + ioff[f + 1]);
+            if (withHulls)
+            {
+                const surtr_hull& h = hulls.Records[f];
+                r.Hull.Record = h;
+                r.Hull.Polygons.assign(hulls.Polygons.begin() + h.face_off, hulls.Polygons.begin() + h.face_off + h.n_faces);
+                r.Hull.Indices.assign(hulls.Indices.begin() + h.idx_off, hulls.Indices.begin() + h.idx_off + h.n_idx);
+            }
             out.back().push_back(std::move(r));
         }
     }
     return out;
 }
 
-std::vector<InitCompoundResult> FractureEngine::InitCompound(int compound, bool renderConvex)
+std::vector<InitCompoundResult> FractureEngine::InitCompound(int compound, bool renderConvex, bool withHulls)
 {
-    return std::move(InitCompounds(std::vector<int>{compound}, renderConvex).front());
+    return std::move(InitCompounds(std::vector<int>{compound}, renderConvex, withHulls).front());
 }
 
 std::vector<int> FractureEngine::OnMouseDownBodies(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,

@@ -173,7 +173,22 @@ void HandleConvexIsland(CompoundInfo& compoundInfo);
 // <PxConvexMeshGeometry, DynamicMesh*> needs PhysX and D3D12: InitCompoundResult holds what those two are built from.
 std::vector<Piece*> FractureTask(const VMACH::Polygon3D& voroPoly, const std::vector<Piece*>& targetPieceVec, const std::set<int>& outside);
 void RefittingTask(Piece* piece);
-struct InitCompoundResult { std::vector<Vector3> ConvexPoints; FragmentRender Mesh; };
+// Hull (filled only when asked for, withHulls): what CookingConvexManual (Src/Surtr.cpp:2555-2614) takes from
+// Compound::PieceExtractedConvex -- the Convex's face loops as PxHullPolygon records with 16-bit indices into ConvexPoints, the planes
+// as include/surtr_hip.h defines them, and the record that says whether the hull can skip quickhull (HullUsable).
+struct HullData { surtr_hull Record{}; std::vector<surtr_hull_polygon> Polygons; std::vector<uint16_t> Indices; };
+struct InitCompoundResult { std::vector<Vector3> ConvexPoints; FragmentRender Mesh; HullData Hull; };
+// No withholding bit, no flat face, and both errors within relTol of the solid's extent.  A hull that fails falls back to
+// ConvexPoints (PxConvexFlag::eCOMPUTE_CONVEX, CookingConvex :2531-2553).
+inline bool HullUsable(const surtr_hull& h, float relTol = 1e-5f)
+{
+    if (h.status & (SURTR_HULL_FEW | SURTR_HULL_OPEN | SURTR_HULL_IRREGULAR | SURTR_HULL_LARGE | SURTR_HULL_FLAT)) return false;
+    const float tol = relTol * h.extent;
+    return h.convexity <= tol && h.planarity <= tol;
+}
+// The hulls of a set of solids as the device wrote them: Records[k]'s polygons are Polygons[face_off .. face_off + n_faces), its
+// indices Indices[idx_off .. idx_off + n_idx), solid-local.
+struct HullSet { std::vector<surtr_hull> Records; std::vector<surtr_hull_polygon> Polygons; std::vector<uint16_t> Indices; };
 InitCompoundResult InitCompoundTask(const Piece* piece, const Poly::Extract* extract, bool renderConvex);
 
 struct Fragment { int cell, piece, island; Piece piece_data; FragmentRender render; int status = 0; };
@@ -245,6 +260,12 @@ public:
     // PxRigidBodyExt::updateMassAndInertia(body, 10.0f) of InitCompound (Src/Surtr.cpp:2520) without PhysX: volume, mass,
     // centre of mass and inertia tensor of every fragment of the last event (set 0 = Mesh, 1 = Convex), on the device
     // (surtr_event_mass; definition in include/surtr_hip.h).  PieceMassProperties: the same for the resident pieces.
+    // Face loops and planes of the Convex of every current fragment / resident piece, on the device (surtr_event_hulls /
+    // surtr_pieces_hulls; definition in include/surtr_hip.h).  SetExtract (Src/Surtr.cpp:2151-2155): the same loops of the current
+    // fragments as Compound::PieceExtractedConvex holds them, from the same download.
+    HullSet Hulls();
+    HullSet PieceHulls();
+    std::vector<Poly::Extract> SetExtract();
     std::vector<surtr_mass> MassProperties(int set, float density = 10.f);
     std::vector<surtr_mass> PieceMassProperties(int set, float density = 10.f);
     // OnMouseDown's scene queries (Src/Surtr.cpp:207-240) on the Convex solids of the resident pieces, on the device
@@ -297,8 +318,9 @@ public:
     // range throws Error(SURTR_E_INVALID).  The current event is replaced (LastCounts() are this call's).  A piece whose faces cannot
     // be extracted is flagged: as everywhere, that throws unless AllowFlagged(true); then it comes back without triangles and
     // LastFlagged().fragments names it by its position in the call's piece order.
-    std::vector<std::vector<InitCompoundResult>> InitCompounds(const std::vector<int>& compounds, bool renderConvex);
-    std::vector<InitCompoundResult> InitCompound(int compound, bool renderConvex);
+    // withHulls: InitCompoundResult::Hull of every piece as well (surtr_event_hulls on the fragments the call presents).
+    std::vector<std::vector<InitCompoundResult>> InitCompounds(const std::vector<int>& compounds, bool renderConvex, bool withHulls = false);
+    std::vector<InitCompoundResult> InitCompound(int compound, bool renderConvex, bool withHulls = false);
     // ---- bodies that move (Update writes each body's pose into m_structuredBufferData[i].WorldMatrix, Src/Surtr.cpp:347-352) ----
     // One rigid pose per compound of the scene (surtr_scene_set_poses: Matrix::m in the layout TransformCompound takes); the resident
     // pieces stay in the frame they were committed in.  ApplyPose bakes a compound's pose into its pieces (:1846-1851) and makes the
