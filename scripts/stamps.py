@@ -15,6 +15,8 @@ c = eng.fracture_event(0, 4096, flags=flags)
 buf = (ctypes.c_ulonglong * 96)()
 L.surtr_debug_stamps(buf, 1)
 b2z = (ctypes.c_ulonglong * 64)(); L.surtr_debug_stamps2(b2z, 1)
+bf = (ctypes.c_ulonglong * 8)()
+if hasattr(L, "surtr_debug_stamps_faces"): L.surtr_debug_stamps_faces(bf, 1)
 c = eng.fracture_event(0, 4096, flags=flags)
 L.surtr_debug_stamps(buf, 1)
 names = ["pre: A1 stream", "pre: A2 exact", "pre: emit", "pre: A3 block counts + scan", "plane: classify", "plane: cut links patch", "plane: relink finalize/serial", "plane: tombstones",
@@ -46,5 +48,9 @@ print("k_refit: task cost histogram (cycles < 2^13, 2^14, ...):", [b2[i] for i i
 print("k_refit: slowest task %d cycles (mesh n %d, convex n %d); sum %d; WG lifetime avg %.3g max %.3g over %d WGs, most tasks in one WG %d" % (b2[16], b2[17], b2[18], b2[19], b2[20] / max(b2[22], 1), b2[21], b2[22], b2[23]))
 print("k_refit: slowest task: hull %d, k-DOP %d cycles, path flags %d (1 = LDS overflow -> global, 2/4 = topology -> literal), convex after %d; tasks through the global variant %d, through the literal clip %d" % (b2[60], b2[61], b2[62], b2[63], b2[30], b2[31]))
 print("k_faces phases (lane-0 cycles, all tasks): successors %d, pointer jumping %d, owners+loops %d, wave ears %d, lane ears %d, compaction %d" % tuple(b2[24:30]))
+if hasattr(L, "surtr_debug_stamps_faces"):
+    L.surtr_debug_stamps_faces(bf, 0)
+    print("k_faces wave ears (wave-cycles, lane 0 of every wave): barrier + LDS staging %d, length ballots %d, per-face set-up %d, sequential loop + closing triangles %d, "
+          "wait at the closing barrier %d, face loop bookkeeping %d; whole phase %d over %d wave faces" % (bf[0], bf[1], bf[2], bf[3], bf[4], bf[6] - sum(bf[0:5]), bf[6], bf[5]))
 print("k_faces: task cost histogram (cycles < 2^13, 2^14, ...):", [b2[32 + i] for i in range(16)])
 print("k_faces: slowest task %d cycles (n %d H %d faces %d | succ %d jump %d own %d wave %d lane %d compact %d); sum %d; WG lifetime avg %.3g max %.3g over %d WGs" % (b2[48], b2[49], b2[50], b2[55], b2[56], b2[57], b2[58], b2[59], b2[60], b2[61], b2[51], b2[52] / max(b2[54], 1), b2[53], b2[54]))

@@ -2137,6 +2137,24 @@ __global__ __launch_bounds__(SURTR_LANES) void k_hull_probe(const float* __restr
 }
 
 // ------------------------------------------------------------------ k_faces
+#ifdef SURTR_STAMP
+// What stamp 63 ("wave ears") is made of, in wave-cycles (lane 0 of EVERY wave, summed): 0 the barrier before and the LDS staging,
+// 1 the length ballots (faceLo / faceLen reads), 2 per-face set-up of the wave clippers (loads, normal, IsCCW, first reflex
+// flags), 3 their sequential loop with the closing triangles, 4 the wait at the closing barrier, 5 faces clipped on a wave, 6 the
+// whole phase per wave (what 0 .. 4 leave of it is the face loop's own bookkeeping).
+__device__ unsigned long long g_stamp_faces[8];
+#define EAR_T0 const unsigned long long ear_t0 = __builtin_readcyclecounter()
+#define EAR_T1 const unsigned long long ear_t1 = __builtin_readcyclecounter()
+#define EAR_T2 do { if (lane == 0) { atomicAdd(&g_stamp_faces[2], ear_t1 - ear_t0); atomicAdd(&g_stamp_faces[3], __builtin_readcyclecounter() - ear_t1); atomicAdd(&g_stamp_faces[5], 1ull); } } while (0)
+#define FACES_T(name) const unsigned long long name = __builtin_readcyclecounter()
+#define FACES_ADD(i, d) do { if (lane_id() == 0) atomicAdd(&g_stamp_faces[i], (unsigned long long)(d)); } while (0)
+#else
+#define EAR_T0
+#define EAR_T1
+#define EAR_T2 do { } while (0)
+#define FACES_T(name)
+#define FACES_ADD(i, d) do { } while (0)
+#endif
 
 __device__ __forceinline__ bool on_right(const float* a, const float* b, const float* c, float nx, float ny, float nz)
 {
@@ -2147,11 +2165,19 @@ __device__ __forceinline__ bool on_right(const float* a, const float* b, const f
     return dot3(cx, cy, cz, nx, ny, nz) > 0.f;
 }
 
+// What all four clippers leave in out[0] of a face that stalled (no vertex id): k_faces places the faces before it knows their fate.
+#define EAR_STALLED 0xFFFFFFFFu
+
 // Poly::EarClipping (Src/Poly.cpp:764-913) for one face, one lane.  loop = vertex ids of the face;
 // tmp = 3*N ints (prev, next, reflex).  Writes vertex ids (3 per triangle) to out; returns the count.
-// pos / loop may be global or LDS (k_faces stages small fragments): always inlined, so that the compiler sees which.
+// The fan finish (all four clippers): the loop only ever clears reflex flags, and once none is set every candidate is an ear, no
+// inside test runs, no flag is looked at again and nothing is skipped -- with p = prv[cur] the remaining triangles are (p, v, nxt[v])
+// for v = cur, nxt[cur], ... along the ring, the last one being the loop's closing triangle (prv[cur], cur, nxt[cur]).  The sequential
+// loop therefore runs only while a reflex vertex is left, and the rest is written without tests.
+// Out of line, on the global copies of positions and loops: k_faces sends it only the faces above SURTR_EAR_WAVE_MAX corners, and
+// inlined into the lane loop it cost the common path registers (k_faces: 23 spilled registers with it inline, 11 without).
 template <class LP>
-__device__ __attribute__((always_inline)) static inline uint32_t ear_clip_face(const float* pos, const LP* loop, int N, int32_t* tmp, uint32_t* out)
+__device__ __attribute__((noinline)) static uint32_t ear_clip_face(const float* pos, const LP* loop, int N, int32_t* tmp, uint32_t* out)
 {
     if (N <= 2) return 0;
     if (N == 3) { out[0] = loop[0]; out[1] = loop[1]; out[2] = loop[2]; return 3; }
@@ -2166,7 +2192,7 @@ __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_face(c
         float sx = 0.f, sy = 0.f, sz = 0.f;
         for (int v = 0; v < N; ++v)
         {
-            const float* p = pos + 3 * loop[v]; const float* q = pos + 3 * loop[(v + 1) % N];
+            const float* p = pos + 3 * loop[v]; const float* q = pos + 3 * loop[v + 1 == N ? 0 : v + 1];
             const float ux = p[0] - A0[0], uy = p[1] - A0[1], uz = p[2] - A0[2];
             const float wx = q[0] - A0[0], wy = q[1] - A0[1], wz = q[2] - A0[2];
             sx = sx + (uy * wz - uz * wy); sy = sy + (uz * wx - ux * wz); sz = sz + (ux * wy - uy * wx);
@@ -2174,12 +2200,16 @@ __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_face(c
         if (dot3(sx, sy, sz, nx, ny, nz) < 0.f) { nx = -nx; ny = -ny; nz = -nz; }
     }
     int32_t* prv = tmp; int32_t* nxt = tmp + N; int32_t* rfx = tmp + 2 * N;
-    for (int i = 0; i < N; ++i) { prv[i] = (i + N - 1) % N; nxt[i] = (i + 1) % N; }
+    for (int i = 0; i < N; ++i) { prv[i] = i == 0 ? N - 1 : i - 1; nxt[i] = i + 1 == N ? 0 : i + 1; }
+    int nrfx = 0;                                              // reflex vertices left
     for (int i = 0; i < N; ++i)
+    {
         rfx[i] = on_right(pos + 3 * loop[prv[i]], pos + 3 * loop[i], pos + 3 * loop[nxt[i]], nx, ny, nz) ? 0 : 1;
+        nrfx += rfx[i];
+    }
     int skipped = 0, left = N, cur = 0;
     uint32_t at = 0;
-    while (left > 3)
+    while (left > 3 && nrfx > 0)
     {
         const int p = prv[cur], n = nxt[cur];
         bool ear = rfx[cur] == 0;
@@ -2207,19 +2237,26 @@ __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_face(c
             {
                 const int v = adj[k];
                 if (!rfx[v]) continue;
-                rfx[v] = on_right(pos + 3 * loop[prv[v]], pos + 3 * loop[v], pos + 3 * loop[nxt[v]], nx, ny, nz) ? 0 : 1;
+                if (on_right(pos + 3 * loop[prv[v]], pos + 3 * loop[v], pos + 3 * loop[nxt[v]], nx, ny, nz)) { rfx[v] = 0; --nrfx; }
             }
             at += 3; --left; skipped = 0;
         }
-        else if (++skipped > left) return 0;             // stalled: the face is dropped (:899-903)
+        else if (++skipped > left) { out[0] = EAR_STALLED; return 0; }      // stalled: the face is dropped (:899-903)
         cur = n;
     }
-    out[at] = loop[prv[cur]]; out[at + 1] = loop[cur]; out[at + 2] = loop[nxt[cur]];
-    return at + 3;
+    const uint32_t lp = (uint32_t)loop[prv[cur]];             // the fan finish
+    for (int v = cur; left > 2; --left)
+    {
+        const int n = nxt[v];
+        out[at] = lp; out[at + 1] = loop[v]; out[at + 2] = loop[n];
+        at += 3; v = n;
+    }
+    return at;
 }
 
 // The same for a face of at most 8 vertices (the quads, in practice: 5..64-gons go to the wave version) with prev / next /
 // reflex packed into registers instead of a scratch array in global memory.  Same traversal, same triangles.
+// pos / loop may be global or LDS (k_faces stages small fragments): always inlined, so that the compiler sees which.
 template <class LP>
 __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_small(const float* pos, const LP* loop, int N, uint32_t* out)
 {
@@ -2237,7 +2274,7 @@ __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_small(
         float sx = 0.f, sy = 0.f, sz = 0.f;
         for (int v = 0; v < N; ++v)
         {
-            const float* p = P(v); const float* q = P((v + 1) % N);
+            const float* p = P(v); const float* q = P(v + 1 == N ? 0 : v + 1);
             const float ux = p[0] - A0[0], uy = p[1] - A0[1], uz = p[2] - A0[2];
             const float wx = q[0] - A0[0], wy = q[1] - A0[1], wz = q[2] - A0[2];
             sx = sx + (uy * wz - uz * wy); sy = sy + (uz * wx - ux * wz); sz = sz + (ux * wy - uy * wx);
@@ -2247,12 +2284,12 @@ __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_small(
     uint32_t prv = 0, nxt = 0, rfx = 0;                        // 4 bits per vertex / 1 bit per vertex
     auto get = [](uint32_t w, int i) -> int { return (int)((w >> (4 * i)) & 15u); };
     auto put = [](uint32_t& w, int i, int v) { w = (w & ~(15u << (4 * i))) | ((uint32_t)v << (4 * i)); };
-    for (int i = 0; i < N; ++i) { put(prv, i, (i + N - 1) % N); put(nxt, i, (i + 1) % N); }
+    for (int i = 0; i < N; ++i) { put(prv, i, i == 0 ? N - 1 : i - 1); put(nxt, i, i + 1 == N ? 0 : i + 1); }
     for (int i = 0; i < N; ++i)
         if (!on_right(P(get(prv, i)), P(i), P(get(nxt, i)), nx, ny, nz)) rfx |= 1u << i;
     int skipped = 0, left = N, cur = 0;
     uint32_t at = 0;
-    while (left > 3)
+    while (left > 3 && rfx != 0u)
     {
         const int p = get(prv, cur), n = get(nxt, cur);
         bool ear = ((rfx >> cur) & 1u) == 0u;
@@ -2284,11 +2321,17 @@ __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_small(
             }
             at += 3; --left; skipped = 0;
         }
-        else if (++skipped > left) return 0;             // stalled: the face is dropped (:899-903)
+        else if (++skipped > left) { out[0] = EAR_STALLED; return 0; }      // stalled: the face is dropped (:899-903)
         cur = n;
     }
-    out[at] = loop[get(prv, cur)]; out[at + 1] = loop[cur]; out[at + 2] = loop[get(nxt, cur)];
-    return at + 3;
+    const uint32_t lp = (uint32_t)loop[get(prv, cur)];        // the fan finish
+    for (int v = cur; left > 2; --left)
+    {
+        const int n = get(nxt, v);
+        out[at] = lp; out[at + 1] = loop[v]; out[at + 2] = loop[n];
+        at += 3; v = n;
+    }
+    return at;
 }
 
 #ifndef SURTR_EAR_WAVE_MAX
@@ -2298,11 +2341,14 @@ __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_small(
 // Poly::EarClipping for one face of 5..64 vertices on one wave: lane i holds vertex i (position, prev/next
 // link, reflex flag) in registers; the sequential ear loop (:868-906) runs wave-uniformly, and the scan of the
 // reflex list (:837-856, an "any reflex vertex inside the candidate ear") is one ballot.  Same triangles, same
-// order, same stall rule as ear_clip_face.
+// order, same stall rule as ear_clip_face.  The fan finish is one step: the ring is the lanes still linked, in cyclic index order
+// from cur (unlinking keeps the order), the place of a lane in it is a popcount of the alive mask, and every lane writes its own
+// triangle (prv[cur], lane, nxt).
 template <class LP>
 __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_face_wave(const float* pos, const LP* loop, int N, uint32_t* out)
 {
     const int lane = (int)lane_id();
+    EAR_T0;
     const bool mine = lane < N;
     const int32_t vid = (int32_t)loop[mine ? lane : 0];
     const float x = pos[3 * vid], y = pos[3 * vid + 1], z = pos[3 * vid + 2];
@@ -2326,14 +2372,14 @@ __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_face_w
         float sx = 0.f, sy = 0.f, sz = 0.f;
         for (int v = 0; v < N; ++v)
         {
-            const int q = (v + 1) % N;
+            const int q = v + 1 == N ? 0 : v + 1;
             const float ux = bx(v) - ax0, uy = by(v) - ay0, uz = bz(v) - az0;
             const float wx = bx(q) - ax0, wy = by(q) - ay0, wz = bz(q) - az0;
             sx = sx + (uy * wz - uz * wy); sy = sy + (uz * wx - ux * wz); sz = sz + (ux * wy - uy * wx);
         }
         if (dot3(sx, sy, sz, nx, ny, nz) < 0.f) { nx = -nx; ny = -ny; nz = -nz; }
     }
-    int prv = (lane + N - 1) % N, nxt = (lane + 1) % N;
+    int prv = lane == 0 ? N - 1 : lane - 1, nxt = lane + 1 >= N ? 0 : lane + 1;
     auto right_of = [&](float ax, float ay, float az, float bx_, float by_, float bz_, float cx, float cy, float cz) {
         const float ux = bx_ - ax, uy = by_ - ay, uz = bz_ - az;
         const float wx = cx - ax, wy = cy - ay, wz = cz - az;
@@ -2347,9 +2393,10 @@ __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_face_w
         const float qx = __shfl(x, nxt, 64), qy = __shfl(y, nxt, 64), qz = __shfl(z, nxt, 64);
         rfx = mine && !right_of(px_, py_, pz_, x, y, z, qx, qy, qz);
     }
+    EAR_T1;
     int skipped = 0, left = N, cur = 0;
     uint32_t at = 0;
-    while (left > 3)
+    while (left > 3 && __ballot(rfx) != 0ull)
     {
         const int p = EAR_BCAST(prv, cur), n = EAR_BCAST(nxt, cur);
         const bool cur_reflex = EAR_BCAST((int)rfx, cur) != 0;
@@ -2374,6 +2421,7 @@ __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_face_w
             if (lane == 0) { out[at] = (uint32_t)loop[p]; out[at + 1] = (uint32_t)loop[cur]; out[at + 2] = (uint32_t)loop[n]; }
             if (lane == p) nxt = n;
             if (lane == n) prv = p;
+            if (lane == cur) nxt = -1;                          // unlinked (nothing reads it again but the fan finish)
             // reflex flags of the two neighbours, only if they were reflex (:885-893)
             // (all broadcasts are done by the whole wave; only the two lanes use them)
             const int np = EAR_BCAST(prv, p), nn = EAR_BCAST(nxt, n);
@@ -2383,14 +2431,22 @@ __device__ __attribute__((always_inline)) static inline uint32_t ear_clip_face_w
             if (lane == n && rfx) rfx = !right_of(ppx, ppy, ppz, x, y, z, nnx, nny, nnz);
             at += 3; --left; skipped = 0;
         }
-        else if (++skipped > left) return 0;             // stalled: the face is dropped (:899-903)
+        else if (++skipped > left) { if (lane == 0) out[0] = EAR_STALLED; return 0; }      // stalled: the face is dropped (:899-903)
         cur = n;
     }
-    {
-        const int p = EAR_BCAST(prv, cur), n = EAR_BCAST(nxt, cur);
-        if (lane == 0) { out[at] = (uint32_t)loop[p]; out[at + 1] = (uint32_t)loop[cur]; out[at + 2] = (uint32_t)loop[n]; }
+    {   // the fan finish: lane v, the k-th of the ring counted from cur, writes triangle k = (prv[cur], v, nxt[v]); the last two have none
+        const int p = EAR_BCAST(prv, cur);
+        const unsigned long long alive = __ballot(mine && nxt >= 0);      // the lanes still linked
+        const unsigned long long below = (1ull << lane) - 1ull, from = ~0ull << cur;
+        const uint32_t k = lane >= cur ? (uint32_t)__popcll(alive & from & below) : (uint32_t)__popcll(alive & from) + (uint32_t)__popcll(alive & below);
+        if (((alive >> lane) & 1ull) != 0ull && k + 2u < (uint32_t)left)
+        {
+            uint32_t* o = out + at + 3u * k;
+            o[0] = (uint32_t)loop[p]; o[1] = (uint32_t)loop[lane]; o[2] = (uint32_t)loop[nxt];
+        }
     }
-    return at + 3;
+    EAR_T2;
+    return at + 3u * (uint32_t)(left - 2);
 }
 
 // The same for a face of up to 64 * K vertices: lane l holds the vertices l, l + 64, ... (K of them) in registers.  Every index
@@ -2403,6 +2459,7 @@ template <int K, class LP>
 __device__ __attribute__((noinline)) static uint32_t ear_clip_face_wave_k(const float* pos, const LP* loop, int N, uint32_t* out)
 {
     const int lane = (int)lane_id();
+    EAR_T0;
     float x[K], y[K], z[K]; int prv[K], nxt[K]; bool rfx[K], mine[K];
 #pragma unroll
     for (int j = 0; j < K; ++j)
@@ -2411,7 +2468,7 @@ __device__ __attribute__((noinline)) static uint32_t ear_clip_face_wave_k(const 
         mine[j] = v < N;
         const int32_t vid = (int32_t)loop[mine[j] ? v : 0];
         x[j] = pos[3 * vid]; y[j] = pos[3 * vid + 1]; z[j] = pos[3 * vid + 2];
-        prv[j] = (v + N - 1) % N; nxt[j] = (v + 1) % N; rfx[j] = false;
+        prv[j] = v == 0 ? N - 1 : v - 1; nxt[j] = v + 1 >= N ? 0 : v + 1; rfx[j] = false;
     }
     // value of vertex i (wave-uniform i)
     auto bf = [&](const float (&a)[K], int i) -> float {
@@ -2447,7 +2504,7 @@ __device__ __attribute__((noinline)) static uint32_t ear_clip_face_wave_k(const 
         float px_ = ax0, py_ = ay0, pz_ = az0;
         for (int v = 0; v < N; ++v)
         {
-            const int q = (v + 1) % N;
+            const int q = v + 1 == N ? 0 : v + 1;
             const float qx = bf(x, q), qy = bf(y, q), qz = bf(z, q);
             const float ux = px_ - ax0, uy = py_ - ay0, uz = pz_ - az0;
             const float wx = qx - ax0, wy = qy - ay0, wz = qz - az0;
@@ -2481,9 +2538,16 @@ __device__ __attribute__((noinline)) static uint32_t ear_clip_face_wave_k(const 
 #pragma unroll
         for (int j = 0; j < K; ++j) if (lane == (i & 63) && (i >> 6) == j) a[j] = val;
     };
+    EAR_T1;
     int skipped = 0, left = N, cur = 0;
     uint32_t at = 0;
-    while (left > 3)
+    auto any_reflex = [&]() -> bool {
+        bool r = false;
+#pragma unroll
+        for (int j = 0; j < K; ++j) r = r || rfx[j];
+        return __ballot(r) != 0ull;
+    };
+    while (left > 3 && any_reflex())
     {
         const int p = bi(prv, cur), n = bi(nxt, cur);
         bool ear = !bb(rfx, cur);
@@ -2511,6 +2575,7 @@ __device__ __attribute__((noinline)) static uint32_t ear_clip_face_wave_k(const 
             if (lane == 0) { out[at] = (uint32_t)loop[p]; out[at + 1] = (uint32_t)loop[cur]; out[at + 2] = (uint32_t)loop[n]; }
             set_i(nxt, p, n);
             set_i(prv, n, p);
+            set_i(nxt, cur, -1);                                // unlinked (nothing reads it again but the fan finish)
             // reflex flags of the two neighbours, only if they were reflex (:885-893)
             const int np = bi(prv, p), nn = bi(nxt, n);
             const float npx = bf(x, np), npy = bf(y, np), npz = bf(z, np), nnx = bf(x, nn), nny = bf(y, nn), nnz = bf(z, nn);
@@ -2524,16 +2589,90 @@ __device__ __attribute__((noinline)) static uint32_t ear_clip_face_wave_k(const 
             }
             at += 3; --left; skipped = 0;
         }
-        else if (++skipped > left) return 0;             // stalled: the face is dropped (:899-903)
+        else if (++skipped > left) { if (lane == 0) out[0] = EAR_STALLED; return 0; }      // stalled: the face is dropped (:899-903)
         cur = n;
     }
-    {
-        const int p = bi(prv, cur), n = bi(nxt, cur);
-        if (lane == 0) { out[at] = (uint32_t)loop[p]; out[at + 1] = (uint32_t)loop[cur]; out[at + 2] = (uint32_t)loop[n]; }
+    {   // the fan finish: vertex v, the k-th of the ring counted from cur, gets triangle k = (prv[cur], v, nxt[v]); the last two have none
+        const uint32_t lp = (uint32_t)loop[bi(prv, cur)];
+        const unsigned long long below = (1ull << lane) - 1ull;
+        unsigned long long alive[K];                           // the vertices still linked, per slot
+        uint32_t before_cur = 0, base = 0;                     // alive vertices of lower index than cur; than slot j
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+        {
+            alive[j] = __ballot(mine[j] && nxt[j] >= 0);
+            if ((cur >> 6) == j) before_cur = base + (uint32_t)__popcll(alive[j] & ((1ull << (cur & 63)) - 1ull));
+            base += (uint32_t)__popcll(alive[j]);
+        }
+        base = 0;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+        {
+            const int v = lane + 64 * j;
+            const uint32_t before_v = base + (uint32_t)__popcll(alive[j] & below);
+            const uint32_t k = v >= cur ? before_v - before_cur : (uint32_t)left - before_cur + before_v;
+            if (((alive[j] >> lane) & 1ull) != 0ull && k + 2u < (uint32_t)left)
+            {
+                uint32_t* o = out + at + 3u * k;
+                o[0] = lp; o[1] = (uint32_t)loop[v]; o[2] = (uint32_t)loop[nxt[j]];
+            }
+            base += (uint32_t)__popcll(alive[j]);
+        }
     }
-    return at + 3;
+    EAR_T2;
+    return at + 3u * (uint32_t)(left - 2);
 }
 #endif
+
+// Step 5 of k_faces for the fragments that need it, out of line so that the common route pays no registers for it: the triangle
+// lists of the faces, compacted in face order.  fcnt != nullptr: the lists lie in tri at 3 * faceLo with their counts in fcnt (the
+// fan, fragments with a face below three corners); the indices are reserved here and the lists copied into the arena.
+// fcnt == nullptr: the lists lie in the arena already, face fi at placed_at + 3 * (faceLo - 2 * fi), and a face that stalled has
+// EAR_STALLED in its first index: the others are gathered in tri and copied back to placed_at.  Every thread must call it.
+struct FacesCompacted { uint32_t at, n; bool full; };
+__device__ __attribute__((noinline)) static FacesCompacted faces_compact(uint32_t nfaces, uint2* blk, Shared& sh, const int32_t* faceLo, const int32_t* faceLen,
+                                                                         const uint32_t* fcnt, uint32_t* tri, uint32_t* idx, uint32_t* cur_i, uint32_t capI, uint32_t placed_at)
+{
+    const bool placed = fcnt == nullptr;
+    auto src_of = [&](uint32_t fi) -> const uint32_t* {
+        const uint32_t lo = (uint32_t)faceLo[fi];
+        return placed ? idx + placed_at + 3u * (lo - 2u * fi) : tri + 3u * (size_t)lo;
+    };
+    auto cntfn = [&](uint32_t fi) -> uint2 {
+        if (!placed) return make_uint2(fcnt[fi], 0u);
+        return make_uint2(src_of(fi)[0] == EAR_STALLED ? 0u : 3u * ((uint32_t)faceLen[fi] - 2u), 0u);
+    };
+    uint32_t nidx = 0, dum = 0, at = placed_at;
+    scan_blocks(nfaces, blk, sh, cntfn, nidx, dum);
+    if (!placed)
+    {
+        if (threadIdx.x == 0) sh.misc[0] = atomicAdd(cur_i, nidx);
+        __syncthreads();
+        at = sh.misc[0];
+        if ((uint64_t)at + nidx > capI) return FacesCompacted{at, nidx, true};
+    }
+    uint32_t* const to = placed ? tri : idx + at;
+    const uint32_t nb = (nfaces + SURTR_LANES - 1u) >> SURTR_LSH;
+    for (uint32_t b = wave_id(); b < nb; b += group_waves())
+    {
+        const uint32_t fi = (b << SURTR_LSH) + lane_id();
+        uint2 c = make_uint2(0u, 0u);
+        if (fi < nfaces) c = cntfn(fi);
+        const uint2 ex = wave_excl2(c);
+        if (fi < nfaces && c.x)
+        {
+            const uint32_t* src = src_of(fi);
+            uint32_t* dst = to + blk[b].x + ex.x;
+            for (uint32_t q = 0; q < c.x; ++q) dst[q] = src[q];
+        }
+    }
+    if (placed)
+    {
+        __syncthreads();
+        for (uint32_t q = threadIdx.x; q < nidx; q += group_size()) idx[at + q] = tri[q];
+    }
+    return FacesCompacted{at, nidx, false};
+}
 
 // fan != 0: RenderPolyhedron's isConvex branch (triangle fan per face, Src/Poly.cpp:696-706) instead of EarClipping.
 // face_n / face_off / face_idx (nullptr in an event): the face loops of Poly::ExtractFaces for the single-solid operators
@@ -2610,7 +2749,12 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
         // Fragments are small: the topology is staged in LDS (16-bit) whenever it fits, and the passes below read that copy.
         const bool topo_lds = n <= FL_V && H <= FL_H && n < 0xFFFFu;
         const bool jump_lds = topo_lds && H <= FL_J;
-        if (tid == 0) sh.flagBad = 0;
+        // The words of sh.misc in this kernel: [0..2] results of the serial ExtractFaces and of faces_compact's reservation, [7] the
+        // ticket.  [3] a face of fewer than three corners was found, [4] a face stalled in its ear clipper, [5] where the fragment's
+        // index range starts (see 4. and 5.): these three are written once per fragment, here and in 3. / 4., always with a barrier
+        // before the first reader, and are READ AGAIN wherever the route or the range is needed (direct(), out_of()) up to the end of
+        // the fragment -- nothing called in between (scan_blocks: sh.wsum only; the clippers: no LDS of sh) may write them.
+        if (tid == 0) { sh.flagBad = 0; sh.misc[3] = 0u; sh.misc[4] = 0u; }
         if (topo_lds)
         {
             for (uint32_t v = tid; v < n; v += group_size()) { f_loff[v] = (uint16_t)(loff[v] - fr.mh_off); f_llen[v] = (uint16_t)llen[v]; }
@@ -2832,6 +2976,7 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
                             prev = curv; curv = nx;
                         }
                         faceLo[fi] = (int32_t)lo; faceLen[fi] = (int32_t)len;
+                        if (len < 3u) sh.misc[3] = 1u;
                     }
                 }
                 return true;
@@ -2881,6 +3026,7 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
                     {
                         const uint32_t fi = blk[b].x + ex.x, lo = blk[b].y + ex.y;
                         faceLo[fi] = (int32_t)lo; faceLen[fi] = (int32_t)c.y;
+                        if (c.y < 3u) sh.misc[3] = 1u;
                         lo_of[e] = (uint16_t)lo; len_of[e] = (uint16_t)c.y;
                     }
                 }
@@ -2935,6 +3081,7 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
                         if (bad) break;
                         visited[slot_of(prev, curv)] = 1;
                         faceLo[nfc] = (int32_t)lo; faceLen[nfc] = (int32_t)len; ++nfc; lo += len;
+                        if (len < 3u) sh.misc[3] = 1u;
                     }
                 }
                 sh.misc[0] = nfc; sh.misc[1] = lo; sh.misc[2] = bad ? 1u : 0u;
@@ -2953,7 +3100,7 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
         __syncthreads();
         if (!pinched) break;
         irregular = true;
-        if (tid == 0) sh.flagBad = 0;
+        if (tid == 0) { sh.flagBad = 0; sh.misc[3] = 0u; }
         __syncthreads();
         }   // attempts
         if (failed)
@@ -2975,17 +3122,34 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
             if (tid == 0) { face_off[nfaces] = lensum; face_n[0] = nfaces; face_n[1] = lensum; }
         }
         STAMP(62);
+        FACES_T(ft_0);
         // 4. triangulate: faces of 5..256 vertices one per wave (registers only), the others one per lane;
         //    room for 3*len indices at 3*lo.  The arrays of the face search are dead now: a small fragment's positions and
         //    loops go there, so that the ear tests read LDS instead of waiting for global memory vertex by vertex.
+        //    The triangles go straight to the index arena: a face of len >= 3 corners gets len - 2 triangles unless it stalls, and the
+        //    loops lie packed in face order (faceLo = the lengths before it), so with no face below three corners face fi writes
+        //    at 3 * (faceLo - 2 * fi) of a range of 3 * (lensum - 2 * nfaces) indices, reserved before the first ear is clipped.  A
+        //    stalled face leaves a mark in its first index; 5. then closes the gaps.  The fan, and a fragment with a face of fewer
+        //    than three corners, go through tri / fcnt and the compaction as before.
         const bool ear_lds = !fan && n <= FL_V && lensum <= FL_J;
+        //    (sh.misc[5]: where the range starts; that and the route are read from LDS where needed: the clippers need the registers)
+        auto direct = [&]() -> bool { return !fan && SURTR_UNIFORM(sh.misc[3]) == 0u; };
+        if (direct() && tid == 0) sh.misc[5] = atomicAdd(&A.cursors[CUR_I], 3u * (lensum - 2u * nfaces));
         __syncthreads();
+        if (direct() && (uint64_t)sh.misc[5] + 3u * (lensum - 2u * nfaces) > A.capI) { if (tid == 0) atomicMax(&A.cursors[CUR_STATUS], (uint32_t)SURTR_E_CAPACITY); continue; }
+        auto out_of = [&](uint32_t fi, uint32_t lo) -> uint32_t* { return direct() ? A.idx + SURTR_UNIFORM(sh.misc[5]) + 3u * (lo - 2u * fi) : tri + 3u * (size_t)lo; };
+        auto count_of = [&](uint32_t fi, uint32_t cnt) {      // what a clipper returned for face fi
+            if (!direct()) fcnt[fi] = cnt;
+            else if (cnt == 0u) sh.misc[4] = 1u;
+        };
         if (ear_lds)
         {
             for (uint32_t i = tid; i < 3u * n; i += group_size()) FU.ear.pos[i] = pos[i];
             for (uint32_t e = tid; e < lensum; e += group_size()) FU.ear.loop[e] = (uint16_t)loopbuf[e];
             __syncthreads();
         }
+        FACES_T(ft_1);
+        FACES_ADD(0, ft_1 - ft_0);
         if (fan)
         {
             // isConvex: (f[0], f[v], f[v+1]) for v = 1 .. size-2 (Src/Poly.cpp:698-705)
@@ -3004,23 +3168,29 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
         // vertices among them: most faces are triangles, and a wave that looked at them one by one spent its time waiting
         for (uint32_t f0 = 0; f0 < (fan ? 0u : nfaces); f0 += SURTR_LANES)
         {
+            FACES_T(ft_b0);
             const uint32_t fl = f0 + lane_id();
             uint32_t mylo = 0, mylen = 0;
             if (fl < nfaces) { mylo = (uint32_t)faceLo[fl]; mylen = (uint32_t)faceLen[fl]; }
             unsigned long long todo = __ballot(mylen >= 5u && mylen <= SURTR_EAR_WAVE_MAX);
+            FACES_ADD(1, __builtin_readcyclecounter() - ft_b0);
             for (uint32_t ord = 0; todo != 0ull; todo &= todo - 1ull, ++ord)
             {
                 if (ord % group_waves() != wave_id()) continue;
                 const uint32_t src = (uint32_t)__builtin_ctzll(todo);
                 const uint32_t lo = lane_bcast(mylo, src), len = lane_bcast(mylen, src);
+                uint32_t* const out = out_of(f0 + src, lo);
                 uint32_t cnt;
-                if (len > 64u) cnt = ear_clip_face_wave_k<SURTR_EAR_WAVE_MAX / 64>(pos, (const int32_t*)loopbuf + lo, (int)len, tri + 3u * (size_t)lo);      // (several vertices per lane)
-                else if (ear_lds) cnt = ear_clip_face_wave((const float*)FU.ear.pos, (const uint16_t*)FU.ear.loop + lo, (int)len, tri + 3u * (size_t)lo);
-                else cnt = ear_clip_face_wave(pos, (const int32_t*)loopbuf + lo, (int)len, tri + 3u * (size_t)lo);
-                if (lane_id() == 0) fcnt[f0 + src] = cnt;
+                if (len > 64u) cnt = ear_clip_face_wave_k<SURTR_EAR_WAVE_MAX / 64>(pos, (const int32_t*)loopbuf + lo, (int)len, out);      // (several vertices per lane)
+                else if (ear_lds) cnt = ear_clip_face_wave((const float*)FU.ear.pos, (const uint16_t*)FU.ear.loop + lo, (int)len, out);
+                else cnt = ear_clip_face_wave(pos, (const int32_t*)loopbuf + lo, (int)len, out);
+                if (lane_id() == 0) count_of(f0 + src, cnt);
             }
         }
+        FACES_T(ft_e0);
         __syncthreads();
+        FACES_ADD(4, __builtin_readcyclecounter() - ft_e0);
+        FACES_ADD(6, __builtin_readcyclecounter() - ft_0);
         STAMP(63);
 #endif
         for (uint32_t fi = tid; fi < (fan ? 0u : nfaces); fi += group_size())
@@ -3029,44 +3199,31 @@ __global__ __launch_bounds__(SURTR_WG) __attribute__((amdgpu_waves_per_eu(4, 8))
 #if SURTR_LANES == 64
             if (len >= 5u && len <= SURTR_EAR_WAVE_MAX) continue;
 #endif
-            uint32_t* out = tri + 3u * (size_t)lo;
+            uint32_t* out = out_of(fi, lo);
             uint32_t cnt = 0u;
             if (len >= 3u && len <= 8u)
                 cnt = ear_lds ? ear_clip_small((const float*)FU.ear.pos, (const uint16_t*)FU.ear.loop + lo, (int)len, out)
                               : ear_clip_small(pos, (const int32_t*)loopbuf + lo, (int)len, out);
             else if (len > 8u) cnt = ear_clip_face(pos, (const int32_t*)loopbuf + lo, (int)len, eartmp + 3 * (size_t)lo, out);
-            fcnt[fi] = cnt;
+            count_of(fi, cnt);
 #ifdef SURTR_STAMP
             if (len > 64u) { atomicAdd(&g_stamp[66], 1ull); atomicAdd(&g_stamp[67], (unsigned long long)len); }
 #endif
         }
         __syncthreads();
         STAMP(64);
-        // 5. compact the triangle lists of the faces, in face order, into the index arena
-        auto cntfn = [&](uint32_t fi) -> uint2 { return make_uint2(fcnt[fi], 0u); };
-        uint32_t nidx = 0, dum = 0;
-        scan_blocks(nfaces, blk, sh, cntfn, nidx, dum);
-        if (tid == 0) sh.misc[0] = atomicAdd(&A.cursors[CUR_I], nidx);
-        __syncthreads();
-        const uint32_t ioff = sh.misc[0];
-        if ((uint64_t)ioff + nidx > A.capI) { if (tid == 0) atomicMax(&A.cursors[CUR_STATUS], (uint32_t)SURTR_E_CAPACITY); continue; }
+        // 5. compact the triangle lists of the faces, in face order, into the index arena: only where they are not there already
+        //    (faces_compact, out of line).  After a stall the faces that have triangles move up inside the range reserved in 4.: idx_n is
+        //    the true count, and the unused tail of the reservation is all that tells the fragment from one compacted before it was placed.
+        const bool placed = direct();
+        uint32_t nidx = placed ? 3u * (lensum - 2u * nfaces) : 0u, idx_at = placed ? sh.misc[5] : 0u;
+        if (!placed || sh.misc[4] != 0u)
         {
-            const uint32_t nb = (nfaces + SURTR_LANES - 1u) >> SURTR_LSH;
-            for (uint32_t b = wave_id(); b < nb; b += group_waves())
-            {
-                const uint32_t fi = (b << SURTR_LSH) + lane_id();
-                uint2 c = make_uint2(0u, 0u);
-                if (fi < nfaces) c = cntfn(fi);
-                const uint2 ex = wave_excl2(c);
-                if (fi < nfaces && c.x)
-                {
-                    const uint32_t* src = tri + 3u * (size_t)(uint32_t)faceLo[fi];
-                    uint32_t* dst = A.idx + ioff + blk[b].x + ex.x;
-                    for (uint32_t q = 0; q < c.x; ++q) dst[q] = src[q];
-                }
-            }
+            const FacesCompacted c = faces_compact(nfaces, blk, sh, faceLo, faceLen, placed ? nullptr : fcnt, tri, A.idx, &A.cursors[CUR_I], A.capI, idx_at);
+            if (c.full) { if (tid == 0) atomicMax(&A.cursors[CUR_STATUS], (uint32_t)SURTR_E_CAPACITY); continue; }
+            idx_at = c.at; nidx = c.n;
         }
-        if (tid == 0) { frags[f].idx_off = ioff; frags[f].idx_n = nidx; }     // field-wise: k_refit runs beside this kernel
+        if (tid == 0) { frags[f].idx_off = idx_at; frags[f].idx_n = nidx; }     // field-wise: k_refit runs beside this kernel
         STAMP(65);
 #ifdef SURTR_STAMP
         if (tid == 0)
@@ -4419,6 +4576,12 @@ int surtr_event_pack_dev(surtr_ctx* ctx, void* dev_blob, size_t capacity)
 }
 
 #ifdef SURTR_STAMP
+int surtr_debug_stamps_faces(unsigned long long out[8], int reset)
+{
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp_faces), sizeof(unsigned long long) * 8) != hipSuccess) return SURTR_E_HIP;
+    if (reset) { unsigned long long z[8] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_faces), z, sizeof(z)); }
+    return SURTR_OK;
+}
 int surtr_debug_stamps2(unsigned long long out[64], int reset)
 {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp2), sizeof(unsigned long long) * 64) != hipSuccess) return SURTR_E_HIP;
