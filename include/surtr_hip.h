@@ -114,6 +114,19 @@ int surtr_set_events_in_flight(surtr_ctx* ctx, uint32_t n);
 int surtr_set_scratch(surtr_ctx* ctx, uint32_t max_verts, uint32_t max_nbrs);
 /* Override the result arena capacities (vertices, neighbour entries, indices); 0 = automatic. */
 int surtr_set_arena(surtr_ctx* ctx, uint64_t verts, uint64_t nbrs, uint64_t idx);
+/* WHAT THE TWO CALLS PROMISE.  Any capacity, however small, gives either the exact event -- bit for bit the one the automatic
+ * capacities give -- or SURTR_E_CAPACITY, and nothing is written past a buffer either way.  An arena of exactly what the event
+ * takes (surtr_queue_stats out[0..2] after an automatic run: the cursors' final values) succeeds; one entry fewer in any of the
+ * three is refused.  Every take adds to its cursor before it compares, so the cursors of a refused event say what it would have
+ * needed from the stages that ran.  A scratch smaller than a solid needs refuses the pairs that reach the global clipper with it
+ * (SURTR_E_CAPACITY, never a topology flag); the literal clipper, which has nobody to hand on to, flags what does not fit it
+ * (out[90]).  The pre-pass's work lists, filled before anything is known to fit, are sized by the largest piece, not by
+ * max_verts.  After a refusal surtr_event_counts and surtr_event_download return SURTR_E_CAPACITY, surtr_event_pack_dev writes the
+ * header alone, a resident scene is unchanged and its commit is SURTR_E_STATE; with the capacities set back (0 = automatic) the
+ * same context gives the event again.  surtr_load_fragments and surtr_scene_fragments size the arena for what they load
+ * whatever was set.  tests/test_capacity_limits.py checks this on the emulation: exact event or SURTR_E_CAPACITY on every route;
+ * writes past the arena, the tables and the blobs through red zones; writes past a scratch slice only where they change the
+ * event, at one probed threshold, and at the end of the pool's last slice (the module says what its zones cannot see). */
 
 /* Per-kernel timing with HIP events recorded on the work stream (the reference's TIMER_* phase
  * timers, Inc/pch.h:122-141, Src/Surtr.cpp:1917-1941).  ms[i] = duration of the last launch of
@@ -219,7 +232,8 @@ int surtr_place_cells_in_pieces(surtr_ctx* ctx, uint32_t n_groups, const uint32_
 /* Bytes of the packed device blob holding the last event's fragments. */
 size_t surtr_event_blob_bytes(const surtr_counts* counts);
 /* Packs the last event's fragments into one contiguous device buffer (for an
- * all-gather over RCCL or a single D2H copy).  Layout: see DESIGN.md. */
+ * all-gather over RCCL or a single D2H copy).  Layout: see DESIGN.md.  A buffer that is too small, or an event that was refused
+ * (its status word is not SURTR_OK: an arena or a scratch too small), gets the header alone: zero counts, n_pairs and the status. */
 int surtr_event_pack_dev(surtr_ctx* ctx, void* dev_blob, size_t capacity_bytes);
 /* Splits a host copy of a blob into the arrays of surtr_fragments. */
 int surtr_blob_unpack_host(const void* host_blob, size_t bytes, surtr_counts* counts, surtr_fragments* out);

@@ -202,9 +202,14 @@ __device__ static Scratch carve(const ScratchPool& P, uint32_t wg)
     S.g_succ = (uint32_t*)take((size_t)P.CV * 4);
     S.g_pred = (uint32_t*)take((size_t)P.CV * 4);
     S.g_pcnt = (uint32_t*)take((size_t)P.CV * 4);
-    S.aux0 = (uint32_t*)take((size_t)P.CV * 4);
+    // (aux0 and aux2 are also the pre-pass's work lists -- prepass_select's needy, up to one entry per vertex of the INPUT, and und,
+    //  one per SURTR_SB of them -- filled before anything is known to fit: they have room for the largest piece even where
+    //  surtr_set_scratch makes CV smaller.  Sized by CV alone, a longer needy list ran on into aux1 .. aux3 of the same slice, where
+    //  nothing shows it, then into und, which the same loop reads, and the masks.  und gets VMAX entries too: more than it needs.)
+    const size_t AV = P.CV > P.VMAX ? P.CV : P.VMAX;
+    S.aux0 = (uint32_t*)take(AV * 4);
     S.aux1 = (uint32_t*)take((size_t)P.CV * 4);
-    S.aux2 = (uint32_t*)take((size_t)P.CV * 4);
+    S.aux2 = (uint32_t*)take(AV * 4);
     S.aux3 = (uint32_t*)take((size_t)P.CV * 4);
     S.g_gcomp = (int8_t*)take((size_t)P.CV);
     S.blk = (uint2*)take((size_t)(P.CV / SURTR_LANES + 4) * 8);
@@ -219,7 +224,7 @@ __device__ static Scratch carve(const ScratchPool& P, uint32_t wg)
 static size_t scratch_bytes_per_wg(uint32_t CV, uint32_t CH, uint32_t VMAX)
 {
     auto r = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    return 2 * r((size_t)CV * 12) + 11 * r((size_t)CV * 4) + 3 * r((size_t)CV) + 2 * r((size_t)CH * 4) + r((size_t)(CV / SURTR_LANES + 4) * 8) +
+    return 2 * r((size_t)CV * 12) + 9 * r((size_t)CV * 4) + 2 * r((size_t)std::max(CV, VMAX) * 4) + 3 * r((size_t)CV) + 2 * r((size_t)CH * 4) + r((size_t)(CV / SURTR_LANES + 4) * 8) +
            2 * r((size_t)(VMAX / SURTR_LANES + 2) * 8);
 }
 

@@ -3331,17 +3331,20 @@ __global__ __launch_bounds__(SURTR_WG) void k_pack(const FragRec* __restrict__ f
 {
     const surtr_counts c = *counts;
     const BlobLayout L = blob_layout(c);
-    if (L.total > capacity)
+    if (L.total > capacity || c.status != 0)
     {
         // the caller's buffer is too small: say so in the blob header (zero counts) and in the event's status word, so
-        // that neither a stale nor a zero-filled blob is taken for a result
+        // that neither a stale nor a zero-filled blob is taken for a result.  An event that was refused (an arena or a scratch
+        // too small) has no result either: its header carries the zero counts and the event's status, as surtr_event_download
+        // refuses it on the host, and the fragments that happened to fit stay where they are.
         if (blockIdx.x == 0 && threadIdx.x == 0)
         {
-            atomicMax(&A.cursors[CUR_STATUS], (uint32_t)SURTR_E_CAPACITY);
-            atomicMax(&counts->status, (uint32_t)SURTR_E_CAPACITY);
+            const uint32_t why = c.status != 0 ? c.status : (uint32_t)SURTR_E_CAPACITY;
+            atomicMax(&A.cursors[CUR_STATUS], why);
+            atomicMax(&counts->status, why);
             if (capacity >= sizeof(surtr_counts))
             {
-                surtr_counts z; memset(&z, 0, sizeof(z)); z.n_pairs = c.n_pairs; z.status = SURTR_E_CAPACITY;
+                surtr_counts z; memset(&z, 0, sizeof(z)); z.n_pairs = c.n_pairs; z.status = why;
                 *(surtr_counts*)blob = z;
             }
         }
@@ -4563,7 +4566,8 @@ int surtr_event_pack_dev(surtr_ctx* ctx, void* dev_blob, size_t capacity)
     (void)hipSetDevice(ctx->device);
     // capacity is checked on the device against the counts it holds (k_pack reports a blob that does not fit in its header
     // and in the event's status word); when the host already holds this event's counts it refuses here
-    if (ctx->last_current && blob_layout(ctx->last).total > capacity) return SURTR_E_CAPACITY;
+    // (the counts of a refused event size nothing: k_pack writes its header alone)
+    if (ctx->last_current && ctx->last.status == 0 && blob_layout(ctx->last).total > capacity) return SURTR_E_CAPACITY;
     const uint32_t grid = std::max(1u, std::min(ctx->cap_frags, 2048u));
     hipStream_t st = ctx->stream;
     PROF_BEGIN(5);

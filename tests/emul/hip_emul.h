@@ -88,20 +88,94 @@ static inline hipError_t hipMemGetInfo(size_t* f, size_t* t) { *f = (size_t)8 <<
 // Allocation bookkeeping shared by every translation unit of the library (tests/test_alloc_failures.py reaches it through ctypes):
 // the number of live allocations, the hipMalloc calls since the last surtr_emul_fail_alloc, and the one of them (0-based; -1: none)
 // that fails.
-struct EmulAllocs { long live = 0, calls = 0, fail_at = -1; };
+//
+// RED ZONES (tests/test_capacity_limits.py).  Every device block lies between two zones of EMUL_ZONE bytes filled with
+// EMUL_ZONE_BYTE: the front zone ends at the payload's first byte, the back zone begins at the byte after its last one (the
+// size is not rounded up, so a write one element past the end lands in the zone).  The payload is zeroed and starts on a
+// 256-byte boundary, as hipMalloc's does (the image arena is read in 16-byte words).  hipFree checks both zones of the block it
+// frees; surtr_emul_guard_check() checks those of every live block as well and returns the number of damaged blocks seen so far.
+// The zones catch WRITES only, and only those that land within EMUL_ZONE bytes of a block: a read past the end returns the fill
+// byte and goes unnoticed, and so does a write that jumps over the zone or lands elsewhere in the same block -- another workgroup's slice
+// of a scratch pool, for one (see BLOCK ORDER below: no order puts the working slice next to a zone).
+#define EMUL_ZONE 4096u
+#define EMUL_ZONE_BYTE 0xA5
+struct EmulBlock { EmulBlock *prev, *next; size_t n; uint64_t magic; bool counted; };      // at the start of the front zone's page
+static_assert(sizeof(EmulBlock) <= 256, "the block header and EMUL_ZONE bytes of fill share the 256 + EMUL_ZONE bytes before the payload");
+struct EmulAllocs { long live = 0, calls = 0, fail_at = -1, damaged = 0; EmulBlock* head = nullptr; int reverse = 0; };
 inline EmulAllocs& emul_allocs() { static EmulAllocs a; return a; }
+inline bool emul_block_damaged(const EmulBlock* b)
+{
+    const unsigned char* front = (const unsigned char*)b + 256, *back = front + EMUL_ZONE + b->n;
+    for (size_t i = 0; i < EMUL_ZONE; ++i) if (front[i] != EMUL_ZONE_BYTE || back[i] != EMUL_ZONE_BYTE) return true;
+    return false;
+}
 extern "C" __attribute__((used, visibility("default"))) inline long surtr_emul_live_allocs() { return emul_allocs().live; }
 extern "C" __attribute__((used, visibility("default"))) inline long surtr_emul_alloc_calls() { return emul_allocs().calls; }
 extern "C" __attribute__((used, visibility("default"))) inline void surtr_emul_fail_alloc(long k) { emul_allocs().calls = 0; emul_allocs().fail_at = k; }
+extern "C" __attribute__((used, visibility("default"))) inline long surtr_emul_guard_check()
+{
+    EmulAllocs& a = emul_allocs();
+    for (EmulBlock* b = a.head; b; b = b->next)
+        if (!b->counted && emul_block_damaged(b))
+        {
+            b->counted = true; ++a.damaged;
+            fprintf(stderr, "hip_emul: a red zone of the live device block %p (%zu bytes) is damaged\n", (void*)((char*)b + 256 + EMUL_ZONE), b->n);
+        }
+    return a.damaged;
+}
+// BLOCK ORDER.  surtr_emul_block_order(1) makes every launch run its blocks last to first.  Forward, block 0 takes every ticket
+// of a queue; reversed, block grid - 1 does, on scratch slice (wg_base +) grid - 1, and whatever a kernel assumes about "block 0
+// runs first" shows.  WHAT THIS DOES NOT GIVE: a scratch pool holds more slices than a launch has blocks (the Mesh clip's pool is
+// max_wg + n_wg_big + 32 catcher slices, a grid is min(pairs, max_wg); pool_small and pool_half likewise), so the working slice is
+// followed by another slice in either order, not by the pool's red zone.  A write past the end of a scratch SLICE -- or past one
+// of its arrays, each rounded up to 256 bytes -- lands in memory that no zone covers: only a changed event (the bit comparisons)
+// or a probe at the exact threshold (tests/test_capacity_limits.py, scratch_threshold_case) can show it.  One case there arranges
+// for the working slice to BE the pool's last (scratch-torus40-last: 32 catcher blocks reversed, block 31 on the last slice, CH a
+// multiple of 64): that one ends at the zone, for the slice's last array only.  The zones do cover every
+// buffer that is one block: the arena's arrays, the tables, the blobs.  A kernel that waits for a
+// lower-numbered block of its own launch would not end when reversed and would have to stay forward, by name, here.  Reading
+// every loop of csrc/ for one found none: no kernel scans with a look-back, and the only loop that waits on another workgroup at
+// all is the polling catcher of k_clip_pairs_catch, which waits for words that ANOTHER launch (k_clip_pairs_main) writes and
+// leaves after a bounded number of polls when that kernel is not running beside it -- in either order.
+extern "C" __attribute__((used, visibility("default"))) inline void surtr_emul_block_order(int reverse) { emul_allocs().reverse = reverse != 0; }
 static inline hipError_t hipMalloc(void** p, size_t n)
 {
     EmulAllocs& a = emul_allocs();
     if (a.calls++ == a.fail_at) { *p = nullptr; return 2; }      // (hipErrorOutOfMemory)
-    *p = calloc(n ? n : 1, 1);
-    if (*p) ++a.live;
-    return *p ? hipSuccess : 1;
+    *p = nullptr;
+    if (n == 0) n = 1;
+    const size_t total = (256 + EMUL_ZONE + n + EMUL_ZONE + 255) & ~(size_t)255;
+    unsigned char* raw = (unsigned char*)aligned_alloc(256, total);
+    if (!raw) return 1;
+    EmulBlock* b = (EmulBlock*)raw;
+    memset(raw, 0, 256);
+    memset(raw + 256, EMUL_ZONE_BYTE, EMUL_ZONE);
+    memset(raw + 256 + EMUL_ZONE, 0, n);
+    memset(raw + 256 + EMUL_ZONE + n, EMUL_ZONE_BYTE, total - (256 + EMUL_ZONE + n));
+    b->n = n; b->magic = 0x5355525452454D55ull; b->counted = false;
+    b->prev = nullptr; b->next = a.head; if (a.head) a.head->prev = b; a.head = b;
+    ++a.live;
+    *p = raw + 256 + EMUL_ZONE;
+    return hipSuccess;
 }
-static inline hipError_t hipFree(void* p) { if (p) --emul_allocs().live; free(p); return hipSuccess; }
+static inline hipError_t hipFree(void* p)
+{
+    if (!p) return hipSuccess;
+    EmulAllocs& a = emul_allocs();
+    EmulBlock* b = (EmulBlock*)((unsigned char*)p - EMUL_ZONE - 256);
+    if (b->magic != 0x5355525452454D55ull) { fprintf(stderr, "hip_emul: hipFree of %p, which is no live device block\n", p); abort(); }
+    if (!b->counted && emul_block_damaged(b))
+    {
+        ++a.damaged;
+        fprintf(stderr, "hip_emul: a red zone of the device block %p (%zu bytes) was damaged when it was freed\n", p, b->n);
+    }
+    if (b->prev) b->prev->next = b->next; else a.head = b->next;
+    if (b->next) b->next->prev = b->prev;
+    b->magic = 0;
+    --a.live;
+    free(b);
+    return hipSuccess;
+}
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { if (n) memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
@@ -151,7 +225,8 @@ struct DeviceScan
     do {                                                                                   \
         dim3 g_ = (grid), b_ = (block);                                                    \
         gridDim.x = g_.x; blockDim.x = b_.x;                                               \
-        for (uint32_t bi_ = 0; bi_ < g_.x; ++bi_)                                          \
-            for (uint32_t ti_ = 0; ti_ < b_.x; ++ti_) { blockIdx.x = bi_; threadIdx.x = ti_; kern(__VA_ARGS__); } \
+        const bool rev_ = emul_allocs().reverse != 0;                                      \
+        for (uint32_t bn_ = 0; bn_ < g_.x; ++bn_)                                          \
+            for (uint32_t ti_ = 0; ti_ < b_.x; ++ti_) { blockIdx.x = rev_ ? g_.x - 1u - bn_ : bn_; threadIdx.x = ti_; kern(__VA_ARGS__); } \
     } while (0)
 template <class T> static inline T __shfl(T v, int, int) { return v; }

@@ -4,7 +4,7 @@ The emulation's hipMalloc can fail on a chosen call (tests/emul/hip_emul.h).  Th
 sequence in turn -- an event with REFIT | RENDER and its download, regroup, build_cells, neighbors_from_mesh, clip_polyhedron and
 extract_faces, so that every translation unit that allocates does so -- and checks for each: the failing call reports
 SURTR_E_HIP, the same sequence on the same engine then gives the clean results (the event against the oracle), and closing the
-engine frees every allocation.  It runs once more with a small faces tier, so that the second tier of k_faces is swept too.
+engine frees every allocation with the red zones round it intact (surtr_emul_guard_check).  It runs once more with a small faces tier, so that the second tier of k_faces is swept too.
 
 The sweep runs in a child process under a time limit: a crash there fails this test instead of ending pytest."""
 import ctypes
@@ -58,6 +58,7 @@ def _sweep(lib_path):
     L.surtr_emul_live_allocs.restype = ctypes.c_long
     L.surtr_emul_alloc_calls.restype = ctypes.c_long
     L.surtr_emul_fail_alloc.argtypes = [ctypes.c_long]
+    L.surtr_emul_guard_check.restype = ctypes.c_long      # (damaged red zones round the device blocks, freed ones included)
     sc = scenes.cube_scene(8)
     planes = oracle.place_cells(sc["v012"], sc["scale"], sc["translate"])
     ref = oracle.event([sc["mesh"]], [sc["convex"]], sc["face_off"], planes, refit=True, render=True)
@@ -70,6 +71,7 @@ def _sweep(lib_path):
     n_alloc = L.surtr_emul_alloc_calls()
     assert_event_equal(clean["event"], ref)
     assert L.surtr_emul_live_allocs() == live0
+    assert L.surtr_emul_guard_check() == 0
     for k in range(n_alloc):
         L.surtr_emul_fail_alloc(k)
         eng = None
@@ -87,6 +89,7 @@ def _sweep(lib_path):
         assert _same({q: v for q, v in again.items() if q != "event"}, {q: v for q, v in clean.items() if q != "event"}), k
         eng.close()
         assert L.surtr_emul_live_allocs() == live0, (k, L.surtr_emul_live_allocs(), live0)
+        assert L.surtr_emul_guard_check() == 0, k
     return n_alloc
 
 
