@@ -195,6 +195,18 @@ int surtr_download_cells(surtr_ctx* ctx, uint32_t* cell_face_off, int32_t* face_
 /* Polygon3D::Scale + Translate + ConstructFacePlane for every face, on the
  * device (Src/VMACH.cpp:506-534; per event at Src/Surtr.cpp:1891-1896). */
 int surtr_place_cells(surtr_ctx* ctx, const float scale[3], const float translate[3]);
+/* n_impacts >= 1 instances of the uploaded pattern in one launch, one per impact of a frame (surtr_scene_fracture_impacts): placed
+ * cell i * n_cells + c is cell c under impact i's scale3[3i..] / translate3[3i..].  The kernel reads every face's v012 once; the
+ * pattern is not uploaded again.  The planes of instance i are bit for bit those surtr_place_cells writes for that scale and
+ * translate.  They live in tables of their own: the plain placement, and any event after it, are untouched.  Enqueued on the
+ * context's stream; a buffer grows (which waits for the device) only when a call places more instances than any before it.
+ * SURTR_E_INVALID: n_impacts == 0; SURTR_E_STATE: no pattern.  A new pattern (surtr_upload_pattern, surtr_build_cells,
+ * surtr_upload_planes) forgets the instances. */
+int surtr_place_cells_impacts(surtr_ctx* ctx, uint32_t n_impacts, const float* scale3, const float* translate3);
+/* Diagnostic, for tests: the placed planes (4 floats each, face after face) of the plain placement (impacts == 0: n_faces planes) or
+ * of surtr_place_cells_impacts (impacts != 0: n_impacts * n_faces, instance-major).  Count-then-fill: planes == NULL returns *n only;
+ * cap = the planes it has room for.  Synchronises the stream. */
+int surtr_download_planes(surtr_ctx* ctx, int impacts, uint32_t cap, uint32_t* n, float* planes);
 
 /* Alternative to pattern+place: give the cell planes directly. */
 int surtr_upload_planes(surtr_ctx* ctx, uint32_t n_cells, const uint32_t* plane_off, const float* planes);
@@ -439,6 +451,16 @@ int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const fl
 int surtr_event_regroup_bodies(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
                                uint32_t* n_pieces, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece,
                                uint32_t* n_bodies, uint32_t* body_compound_off);
+/* surtr_event_regroup_bodies after surtr_scene_fracture_impacts, with the sphere of each body's own impact: impact i has origin
+ * origins[3i..], radius radii[i] and the points [sphere_off[i], sphere_off[i + 1]) of sphere_points (3 floats each; sphere_off[0] = 0,
+ * ascending).  A body is a target, in the order the targets were given (impact after impact); ConvexOutOfSphere of a fragment
+ * (k_rg_faces) uses the impact its body belongs to.  The per-body binds, the move to a body's own bind 0 and the island groups are
+ * those of surtr_event_regroup_bodies; the kernels run once over all the pieces.  Each body's compounds are what
+ * surtr_event_regroup returns for the event of that body's impact alone.  !partial: no sphere is read (the arrays may be NULL).
+ * SURTR_E_STATE: the last event is not surtr_scene_fracture_impacts' over n_impacts impacts.  Sizes as surtr_event_regroup_bodies. */
+int surtr_event_regroup_impacts(surtr_ctx* ctx, int partial, uint32_t n_impacts, const uint32_t* sphere_off, const float* sphere_points,
+                                const float* origins, const float* radii, uint32_t* n_pieces, uint32_t* n_compounds, uint32_t* compound_off,
+                                int32_t* compound_piece, uint32_t* n_bodies, uint32_t* body_compound_off);
 
 /* Runs m_refittingTask (and the output scan) on the fragments of the last event: the reference regroups on the
  * un-refitted Convex solids and refits afterwards (Src/Surtr.cpp:1921-1939). */
@@ -605,6 +627,37 @@ int surtr_scene_outside(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* comp
                         const float origin[3], float radius, uint32_t cap, uint32_t* n, uint8_t* outside);
 int surtr_scene_outside_dev(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t n_sphere, const float* dev_sphere_points,
                             const float origin[3], float radius, uint8_t* dev_outside, size_t capacity_bytes);
+/* ---- several impacts in one frame: one event, one regroup, one commit ----
+ * A solver reports several contacts above the threshold in one frame (setContactReportThreshold and the contact callback,
+ * Src/Surtr.cpp:1163, 2518).  An IMPACT is an origin, a radius, a placement of the pattern, a range of cloud points and a list of
+ * target compounds.  A call takes n_impacts >= 1 of them: impact i owns compounds[target_off[i] .. target_off[i + 1]) (target_off[0]
+ * = 0).  The lists are pairwise disjoint; inside an impact the targets are strictly descending; across impacts any order.
+ * THE RULE: every result is, bit for bit, what the one-impact calls leave when they run impact after impact in the order given
+ * (surtr_scene_apply_poses, surtr_place_cells, surtr_scene_outside, surtr_scene_fracture_bodies, surtr_event_regroup_bodies,
+ * surtr_event_refit, surtr_scene_commit; the later impacts' compound numbers moved down by the commits before them).  The committed
+ * scene: every untouched compound in its old order with its pose, then what impact 0 made, then impact 1's, ...
+ * Errors, each leaving the scene, table, poses and any current event as they were: SURTR_E_INVALID for n_impacts == 0, an impact
+ * without a target, a compound out of range or listed twice (inside one impact or under two), targets inside an impact that do not
+ * strictly descend; the event calls return SURTR_E_STATE without surtr_place_cells_impacts, or with another n_impacts than was placed.
+ * Two impacts on one body are out of scope (the second would meet the first's fragments: a second call).
+ *
+ * surtr_scene_outside_impacts(_dev): surtr_scene_outside with a sphere per piece, one launch, one wave per listed piece
+ * (k_scene_outside_impacts); every piece reads its impact's origin, radius and cloud range [sphere_off[i], sphere_off[i + 1]) from a
+ * small device table.  The bytes come impact-major, then in surtr_scene_outside's layout, and equal surtr_scene_outside of each impact
+ * alone.  Same 4096-half-edge rule, refused before anything is enqueued.  Count-then-fill / _dev as surtr_scene_outside.
+ * surtr_scene_fracture_impacts(_async): the event over instance cells [cell_begin, cell_end) of each impact's placement.  The pair
+ * list is impact-major, then target-major, then cell-major; frag_ids carry i * n_cells + c and resident piece numbers; outside (may be
+ * NULL) is what surtr_scene_outside_impacts returns.  With one impact every result equals surtr_scene_fracture_bodies' bit for bit.
+ * Follow with surtr_event_regroup_impacts, surtr_event_refit and ONE surtr_scene_commit, which erases every target of every impact
+ * with its pose and appends the returned compounds in order. */
+int surtr_scene_outside_impacts(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, const uint32_t* sphere_off,
+                                const float* sphere_points, const float* origins, const float* radii, uint32_t cap, uint32_t* n, uint8_t* outside);
+int surtr_scene_outside_impacts_dev(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, const uint32_t* sphere_off,
+                                    const float* dev_sphere_points, const float* origins, const float* radii, uint8_t* dev_outside, size_t capacity_bytes);
+int surtr_scene_fracture_impacts(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, uint32_t cell_begin,
+                                 uint32_t cell_end, const uint8_t* outside, uint32_t flags, surtr_counts* counts);
+int surtr_scene_fracture_impacts_async(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, uint32_t cell_begin,
+                                       uint32_t cell_end, const uint8_t* outside, uint32_t flags);
 /* Makes the resident set what :1856-1875 make CompoundVec: the event's compound is erased, the compounds it broke into are pushed
  * to the back.  (n_compounds, compound_off, compound_piece) are the compounds exactly as surtr_event_regroup returned them for the
  * last scene event (compound 0, the pieces out of the impact, included).

@@ -495,7 +495,7 @@ int surtr_build_cells(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* group_s
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     ctx->h_plane_off.assign(cfo.begin(), cfo.end());
-    ctx->n_cells = n; ctx->n_faces = nf; ctx->planes_ready = false; ctx->pair_order_count = 0;
+    ctx->n_cells = n; ctx->n_faces = nf; ctx->planes_ready = false; ctx->pair_order_count = 0; ctx->n_impacts_placed = 0;
     B.n = n; B.nf = nf; B.nfv = nfv;
     if (getenv("SURTR_TIMING"))
         fprintf(stderr, "surtr_build_cells: %u cells, kernel + size read-back %.3f ms, pack + pattern %.3f ms\n", n,

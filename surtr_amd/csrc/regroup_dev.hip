@@ -9,10 +9,12 @@
 //                             point-in-polygon both ways (VMACH::OnYourRight) -> an edge between the two pieces
 //   k_rg_labels               min-label propagation over the pieces until nothing changes
 //   k_scene_outside           ConvexOutOfSphere of resident pieces before an event (surtr_scene_outside): one wave per piece
+//   k_scene_outside_impacts   the same with a sphere per piece, for the impacts of one frame (surtr_scene_outside_impacts)
 // Only per-piece flags and labels (a few bytes per piece) cross the bus; the host turns them into the reference's bind sets
 // (first group of a compound stays, the others are appended in discovery order).  Pieces are numbered as in
 // surtr_regroup: the resident pieces the event skipped (its `outside` mask), ascending, then the event's fragments.  After an event
-// over several bodies (surtr_scene_fracture_bodies) a bind set belongs to one body (surtr_event_regroup_bodies).
+// over several bodies (surtr_scene_fracture_bodies) a bind set belongs to one body (surtr_event_regroup_bodies); after an event over
+// several impacts (surtr_scene_fracture_impacts) every body is tested against its own impact's sphere (surtr_event_regroup_impacts).
 #include <array>
 #include <cstring>
 #include <mutex>
@@ -110,13 +112,20 @@ __global__ __launch_bounds__(SURTR_LANES) void k_rg_faces(uint32_t n_pieces, RgS
                                                           uint32_t* __restrict__ cnt /* 2 per piece */, const uint32_t* __restrict__ face_off,
                                                           const uint32_t* __restrict__ pts_off, FaceNode* __restrict__ nodes, P3* __restrict__ pts,
                                                           uint32_t n_sphere, const float* __restrict__ sphere, float ox, float oy, float oz, float radius,
-                                                          uint8_t* __restrict__ out_flag, uint32_t* __restrict__ err)
+                                                          uint8_t* __restrict__ out_flag, uint32_t* __restrict__ err,
+                                                          const uint32_t* __restrict__ piece_imp, const ImpSphere* __restrict__ imp_tab)
 {
     __shared__ uint8_t seen[RG_MAXH];
     __shared__ uint32_t base[RG_MAXH];
     __shared__ uint32_t sh_in;
     const uint32_t p = blockIdx.x;
     if (p >= n_pieces) return;
+    if (piece_imp)      // surtr_event_regroup_impacts: the sphere of the impact this piece's body belongs to
+    {
+        const ImpSphere s = imp_tab[piece_imp[p]];
+        ox = s.ox; oy = s.oy; oz = s.oz; radius = s.radius;
+        sphere += 3 * (size_t)s.cloud_begin; n_sphere = s.cloud_n;
+    }
     const RgSolid S = rg_solid(p, src, frags, A, cpos, cloff, cnbr, cvo);
     if (threadIdx.x == 0)
     {
@@ -195,14 +204,12 @@ __global__ __launch_bounds__(SURTR_LANES) void k_rg_faces(uint32_t n_pieces, RgS
 // per half-edge.
 // LDS: static, RG_MAXH planes = 64 KiB, two one-wave blocks per CU.  The grid is the handful of pieces a click touches; a size
 // taken from the largest piece of the list would need dynamic LDS, which the one-lane emulation build does not have.
-__global__ __launch_bounds__(SURTR_LANES) void k_scene_outside(uint32_t n, const uint32_t* __restrict__ list, const float* __restrict__ cpos,
-                                                               const uint32_t* __restrict__ cloff, const int32_t* __restrict__ cnbr,
-                                                               const uint32_t* __restrict__ cvo, uint32_t n_sphere, const float* __restrict__ sphere,
-                                                               float ox, float oy, float oz, float radius, uint8_t* __restrict__ out)
+// (the body, shared by k_scene_outside and k_scene_outside_impacts: listed piece i against one sphere; `plane` is the block's LDS)
+__device__ __forceinline__ void scene_outside_piece(uint32_t i, const uint32_t* __restrict__ list, const float* __restrict__ cpos,
+                                                    const uint32_t* __restrict__ cloff, const int32_t* __restrict__ cnbr, const uint32_t* __restrict__ cvo,
+                                                    uint32_t n_sphere, const float* __restrict__ sphere, float ox, float oy, float oz, float radius,
+                                                    uint8_t* __restrict__ out, float4* plane)
 {
-    __shared__ float4 plane[RG_MAXH];
-    const uint32_t i = blockIdx.x;
-    if (i >= n) return;
     const uint32_t lane = threadIdx.x, G = group_size();
     const uint32_t p = list[i], a0 = cvo[p];
     const RgSolid S{cpos + 3 * (size_t)a0, cloff + a0, nullptr, cnbr, cvo[p + 1] - a0};
@@ -271,6 +278,33 @@ __global__ __launch_bounds__(SURTR_LANES) void k_scene_outside(uint32_t n, const
     }
     const bool any = __ballot(hit) != 0ull;
     if (lane == 0u) out[i] = any ? 0 : 1;
+}
+
+__global__ __launch_bounds__(SURTR_LANES) void k_scene_outside(uint32_t n, const uint32_t* __restrict__ list, const float* __restrict__ cpos,
+                                                               const uint32_t* __restrict__ cloff, const int32_t* __restrict__ cnbr,
+                                                               const uint32_t* __restrict__ cvo, uint32_t n_sphere, const float* __restrict__ sphere,
+                                                               float ox, float oy, float oz, float radius, uint8_t* __restrict__ out)
+{
+    __shared__ float4 plane[RG_MAXH];
+    const uint32_t i = blockIdx.x;
+    if (i >= n) return;
+    scene_outside_piece(i, list, cpos, cloff, cnbr, cvo, n_sphere, sphere, ox, oy, oz, radius, out, plane);
+}
+
+// The same with a sphere per piece (surtr_scene_outside_impacts): listed piece i belongs to impact imp[i], whose origin, radius and
+// range of the cloud stand in the small table `tab`.  One launch for the pieces of every impact of a frame; the byte of a piece is
+// the one k_scene_outside writes for it with that impact's sphere alone (the same body on the same arguments).
+__global__ __launch_bounds__(SURTR_LANES) void k_scene_outside_impacts(uint32_t n, const uint32_t* __restrict__ list, const uint32_t* __restrict__ imp,
+                                                                       const ImpSphere* __restrict__ tab, const float* __restrict__ cpos,
+                                                                       const uint32_t* __restrict__ cloff, const int32_t* __restrict__ cnbr,
+                                                                       const uint32_t* __restrict__ cvo, const float* __restrict__ sphere,
+                                                                       uint8_t* __restrict__ out)
+{
+    __shared__ float4 plane[RG_MAXH];
+    const uint32_t i = blockIdx.x;
+    if (i >= n) return;
+    const ImpSphere s = tab[imp[i]];
+    scene_outside_piece(i, list, cpos, cloff, cnbr, cvo, s.cloud_n, sphere + 3 * (size_t)s.cloud_begin, s.ox, s.oy, s.oz, s.radius, out, plane);
 }
 
 __global__ void k_rg_keys(uint32_t nf, const FaceNode* __restrict__ nodes, const uint32_t* __restrict__ set_of, unsigned long long* __restrict__ key,
@@ -400,12 +434,16 @@ extern "C" void surtr_regroup_forget(const surtr_ctx* ctx)
     g_stats.erase(ctx);
 }
 
+// The spheres of surtr_event_regroup_impacts: impact i's origin, radius and points [sphere_off[i], sphere_off[i + 1]) of the cloud.
+struct ImpactSpheres { uint32_t n; const uint32_t* sphere_off; const float* origins; const float* radii; };
+
 static int regroup_bodies(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, int partial, uint32_t n_sphere, const float* sphere_points,
                           const float origin[3], float radius, uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece,
-                          uint32_t* body_compound_off);
+                          uint32_t* body_compound_off, const ImpactSpheres* impacts = nullptr);
 
 static int regroup_event(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
-                         uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece, uint32_t* body_compound_off)
+                         uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece, uint32_t* body_compound_off,
+                         const ImpactSpheres* impacts = nullptr)
 {
     if (!ctx || !n_compounds) return SURTR_E_INVALID;
     if (!ctx->have_event) return SURTR_E_STATE;
@@ -429,7 +467,8 @@ static int regroup_event(surtr_ctx* ctx, int partial, uint32_t n_sphere, const f
     std::vector<uint32_t> skipped;
     for (uint32_t p = 0; masked && p < ctx->n_pieces; ++p)
         if (ctx->last_outside[p]) skipped.push_back(p);
-    return regroup_bodies(ctx, skipped, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off);
+    return regroup_bodies(ctx, skipped, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off,
+                          impacts);
 }
 
 extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
@@ -447,11 +486,31 @@ extern "C" int surtr_event_regroup_bodies(surtr_ctx* ctx, int partial, uint32_t 
     return regroup_event(ctx, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off);
 }
 
+extern "C" int surtr_event_regroup_impacts(surtr_ctx* ctx, int partial, uint32_t n_impacts, const uint32_t* sphere_off, const float* sphere_points,
+                                           const float* origins, const float* radii, uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off,
+                                           int32_t* compound_piece, uint32_t* n_bodies, uint32_t* body_compound_off)
+{
+    if (!ctx || !n_bodies || !n_impacts) return SURTR_E_INVALID;
+    // the last event must be surtr_scene_fracture_impacts' over as many impacts: their target lists say which body is whose
+    if (!ctx->have_event || ctx->scene_event_compound.empty() || ctx->scene_event_impacts.size() != (size_t)n_impacts + 1 ||
+        ctx->scene_event_impacts.back() != ctx->scene_event_compound.size())
+        return SURTR_E_STATE;
+    *n_bodies = (uint32_t)ctx->scene_event_compound.size();
+    if (!partial) return regroup_event(ctx, 0, 0, nullptr, nullptr, 0.f, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off);
+    if (!sphere_off || !origins || !radii || sphere_off[0] != 0u) return SURTR_E_INVALID;
+    for (uint32_t i = 0; i < n_impacts; ++i) if (sphere_off[i + 1] < sphere_off[i]) return SURTR_E_INVALID;
+    if (sphere_off[n_impacts] && !sphere_points) return SURTR_E_INVALID;
+    const ImpactSpheres imp{n_impacts, sphere_off, origins, radii};
+    return regroup_event(ctx, 1, sphere_off[n_impacts], sphere_points, origins, radii[0], n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off, &imp);
+}
+
 // The bodies of the event: after surtr_scene_fracture_bodies one per target, in the order the targets were given (a bind set belongs
 // to one body); after any other event one body holding everything, which is the regrouping as it was before there were bodies.
+// With `impacts` (surtr_event_regroup_impacts, after surtr_scene_fracture_impacts) every piece is tested against the sphere of the
+// impact its body belongs to; n_sphere / sphere_points are then the whole cloud, and origin / radius are not read.
 static int regroup_bodies(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, int partial, uint32_t n_sphere, const float* sphere_points,
                           const float origin[3], float radius, uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece,
-                          uint32_t* body_compound_off)
+                          uint32_t* body_compound_off, const ImpactSpheres* impacts)
 {
     if (!ctx || !n_compounds) return SURTR_E_INVALID;
     if (!ctx->have_event) return SURTR_E_STATE;
@@ -507,13 +566,30 @@ static int regroup_bodies(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, 
     HIPCHK(hipMemcpyAsync(d_index.p, index.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_flag32.p, 0, 16, st));
     if (n_sphere) HIPCHK(hipMemcpyAsync(d_sph.p, sphere_points, (size_t)n_sphere * 12, hipMemcpyHostToDevice, st));
+    // the impact of every piece (its body's) and the impacts' spheres; the vectors live until the synchronisations below
+    DevBuf<uint32_t> d_pimp; DevBuf<ImpSphere> d_imptab;
+    std::vector<uint32_t> pimp; std::vector<ImpSphere> imptab;
+    if (impacts && partial)
+    {
+        const std::vector<uint32_t>& ioff = ctx->scene_event_impacts;
+        auto impact_of = [&](uint32_t body) { return (uint32_t)(std::upper_bound(ioff.begin(), ioff.end(), body) - ioff.begin()) - 1u; };
+        pimp.resize(n);
+        for (uint32_t p = 0; p < n_outside; ++p) pimp[p] = impact_of(body_of(skipped[p]));
+        for (uint32_t f = 0; f < c.n_frag; ++f) pimp[n_outside + f] = impact_of(frag_body[f]);
+        for (uint32_t i = 0; i < impacts->n; ++i)
+            imptab.push_back(ImpSphere{impacts->origins[3 * i], impacts->origins[3 * i + 1], impacts->origins[3 * i + 2], impacts->radii[i], impacts->sphere_off[i],
+                                       impacts->sphere_off[i + 1] - impacts->sphere_off[i], 0u, 0u});
+        if (!alloc(d_pimp, n) || !alloc(d_imptab, imptab.size())) return SURTR_E_HIP;
+        HIPCHK(hipMemcpyAsync(d_pimp.p, pimp.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_imptab.p, imptab.data(), imptab.size() * sizeof(ImpSphere), hipMemcpyHostToDevice, st));
+    }
     const RgSrc src{d_kind.p, d_index.p};
     const PieceSet& C = ctx->cset;
     const float ox = origin ? origin[0] : 0.f, oy = origin ? origin[1] : 0.f, oz = origin ? origin[2] : 0.f;
     uint32_t* d_err = d_flag32.p;            // [0] error, [1] edges, [2] changed
     hipLaunchKernelGGL(k_rg_faces, dim3(n), dim3(SURTR_LANES), 0, st, n, src, ctx->d_frags, ctx->arena, C.pos, C.loff, C.nbr, C.vo, 0u, d_cnt.p,
                        (const uint32_t*)nullptr, (const uint32_t*)nullptr, (FaceNode*)nullptr, (P3*)nullptr, 0u, (const float*)nullptr, 0.f, 0.f, 0.f, 0.f,
-                       (uint8_t*)nullptr, d_err);
+                       (uint8_t*)nullptr, d_err, (const uint32_t*)nullptr, (const ImpSphere*)nullptr);
     std::vector<uint32_t> cnt(2 * (size_t)n), foff(n + 1, 0u), poff(n + 1, 0u);
     HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, cnt.size() * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -532,7 +608,8 @@ static int regroup_bodies(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, 
     HIPCHK(hipMemcpyAsync(d_foff.p, foff.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_poff.p, poff.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_rg_faces, dim3(n), dim3(SURTR_LANES), 0, st, n, src, ctx->d_frags, ctx->arena, C.pos, C.loff, C.nbr, C.vo, 1u, d_cnt.p,
-                       d_foff.p, d_poff.p, d_nodes.p, d_pts.p, n_sphere, d_sph.p, ox, oy, oz, radius, partial ? d_out.p : (uint8_t*)nullptr, d_err);
+                       d_foff.p, d_poff.p, d_nodes.p, d_pts.p, n_sphere, d_sph.p, ox, oy, oz, radius, partial ? d_out.p : (uint8_t*)nullptr, d_err,
+                       (const uint32_t*)d_pimp.p, (const ImpSphere*)d_imptab.p);
     HIPCHK(hipGetLastError());
     if (partial)       // MergeOutOfImpact (:2368-2403): fragments out of the impact sphere move to bind 0; emptied compounds go
     {
@@ -695,6 +772,88 @@ extern "C" int surtr_scene_outside(surtr_ctx* ctx, uint32_t n_targets, const uin
     if (d_sph.grow(ctx, 3 * (size_t)n_sphere + 3) || d_out.grow(ctx, std::max<size_t>(*n, 4))) return SURTR_E_HIP;
     if (n_sphere) HIPCHK(hipMemcpyAsync(d_sph.p, sphere_points, (size_t)n_sphere * 12, hipMemcpyHostToDevice, ctx->stream));
     rc = outside_enqueue(ctx, list, n_sphere, d_sph.p, origin, radius, d_out.p);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(outside, d_out.p, *n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));      // (also: the temporaries are freed below)
+    return SURTR_OK;
+}
+
+// ---- the same mask for the impacts of one frame, a sphere per piece (k_scene_outside_impacts) ----
+// Checks everything and lays out the staged words: list[n] | impact of every listed piece [n] | ImpSphere[n_impacts].  Nothing has been
+// enqueued when an error is returned.
+static int outside_impacts_stage(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, const uint32_t* sphere_off,
+                                 const float* origins, const float* radii, bool have_points, uint32_t* n_out)
+{
+    if (!ctx || !n_impacts || !sphere_off || !origins || !radii) return SURTR_E_INVALID;
+    if (!ctx->n_pieces || ctx->scene_off.size() < 2 || ctx->scene_off.back() != ctx->n_pieces) return SURTR_E_STATE;
+    int rc = impacts_valid(ctx, n_impacts, target_off, compounds);
+    if (rc) return rc;
+    if (sphere_off[0] != 0u) return SURTR_E_INVALID;
+    for (uint32_t i = 0; i < n_impacts; ++i) if (sphere_off[i + 1] < sphere_off[i]) return SURTR_E_INVALID;
+    if (sphere_off[n_impacts] && !have_points) return SURTR_E_INVALID;
+    std::vector<uint32_t> list, imp, one;
+    for (uint32_t i = 0; i < n_impacts; ++i)
+    {
+        rc = outside_list(ctx, target_off[i + 1] - target_off[i], compounds + target_off[i], one);
+        if (rc) return rc;
+        list.insert(list.end(), one.begin(), one.end()); imp.insert(imp.end(), one.size(), i);
+    }
+    static_assert(sizeof(ImpSphere) == 32, "the sphere table is staged as eight words per impact");
+    const size_t n = list.size(), at_tab = (2 * n + 3) & ~(size_t)3;      // (the table 16-byte aligned)
+    std::vector<uint32_t>& H = ctx->h_outside_stage;
+    H.assign(at_tab + 8 * (size_t)n_impacts, 0u);
+    memcpy(H.data(), list.data(), n * 4); memcpy(H.data() + n, imp.data(), n * 4);
+    for (uint32_t i = 0; i < n_impacts; ++i)
+    {
+        const ImpSphere s{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], radii[i], sphere_off[i], sphere_off[i + 1] - sphere_off[i], 0u, 0u};
+        memcpy(H.data() + at_tab + 8 * (size_t)i, &s, sizeof(s));
+    }
+    *n_out = (uint32_t)n;
+    return SURTR_OK;
+}
+
+// One copy of the staged words (the context's vector: pageable memory has left its source when hipMemcpyAsync returns) and one launch.
+static int outside_impacts_enqueue(surtr_ctx* ctx, uint32_t n, const float* dev_sphere_points, uint8_t* dev_outside)
+{
+    const std::vector<uint32_t>& H = ctx->h_outside_stage;
+    (void)hipSetDevice(ctx->device);
+    const int rc = ctx->d_outside_list.grow(ctx, H.size(), H.size() + H.size() / 4 + 64);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_outside_list.p, H.data(), H.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    const uint32_t* d = ctx->d_outside_list.p; const size_t at_tab = (2 * (size_t)n + 3) & ~(size_t)3;
+    const PieceSet& C = ctx->cset;
+    hipLaunchKernelGGL(k_scene_outside_impacts, dim3(n), dim3(SURTR_LANES), 0, ctx->stream, n, d, d + n, (const ImpSphere*)(d + at_tab), (const float*)C.pos.p,
+                       (const uint32_t*)C.loff.p, (const int32_t*)C.nbr.p, (const uint32_t*)C.vo.p, dev_sphere_points, dev_outside);
+    HIPCHK(hipGetLastError());
+    return SURTR_OK;
+}
+
+extern "C" int surtr_scene_outside_impacts_dev(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, const uint32_t* sphere_off,
+                                               const float* dev_sphere_points, const float* origins, const float* radii, uint8_t* dev_outside,
+                                               size_t capacity_bytes)
+{
+    if (!ctx || !dev_outside) return SURTR_E_INVALID;
+    uint32_t n = 0;
+    const int rc = outside_impacts_stage(ctx, n_impacts, target_off, compounds, sphere_off, origins, radii, dev_sphere_points != nullptr, &n);
+    if (rc) return rc;
+    if (capacity_bytes < n) return SURTR_E_CAPACITY;
+    return outside_impacts_enqueue(ctx, n, dev_sphere_points, dev_outside);
+}
+
+extern "C" int surtr_scene_outside_impacts(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, const uint32_t* sphere_off,
+                                           const float* sphere_points, const float* origins, const float* radii, uint32_t cap, uint32_t* n, uint8_t* outside)
+{
+    if (!ctx || !n) return SURTR_E_INVALID;
+    int rc = outside_impacts_stage(ctx, n_impacts, target_off, compounds, sphere_off, origins, radii, sphere_points != nullptr, n);
+    if (rc) return rc;
+    if (!outside) return SURTR_OK;
+    if (cap < *n) return SURTR_E_CAPACITY;
+    (void)hipSetDevice(ctx->device);
+    const uint32_t n_sphere = sphere_off[n_impacts];
+    DevBuf<float> d_sph; DevBuf<uint8_t> d_out;
+    if (d_sph.grow(ctx, 3 * (size_t)n_sphere + 3) || d_out.grow(ctx, std::max<size_t>(*n, 4))) return SURTR_E_HIP;
+    if (n_sphere) HIPCHK(hipMemcpyAsync(d_sph.p, sphere_points, (size_t)n_sphere * 12, hipMemcpyHostToDevice, ctx->stream));
+    rc = outside_impacts_enqueue(ctx, *n, d_sph.p, d_out.p);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(outside, d_out.p, *n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));      // (also: the temporaries are freed below)

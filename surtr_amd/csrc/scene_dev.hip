@@ -8,14 +8,18 @@
 //   surtr_scene_fracture_event(_async)            the event over the pieces of one compound
 //   surtr_scene_apply_poses / _fracture_bodies(_async)   the same for every body a click hits at once: one bake, one event whose pair
 //                                                 list is target-major (the mask of surtr_scene_outside, regroup_dev.hip)
+//   surtr_scene_fracture_impacts(_async)          the same for the impacts of one frame, each with its own sphere and its own instance
+//                                                 of the pattern (surtr_place_cells_impacts): the pair list is impact-major
 //   surtr_scene_fragments(_async)                 the resident pieces of some compounds as the current fragments (InitCompound, :2499-2529):
 //                                                 the device twin of surtr_load_fragments, one chunked copy kernel into the event arena
 //   surtr_scene_commit                            erase the event's compound(s), push back what they broke into (:1856-1875): one
 //                                                 gather kernel from the old pieces and the event arena into spare buffers, then a swap
 // The layout of the new pieces is laid out on the host from the small tables (piece offsets, fragment records), as
 // surtr_pieces_from_event does; no solid leaves HBM.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <utility>
 
 #include "surtr_ctx.h"
@@ -297,6 +301,55 @@ int surtr_scene_fracture_bodies(surtr_ctx* ctx, uint32_t n_targets, const uint32
     return rc;
 }
 
+int surtr_scene_fracture_impacts_async(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, uint32_t cell_begin,
+                                       uint32_t cell_end, const uint8_t* outside, uint32_t flags)
+{
+    if (!ctx || !n_impacts) return SURTR_E_INVALID;
+    if (!ctx->n_pieces || !ctx->n_impacts_placed || ctx->n_impacts_placed != n_impacts) return SURTR_E_STATE;
+    int rc = impacts_valid(ctx, n_impacts, target_off, compounds);
+    if (rc) return rc;
+    if (cell_end > ctx->n_cells || cell_begin > cell_end) return SURTR_E_INVALID;
+    const uint32_t n_targets = target_off[n_impacts], nc = cell_end - cell_begin;
+    uint64_t total = 0;
+    for (uint32_t t = 0; t < n_targets; ++t) total += ctx->scene_off[compounds[t] + 1] - ctx->scene_off[compounds[t]];
+    if ((uint64_t)nc * total > 0xFFFFFFFFull) return SURTR_E_INVALID;
+    // the pairs impact-major, then target-major in the order given, then cell-major over the target's pieces -- over the cells of the
+    // impact's own instance of the pattern: every target's fragments come out as the event of its impact alone gives them
+    std::vector<uint32_t> cell, piece;
+    cell.reserve((size_t)nc * total); piece.reserve((size_t)nc * total);
+    std::vector<uint8_t> mask;
+    if (outside) mask.assign(ctx->n_pieces, 0);
+    size_t at = 0;
+    for (uint32_t i = 0; i < n_impacts; ++i)
+        for (uint32_t t = target_off[i]; t < target_off[i + 1]; ++t)
+        {
+            const uint32_t p0 = ctx->scene_off[compounds[t]], m = ctx->scene_off[compounds[t] + 1] - p0;
+            for (uint32_t c = 0; c < nc; ++c)
+                for (uint32_t q = 0; q < m; ++q) { cell.push_back(i * ctx->n_cells + cell_begin + c); piece.push_back(p0 + q); }
+            if (outside) memcpy(mask.data() + p0, outside + at, m);
+            at += m;
+        }
+    const std::vector<uint32_t> targets(compounds, compounds + n_targets), offs(target_off, target_off + n_impacts + 1);      // (launch_event clears the context's)
+    {
+        ImpactPlanesScope instance_planes(ctx);
+        rc = surtr_event_pairs_masked(ctx, (uint32_t)cell.size(), cell.data(), piece.data(), outside ? mask.data() : nullptr, flags);
+    }
+    if (rc) return rc;
+    ctx->scene_event_compound = targets; ctx->scene_event_impacts = offs;
+    return SURTR_OK;
+}
+
+int surtr_scene_fracture_impacts(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, uint32_t cell_begin,
+                                 uint32_t cell_end, const uint8_t* outside, uint32_t flags, surtr_counts* counts)
+{
+    int rc = surtr_scene_fracture_impacts_async(ctx, n_impacts, target_off, compounds, cell_begin, cell_end, outside, flags);
+    if (rc) return rc;
+    surtr_counts c;
+    rc = surtr_event_counts(ctx, &c);
+    if (counts) *counts = c;
+    return rc;
+}
+
 int surtr_scene_fragments_async(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, int render_convex, uint32_t flags)
 {
     if (!ctx) return SURTR_E_INVALID;
@@ -439,7 +492,7 @@ int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* com
 {
     if (!ctx || !compound_off || (n_compounds && compound_off[n_compounds] && !compound_piece)) return SURTR_E_INVALID;
     if (!ctx->n_pieces || !ctx->have_event || !ctx->frags_of_pieces || ctx->scene_event_compound.empty() ||
-        (size_t)ctx->scene_event_compound[0] + 1 >= ctx->scene_off.size())      // (descending: the first is the highest)
+        (size_t)*std::max_element(ctx->scene_event_compound.begin(), ctx->scene_event_compound.end()) + 1 >= ctx->scene_off.size())
         return SURTR_E_STATE;
     (void)hipSetDevice(ctx->device);
     Timer timer(ctx);
@@ -449,7 +502,10 @@ int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* com
     if (surtr_event_counts(ctx, &c) != SURTR_OK) return SURTR_E_STATE;      // the event failed: nothing to commit
     // ---- everything is checked and laid out before anything is written
     const uint32_t np = ctx->n_pieces;
-    const std::vector<uint32_t> targets = ctx->scene_event_compound;      // strictly descending
+    // strictly descending; after surtr_scene_fracture_impacts inside an impact only: sorted here, for the poses below (the layout
+    // reads is_target and the order of the returned compounds, neither of which asks for an order of the targets)
+    std::vector<uint32_t> targets = ctx->scene_event_compound;
+    std::sort(targets.begin(), targets.end(), std::greater<uint32_t>());
     std::vector<uint8_t> is_target(ctx->scene_off.size() - 1, 0);
     for (uint32_t t : targets) is_target[t] = 1;
     std::vector<uint32_t> skipped;      // of every target, ascending: surtr_event_regroup's numbers

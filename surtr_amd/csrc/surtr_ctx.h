@@ -328,7 +328,11 @@ struct surtr_ctx
     // the compounds the last event ran over, strictly descending (surtr_scene_fracture_event: one; surtr_scene_fracture_bodies: the
     // click's targets); empty: none, or committed
     std::vector<uint32_t> scene_event_compound;
+    // after surtr_scene_fracture_impacts: scene_event_compound holds the targets impact after impact (descending inside an impact
+    // only), and impact i owns entries [scene_event_impacts[i], scene_event_impacts[i + 1]); empty after any other event
+    std::vector<uint32_t> scene_event_impacts;
     DevBuf<uint32_t> d_outside_list;                     // surtr_scene_outside(_dev): the pieces it was asked about
+    std::vector<uint32_t> h_outside_stage;               // surtr_scene_outside_impacts(_dev): list, impact of every piece, sphere table
     // per-body poses (surtr_scene_set_poses): 16 floats per compound, x' = A x + b as surtr_transform_pieces takes them; empty: every
     // pose is the identity.  The device copy (scene_sync_device below) is made by the first query after the poses or the table change.
     std::vector<float> scene_pose;
@@ -352,6 +356,11 @@ struct surtr_ctx
     DevBuf<float> d_v012; DevBuf<float4> d_planes; DevBuf<uint32_t> d_plane_off;
     std::vector<uint32_t> h_plane_off;
     bool planes_ready = false;
+    // surtr_place_cells_impacts: n_impacts_placed instances of the pattern, instance i's cell c at i * n_cells + c, in tables of their
+    // own (the plain placement keeps d_planes); 0: none, or the pattern has been replaced since
+    uint32_t n_impacts_placed = 0;
+    DevBuf<float4> d_planes_imp; DevBuf<uint32_t> d_plane_off_imp; DevBuf<float> d_imp_xf;
+    std::vector<uint32_t> h_plane_off_imp; std::vector<float> h_imp_xf;
     // scratch + arena
     uint32_t user_cv = 0, user_ch = 0;
     uint64_t user_av = 0, user_ah = 0, user_ai = 0;
@@ -501,3 +510,37 @@ int frags_present(surtr_ctx* ctx, bool render, int is_convex);
 
 // placement of cell groups with per-group scale / shift already in device memory (surtr_hip.hip)
 extern "C" int surtr_place_cells_groups_dev(surtr_ctx* ctx, uint32_t n_groups, const uint32_t* group_cell_off, const float* d_scale3, const float* d_shift3);
+
+// ---- several impacts in one event (surtr_place_cells_impacts, surtr_scene_outside_impacts, surtr_scene_fracture_impacts,
+//      surtr_event_regroup_impacts) ----
+// One impact's sphere as the kernels read it: origin, radius, and its points [cloud_begin, cloud_begin + cloud_n) of the cloud.
+struct alignas(16) ImpSphere { float ox, oy, oz, radius; uint32_t cloud_begin, cloud_n, pad0, pad1; };
+// The target lists of a call: impact i owns compounds[target_off[i] .. target_off[i + 1]).  K >= 1, no impact without a target, every
+// compound in range and named once over all impacts, strictly descending inside an impact.  Anything else: SURTR_E_INVALID.
+static inline int impacts_valid(const surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds)
+{
+    if (!n_impacts || !target_off || !compounds || target_off[0] != 0u) return SURTR_E_INVALID;
+    std::vector<uint8_t> seen(ctx->scene_off.empty() ? 0 : ctx->scene_off.size() - 1, 0);
+    for (uint32_t i = 0; i < n_impacts; ++i)
+    {
+        if (target_off[i + 1] <= target_off[i]) return SURTR_E_INVALID;
+        for (uint32_t t = target_off[i]; t < target_off[i + 1]; ++t)
+        {
+            const uint32_t c = compounds[t];
+            if (c >= seen.size() || seen[c] || (t > target_off[i] && c >= compounds[t - 1])) return SURTR_E_INVALID;
+            seen[c] = 1;
+        }
+    }
+    return SURTR_OK;
+}
+// While one of these lives the event's kernels read the instance planes of surtr_place_cells_impacts: the plain placement's tables are
+// swapped out and come back, untouched, when it goes.
+struct ImpactPlanesScope
+{
+    surtr_ctx* ctx; bool ready;
+    void flip() { std::swap(ctx->d_planes, ctx->d_planes_imp); std::swap(ctx->d_plane_off, ctx->d_plane_off_imp); std::swap(ctx->h_plane_off, ctx->h_plane_off_imp); }
+    explicit ImpactPlanesScope(surtr_ctx* c) : ctx(c), ready(c->planes_ready) { flip(); ctx->n_cells *= ctx->n_impacts_placed; ctx->planes_ready = true; }
+    ~ImpactPlanesScope() { flip(); ctx->n_cells /= ctx->n_impacts_placed; ctx->planes_ready = ready; }
+    ImpactPlanesScope(const ImpactPlanesScope&) = delete;
+    ImpactPlanesScope& operator=(const ImpactPlanesScope&) = delete;
+};

@@ -3,6 +3,7 @@
 // Event pipeline (on the caller's HIP stream plus two internal streams for the kernels that may overlap -- k_clip_pairs and
 // k_clip_pairs_half beside k_clip_pairs_big, k_refit beside k_faces -- fenced by events; inputs resident in HBM):
 //   k_place_cells   A3   Polygon3D::Scale/Translate + ConstructFacePlane      (Src/VMACH.cpp:302-310, 506-534)
+//   k_place_cells_impacts  the same for several instances of the pattern, one per impact of a frame (surtr_place_cells_impacts)
 //   k_clip_convex   A7   Convex of every (cell, piece) pair, one wave per task (Src/Surtr.cpp:1466-1468)
 //   k_prep_pairs    A7   pre-pass of the Mesh of every pair whose Convex survived: the vertices the planes can touch,
 //                        left in HBM in the layout of the LDS topology
@@ -274,6 +275,31 @@ __global__ void k_place_cells_groups(uint32_t nfaces, const float* __restrict__ 
         p[3 * i + 2] = v012[9 * f + 3 * i + 2] * sz + tz;
     }
     planes[f] = plane_from_points(p, p + 3, p + 6);
+}
+
+// Several instances of the pattern in one launch, one per impact of a frame (surtr_place_cells_impacts): plane i * nfaces + f is face f
+// under impact i's (scale, translate).  A thread reads its face's nine floats once and places them n_imp times with the expressions
+// of k_place_cells, so instance i carries the bits surtr_place_cells writes for that scale and translate.
+__global__ void k_place_cells_impacts(uint32_t nfaces, uint32_t n_imp, const float* __restrict__ v012, const float* __restrict__ scale3,
+                                      const float* __restrict__ shift3, float4* __restrict__ planes)
+{
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nfaces) return;
+    float v[9];
+    for (int i = 0; i < 9; ++i) v[i] = v012[9 * (size_t)f + i];
+    for (uint32_t g = 0; g < n_imp; ++g)
+    {
+        const float sx = scale3[3 * g], sy = scale3[3 * g + 1], sz = scale3[3 * g + 2];
+        const float tx = shift3[3 * g], ty = shift3[3 * g + 1], tz = shift3[3 * g + 2];
+        float p[9];
+        for (int i = 0; i < 3; ++i)
+        {
+            p[3 * i] = v[3 * i] * sx + tx;
+            p[3 * i + 1] = v[3 * i + 1] * sy + ty;
+            p[3 * i + 2] = v[3 * i + 2] * sz + tz;
+        }
+        planes[(size_t)g * nfaces + f] = plane_from_points(p, p + 3, p + 6);
+    }
 }
 
 // A pair whose Mesh clip has no valid answer in the reference (SURTR_E_TOPOLOGY: the degenerate policy of literal_clip.h) yields
@@ -3589,7 +3615,7 @@ int surtr_upload_pattern(surtr_ctx* ctx, uint32_t n_cells, const uint32_t* face_
     HIPCHK(hipMemcpy(ctx->d_v012, v012, (size_t)nf * 36, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ctx->d_plane_off, face_off, (size_t)(n_cells + 1) * 4, hipMemcpyHostToDevice));
     ctx->h_plane_off.assign(face_off, face_off + n_cells + 1);
-    ctx->n_cells = n_cells; ctx->n_faces = nf; ctx->planes_ready = false; ctx->pair_order_count = 0;
+    ctx->n_cells = n_cells; ctx->n_faces = nf; ctx->planes_ready = false; ctx->pair_order_count = 0; ctx->n_impacts_placed = 0;
     return SURTR_OK;
 }
 
@@ -3604,6 +3630,52 @@ int surtr_place_cells(surtr_ctx* ctx, const float scale[3], const float translat
                            scale[2], translate[0], translate[1], translate[2], ctx->d_planes);
     HIPCHK(hipGetLastError());
     ctx->planes_ready = true;
+    return SURTR_OK;
+}
+
+int surtr_place_cells_impacts(surtr_ctx* ctx, uint32_t n_impacts, const float* scale3, const float* translate3)
+{
+    if (!ctx || !n_impacts || !scale3 || !translate3) return SURTR_E_INVALID;
+    if (!ctx->d_v012) return SURTR_E_STATE;
+    const uint32_t nf = ctx->n_faces, nc = ctx->n_cells;
+    if ((uint64_t)n_impacts * std::max(nf, nc) > 0x7FFFFFFFull) return SURTR_E_CAPACITY;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    // (an event in flight may read the tables: hipFree, which a growth goes through, waits for the device)
+    int rc = ctx->d_planes_imp.grow(ctx, std::max<size_t>((size_t)n_impacts * nf, 1));
+    if (rc == SURTR_OK) rc = ctx->d_plane_off_imp.grow(ctx, (size_t)n_impacts * nc + 1);
+    if (rc == SURTR_OK) rc = ctx->d_imp_xf.grow(ctx, (size_t)6 * n_impacts);
+    if (rc) { ctx->n_impacts_placed = 0; return rc; }
+    // instance i's cell c is cell i * n_cells + c: its planes follow instance i - 1's.  The staging vectors are the context's (pageable
+    // memory has left its source when hipMemcpyAsync returns, as for the tables of surtr_scene_commit).
+    std::vector<uint32_t>& off = ctx->h_plane_off_imp;
+    off.resize((size_t)n_impacts * nc + 1);
+    for (uint32_t i = 0; i < n_impacts; ++i)
+        for (uint32_t c = 0; c < nc; ++c) off[(size_t)i * nc + c] = i * nf + ctx->h_plane_off[c];
+    off[(size_t)n_impacts * nc] = n_impacts * nf;
+    std::vector<float>& xf = ctx->h_imp_xf;
+    xf.assign(scale3, scale3 + 3 * (size_t)n_impacts);
+    xf.insert(xf.end(), translate3, translate3 + 3 * (size_t)n_impacts);
+    HIPCHK(hipMemcpyAsync(ctx->d_plane_off_imp, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctx->d_imp_xf, xf.data(), xf.size() * 4, hipMemcpyHostToDevice, st));
+    if (nf)
+        hipLaunchKernelGGL(k_place_cells_impacts, dim3((nf + 255) / 256), dim3(256), 0, st, nf, n_impacts, (const float*)ctx->d_v012, (const float*)ctx->d_imp_xf,
+                           (const float*)ctx->d_imp_xf + 3 * (size_t)n_impacts, (float4*)ctx->d_planes_imp);
+    HIPCHK(hipGetLastError());
+    ctx->n_impacts_placed = n_impacts;
+    return SURTR_OK;
+}
+
+int surtr_download_planes(surtr_ctx* ctx, int impacts, uint32_t cap, uint32_t* n, float* planes)
+{
+    if (!ctx || !n) return SURTR_E_INVALID;
+    if (impacts ? ctx->n_impacts_placed == 0u : !ctx->planes_ready) return SURTR_E_STATE;
+    *n = impacts ? ctx->n_impacts_placed * ctx->n_faces : ctx->n_faces;
+    if (!planes) return SURTR_OK;
+    if (cap < *n) return SURTR_E_CAPACITY;
+    (void)hipSetDevice(ctx->device);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (*n) HIPCHK(hipMemcpy(planes, impacts ? ctx->d_planes_imp.p : ctx->d_planes.p, (size_t)*n * 16, hipMemcpyDeviceToHost));
     return SURTR_OK;
 }
 
@@ -3622,7 +3694,7 @@ int surtr_upload_planes(surtr_ctx* ctx, uint32_t n_cells, const uint32_t* plane_
     HIPCHK(hipMemcpy(ctx->d_planes, planes, (size_t)nf * 16, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ctx->d_plane_off, plane_off, (size_t)(n_cells + 1) * 4, hipMemcpyHostToDevice));
     ctx->h_plane_off.assign(plane_off, plane_off + n_cells + 1);
-    ctx->n_cells = n_cells; ctx->n_faces = nf; ctx->planes_ready = true; ctx->pair_order_count = 0;
+    ctx->n_cells = n_cells; ctx->n_faces = nf; ctx->planes_ready = true; ctx->pair_order_count = 0; ctx->n_impacts_placed = 0;
     return SURTR_OK;
 }
 
@@ -4202,7 +4274,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     PROF_END(4);
     HIPCHK(hipGetLastError());
     ctx->have_event = true; ctx->last_flags = flags; ctx->last_current = false; ctx->frags_of_pieces = true;
-    ctx->scene_event_compound.clear();      // (surtr_scene_fracture_event / _bodies set it after this)
+    ctx->scene_event_compound.clear(); ctx->scene_event_impacts.clear();      // (surtr_scene_fracture_event / _bodies / _impacts set them after this)
     return SURTR_OK;
 }
 

@@ -169,6 +169,33 @@ def pack_solids(solids):
             np.concatenate(off).astype(np.uint32), np.ascontiguousarray(np.concatenate(nbr), np.int32))
 
 
+def _impact_targets(targets):
+    """One list of compounds per impact -> (target_off uint32[K + 1], compounds uint32[n])."""
+    lists = [np.ascontiguousarray(t, np.uint32).reshape(-1) for t in targets]
+    to = np.zeros(len(lists) + 1, np.uint32)
+    to[1:] = np.cumsum([x.shape[0] for x in lists])
+    return to, (np.concatenate(lists) if lists else np.zeros(0, np.uint32)).astype(np.uint32)
+
+
+def _impact_spheres(sphere_points, origins, radii, k=None):
+    """One cloud, origin and radius per impact -> (K, sphere_off uint32[K + 1], points f32[n,3], origins f32[K,3], radii f32[K])."""
+    if origins is not None:
+        k = np.ascontiguousarray(origins, np.float32).reshape(-1, 3).shape[0]
+    k = int(k or 0)
+    org = np.zeros((k, 3), np.float32) if origins is None else np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    rad = np.zeros(k, np.float32) if radii is None else np.ascontiguousarray(radii, np.float32).reshape(-1)
+    clouds = [np.zeros((0, 3), np.float32)] * k if sphere_points is None else \
+        [np.zeros((0, 3), np.float32) if c is None else np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in sphere_points]
+    if not len(clouds) == org.shape[0] == rad.shape[0] == k:
+        raise SurtrError(E_INVALID, "one cloud, origin and radius per impact")
+    so = np.zeros(k + 1, np.uint32)
+    so[1:] = np.cumsum([c.shape[0] for c in clouds])
+    sp = np.ascontiguousarray(np.concatenate(clouds) if clouds else np.zeros((0, 3), np.float32), np.float32)
+    if sp.shape[0] == 0:
+        sp = np.zeros((1, 3), np.float32)      # (a pointer the library may check, never read)
+    return k, so, sp, org, rad
+
+
 class Engine:
     """One context per GPU (surtr_create / surtr_destroy)."""
 
@@ -304,6 +331,23 @@ class Engine:
         t = np.ascontiguousarray(translate, np.float32)
         self._ck(lib().surtr_place_cells(self._h, _p(s), _p(t)))
 
+    def place_cells_impacts(self, scales, translates):
+        """surtr_place_cells_impacts: one instance of the pattern per impact, in one launch; instance i's cell c is cell
+        i * n_cells + c.  scales / translates: f32[K,3]."""
+        s = np.ascontiguousarray(scales, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(translates, np.float32).reshape(-1, 3)
+        if s.shape[0] != t.shape[0]:
+            raise SurtrError(E_INVALID, "%d scales, %d translates" % (s.shape[0], t.shape[0]))
+        self._ck(lib().surtr_place_cells_impacts(self._h, ctypes.c_uint32(s.shape[0]), _p(s), _p(t)))
+
+    def download_planes(self, impacts=False):
+        """surtr_download_planes (diagnostic): the placed planes as f32[n,4]; impacts: those of place_cells_impacts, instance-major."""
+        n = ctypes.c_uint32()
+        self._ck(lib().surtr_download_planes(self._h, ctypes.c_int(int(impacts)), ctypes.c_uint32(0), ctypes.byref(n), None))
+        out = np.zeros((max(n.value, 1), 4), np.float32)
+        self._ck(lib().surtr_download_planes(self._h, ctypes.c_int(int(impacts)), ctypes.c_uint32(n.value), ctypes.byref(n), _p(out)))
+        return out[:n.value].copy()
+
     def upload_planes(self, plane_off, planes):
         po = np.ascontiguousarray(plane_off, np.uint32)
         pl = np.ascontiguousarray(planes, np.float32).reshape(-1, 4)
@@ -368,6 +412,18 @@ class Engine:
         self._ck(lib().surtr_event_regroup_bodies(*args, ctypes.byref(n), ctypes.byref(nc), None, None, ctypes.byref(nb), None))
         co = np.zeros(n.value + nb.value + 1, np.uint32); cp = np.zeros(max(n.value, 1), np.int32); bo = np.zeros(nb.value + 1, np.uint32)
         self._ck(lib().surtr_event_regroup_bodies(*args, ctypes.byref(n), ctypes.byref(nc), _p(co), _p(cp), ctypes.byref(nb), _p(bo)))
+        return co[:nc.value + 1].copy(), cp[:co[nc.value]].copy(), bo
+
+    def event_regroup_impacts(self, partial=False, sphere_points=None, origins=None, radii=None, n_impacts=None):
+        """surtr_event_regroup_impacts: event_regroup_bodies after scene_fracture_impacts, every body against the sphere of its own
+        impact.  sphere_points: one f32[n_i,3] cloud per impact; origins f32[K,3]; radii f32[K].  -> (compound_off, compound_piece,
+        body_compound_off), a body being a target in the order given."""
+        k, so, sp, org, rad = _impact_spheres(sphere_points, origins, radii, n_impacts)
+        n, nc, nb = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        args = [self._h, ctypes.c_int(int(partial)), ctypes.c_uint32(k), _p(so), _p(sp), _p(org), _p(rad)]
+        self._ck(lib().surtr_event_regroup_impacts(*args, ctypes.byref(n), ctypes.byref(nc), None, None, ctypes.byref(nb), None))
+        co = np.zeros(n.value + nb.value + 1, np.uint32); cp = np.zeros(max(n.value, 1), np.int32); bo = np.zeros(nb.value + 1, np.uint32)
+        self._ck(lib().surtr_event_regroup_impacts(*args, ctypes.byref(n), ctypes.byref(nc), _p(co), _p(cp), ctypes.byref(nb), _p(bo)))
         return co[:nc.value + 1].copy(), cp[:co[nc.value]].copy(), bo
 
     def regroup_stats(self):
@@ -668,6 +724,57 @@ class Engine:
         org = np.ascontiguousarray(origin, np.float32)
         self._ck(lib().surtr_scene_outside_dev(self._h, ctypes.c_uint32(t.shape[0]), _p(t), ctypes.c_uint32(int(n_sphere)), ctypes.c_void_p(dev_sphere_points),
                                                _p(org), ctypes.c_float(radius), ctypes.c_void_p(dev_outside), ctypes.c_size_t(capacity)))
+
+    # ---- several impacts in one frame (include/surtr_hip.h): `targets` is one list of compounds per impact
+    def _impacts_mask(self, targets, outside):
+        to, t = _impact_targets(targets)
+        om = None if outside is None else np.ascontiguousarray(outside, np.uint8).reshape(-1)
+        if om is not None:
+            co = self.scene_compounds()
+            if any(int(c) >= co.shape[0] - 1 for c in t) or om.shape[0] != sum(int(co[int(c) + 1]) - int(co[int(c)]) for c in t):
+                raise SurtrError(E_INVALID, "outside holds %d bytes" % om.shape[0])
+        return to, t, om
+
+    def scene_fracture_impacts(self, targets, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
+        """surtr_scene_fracture_impacts: one event over the targets of every impact, each over the cells of its impact's own
+        placement (place_cells_impacts); outside: what scene_outside_impacts returns."""
+        to, t, om = self._impacts_mask(targets, outside)
+        c = Counts()
+        self._ck(lib().surtr_scene_fracture_impacts(self._h, ctypes.c_uint32(to.shape[0] - 1), _p(to), _p(t), ctypes.c_uint32(cell_begin),
+                                                    ctypes.c_uint32(cell_end), _p(om), ctypes.c_uint32(flags), ctypes.byref(c)))
+        return c
+
+    def scene_fracture_impacts_async(self, targets, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
+        to, t, om = self._impacts_mask(targets, outside)
+        self._ck(lib().surtr_scene_fracture_impacts_async(self._h, ctypes.c_uint32(to.shape[0] - 1), _p(to), _p(t), ctypes.c_uint32(cell_begin),
+                                                          ctypes.c_uint32(cell_end), _p(om), ctypes.c_uint32(flags)))
+
+    def scene_outside_impacts(self, targets, sphere_points, origins, radii, capacity=None):
+        """surtr_scene_outside_impacts: scene_outside with a sphere per impact, in one launch -> uint8, impact after impact, each as
+        scene_outside returns it.  sphere_points: one cloud per impact (None or empty: no points)."""
+        to, t = _impact_targets(targets)
+        k, so, sp, org, rad = _impact_spheres(sphere_points, origins, radii, to.shape[0] - 1)
+        if k != to.shape[0] - 1:
+            raise SurtrError(E_INVALID, "%d spheres for %d impacts" % (k, to.shape[0] - 1))
+        n = ctypes.c_uint32()
+        args = [self._h, ctypes.c_uint32(to.shape[0] - 1), _p(to), _p(t), _p(so), _p(sp), _p(org), _p(rad)]
+        self._ck(lib().surtr_scene_outside_impacts(*args, ctypes.c_uint32(0), ctypes.byref(n), None))
+        cap = n.value if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 1), np.uint8)
+        self._ck(lib().surtr_scene_outside_impacts(*args, ctypes.c_uint32(cap), ctypes.byref(n), _p(out)))
+        return out[:n.value].copy()
+
+    def scene_outside_impacts_dev(self, targets, sphere_off, dev_sphere_points, origins, radii, dev_outside, capacity):
+        """surtr_scene_outside_impacts_dev: cloud (all impacts' points, impact i's at [sphere_off[i], sphere_off[i + 1])) and mask in
+        device memory, on the context's stream; nothing is read back."""
+        to, t = _impact_targets(targets)
+        so = np.ascontiguousarray(sphere_off, np.uint32).reshape(-1)
+        org = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        rad = np.ascontiguousarray(radii, np.float32).reshape(-1)
+        if not so.shape[0] - 1 == org.shape[0] == rad.shape[0] == to.shape[0] - 1:
+            raise SurtrError(E_INVALID, "one cloud range, origin and radius per impact")
+        self._ck(lib().surtr_scene_outside_impacts_dev(self._h, ctypes.c_uint32(to.shape[0] - 1), _p(to), _p(t), _p(so), ctypes.c_void_p(dev_sphere_points),
+                                                       _p(org), _p(rad), ctypes.c_void_p(dev_outside), ctypes.c_size_t(capacity)))
 
     def scene_apply_poses(self, compounds):
         """surtr_scene_apply_poses: scene_apply_pose for several compounds with the derived data rebuilt once."""

@@ -13,6 +13,10 @@
 //                 --radial: every body the sphere of radius R / 2 touches and whose mass is above 1e-4) has its pose baked in and is
 //                 broken.  After each click one JSON line: the piece and compound hit, the body mask of the impact sphere, the
 //                 compounds hit and made, the table, the poses and the body masses after the click.
+// --impacts "x,y,z,r;..." [--scene-poses ...] [--one-event]: the scene of --body-clicks; every sphere of the list is an impact of ONE
+//                 frame (OnImpacts: one overlap query for all of them, a body to the first impact that reaches it).  Without
+//                 --one-event the impacts run one after the other through the several-compound routine; with it through one event,
+//                 one regrouping and one commit.  One JSON line: the compounds each impact acted on, then what --body-clicks prints.
 // --one-event (with --scene-clicks or --body-clicks): every compound a click hits goes through ONE event, one regrouping and one
 //                 commit (ExecuteFractureRoutine over several compounds) instead of one of each per compound; the JSON is the same.
 // --init-compounds [--init-compounds-obj DIR] (with --scene-clicks or --body-clicks): after each click, InitCompounds on the compounds it
@@ -512,12 +516,66 @@ static void body_clicks(FractureEngine& eng, const std::vector<std::array<float,
     }
 }
 
+// --impacts: OnImpacts with every sphere of the list on the posed scene of --body-clicks; one JSON line for the frame.
+static void impacts_frame(FractureEngine& eng, const std::vector<std::array<float, 4>>& spheres, const std::vector<std::pair<int, Matrix>>& poses, bool one_event)
+{
+    const uint32_t n0 = eng.CompoundFromLastEvent();
+    std::vector<uint32_t> off;
+    for (uint32_t p = 0; p < n0; p += 2) off.push_back(p);
+    off.push_back(n0);
+    const int rc = surtr_scene_set_compounds(eng.Raw(), (uint32_t)off.size() - 1u, off.data());
+    if (rc) throw Error(rc, "surtr_scene_set_compounds");
+    if (!poses.empty())
+    {
+        std::vector<Matrix> world(off.size() - 1);
+        for (const auto& p : poses)
+        {
+            if (p.first < 0 || (size_t)p.first >= world.size()) throw Error(SURTR_E_INVALID, "--scene-poses: no such compound");
+            world[(size_t)p.first] = p.second;
+        }
+        eng.SetPoses(world);
+    }
+    const std::vector<Vector3> cloud = lattice_cloud();
+    std::vector<Impact> in, acted;
+    float rmax = 0.f;
+    for (const auto& s : spheres) { in.push_back(Impact{Vector3(s[0], s[1], s[2]), s[3], {}}); rmax = std::max(rmax, s[3]); }
+    FractureArgs args;
+    args.PartialFracture = true; args.RadialMode = true;
+    const std::vector<int> made = eng.OnImpacts(in, args, rmax, cloud, &acted, one_event);
+    const std::vector<uint32_t> table = eng.SceneCompounds();
+    const std::vector<Matrix> world = eng.Poses();
+    const std::vector<surtr_mass> bm = eng.BodyMassProperties(1);
+    printf("{\"impacts\": %zu, \"compounds_hit\": [", acted.size());
+    for (size_t i = 0; i < acted.size(); ++i)
+    {
+        printf("%s[", i ? ", " : "");
+        for (size_t k = 0; k < acted[i].compounds.size(); ++k) printf("%s%d", k ? ", " : "", acted[i].compounds[k]);
+        printf("]");
+    }
+    printf("], \"compounds_made\": [");
+    for (size_t i = 0; i < made.size(); ++i) printf("%s%d", i ? ", " : "", made[i]);
+    printf("], \"table\": [");
+    for (size_t i = 0; i < table.size(); ++i) printf("%s%u", i ? ", " : "", table[i]);
+    printf("], \"poses\": [");
+    for (size_t c = 0; c < world.size(); ++c)
+    {
+        printf("%s[", c ? ", " : "");
+        for (int k = 0; k < 16; ++k) printf("%s%.9g", k ? ", " : "", world[c].m[k]);
+        printf("]");
+    }
+    printf("], \"mass\": [");
+    for (size_t i = 0; i < bm.size(); ++i) printf("%s%.17g", i ? ", " : "", bm[i].mass);
+    printf("]}\n");
+    init_compounds(eng, 0, made);
+}
+
 int main(int argc, char** argv)
 {
     std::string mesh = "cube", obj, obj_in, dump;
     int cells = 8, nu = 250, nv = 200;
     std::vector<std::array<float, 6>> clicks, bclicks;
     std::vector<std::pair<int, Matrix>> poses;
+    std::vector<std::array<float, 4>> impacts;
     bool radial = false, one_event = false;
     bool ach = false, do_pick = false; float in_scale = 1.f, pick_ray[6] = {0, 0, 0, 1, 0, 0}, impact_radius = 1.f;
     for (int i = 1; i < argc; ++i)
@@ -570,6 +628,19 @@ int main(int argc, char** argv)
                 if (*c == ';') ++c;
             }
         }
+        else if (!strcmp(argv[i], "--impacts") && i + 1 < argc)
+        {
+            const char* c = argv[++i];
+            while (*c)
+            {
+                std::array<float, 4> r; int used = 0;
+                if (sscanf(c, "%f,%f,%f,%f%n", &r[0], &r[1], &r[2], &r[3], &used) != 4)
+                { fprintf(stderr, "surtr_harness: --impacts takes x,y,z,r;...\n"); return 2; }
+                impacts.push_back(r);
+                c += used;
+                if (*c == ';') ++c;
+            }
+        }
         else if (!strcmp(argv[i], "--pick") && i + 1 < argc)
         {
             do_pick = sscanf(argv[++i], "%f,%f,%f,%f,%f,%f", pick_ray, pick_ray + 1, pick_ray + 2, pick_ray + 3, pick_ray + 4, pick_ray + 5) == 6;
@@ -616,6 +687,7 @@ int main(int argc, char** argv)
         if (do_pick) pick(eng, frags, pick_ray, impact_radius);
         if (!clicks.empty()) scene_clicks(eng, clicks, impact_radius, one_event);
         else if (!bclicks.empty()) body_clicks(eng, bclicks, poses, impact_radius, radial, one_event);
+        else if (!impacts.empty()) impacts_frame(eng, impacts, poses, one_event);
         if (!obj.empty())
         {
             FILE* f = fopen(obj.c_str(), "w");

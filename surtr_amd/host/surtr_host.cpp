@@ -959,6 +959,121 @@ std::vector<int> FractureEngine::OnMouseDownBodies(const Vector3& origin, const 
     return made;
 }
 
+std::vector<int> FractureEngine::ExecuteFractureRoutine(const std::vector<Impact>& impacts, float maxAxisScale, const FractureArgs& args,
+                                                        const std::vector<Vector3>& spherePointCloud)
+{
+    if (impacts.empty()) throw Error(SURTR_E_INVALID, "ExecuteFractureRoutine: no impact");
+    const uint32_t K = (uint32_t)impacts.size();
+    std::vector<uint32_t> toff{0u}, t, soff{0u};
+    std::vector<int> all;
+    std::vector<float> scale3, shift3, rad, fc;
+    const float s2 = maxAxisScale * 2.f;
+    for (const Impact& im : impacts)
+    {
+        std::vector<int> sorted(im.compounds);
+        std::sort(sorted.begin(), sorted.end(), [](int a, int b) { return a > b; });
+        if (sorted.empty()) throw Error(SURTR_E_INVALID, "ExecuteFractureRoutine: an impact without a compound");
+        const std::vector<uint32_t> tn = compound_numbers(sorted, "ExecuteFractureRoutine");
+        t.insert(t.end(), tn.begin(), tn.end()); toff.push_back((uint32_t)t.size());
+        all.insert(all.end(), sorted.begin(), sorted.end());
+        // DoFracture's placement per impact (:1890-1915)
+        scale3.insert(scale3.end(), {s2, s2, s2});
+        shift3.insert(shift3.end(), {im.position.x, im.position.y, im.position.z});
+        rad.push_back(im.radius);
+        std::vector<Vector3> cloud = spherePointCloud;
+        for (auto& v : cloud)
+        {
+            v.x *= im.radius; v.y *= im.radius; v.z *= im.radius;
+            v.x += im.position.x; v.y += im.position.y; v.z += im.position.z;
+        }
+        const std::vector<float> one = flat_points(cloud);
+        fc.insert(fc.end(), one.begin(), one.end()); soff.push_back((uint32_t)(fc.size() / 3));
+    }
+    {
+        std::vector<int> s(all);
+        std::sort(s.begin(), s.end());
+        if (std::adjacent_find(s.begin(), s.end()) != s.end()) throw Error(SURTR_E_INVALID, "ExecuteFractureRoutine: a compound is named twice");
+    }
+    ApplyPoses(all);
+    SetRefittingPointLimit(args.RefittingPointLimit);
+    check(surtr_place_cells_impacts(ctx_, K, scale3.data(), shift3.data()), "surtr_place_cells_impacts");
+    if (fc.empty()) fc.assign(3, 0.f);
+    std::vector<uint8_t> mask;
+    if (args.PartialFracture)
+    {
+        uint32_t n = 0;
+        check(surtr_scene_outside_impacts(ctx_, K, toff.data(), t.data(), soff.data(), fc.data(), shift3.data(), rad.data(), 0, &n, nullptr), "surtr_scene_outside_impacts");
+        mask.resize(n + 1);
+        check(surtr_scene_outside_impacts(ctx_, K, toff.data(), t.data(), soff.data(), fc.data(), shift3.data(), rad.data(), n, &n, mask.data()), "surtr_scene_outside_impacts");
+        mask.resize(n);
+    }
+    const bool any = std::find_if(mask.begin(), mask.end(), [](uint8_t o) { return o != 0; }) != mask.end();
+    check(surtr_scene_fracture_impacts(ctx_, K, toff.data(), t.data(), 0, n_cells_, any ? mask.data() : nullptr, 0u, &counts_), "surtr_scene_fracture_impacts");
+    const int partial = args.PartialFracture ? 1 : 0;
+    uint32_t np = 0, nc = 0, nb = 0;
+    check(surtr_event_regroup_impacts(ctx_, partial, K, soff.data(), fc.data(), shift3.data(), rad.data(), &np, &nc, nullptr, nullptr, &nb, nullptr),
+          "surtr_event_regroup_impacts");
+    std::vector<uint32_t> off((size_t)np + nb + 1), body(nb + 1);
+    std::vector<int32_t> piece(np + 1);
+    check(surtr_event_regroup_impacts(ctx_, partial, K, soff.data(), fc.data(), shift3.data(), rad.data(), &np, &nc, off.data(), piece.data(), &nb, body.data()),
+          "surtr_event_regroup_impacts");
+    check(surtr_event_refit(ctx_), "surtr_event_refit");
+    check(surtr_event_counts(ctx_, &counts_), "surtr_event_counts");
+    flagged_ = FlaggedUnits();
+    flagged_.n_failed = counts_.n_failed;
+    if (counts_.n_failed && !allow_flagged_)
+        throw Error(SURTR_E_TOPOLOGY, "ExecuteFractureRoutine: the event flagged " + std::to_string(counts_.n_failed) + " unit(s); nothing was committed");
+    uint32_t n = 0, first = 0, n_new = 0;
+    check(surtr_scene_commit(ctx_, nc, off.data(), piece.data(), &n, &first, &n_new, nullptr), "surtr_scene_commit");
+    n_pieces_ = n;
+    std::vector<int> made(n_new);
+    for (uint32_t k = 0; k < n_new; ++k) made[k] = (int)(first + k);
+    return made;
+}
+
+std::vector<int> FractureEngine::OnImpacts(const std::vector<Impact>& spheres, const FractureArgs& args, float maxAxisScale,
+                                           const std::vector<Vector3>& spherePointCloud, std::vector<Impact>* acted, bool oneEvent)
+{
+    if (acted) acted->clear();
+    if (spheres.empty()) return {};
+    // every sphere in one query, with PickBodies' radius and mass gate (:228)
+    std::vector<float> q;
+    for (const Impact& s : spheres) q.insert(q.end(), {s.position.x, s.position.y, s.position.z, s.radius / 2.f});
+    uint32_t nc = 0;
+    check(surtr_scene_overlap(ctx_, (uint32_t)spheres.size(), q.data(), nullptr, 0.f, &nc, nullptr), "surtr_scene_overlap");
+    std::vector<uint8_t> mask((size_t)nc * spheres.size());
+    const std::vector<surtr_mass> mass = BodyMassProperties(1);
+    check(surtr_scene_overlap(ctx_, (uint32_t)spheres.size(), q.data(), mass.data(), 1e-4f, &nc, mask.data()), "surtr_scene_overlap");
+    std::vector<uint8_t> taken(nc, 0);
+    std::vector<Impact> impacts;
+    for (size_t s = 0; s < spheres.size(); ++s)
+    {
+        Impact im{spheres[s].position, spheres[s].radius, {}};
+        for (uint32_t c = 0; c < nc; ++c)
+            if (mask[s * nc + c] == 1 && !taken[c]) { taken[c] = 1; im.compounds.push_back((int)c); }      // (the first impact in list order has it)
+        if (!im.compounds.empty()) impacts.push_back(im);
+    }
+    if (acted) *acted = impacts;
+    if (impacts.empty()) return {};
+    if (oneEvent) return ExecuteFractureRoutine(impacts, maxAxisScale, args, spherePointCloud);
+    // the loop of one-impact routines: a commit erases its targets, so every compound still to come moves down by the number of
+    // erased ones below it, and the compounds made so far (which sit above every old one) by all of them
+    std::vector<int> made;
+    std::vector<int> gone;
+    for (const Impact& im : impacts)
+    {
+        std::vector<int> now;
+        for (int c : im.compounds) now.push_back(c - (int)std::count_if(gone.begin(), gone.end(), [c](int g) { return g < c; }));
+        FractureArgs one = args;
+        one.ImpactPosition = im.position; one.ImpactRadius = im.radius;
+        for (int& c : made) c -= (int)now.size();
+        const std::vector<int> more = ExecuteFractureRoutine(now, maxAxisScale, one, spherePointCloud);
+        made.insert(made.end(), more.begin(), more.end());
+        gone.insert(gone.end(), im.compounds.begin(), im.compounds.end());
+    }
+    return made;
+}
+
 bool ConvexRayIntersection(const VMACH::Polygon3D& convex, const Ray ray, float& dist)
 {
     const double o[3] = {ray.position.x, ray.position.y, ray.position.z}, d[3] = {ray.direction.x, ray.direction.y, ray.direction.z};

@@ -150,6 +150,8 @@ struct FractureArgs
 };
 
 // DirectX::SimpleMath::Ray as OnMouseDown builds it (Src/Surtr.cpp:178-200): the direction is expected to be of unit length.
+// One contact of a frame above the report threshold: where, how large, and the compounds it breaks.
+struct Impact { Vector3 position; float radius = 0.f; std::vector<int> compounds; };
 struct Ray { Vector3 position, direction; Ray() = default; Ray(const Vector3& p, const Vector3& d) : position(p), direction(d) {} };
 // Surtr::ConvexRayIntersection (Src/Surtr.cpp:2460-2497), on the host from the definition of include/surtr_hip.h: the ray's
 // interval [0, inf) clipped by the half-space of every face plane (FacePlane; built from the first three vertices where it was
@@ -347,6 +349,25 @@ public:
     std::vector<int> OnMouseDownBodies(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
                                        const std::vector<Vector3>& spherePointCloud, std::vector<int>* hitCompounds = nullptr,
                                        surtr_scene_ray_hit* hit = nullptr, std::vector<uint8_t>* bodyMask = nullptr, bool oneEvent = false);
+    // ---- several impacts in one frame (the contact callback behind setContactReportThreshold, Src/Surtr.cpp:1163, 2518) ----
+    // ExecuteFractureRoutine for the impacts a solver reported in one frame, in ONE pass (surtr_scene_fracture_impacts): the pattern
+    // and the modes come from `args`, position and radius from each impact; the pattern is placed per impact at maxAxisScale * 2
+    // around its position and the cloud scaled and shifted per impact (:1911-1915).  The compounds of an impact may come in any order
+    // (sorted descending); one named twice, inside one impact or under two, throws Error(SURTR_E_INVALID), as does an impact without
+    // a compound.  In order: ApplyPoses over all of them, one placement launch, one mask launch when PartialFracture, one event, one
+    // regrouping with each body's own sphere, one refit, one commit.  Returns the compounds made: the scene is the one the
+    // several-compound routine called per impact, in the order given, leaves.  When the event flagged a unit and AllowFlagged is off,
+    // NOTHING is committed.
+    std::vector<int> ExecuteFractureRoutine(const std::vector<Impact>& impacts, float maxAxisScale, const FractureArgs& args,
+                                            const std::vector<Vector3>& spherePointCloud);
+    // The contact callback's work: which bodies does each sphere reach (ONE surtr_scene_overlap call with all the spheres, each of
+    // radius `radius / 2` as in PickBodies, with PickBodies' gate on the body's mass), then the routine above (oneEvent) or the
+    // several-compound routine per impact in the order given.  Only position and radius of `spheres` are read.  A body reached by
+    // several impacts goes to the FIRST of them in list order: the later ones do not see it (sequentially they would meet its
+    // fragments; that takes a second call).  An impact left without a body is dropped.  acted (may be null) receives the impacts as
+    // they ran.  Returns the compounds made, numbered as after the last commit.
+    std::vector<int> OnImpacts(const std::vector<Impact>& spheres, const FractureArgs& args, float maxAxisScale,
+                               const std::vector<Vector3>& spherePointCloud, std::vector<Impact>* acted = nullptr, bool oneEvent = true);
     surtr_counts LastCounts() const { return counts_; }
     // The degenerate policy at this level (include/surtr_hip.h, surtr_counts::n_failed): where the reference leaves its own
     // arrays the engine flags the unit instead of emulating what the reference's memory happens to hold -- a flagged (cell,
