@@ -437,10 +437,10 @@ extern "C" void surtr_regroup_forget(const surtr_ctx* ctx)
 // The spheres of surtr_event_regroup_impacts: impact i's origin, radius and points [sphere_off[i], sphere_off[i + 1]) of the cloud.
 struct ImpactSpheres { uint32_t n; const uint32_t* sphere_off; const float* origins; const float* radii; };
 
-static int regroup_bodies(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, int partial, uint32_t n_sphere, const float* sphere_points,
-                          const float origin[3], float radius, uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece,
-                          uint32_t* body_compound_off, const ImpactSpheres* impacts = nullptr);
-
+// The bodies of the event: after surtr_scene_fracture_bodies one per target, in the order the targets were given (a bind set belongs
+// to one body); after any other event one body holding everything, which is the regrouping as it was before there were bodies.
+// With `impacts` (surtr_event_regroup_impacts, after surtr_scene_fracture_impacts) every piece is tested against the sphere of the
+// impact its body belongs to; n_sphere / sphere_points are then the whole cloud, and origin / radius are not read.
 static int regroup_event(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
                          uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece, uint32_t* body_compound_off,
                          const ImpactSpheres* impacts = nullptr)
@@ -448,11 +448,9 @@ static int regroup_event(surtr_ctx* ctx, int partial, uint32_t n_sphere, const f
     if (!ctx || !n_compounds) return SURTR_E_INVALID;
     if (!ctx->have_event) return SURTR_E_STATE;
     if (partial && (!origin || (n_sphere && !sphere_points))) return SURTR_E_INVALID;
-    {
-        surtr_counts c;
-        const int rc = surtr_event_counts(ctx, &c);
-        if (rc) return rc;
-    }
+    surtr_counts c;
+    int rc = surtr_event_counts(ctx, &c);
+    if (rc) return rc;
     // pieces: the resident pieces the event skipped, then its fragments; bind sets as ApplyFracture leaves them.  The `outside`
     // mask belongs to the event that took it and to the pieces it ran over: surtr_load_fragments drops it (its fragments are
     // nobody's event), and once surtr_pieces_from_event has replaced the pieces a mask that kept any of them out names solids
@@ -467,58 +465,11 @@ static int regroup_event(surtr_ctx* ctx, int partial, uint32_t n_sphere, const f
     std::vector<uint32_t> skipped;
     for (uint32_t p = 0; masked && p < ctx->n_pieces; ++p)
         if (ctx->last_outside[p]) skipped.push_back(p);
-    return regroup_bodies(ctx, skipped, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off,
-                          impacts);
-}
-
-extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
-                                   uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece)
-{
-    return regroup_event(ctx, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece, nullptr);
-}
-
-extern "C" int surtr_event_regroup_bodies(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
-                                          uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece,
-                                          uint32_t* n_bodies, uint32_t* body_compound_off)
-{
-    if (!ctx || !n_bodies) return SURTR_E_INVALID;
-    *n_bodies = (uint32_t)std::max<size_t>(ctx->scene_event_compound.size(), 1);
-    return regroup_event(ctx, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off);
-}
-
-extern "C" int surtr_event_regroup_impacts(surtr_ctx* ctx, int partial, uint32_t n_impacts, const uint32_t* sphere_off, const float* sphere_points,
-                                           const float* origins, const float* radii, uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off,
-                                           int32_t* compound_piece, uint32_t* n_bodies, uint32_t* body_compound_off)
-{
-    if (!ctx || !n_bodies || !n_impacts) return SURTR_E_INVALID;
-    // the last event must be surtr_scene_fracture_impacts' over as many impacts: their target lists say which body is whose
-    if (!ctx->have_event || ctx->scene_event_compound.empty() || ctx->scene_event_impacts.size() != (size_t)n_impacts + 1 ||
-        ctx->scene_event_impacts.back() != ctx->scene_event_compound.size())
-        return SURTR_E_STATE;
-    *n_bodies = (uint32_t)ctx->scene_event_compound.size();
-    if (!partial) return regroup_event(ctx, 0, 0, nullptr, nullptr, 0.f, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off);
-    if (!sphere_off || !origins || !radii || sphere_off[0] != 0u) return SURTR_E_INVALID;
-    for (uint32_t i = 0; i < n_impacts; ++i) if (sphere_off[i + 1] < sphere_off[i]) return SURTR_E_INVALID;
-    if (sphere_off[n_impacts] && !sphere_points) return SURTR_E_INVALID;
-    const ImpactSpheres imp{n_impacts, sphere_off, origins, radii};
-    return regroup_event(ctx, 1, sphere_off[n_impacts], sphere_points, origins, radii[0], n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off, &imp);
-}
-
-// The bodies of the event: after surtr_scene_fracture_bodies one per target, in the order the targets were given (a bind set belongs
-// to one body); after any other event one body holding everything, which is the regrouping as it was before there were bodies.
-// With `impacts` (surtr_event_regroup_impacts, after surtr_scene_fracture_impacts) every piece is tested against the sphere of the
-// impact its body belongs to; n_sphere / sphere_points are then the whole cloud, and origin / radius are not read.
-static int regroup_bodies(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, int partial, uint32_t n_sphere, const float* sphere_points,
-                          const float origin[3], float radius, uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece,
-                          uint32_t* body_compound_off, const ImpactSpheres* impacts)
-{
-    if (!ctx || !n_compounds) return SURTR_E_INVALID;
-    if (!ctx->have_event) return SURTR_E_STATE;
-    if (partial && (!origin || (n_sphere && !sphere_points))) return SURTR_E_INVALID;
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    surtr_counts c;
-    int rc = surtr_event_counts(ctx, &c);
+    // (the counts once more, as when this function was two: a small copy and a synchronisation of a stream with nothing queued, kept so
+    //  that a regroup enqueues exactly what it always did)
+    rc = surtr_event_counts(ctx, &c);
     if (rc) return rc;
     std::vector<uint32_t> kind(skipped.size(), 0u), index(skipped), set_of;
     const uint32_t n_outside = (uint32_t)kind.size();
@@ -576,9 +527,8 @@ static int regroup_bodies(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, 
         pimp.resize(n);
         for (uint32_t p = 0; p < n_outside; ++p) pimp[p] = impact_of(body_of(skipped[p]));
         for (uint32_t f = 0; f < c.n_frag; ++f) pimp[n_outside + f] = impact_of(frag_body[f]);
-        for (uint32_t i = 0; i < impacts->n; ++i)
-            imptab.push_back(ImpSphere{impacts->origins[3 * i], impacts->origins[3 * i + 1], impacts->origins[3 * i + 2], impacts->radii[i], impacts->sphere_off[i],
-                                       impacts->sphere_off[i + 1] - impacts->sphere_off[i], 0u, 0u});
+        imptab.resize(impacts->n);
+        fill_spheres(imptab.data(), impacts->n, impacts->sphere_off, impacts->origins, impacts->radii);
         if (!alloc(d_pimp, n) || !alloc(d_imptab, imptab.size())) return SURTR_E_HIP;
         HIPCHK(hipMemcpyAsync(d_pimp.p, pimp.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_imptab.p, imptab.data(), imptab.size() * sizeof(ImpSphere), hipMemcpyHostToDevice, st));
@@ -702,6 +652,38 @@ static int regroup_bodies(surtr_ctx* ctx, const std::vector<uint32_t>& skipped, 
     return SURTR_OK;
 }
 
+extern "C" int surtr_event_regroup(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
+                                   uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece)
+{
+    return regroup_event(ctx, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece, nullptr);
+}
+
+extern "C" int surtr_event_regroup_bodies(surtr_ctx* ctx, int partial, uint32_t n_sphere, const float* sphere_points, const float origin[3], float radius,
+                                          uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off, int32_t* compound_piece,
+                                          uint32_t* n_bodies, uint32_t* body_compound_off)
+{
+    if (!ctx || !n_bodies) return SURTR_E_INVALID;
+    *n_bodies = (uint32_t)std::max<size_t>(ctx->scene_event_compound.size(), 1);
+    return regroup_event(ctx, partial, n_sphere, sphere_points, origin, radius, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off);
+}
+
+extern "C" int surtr_event_regroup_impacts(surtr_ctx* ctx, int partial, uint32_t n_impacts, const uint32_t* sphere_off, const float* sphere_points,
+                                           const float* origins, const float* radii, uint32_t* n_pieces_out, uint32_t* n_compounds, uint32_t* compound_off,
+                                           int32_t* compound_piece, uint32_t* n_bodies, uint32_t* body_compound_off)
+{
+    if (!ctx || !n_bodies || !n_impacts) return SURTR_E_INVALID;
+    // the last event must be surtr_scene_fracture_impacts' over as many impacts: their target lists say which body is whose
+    if (!ctx->have_event || ctx->scene_event_compound.empty() || ctx->scene_event_impacts.size() != (size_t)n_impacts + 1 ||
+        ctx->scene_event_impacts.back() != ctx->scene_event_compound.size())
+        return SURTR_E_STATE;
+    *n_bodies = (uint32_t)ctx->scene_event_compound.size();
+    if (!partial) return regroup_event(ctx, 0, 0, nullptr, nullptr, 0.f, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off);
+    const int rc = spheres_valid(n_impacts, sphere_off, origins, radii, sphere_points != nullptr);
+    if (rc) return rc;
+    const ImpactSpheres imp{n_impacts, sphere_off, origins, radii};
+    return regroup_event(ctx, 1, sphere_off[n_impacts], sphere_points, origins, radii[0], n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off, &imp);
+}
+
 // ---- the out-of-sphere mask of the pieces a click is about to break (k_scene_outside) ----
 // The listed compounds' pieces, in the order given, each compound in resident order; SURTR_E_CAPACITY for a Convex k_scene_outside
 // has no room for.  Nothing has been enqueued when an error is returned.
@@ -757,25 +739,34 @@ extern "C" int surtr_scene_outside_dev(surtr_ctx* ctx, uint32_t n_targets, const
     return outside_enqueue(ctx, list, n_sphere, dev_sphere_points, origin, radius, dev_outside);
 }
 
+// The host half of surtr_scene_outside and surtr_scene_outside_impacts, once the list is laid out and the capacity checked: the cloud goes
+// up, `enqueue(dev cloud, dev mask)` runs the kernel, the n bytes come down; synchronises (the temporaries are freed when it returns).
+template <class Enqueue>
+static int outside_host(surtr_ctx* ctx, uint32_t n_sphere, const float* sphere_points, uint32_t n, uint8_t* outside, Enqueue enqueue)
+{
+    (void)hipSetDevice(ctx->device);
+    DevBuf<float> d_sph; DevBuf<uint8_t> d_out;
+    if (d_sph.grow(ctx, 3 * (size_t)n_sphere + 3) || d_out.grow(ctx, std::max<size_t>(n, 4))) return SURTR_E_HIP;
+    if (n_sphere) HIPCHK(hipMemcpyAsync(d_sph.p, sphere_points, (size_t)n_sphere * 12, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = enqueue(d_sph.p, d_out.p);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(outside, d_out.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SURTR_OK;
+}
+
 extern "C" int surtr_scene_outside(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t n_sphere, const float* sphere_points,
                                    const float origin[3], float radius, uint32_t cap, uint32_t* n, uint8_t* outside)
 {
     if (!ctx || !n || !origin || (n_sphere && !sphere_points)) return SURTR_E_INVALID;
     std::vector<uint32_t> list;
-    int rc = outside_list(ctx, n_targets, compounds, list);
+    const int rc = outside_list(ctx, n_targets, compounds, list);
     if (rc) return rc;
     *n = (uint32_t)list.size();
     if (!outside) return SURTR_OK;
     if (cap < *n) return SURTR_E_CAPACITY;
-    (void)hipSetDevice(ctx->device);
-    DevBuf<float> d_sph; DevBuf<uint8_t> d_out;
-    if (d_sph.grow(ctx, 3 * (size_t)n_sphere + 3) || d_out.grow(ctx, std::max<size_t>(*n, 4))) return SURTR_E_HIP;
-    if (n_sphere) HIPCHK(hipMemcpyAsync(d_sph.p, sphere_points, (size_t)n_sphere * 12, hipMemcpyHostToDevice, ctx->stream));
-    rc = outside_enqueue(ctx, list, n_sphere, d_sph.p, origin, radius, d_out.p);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(outside, d_out.p, *n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));      // (also: the temporaries are freed below)
-    return SURTR_OK;
+    return outside_host(ctx, n_sphere, sphere_points, *n, outside,
+                        [&](const float* d_sph, uint8_t* d_out) { return outside_enqueue(ctx, list, n_sphere, d_sph, origin, radius, d_out); });
 }
 
 // ---- the same mask for the impacts of one frame, a sphere per piece (k_scene_outside_impacts) ----
@@ -788,9 +779,7 @@ static int outside_impacts_stage(surtr_ctx* ctx, uint32_t n_impacts, const uint3
     if (!ctx->n_pieces || ctx->scene_off.size() < 2 || ctx->scene_off.back() != ctx->n_pieces) return SURTR_E_STATE;
     int rc = impacts_valid(ctx, n_impacts, target_off, compounds);
     if (rc) return rc;
-    if (sphere_off[0] != 0u) return SURTR_E_INVALID;
-    for (uint32_t i = 0; i < n_impacts; ++i) if (sphere_off[i + 1] < sphere_off[i]) return SURTR_E_INVALID;
-    if (sphere_off[n_impacts] && !have_points) return SURTR_E_INVALID;
+    if ((rc = spheres_valid(n_impacts, sphere_off, origins, radii, have_points)) != SURTR_OK) return rc;
     std::vector<uint32_t> list, imp, one;
     for (uint32_t i = 0; i < n_impacts; ++i)
     {
@@ -803,11 +792,9 @@ static int outside_impacts_stage(surtr_ctx* ctx, uint32_t n_impacts, const uint3
     std::vector<uint32_t>& H = ctx->h_outside_stage;
     H.assign(at_tab + 8 * (size_t)n_impacts, 0u);
     memcpy(H.data(), list.data(), n * 4); memcpy(H.data() + n, imp.data(), n * 4);
-    for (uint32_t i = 0; i < n_impacts; ++i)
-    {
-        const ImpSphere s{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], radii[i], sphere_off[i], sphere_off[i + 1] - sphere_off[i], 0u, 0u};
-        memcpy(H.data() + at_tab + 8 * (size_t)i, &s, sizeof(s));
-    }
+    std::vector<ImpSphere> tab(n_impacts);
+    fill_spheres(tab.data(), n_impacts, sphere_off, origins, radii);
+    memcpy(H.data() + at_tab, tab.data(), tab.size() * sizeof(ImpSphere));
     *n_out = (uint32_t)n;
     return SURTR_OK;
 }
@@ -844,18 +831,10 @@ extern "C" int surtr_scene_outside_impacts(surtr_ctx* ctx, uint32_t n_impacts, c
                                            const float* sphere_points, const float* origins, const float* radii, uint32_t cap, uint32_t* n, uint8_t* outside)
 {
     if (!ctx || !n) return SURTR_E_INVALID;
-    int rc = outside_impacts_stage(ctx, n_impacts, target_off, compounds, sphere_off, origins, radii, sphere_points != nullptr, n);
+    const int rc = outside_impacts_stage(ctx, n_impacts, target_off, compounds, sphere_off, origins, radii, sphere_points != nullptr, n);
     if (rc) return rc;
     if (!outside) return SURTR_OK;
     if (cap < *n) return SURTR_E_CAPACITY;
-    (void)hipSetDevice(ctx->device);
-    const uint32_t n_sphere = sphere_off[n_impacts];
-    DevBuf<float> d_sph; DevBuf<uint8_t> d_out;
-    if (d_sph.grow(ctx, 3 * (size_t)n_sphere + 3) || d_out.grow(ctx, std::max<size_t>(*n, 4))) return SURTR_E_HIP;
-    if (n_sphere) HIPCHK(hipMemcpyAsync(d_sph.p, sphere_points, (size_t)n_sphere * 12, hipMemcpyHostToDevice, ctx->stream));
-    rc = outside_impacts_enqueue(ctx, *n, d_sph.p, d_out.p);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(outside, d_out.p, *n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));      // (also: the temporaries are freed below)
-    return SURTR_OK;
+    return outside_host(ctx, sphere_off[n_impacts], sphere_points, *n, outside,
+                        [&](const float* d_sph, uint8_t* d_out) { return outside_impacts_enqueue(ctx, *n, d_sph, d_out); });
 }

@@ -126,6 +126,47 @@ bool rigid_pose(const float* W)
     return det > 0.0;
 }
 
+// The event of every scene entrance.  Impact i owns compounds[target_off[i] .. target_off[i + 1]), all checked by the caller; the
+// one-compound and the bodies entrance are one "impact" over the plain placement.  The pairs are impact-major, then target-major in
+// the order given, then cell-major over the target's pieces, as surtr_fracture_event takes them: every target's fragments come out as
+// the event of that target alone gives them.  `outside` holds one byte per piece of the listed compounds in that order and is spread
+// over all resident pieces.  instance_cells (surtr_scene_fracture_impacts): impact i's cells are those of its own instance of the
+// pattern, i * n_cells + c, and the event reads the instance planes.
+int scene_event(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, uint32_t cell_begin, uint32_t cell_end,
+                const uint8_t* outside, uint32_t flags, bool instance_cells)
+{
+    const uint32_t n_targets = target_off[n_impacts], nc = cell_end - cell_begin;
+    uint64_t total = 0;
+    for (uint32_t t = 0; t < n_targets; ++t) total += ctx->scene_off[compounds[t] + 1] - ctx->scene_off[compounds[t]];
+    if ((uint64_t)nc * total > 0xFFFFFFFFull) return SURTR_E_INVALID;
+    std::vector<uint32_t> cell, piece;
+    cell.reserve((size_t)nc * total); piece.reserve((size_t)nc * total);
+    std::vector<uint8_t> mask;
+    if (outside) mask.assign(ctx->n_pieces, 0);
+    size_t at = 0;
+    for (uint32_t i = 0; i < n_impacts; ++i)
+        for (uint32_t t = target_off[i]; t < target_off[i + 1]; ++t)
+        {
+            const uint32_t p0 = ctx->scene_off[compounds[t]], m = ctx->scene_off[compounds[t] + 1] - p0, c0 = (instance_cells ? i * ctx->n_cells : 0u) + cell_begin;
+            for (uint32_t c = 0; c < nc; ++c)
+                for (uint32_t q = 0; q < m; ++q) { cell.push_back(c0 + c); piece.push_back(p0 + q); }
+            if (outside) memcpy(mask.data() + p0, outside + at, m);
+            at += m;
+        }
+    const std::vector<uint32_t> targets(compounds, compounds + n_targets), offs(target_off, target_off + n_impacts + 1);      // (launch_event clears the context's)
+    int rc;
+    if (instance_cells)
+    {
+        ImpactPlanesScope instance_planes(ctx);
+        rc = surtr_event_pairs_masked(ctx, (uint32_t)cell.size(), cell.data(), piece.data(), outside ? mask.data() : nullptr, flags);
+    }
+    else rc = surtr_event_pairs_masked(ctx, (uint32_t)cell.size(), cell.data(), piece.data(), outside ? mask.data() : nullptr, flags);
+    if (rc) return rc;
+    ctx->scene_event_compound = targets;
+    if (instance_cells) ctx->scene_event_impacts = offs;
+    return SURTR_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -228,30 +269,15 @@ int surtr_scene_fracture_event_async(surtr_ctx* ctx, uint32_t compound, uint32_t
 {
     if (!ctx) return SURTR_E_INVALID;
     if (!ctx->n_pieces || !ctx->planes_ready) return SURTR_E_STATE;
-    if (compound + 1u >= ctx->scene_off.size() || cell_end > ctx->n_cells || cell_begin > cell_end) return SURTR_E_INVALID;
-    const uint32_t p0 = ctx->scene_off[compound], m = ctx->scene_off[compound + 1] - p0, nc = cell_end - cell_begin;
-    if ((uint64_t)nc * m > 0xFFFFFFFFull) return SURTR_E_INVALID;
-    // the pairs of this compound alone, cell-major as surtr_fracture_event takes them; the mask over all resident pieces
-    std::vector<uint32_t> cell((size_t)nc * m), piece((size_t)nc * m);
-    for (uint32_t c = 0; c < nc; ++c)
-        for (uint32_t q = 0; q < m; ++q) { cell[(size_t)c * m + q] = cell_begin + c; piece[(size_t)c * m + q] = p0 + q; }
-    std::vector<uint8_t> mask;
-    if (outside) { mask.assign(ctx->n_pieces, 0); memcpy(mask.data() + p0, outside, m); }
-    const int rc = surtr_event_pairs_masked(ctx, nc * m, cell.data(), piece.data(), outside ? mask.data() : nullptr, flags);
-    if (rc) return rc;
-    ctx->scene_event_compound.assign(1, compound);
-    return SURTR_OK;
+    if ((size_t)compound + 1 >= ctx->scene_off.size() || cell_end > ctx->n_cells || cell_begin > cell_end) return SURTR_E_INVALID;
+    const uint32_t one[2] = {0u, 1u};
+    return scene_event(ctx, 1, one, &compound, cell_begin, cell_end, outside, flags, false);
 }
 
 int surtr_scene_fracture_event(surtr_ctx* ctx, uint32_t compound, uint32_t cell_begin, uint32_t cell_end, const uint8_t* outside, uint32_t flags,
                                surtr_counts* counts)
 {
-    int rc = surtr_scene_fracture_event_async(ctx, compound, cell_begin, cell_end, outside, flags);
-    if (rc) return rc;
-    surtr_counts c;
-    rc = surtr_event_counts(ctx, &c);
-    if (counts) *counts = c;
-    return rc;
+    return event_sync_counts(ctx, surtr_scene_fracture_event_async(ctx, compound, cell_begin, cell_end, outside, flags), counts);
 }
 
 int surtr_scene_fracture_bodies_async(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t cell_begin, uint32_t cell_end,
@@ -260,45 +286,16 @@ int surtr_scene_fracture_bodies_async(surtr_ctx* ctx, uint32_t n_targets, const 
     if (!ctx) return SURTR_E_INVALID;
     if (!ctx->n_pieces || !ctx->planes_ready) return SURTR_E_STATE;
     if (!n_targets || !compounds || cell_end > ctx->n_cells || cell_begin > cell_end) return SURTR_E_INVALID;
-    uint64_t total = 0;
     for (uint32_t t = 0; t < n_targets; ++t)
-    {
         if ((size_t)compounds[t] + 1 >= ctx->scene_off.size() || (t && compounds[t] >= compounds[t - 1])) return SURTR_E_INVALID;      // strictly descending
-        total += ctx->scene_off[compounds[t] + 1] - ctx->scene_off[compounds[t]];
-    }
-    const uint32_t nc = cell_end - cell_begin;
-    if ((uint64_t)nc * total > 0xFFFFFFFFull) return SURTR_E_INVALID;
-    // the pairs target-major in the order given, cell-major over the target's pieces within a target: every target's fragments come
-    // out as its own surtr_scene_fracture_event gives them; the mask is spread over all resident pieces
-    std::vector<uint32_t> cell, piece;
-    cell.reserve((size_t)nc * total); piece.reserve((size_t)nc * total);
-    std::vector<uint8_t> mask;
-    if (outside) mask.assign(ctx->n_pieces, 0);
-    size_t at = 0;
-    for (uint32_t t = 0; t < n_targets; ++t)
-    {
-        const uint32_t p0 = ctx->scene_off[compounds[t]], m = ctx->scene_off[compounds[t] + 1] - p0;
-        for (uint32_t c = 0; c < nc; ++c)
-            for (uint32_t q = 0; q < m; ++q) { cell.push_back(cell_begin + c); piece.push_back(p0 + q); }
-        if (outside) memcpy(mask.data() + p0, outside + at, m);
-        at += m;
-    }
-    const std::vector<uint32_t> targets(compounds, compounds + n_targets);      // (launch_event clears the context's list)
-    const int rc = surtr_event_pairs_masked(ctx, (uint32_t)cell.size(), cell.data(), piece.data(), outside ? mask.data() : nullptr, flags);
-    if (rc) return rc;
-    ctx->scene_event_compound = targets;
-    return SURTR_OK;
+    const uint32_t one[2] = {0u, n_targets};
+    return scene_event(ctx, 1, one, compounds, cell_begin, cell_end, outside, flags, false);
 }
 
 int surtr_scene_fracture_bodies(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, uint32_t cell_begin, uint32_t cell_end,
                                 const uint8_t* outside, uint32_t flags, surtr_counts* counts)
 {
-    int rc = surtr_scene_fracture_bodies_async(ctx, n_targets, compounds, cell_begin, cell_end, outside, flags);
-    if (rc) return rc;
-    surtr_counts c;
-    rc = surtr_event_counts(ctx, &c);
-    if (counts) *counts = c;
-    return rc;
+    return event_sync_counts(ctx, surtr_scene_fracture_bodies_async(ctx, n_targets, compounds, cell_begin, cell_end, outside, flags), counts);
 }
 
 int surtr_scene_fracture_impacts_async(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, uint32_t cell_begin,
@@ -306,48 +303,16 @@ int surtr_scene_fracture_impacts_async(surtr_ctx* ctx, uint32_t n_impacts, const
 {
     if (!ctx || !n_impacts) return SURTR_E_INVALID;
     if (!ctx->n_pieces || !ctx->n_impacts_placed || ctx->n_impacts_placed != n_impacts) return SURTR_E_STATE;
-    int rc = impacts_valid(ctx, n_impacts, target_off, compounds);
+    const int rc = impacts_valid(ctx, n_impacts, target_off, compounds);
     if (rc) return rc;
     if (cell_end > ctx->n_cells || cell_begin > cell_end) return SURTR_E_INVALID;
-    const uint32_t n_targets = target_off[n_impacts], nc = cell_end - cell_begin;
-    uint64_t total = 0;
-    for (uint32_t t = 0; t < n_targets; ++t) total += ctx->scene_off[compounds[t] + 1] - ctx->scene_off[compounds[t]];
-    if ((uint64_t)nc * total > 0xFFFFFFFFull) return SURTR_E_INVALID;
-    // the pairs impact-major, then target-major in the order given, then cell-major over the target's pieces -- over the cells of the
-    // impact's own instance of the pattern: every target's fragments come out as the event of its impact alone gives them
-    std::vector<uint32_t> cell, piece;
-    cell.reserve((size_t)nc * total); piece.reserve((size_t)nc * total);
-    std::vector<uint8_t> mask;
-    if (outside) mask.assign(ctx->n_pieces, 0);
-    size_t at = 0;
-    for (uint32_t i = 0; i < n_impacts; ++i)
-        for (uint32_t t = target_off[i]; t < target_off[i + 1]; ++t)
-        {
-            const uint32_t p0 = ctx->scene_off[compounds[t]], m = ctx->scene_off[compounds[t] + 1] - p0;
-            for (uint32_t c = 0; c < nc; ++c)
-                for (uint32_t q = 0; q < m; ++q) { cell.push_back(i * ctx->n_cells + cell_begin + c); piece.push_back(p0 + q); }
-            if (outside) memcpy(mask.data() + p0, outside + at, m);
-            at += m;
-        }
-    const std::vector<uint32_t> targets(compounds, compounds + n_targets), offs(target_off, target_off + n_impacts + 1);      // (launch_event clears the context's)
-    {
-        ImpactPlanesScope instance_planes(ctx);
-        rc = surtr_event_pairs_masked(ctx, (uint32_t)cell.size(), cell.data(), piece.data(), outside ? mask.data() : nullptr, flags);
-    }
-    if (rc) return rc;
-    ctx->scene_event_compound = targets; ctx->scene_event_impacts = offs;
-    return SURTR_OK;
+    return scene_event(ctx, n_impacts, target_off, compounds, cell_begin, cell_end, outside, flags, true);
 }
 
 int surtr_scene_fracture_impacts(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, uint32_t cell_begin,
                                  uint32_t cell_end, const uint8_t* outside, uint32_t flags, surtr_counts* counts)
 {
-    int rc = surtr_scene_fracture_impacts_async(ctx, n_impacts, target_off, compounds, cell_begin, cell_end, outside, flags);
-    if (rc) return rc;
-    surtr_counts c;
-    rc = surtr_event_counts(ctx, &c);
-    if (counts) *counts = c;
-    return rc;
+    return event_sync_counts(ctx, surtr_scene_fracture_impacts_async(ctx, n_impacts, target_off, compounds, cell_begin, cell_end, outside, flags), counts);
 }
 
 int surtr_scene_fragments_async(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, int render_convex, uint32_t flags)
@@ -479,12 +444,7 @@ int surtr_scene_fragments_async(surtr_ctx* ctx, uint32_t n_targets, const uint32
 
 int surtr_scene_fragments(surtr_ctx* ctx, uint32_t n_targets, const uint32_t* compounds, int render_convex, uint32_t flags, surtr_counts* counts)
 {
-    int rc = surtr_scene_fragments_async(ctx, n_targets, compounds, render_convex, flags);
-    if (rc) return rc;
-    surtr_counts c;
-    rc = surtr_event_counts(ctx, &c);
-    if (counts) *counts = c;
-    return rc;
+    return event_sync_counts(ctx, surtr_scene_fragments_async(ctx, n_targets, compounds, render_convex, flags), counts);
 }
 
 int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* compound_off, const int32_t* compound_piece, uint32_t* n_pieces_out,

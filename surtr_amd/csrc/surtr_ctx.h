@@ -499,6 +499,16 @@ static inline int scene_sync_device(surtr_ctx* ctx, SceneDev* out)
 
 // an event over an explicit pair list with an `outside` mask over all resident pieces (surtr_hip.hip); NULL: no mask
 int surtr_event_pairs_masked(surtr_ctx* ctx, uint32_t n_pairs, const uint32_t* pair_cell, const uint32_t* pair_piece, const uint8_t* outside, uint32_t flags);
+// The synchronous twin of an _async event call: given what the _async call returned, reads the counts back (surtr_event_counts: one
+// small copy and a synchronisation of the context's stream).
+static inline int event_sync_counts(surtr_ctx* ctx, int rc_async, surtr_counts* counts)
+{
+    if (rc_async) return rc_async;
+    surtr_counts c{};
+    const int rc = surtr_event_counts(ctx, &c);
+    if (counts) *counts = c;
+    return rc;
+}
 
 // Room for n loaded fragments of MV + CV vertices and MH + CH ring entries (Mesh + Convex slots), the largest of them vmax / hmax
 // (Mesh slot) and cvmax / chmax (Convex slot): the context's maxima are raised, then scratch, one-wave scratch and arena get the bounds
@@ -532,6 +542,19 @@ static inline int impacts_valid(const surtr_ctx* ctx, uint32_t n_impacts, const 
         }
     }
     return SURTR_OK;
+}
+// The spheres of a call: impact i's origin, radius and points [sphere_off[i], sphere_off[i + 1]) of one cloud.  sphere_off starts at 0
+// and does not decrease; the cloud may be missing only when it is empty.  Anything else: SURTR_E_INVALID.
+static inline int spheres_valid(uint32_t n_impacts, const uint32_t* sphere_off, const float* origins, const float* radii, bool have_points)
+{
+    if (!sphere_off || !origins || !radii || sphere_off[0] != 0u) return SURTR_E_INVALID;
+    for (uint32_t i = 0; i < n_impacts; ++i) if (sphere_off[i + 1] < sphere_off[i]) return SURTR_E_INVALID;
+    return sphere_off[n_impacts] && !have_points ? SURTR_E_INVALID : SURTR_OK;
+}
+static inline void fill_spheres(ImpSphere* tab, uint32_t n_impacts, const uint32_t* sphere_off, const float* origins, const float* radii)
+{
+    for (uint32_t i = 0; i < n_impacts; ++i)
+        tab[i] = ImpSphere{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], radii[i], sphere_off[i], sphere_off[i + 1] - sphere_off[i], 0u, 0u};
 }
 // While one of these lives the event's kernels read the instance planes of surtr_place_cells_impacts: the plain placement's tables are
 // swapped out and come back, untouched, when it goes.

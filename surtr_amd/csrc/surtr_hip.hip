@@ -241,20 +241,26 @@ __device__ __forceinline__ float4 plane_from_points(const float* p0, const float
     return make_float4(nx, ny, nz, -dot3(nx, ny, nz, p0[0], p0[1], p0[2]));
 }
 
+// The plane of a pattern face (its three points v[0..9)) under a scale and a translate: Polygon3D::Scale / Translate, then Plane(p0, p1, p2).
+__device__ __forceinline__ float4 placed_plane(const float* v, float sx, float sy, float sz, float tx, float ty, float tz)
+{
+    float p[9];
+    for (int i = 0; i < 3; ++i)
+    {
+        p[3 * i] = v[3 * i] * sx + tx;
+        p[3 * i + 1] = v[3 * i + 1] * sy + ty;
+        p[3 * i + 2] = v[3 * i + 2] * sz + tz;
+    }
+    return plane_from_points(p, p + 3, p + 6);
+}
+
 // ------------------------------------------------------------ k_place_cells
 __global__ void k_place_cells(uint32_t nfaces, const float* __restrict__ v012, float sx, float sy, float sz,
                               float tx, float ty, float tz, float4* __restrict__ planes)
 {
     const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nfaces) return;
-    float p[9];
-    for (int i = 0; i < 3; ++i)
-    {
-        p[3 * i] = v012[9 * f + 3 * i] * sx + tx;
-        p[3 * i + 1] = v012[9 * f + 3 * i + 1] * sy + ty;
-        p[3 * i + 2] = v012[9 * f + 3 * i + 2] * sz + tz;
-    }
-    planes[f] = plane_from_points(p, p + 3, p + 6);
+    planes[f] = placed_plane(v012 + 9 * f, sx, sy, sz, tx, ty, tz);
 }
 
 // Same with one (scale, translate) per group of cells (recursive refracture: every first-level fragment places its own
@@ -267,14 +273,7 @@ __global__ void k_place_cells_groups(uint32_t nfaces, const float* __restrict__ 
     const uint32_t g = face_group[f];
     const float sx = scale3[3 * g], sy = scale3[3 * g + 1], sz = scale3[3 * g + 2];
     const float tx = shift3[3 * g], ty = shift3[3 * g + 1], tz = shift3[3 * g + 2];
-    float p[9];
-    for (int i = 0; i < 3; ++i)
-    {
-        p[3 * i] = v012[9 * f + 3 * i] * sx + tx;
-        p[3 * i + 1] = v012[9 * f + 3 * i + 1] * sy + ty;
-        p[3 * i + 2] = v012[9 * f + 3 * i + 2] * sz + tz;
-    }
-    planes[f] = plane_from_points(p, p + 3, p + 6);
+    planes[f] = placed_plane(v012 + 9 * f, sx, sy, sz, tx, ty, tz);
 }
 
 // Several instances of the pattern in one launch, one per impact of a frame (surtr_place_cells_impacts): plane i * nfaces + f is face f
@@ -291,14 +290,7 @@ __global__ void k_place_cells_impacts(uint32_t nfaces, uint32_t n_imp, const flo
     {
         const float sx = scale3[3 * g], sy = scale3[3 * g + 1], sz = scale3[3 * g + 2];
         const float tx = shift3[3 * g], ty = shift3[3 * g + 1], tz = shift3[3 * g + 2];
-        float p[9];
-        for (int i = 0; i < 3; ++i)
-        {
-            p[3 * i] = v[3 * i] * sx + tx;
-            p[3 * i + 1] = v[3 * i + 1] * sy + ty;
-            p[3 * i + 2] = v[3 * i + 2] * sz + tz;
-        }
-        planes[(size_t)g * nfaces + f] = plane_from_points(p, p + 3, p + 6);
+        planes[(size_t)g * nfaces + f] = placed_plane(v, sx, sy, sz, tx, ty, tz);
     }
 }
 
@@ -4617,12 +4609,7 @@ int surtr_event_counts(surtr_ctx* ctx, surtr_counts* counts)
 int surtr_fracture_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t cell_end, const uint8_t* outside, uint32_t flags,
                          surtr_counts* counts)
 {
-    int rc = surtr_fracture_event_async(ctx, cell_begin, cell_end, outside, flags);
-    if (rc) return rc;
-    surtr_counts c;
-    rc = surtr_event_counts(ctx, &c);
-    if (counts) *counts = c;
-    return rc;
+    return event_sync_counts(ctx, surtr_fracture_event_async(ctx, cell_begin, cell_end, outside, flags), counts);
 }
 
 size_t surtr_event_blob_bytes(const surtr_counts* counts)

@@ -390,41 +390,38 @@ class Engine:
         assert pc.shape == pp.shape
         self._ck(lib().surtr_fracture_pairs_async(self._h, ctypes.c_uint32(pc.shape[0]), _p(pc), _p(pp), ctypes.c_uint32(flags)))
 
-    def event_regroup(self, partial=False, sphere_points=None, origin=(0, 0, 0), radius=1.0):
-        """surtr_event_regroup: bind sets + MergeOutOfImpact + HandleConvexIsland of the last event, on the device."""
+    def _regroup(self, symbol, args, with_bodies):
+        """The regroup calls: sizes first, then the fill through `symbol` -> (compound_off, compound_piece[, body_compound_off])."""
+        n, nc, nb = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        sizes = lib().surtr_event_regroup_bodies if symbol == "surtr_event_regroup" else getattr(lib(), symbol)
+        # (the sizes: after scene_fracture_bodies every body has a bind 0 of its own, so n_pieces + n_bodies + 1 offsets)
+        self._ck(sizes(*args, ctypes.byref(n), ctypes.byref(nc), None, None, ctypes.byref(nb), None))
+        co = np.zeros(n.value + nb.value + 1, np.uint32); cp = np.zeros(max(n.value, 1), np.int32); bo = np.zeros(nb.value + 1, np.uint32)
+        tail = (ctypes.byref(nb), _p(bo)) if with_bodies else ()
+        self._ck(getattr(lib(), symbol)(*args, ctypes.byref(n), ctypes.byref(nc), _p(co), _p(cp), *tail))
+        out = (co[:nc.value + 1].copy(), cp[:co[nc.value]].copy())
+        return out + (bo,) if with_bodies else out
+
+    def _sphere_args(self, partial, sphere_points, origin, radius):
         sp = np.zeros((0, 3), np.float32) if sphere_points is None else np.ascontiguousarray(sphere_points, np.float32).reshape(-1, 3)
         org = np.ascontiguousarray(origin, np.float32)
-        n, nc, nb = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
-        args = [self._h, ctypes.c_int(int(partial)), ctypes.c_uint32(sp.shape[0]), _p(sp), _p(org), ctypes.c_float(radius)]
-        # (the sizes: after scene_fracture_bodies every body has a bind 0 of its own, so n_pieces + n_bodies + 1 offsets)
-        self._ck(lib().surtr_event_regroup_bodies(*args, ctypes.byref(n), ctypes.byref(nc), None, None, ctypes.byref(nb), None))
-        co = np.zeros(n.value + nb.value + 1, np.uint32); cp = np.zeros(max(n.value, 1), np.int32)
-        self._ck(lib().surtr_event_regroup(*args, ctypes.byref(n), ctypes.byref(nc), _p(co), _p(cp)))
-        return co[:nc.value + 1].copy(), cp[:co[nc.value]].copy()
+        return [self._h, ctypes.c_int(int(partial)), ctypes.c_uint32(sp.shape[0]), _p(sp), _p(org), ctypes.c_float(radius)]
+
+    def event_regroup(self, partial=False, sphere_points=None, origin=(0, 0, 0), radius=1.0):
+        """surtr_event_regroup: bind sets + MergeOutOfImpact + HandleConvexIsland of the last event, on the device."""
+        return self._regroup("surtr_event_regroup", self._sphere_args(partial, sphere_points, origin, radius), False)
 
     def event_regroup_bodies(self, partial=False, sphere_points=None, origin=(0, 0, 0), radius=1.0):
         """surtr_event_regroup_bodies: event_regroup with the compounds of every body of the event -> (compound_off, compound_piece,
         body_compound_off): body b (target b of scene_fracture_bodies) owns compounds [body_off[b], body_off[b + 1])."""
-        sp = np.zeros((0, 3), np.float32) if sphere_points is None else np.ascontiguousarray(sphere_points, np.float32).reshape(-1, 3)
-        org = np.ascontiguousarray(origin, np.float32)
-        n, nc, nb = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
-        args = [self._h, ctypes.c_int(int(partial)), ctypes.c_uint32(sp.shape[0]), _p(sp), _p(org), ctypes.c_float(radius)]
-        self._ck(lib().surtr_event_regroup_bodies(*args, ctypes.byref(n), ctypes.byref(nc), None, None, ctypes.byref(nb), None))
-        co = np.zeros(n.value + nb.value + 1, np.uint32); cp = np.zeros(max(n.value, 1), np.int32); bo = np.zeros(nb.value + 1, np.uint32)
-        self._ck(lib().surtr_event_regroup_bodies(*args, ctypes.byref(n), ctypes.byref(nc), _p(co), _p(cp), ctypes.byref(nb), _p(bo)))
-        return co[:nc.value + 1].copy(), cp[:co[nc.value]].copy(), bo
+        return self._regroup("surtr_event_regroup_bodies", self._sphere_args(partial, sphere_points, origin, radius), True)
 
     def event_regroup_impacts(self, partial=False, sphere_points=None, origins=None, radii=None, n_impacts=None):
         """surtr_event_regroup_impacts: event_regroup_bodies after scene_fracture_impacts, every body against the sphere of its own
         impact.  sphere_points: one f32[n_i,3] cloud per impact; origins f32[K,3]; radii f32[K].  -> (compound_off, compound_piece,
         body_compound_off), a body being a target in the order given."""
         k, so, sp, org, rad = _impact_spheres(sphere_points, origins, radii, n_impacts)
-        n, nc, nb = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
-        args = [self._h, ctypes.c_int(int(partial)), ctypes.c_uint32(k), _p(so), _p(sp), _p(org), _p(rad)]
-        self._ck(lib().surtr_event_regroup_impacts(*args, ctypes.byref(n), ctypes.byref(nc), None, None, ctypes.byref(nb), None))
-        co = np.zeros(n.value + nb.value + 1, np.uint32); cp = np.zeros(max(n.value, 1), np.int32); bo = np.zeros(nb.value + 1, np.uint32)
-        self._ck(lib().surtr_event_regroup_impacts(*args, ctypes.byref(n), ctypes.byref(nc), _p(co), _p(cp), ctypes.byref(nb), _p(bo)))
-        return co[:nc.value + 1].copy(), cp[:co[nc.value]].copy(), bo
+        return self._regroup("surtr_event_regroup_impacts", [self._h, ctypes.c_int(int(partial)), ctypes.c_uint32(k), _p(so), _p(sp), _p(org), _p(rad)], True)
 
     def regroup_stats(self):
         """What the last event_regroup counted (include/surtr_hip.h: surtr_regroup_stats); no synchronisation."""
@@ -664,45 +661,58 @@ class Engine:
         w = np.ascontiguousarray(world, np.float32).reshape(-1, 16)
         self._ck(lib().surtr_scene_transform_compound(self._h, ctypes.c_uint32(int(compound)), ctypes.c_uint32(w.shape[0]), _p(w)))
 
-    def scene_fracture_event(self, compound, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
-        """surtr_scene_fracture_event: the event over the pieces of one compound; outside: one byte per piece of that compound."""
-        c = Counts()
-        om = None if outside is None else np.ascontiguousarray(outside, np.uint8)
-        if om is not None:
-            co = self.scene_compounds()
-            if not 0 <= int(compound) < co.shape[0] - 1 or om.shape[0] != int(co[int(compound) + 1]) - int(co[int(compound)]):
-                raise SurtrError(E_INVALID, "outside holds %d bytes" % om.shape[0])
-        self._ck(lib().surtr_scene_fracture_event(self._h, ctypes.c_uint32(int(compound)), ctypes.c_uint32(cell_begin), ctypes.c_uint32(cell_end),
-                                                  _p(om), ctypes.c_uint32(flags), ctypes.byref(c)))
-        return c
-
-    def scene_fracture_event_async(self, compound, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
-        om = None if outside is None else np.ascontiguousarray(outside, np.uint8)
-        self._ck(lib().surtr_scene_fracture_event_async(self._h, ctypes.c_uint32(int(compound)), ctypes.c_uint32(cell_begin),
-                                                        ctypes.c_uint32(cell_end), _p(om), ctypes.c_uint32(flags)))
-
-    def _bodies_mask(self, compounds, outside):
-        t = np.ascontiguousarray(compounds, np.uint32).reshape(-1)
+    def _targets_mask(self, t, outside):
+        """The `outside` bytes of a fracture call over compounds t, checked against the compound table: one byte per piece of t."""
         om = None if outside is None else np.ascontiguousarray(outside, np.uint8).reshape(-1)
         if om is not None:
             co = self.scene_compounds()
-            if any(int(c) >= co.shape[0] - 1 for c in t) or om.shape[0] != sum(int(co[int(c) + 1]) - int(co[int(c)]) for c in t):
+            if any(not 0 <= int(c) < co.shape[0] - 1 for c in t) or om.shape[0] != sum(int(co[int(c) + 1]) - int(co[int(c)]) for c in t):
                 raise SurtrError(E_INVALID, "outside holds %d bytes" % om.shape[0])
-        return t, om
+        return om
+
+    def _scene_fracture(self, kind, targets, cell_begin, cell_end, outside, flags, sync):
+        """The three fracture entrances: kind "event" (targets: one compound), "bodies" (a list) or "impacts" (a list per impact).
+        sync -> Counts; else the _async symbol, and nothing waits for the event."""
+        if kind == "event":
+            t = [int(targets)]
+            head = [ctypes.c_uint32(t[0])]
+        elif kind == "bodies":
+            t = np.ascontiguousarray(targets, np.uint32).reshape(-1)
+            head = [ctypes.c_uint32(t.shape[0]), _p(t)]
+        else:
+            to, t = _impact_targets(targets)
+            head = [ctypes.c_uint32(to.shape[0] - 1), _p(to), _p(t)]
+        om = self._targets_mask(t, outside)
+        args = [self._h] + head + [ctypes.c_uint32(cell_begin), ctypes.c_uint32(cell_end), _p(om), ctypes.c_uint32(flags)]
+        if not sync:
+            return self._ck(getattr(lib(), "surtr_scene_fracture_%s_async" % kind)(*args))
+        c = Counts()
+        self._ck(getattr(lib(), "surtr_scene_fracture_" + kind)(*args, ctypes.byref(c)))
+        return c
+
+    def scene_fracture_event(self, compound, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
+        """surtr_scene_fracture_event: the event over the pieces of one compound; outside: one byte per piece of that compound."""
+        return self._scene_fracture("event", compound, cell_begin, cell_end, outside, flags, True)
+
+    def scene_fracture_event_async(self, compound, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
+        self._scene_fracture("event", compound, cell_begin, cell_end, outside, flags, False)
 
     def scene_fracture_bodies(self, compounds, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
         """surtr_scene_fracture_bodies: one event over the pieces of several compounds (strictly descending); outside: one byte per
         piece of the listed compounds, concatenated in the order given (what scene_outside returns)."""
-        t, om = self._bodies_mask(compounds, outside)
-        c = Counts()
-        self._ck(lib().surtr_scene_fracture_bodies(self._h, ctypes.c_uint32(t.shape[0]), _p(t), ctypes.c_uint32(cell_begin), ctypes.c_uint32(cell_end),
-                                                   _p(om), ctypes.c_uint32(flags), ctypes.byref(c)))
-        return c
+        return self._scene_fracture("bodies", compounds, cell_begin, cell_end, outside, flags, True)
 
     def scene_fracture_bodies_async(self, compounds, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
-        t, om = self._bodies_mask(compounds, outside)
-        self._ck(lib().surtr_scene_fracture_bodies_async(self._h, ctypes.c_uint32(t.shape[0]), _p(t), ctypes.c_uint32(cell_begin),
-                                                         ctypes.c_uint32(cell_end), _p(om), ctypes.c_uint32(flags)))
+        self._scene_fracture("bodies", compounds, cell_begin, cell_end, outside, flags, False)
+
+    def _two_call_bytes(self, symbol, args, capacity):
+        """Count-then-fill of a byte mask: capacity is the bytes to offer (None: what the sizes call asks for)."""
+        n = ctypes.c_uint32()
+        self._ck(getattr(lib(), symbol)(*args, ctypes.c_uint32(0), ctypes.byref(n), None))
+        cap = n.value if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 1), np.uint8)
+        self._ck(getattr(lib(), symbol)(*args, ctypes.c_uint32(cap), ctypes.byref(n), _p(out)))
+        return out[:n.value].copy()
 
     def scene_outside(self, compounds, sphere_points, origin, radius, capacity=None):
         """surtr_scene_outside: Surtr::ConvexOutOfSphere of every resident Convex of the listed compounds, on the device -> uint8, one
@@ -710,13 +720,8 @@ class Engine:
         t = np.ascontiguousarray(compounds, np.uint32).reshape(-1)
         sp = np.zeros((0, 3), np.float32) if sphere_points is None else np.ascontiguousarray(sphere_points, np.float32).reshape(-1, 3)
         org = np.ascontiguousarray(origin, np.float32)
-        n = ctypes.c_uint32()
         args = [self._h, ctypes.c_uint32(t.shape[0]), _p(t), ctypes.c_uint32(sp.shape[0]), _p(sp), _p(org), ctypes.c_float(radius)]
-        self._ck(lib().surtr_scene_outside(*args, ctypes.c_uint32(0), ctypes.byref(n), None))
-        cap = n.value if capacity is None else int(capacity)
-        out = np.zeros(max(cap, 1), np.uint8)
-        self._ck(lib().surtr_scene_outside(*args, ctypes.c_uint32(cap), ctypes.byref(n), _p(out)))
-        return out[:n.value].copy()
+        return self._two_call_bytes("surtr_scene_outside", args, capacity)
 
     def scene_outside_dev(self, compounds, n_sphere, dev_sphere_points, origin, radius, dev_outside, capacity):
         """surtr_scene_outside_dev: cloud and mask in device memory, on the context's stream; nothing is read back."""
@@ -726,28 +731,13 @@ class Engine:
                                                _p(org), ctypes.c_float(radius), ctypes.c_void_p(dev_outside), ctypes.c_size_t(capacity)))
 
     # ---- several impacts in one frame (include/surtr_hip.h): `targets` is one list of compounds per impact
-    def _impacts_mask(self, targets, outside):
-        to, t = _impact_targets(targets)
-        om = None if outside is None else np.ascontiguousarray(outside, np.uint8).reshape(-1)
-        if om is not None:
-            co = self.scene_compounds()
-            if any(int(c) >= co.shape[0] - 1 for c in t) or om.shape[0] != sum(int(co[int(c) + 1]) - int(co[int(c)]) for c in t):
-                raise SurtrError(E_INVALID, "outside holds %d bytes" % om.shape[0])
-        return to, t, om
-
     def scene_fracture_impacts(self, targets, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
         """surtr_scene_fracture_impacts: one event over the targets of every impact, each over the cells of its impact's own
         placement (place_cells_impacts); outside: what scene_outside_impacts returns."""
-        to, t, om = self._impacts_mask(targets, outside)
-        c = Counts()
-        self._ck(lib().surtr_scene_fracture_impacts(self._h, ctypes.c_uint32(to.shape[0] - 1), _p(to), _p(t), ctypes.c_uint32(cell_begin),
-                                                    ctypes.c_uint32(cell_end), _p(om), ctypes.c_uint32(flags), ctypes.byref(c)))
-        return c
+        return self._scene_fracture("impacts", targets, cell_begin, cell_end, outside, flags, True)
 
     def scene_fracture_impacts_async(self, targets, cell_begin, cell_end, outside=None, flags=EVT_REFIT | EVT_RENDER):
-        to, t, om = self._impacts_mask(targets, outside)
-        self._ck(lib().surtr_scene_fracture_impacts_async(self._h, ctypes.c_uint32(to.shape[0] - 1), _p(to), _p(t), ctypes.c_uint32(cell_begin),
-                                                          ctypes.c_uint32(cell_end), _p(om), ctypes.c_uint32(flags)))
+        self._scene_fracture("impacts", targets, cell_begin, cell_end, outside, flags, False)
 
     def scene_outside_impacts(self, targets, sphere_points, origins, radii, capacity=None):
         """surtr_scene_outside_impacts: scene_outside with a sphere per impact, in one launch -> uint8, impact after impact, each as
@@ -756,13 +746,8 @@ class Engine:
         k, so, sp, org, rad = _impact_spheres(sphere_points, origins, radii, to.shape[0] - 1)
         if k != to.shape[0] - 1:
             raise SurtrError(E_INVALID, "%d spheres for %d impacts" % (k, to.shape[0] - 1))
-        n = ctypes.c_uint32()
         args = [self._h, ctypes.c_uint32(to.shape[0] - 1), _p(to), _p(t), _p(so), _p(sp), _p(org), _p(rad)]
-        self._ck(lib().surtr_scene_outside_impacts(*args, ctypes.c_uint32(0), ctypes.byref(n), None))
-        cap = n.value if capacity is None else int(capacity)
-        out = np.zeros(max(cap, 1), np.uint8)
-        self._ck(lib().surtr_scene_outside_impacts(*args, ctypes.c_uint32(cap), ctypes.byref(n), _p(out)))
-        return out[:n.value].copy()
+        return self._two_call_bytes("surtr_scene_outside_impacts", args, capacity)
 
     def scene_outside_impacts_dev(self, targets, sphere_off, dev_sphere_points, origins, radii, dev_outside, capacity):
         """surtr_scene_outside_impacts_dev: cloud (all impacts' points, impact i's at [sphere_off[i], sphere_off[i + 1])) and mask in

@@ -406,15 +406,8 @@ static void init_compounds(FractureEngine& eng, size_t click, const std::vector<
     }
 }
 
-// --scene-clicks: OnMouseDown per click on the resident scene; one JSON line per click.
-static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float, 6>>& clicks, float impact_radius, bool one_event)
+static std::vector<Vector3> lattice_cloud()
 {
-    const uint32_t n0 = eng.CompoundFromLastEvent();
-    std::vector<uint32_t> off;
-    for (uint32_t p = 0; p < n0; p += 2) off.push_back(p);
-    off.push_back(n0);
-    const int rc = surtr_scene_set_compounds(eng.Raw(), (uint32_t)off.size() - 1u, off.data());
-    if (rc) throw Error(rc, "surtr_scene_set_compounds");
     // the 26 directions of the 3 x 3 x 3 lattice, unit length (double arithmetic, narrowed): the sphere point cloud
     std::vector<Vector3> cloud;
     for (int i = -1; i <= 1; ++i) for (int j = -1; j <= 1; ++j) for (int k = -1; k <= 1; ++k)
@@ -423,6 +416,52 @@ static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float
         const double l = std::sqrt((double)(i * i + j * j + k * k));
         cloud.emplace_back((float)(i / l), (float)(j / l), (float)(k / l));
     }
+    return cloud;
+}
+
+// The scene of --scene-clicks, --body-clicks and --impacts: the last event's fragments, piece k in compound k / 2, with the given poses.
+static void paired_scene(FractureEngine& eng, const std::vector<std::pair<int, Matrix>>& poses)
+{
+    const uint32_t n0 = eng.CompoundFromLastEvent();
+    std::vector<uint32_t> off;
+    for (uint32_t p = 0; p < n0; p += 2) off.push_back(p);
+    off.push_back(n0);
+    const int rc = surtr_scene_set_compounds(eng.Raw(), (uint32_t)off.size() - 1u, off.data());
+    if (rc) throw Error(rc, "surtr_scene_set_compounds");
+    if (poses.empty()) return;
+    std::vector<Matrix> world(off.size() - 1);
+    for (const auto& p : poses)
+    {
+        if (p.first < 0 || (size_t)p.first >= world.size()) throw Error(SURTR_E_INVALID, "--scene-poses: no such compound");
+        world[(size_t)p.first] = p.second;
+    }
+    eng.SetPoses(world);
+}
+
+// The end of a --body-clicks / --impacts line: the compounds made, the table, the poses and the bodies' masses.
+static void print_made_and_scene(const std::vector<int>& made, const std::vector<uint32_t>& table, const std::vector<Matrix>& world, const std::vector<surtr_mass>& bm)
+{
+    printf("], \"compounds_made\": [");
+    for (size_t i = 0; i < made.size(); ++i) printf("%s%d", i ? ", " : "", made[i]);
+    printf("], \"table\": [");
+    for (size_t i = 0; i < table.size(); ++i) printf("%s%u", i ? ", " : "", table[i]);
+    printf("], \"poses\": [");
+    for (size_t c = 0; c < world.size(); ++c)
+    {
+        printf("%s[", c ? ", " : "");
+        for (int k = 0; k < 16; ++k) printf("%s%.9g", k ? ", " : "", world[c].m[k]);
+        printf("]");
+    }
+    printf("], \"mass\": [");
+    for (size_t i = 0; i < bm.size(); ++i) printf("%s%.17g", i ? ", " : "", bm[i].mass);
+    printf("]}\n");
+}
+
+// --scene-clicks: OnMouseDown per click on the resident scene; one JSON line per click.
+static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float, 6>>& clicks, float impact_radius, bool one_event)
+{
+    paired_scene(eng, {});
+    const std::vector<Vector3> cloud = lattice_cloud();
     for (size_t q = 0; q < clicks.size(); ++q)
     {
         const Vector3 o(clicks[q][0], clicks[q][1], clicks[q][2]), d(clicks[q][3], clicks[q][4], clicks[q][5]);
@@ -448,39 +487,11 @@ static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float
     }
 }
 
-static std::vector<Vector3> lattice_cloud()
-{
-    // the 26 directions of the 3 x 3 x 3 lattice, unit length (double arithmetic, narrowed): the sphere point cloud
-    std::vector<Vector3> cloud;
-    for (int i = -1; i <= 1; ++i) for (int j = -1; j <= 1; ++j) for (int k = -1; k <= 1; ++k)
-    {
-        if (!i && !j && !k) continue;
-        const double l = std::sqrt((double)(i * i + j * j + k * k));
-        cloud.emplace_back((float)(i / l), (float)(j / l), (float)(k / l));
-    }
-    return cloud;
-}
-
 // --body-clicks: OnMouseDownBodies per click on the posed scene; one JSON line per click.
 static void body_clicks(FractureEngine& eng, const std::vector<std::array<float, 6>>& clicks, const std::vector<std::pair<int, Matrix>>& poses,
                         float impact_radius, bool radial, bool one_event)
 {
-    const uint32_t n0 = eng.CompoundFromLastEvent();
-    std::vector<uint32_t> off;
-    for (uint32_t p = 0; p < n0; p += 2) off.push_back(p);
-    off.push_back(n0);
-    const int rc = surtr_scene_set_compounds(eng.Raw(), (uint32_t)off.size() - 1u, off.data());
-    if (rc) throw Error(rc, "surtr_scene_set_compounds");
-    if (!poses.empty())
-    {
-        std::vector<Matrix> world(off.size() - 1);
-        for (const auto& p : poses)
-        {
-            if (p.first < 0 || (size_t)p.first >= world.size()) throw Error(SURTR_E_INVALID, "--scene-poses: no such compound");
-            world[(size_t)p.first] = p.second;
-        }
-        eng.SetPoses(world);
-    }
+    paired_scene(eng, poses);
     const std::vector<Vector3> cloud = lattice_cloud();
     for (size_t q = 0; q < clicks.size(); ++q)
     {
@@ -498,20 +509,7 @@ static void body_clicks(FractureEngine& eng, const std::vector<std::array<float,
         for (size_t i = 0; i < body.size(); ++i) printf("%s%d", i ? ", " : "", (int)body[i]);
         printf("], \"compounds_hit\": [");
         for (size_t i = 0; i < hitc.size(); ++i) printf("%s%d", i ? ", " : "", hitc[i]);
-        printf("], \"compounds_made\": [");
-        for (size_t i = 0; i < made.size(); ++i) printf("%s%d", i ? ", " : "", made[i]);
-        printf("], \"table\": [");
-        for (size_t i = 0; i < table.size(); ++i) printf("%s%u", i ? ", " : "", table[i]);
-        printf("], \"poses\": [");
-        for (size_t c = 0; c < world.size(); ++c)
-        {
-            printf("%s[", c ? ", " : "");
-            for (int k = 0; k < 16; ++k) printf("%s%.9g", k ? ", " : "", world[c].m[k]);
-            printf("]");
-        }
-        printf("], \"mass\": [");
-        for (size_t i = 0; i < bm.size(); ++i) printf("%s%.17g", i ? ", " : "", bm[i].mass);
-        printf("]}\n");
+        print_made_and_scene(made, table, world, bm);
         init_compounds(eng, q, made);
     }
 }
@@ -519,22 +517,7 @@ static void body_clicks(FractureEngine& eng, const std::vector<std::array<float,
 // --impacts: OnImpacts with every sphere of the list on the posed scene of --body-clicks; one JSON line for the frame.
 static void impacts_frame(FractureEngine& eng, const std::vector<std::array<float, 4>>& spheres, const std::vector<std::pair<int, Matrix>>& poses, bool one_event)
 {
-    const uint32_t n0 = eng.CompoundFromLastEvent();
-    std::vector<uint32_t> off;
-    for (uint32_t p = 0; p < n0; p += 2) off.push_back(p);
-    off.push_back(n0);
-    const int rc = surtr_scene_set_compounds(eng.Raw(), (uint32_t)off.size() - 1u, off.data());
-    if (rc) throw Error(rc, "surtr_scene_set_compounds");
-    if (!poses.empty())
-    {
-        std::vector<Matrix> world(off.size() - 1);
-        for (const auto& p : poses)
-        {
-            if (p.first < 0 || (size_t)p.first >= world.size()) throw Error(SURTR_E_INVALID, "--scene-poses: no such compound");
-            world[(size_t)p.first] = p.second;
-        }
-        eng.SetPoses(world);
-    }
+    paired_scene(eng, poses);
     const std::vector<Vector3> cloud = lattice_cloud();
     std::vector<Impact> in, acted;
     float rmax = 0.f;
@@ -552,20 +535,7 @@ static void impacts_frame(FractureEngine& eng, const std::vector<std::array<floa
         for (size_t k = 0; k < acted[i].compounds.size(); ++k) printf("%s%d", k ? ", " : "", acted[i].compounds[k]);
         printf("]");
     }
-    printf("], \"compounds_made\": [");
-    for (size_t i = 0; i < made.size(); ++i) printf("%s%d", i ? ", " : "", made[i]);
-    printf("], \"table\": [");
-    for (size_t i = 0; i < table.size(); ++i) printf("%s%u", i ? ", " : "", table[i]);
-    printf("], \"poses\": [");
-    for (size_t c = 0; c < world.size(); ++c)
-    {
-        printf("%s[", c ? ", " : "");
-        for (int k = 0; k < 16; ++k) printf("%s%.9g", k ? ", " : "", world[c].m[k]);
-        printf("]");
-    }
-    printf("], \"mass\": [");
-    for (size_t i = 0; i < bm.size(); ++i) printf("%s%.17g", i ? ", " : "", bm[i].mass);
-    printf("]}\n");
+    print_made_and_scene(made, table, world, bm);
     init_compounds(eng, 0, made);
 }
 

@@ -662,6 +662,67 @@ std::vector<int> FractureEngine::PickImpact(const Vector3& origin, const Vector3
     return PickImpact(origin, dir, args, pieceCompound);
 }
 
+// DoFracture's cloud (:1911-1915): every point scaled by the radius, then moved to the impact; flat, three floats per point.
+std::vector<float> FractureEngine::placed_cloud(const std::vector<Vector3>& spherePointCloud, float radius, const Vector3& position)
+{
+    std::vector<Vector3> cloud = spherePointCloud;
+    for (auto& v : cloud)
+    {
+        v.x *= radius; v.y *= radius; v.z *= radius;
+        v.x += position.x; v.y += position.y; v.z += position.z;
+    }
+    return flat_points(cloud);
+}
+
+// The end of every ExecuteFractureRoutine: the regrouping (sizes, then the compounds; a call without bodies leaves nb at one), the
+// refit, the flagged check, the commit.  -> the compounds made.
+std::vector<int> FractureEngine::regroup_refit_commit(const char* what, const std::function<int(uint32_t*, uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*)>& regroup)
+{
+    uint32_t np = 0, nc = 0, nb = 1;
+    check(regroup(&np, &nc, nullptr, nullptr, &nb, nullptr), what);
+    std::vector<uint32_t> off((size_t)np + nb + 1), body(nb + 1);
+    std::vector<int32_t> piece(np + 1);
+    check(regroup(&np, &nc, off.data(), piece.data(), &nb, body.data()), what);
+    check(surtr_event_refit(ctx_), "surtr_event_refit");
+    check(surtr_event_counts(ctx_, &counts_), "surtr_event_counts");
+    flagged_ = FlaggedUnits();
+    flagged_.n_failed = counts_.n_failed;
+    if (counts_.n_failed && !allow_flagged_)
+        throw Error(SURTR_E_TOPOLOGY, "ExecuteFractureRoutine: the event flagged " + std::to_string(counts_.n_failed) + " unit(s); nothing was committed");
+    uint32_t n = 0, first = 0, n_new = 0;
+    check(surtr_scene_commit(ctx_, nc, off.data(), piece.data(), &n, &first, &n_new, nullptr), "surtr_scene_commit");
+    n_pieces_ = n;
+    std::vector<int> made(n_new);
+    for (uint32_t k = 0; k < n_new; ++k) made[k] = (int)(first + k);
+    return made;
+}
+
+// The loop of one-compound routines of OnMouseDown / OnMouseDownBodies, in DESCENDING number: a commit moves only the compounds above its
+// target, and those have been dealt with.
+std::vector<int> FractureEngine::fracture_descending(const std::vector<int>& hit, float maxAxisScale, const FractureArgs& args,
+                                                     const std::vector<Vector3>& spherePointCloud)
+{
+    std::vector<int> made;
+    for (auto it = hit.rbegin(); it != hit.rend(); ++it)
+    {
+        for (int& c : made) --c;      // (the compounds made so far sit above every target still to come: each moves down by one)
+        const std::vector<int> more = ExecuteFractureRoutine(*it, {}, maxAxisScale, args, spherePointCloud);
+        made.insert(made.end(), more.begin(), more.end());
+    }
+    return made;
+}
+
+// Count-then-fill of a byte mask: call(cap, &n, bytes).
+std::vector<uint8_t> FractureEngine::two_call_mask(const char* what, const std::function<int(uint32_t, uint32_t*, uint8_t*)>& call)
+{
+    uint32_t n = 0;
+    check(call(0, &n, nullptr), what);
+    std::vector<uint8_t> mask(n + 1);
+    check(call(n, &n, mask.data()), what);
+    mask.resize(n);
+    return mask;
+}
+
 std::vector<int> FractureEngine::ExecuteFractureRoutine(int compound, const std::vector<Matrix>& world, float maxAxisScale, const FractureArgs& args,
                                                         const std::vector<Vector3>& spherePointCloud)
 {
@@ -681,13 +742,7 @@ std::vector<int> FractureEngine::ExecuteFractureRoutine(int compound, const std:
     const float s2 = maxAxisScale * 2.f;
     SetRefittingPointLimit(args.RefittingPointLimit);
     PlacePattern(Vector3(s2, s2, s2), args.ImpactPosition);
-    std::vector<Vector3> cloud = spherePointCloud;
-    for (auto& v : cloud)
-    {
-        v.x *= args.ImpactRadius; v.y *= args.ImpactRadius; v.z *= args.ImpactRadius;
-        v.x += args.ImpactPosition.x; v.y += args.ImpactPosition.y; v.z += args.ImpactPosition.z;
-    }
-    const std::vector<float> fc = flat_points(cloud);
+    const std::vector<float> fc = placed_cloud(spherePointCloud, args.ImpactRadius, args.ImpactPosition);
     const float org[3] = {args.ImpactPosition.x, args.ImpactPosition.y, args.ImpactPosition.z};
     // the pieces of the compound out of the sphere are kept whole
     std::vector<uint8_t> mask(m, 0);
@@ -699,30 +754,15 @@ std::vector<int> FractureEngine::ExecuteFractureRoutine(int compound, const std:
         std::vector<float> pos(3 * (size_t)nv + 3); std::vector<uint32_t> no(nv + 1); std::vector<int32_t> nbr(nh + 1);
         check(surtr_download_piece(ctx_, p0 + k, 1, &nv, &nh, pos.data(), no.data(), nbr.data()), "surtr_download_piece");
         int out = 0;
-        const int rc = surtr_convex_out_of_sphere(nv, pos.data(), no.data(), nbr.data(), (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, &out);
+        const int rc = surtr_convex_out_of_sphere(nv, pos.data(), no.data(), nbr.data(), (uint32_t)(fc.size() / 3), fc.data(), org, args.ImpactRadius, &out);
         if (rc) throw Error(rc, std::string("surtr_convex_out_of_sphere: ") + surtr_strerror(rc));
         mask[k] = out ? 1 : 0; any = any || out;
     }
     check(surtr_scene_fracture_event(ctx_, (uint32_t)compound, 0, n_cells_, any ? mask.data() : nullptr, 0u, &counts_), "surtr_scene_fracture_event");
-    uint32_t np = 0, nc = 0;
-    check(surtr_event_regroup(ctx_, args.PartialFracture ? 1 : 0, (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, &np, &nc, nullptr, nullptr),
-          "surtr_event_regroup");
-    std::vector<uint32_t> off(np + 2);
-    std::vector<int32_t> piece(np + 1);
-    check(surtr_event_regroup(ctx_, args.PartialFracture ? 1 : 0, (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, &np, &nc, off.data(), piece.data()),
-          "surtr_event_regroup");
-    check(surtr_event_refit(ctx_), "surtr_event_refit");
-    check(surtr_event_counts(ctx_, &counts_), "surtr_event_counts");
-    flagged_ = FlaggedUnits();
-    flagged_.n_failed = counts_.n_failed;
-    if (counts_.n_failed && !allow_flagged_)
-        throw Error(SURTR_E_TOPOLOGY, "ExecuteFractureRoutine: the event flagged " + std::to_string(counts_.n_failed) + " unit(s); nothing was committed");
-    uint32_t n = 0, first = 0, n_new = 0;
-    check(surtr_scene_commit(ctx_, nc, off.data(), piece.data(), &n, &first, &n_new, nullptr), "surtr_scene_commit");
-    n_pieces_ = n;
-    std::vector<int> made(n_new);
-    for (uint32_t k = 0; k < n_new; ++k) made[k] = (int)(first + k);
-    return made;
+    const int partial = args.PartialFracture ? 1 : 0;
+    return regroup_refit_commit("surtr_event_regroup", [&](uint32_t* np, uint32_t* nc, uint32_t* off, int32_t* piece, uint32_t*, uint32_t*) {
+        return surtr_event_regroup(ctx_, partial, (uint32_t)(fc.size() / 3), fc.data(), org, args.ImpactRadius, np, nc, off, piece);
+    });
 }
 
 static std::vector<uint32_t> compound_numbers(const std::vector<int>& compounds, const char* who)
@@ -736,17 +776,17 @@ static std::vector<uint32_t> compound_numbers(const std::vector<int>& compounds,
     return out;
 }
 
+std::vector<uint8_t> FractureEngine::outside_mask(const std::vector<uint32_t>& t, const std::vector<float>& fc, const float org[3], float radius)
+{
+    return two_call_mask("surtr_scene_outside", [&](uint32_t cap, uint32_t* n, uint8_t* bytes) {
+        return surtr_scene_outside(ctx_, (uint32_t)t.size(), t.data(), (uint32_t)(fc.size() / 3), fc.data(), org, radius, cap, n, bytes);
+    });
+}
+
 std::vector<uint8_t> FractureEngine::OutsideMask(const std::vector<int>& compounds, const FractureArgs& args, const std::vector<Vector3>& cloud)
 {
-    const std::vector<uint32_t> t = compound_numbers(compounds, "OutsideMask");
-    const std::vector<float> fc = flat_points(cloud);
     const float org[3] = {args.ImpactPosition.x, args.ImpactPosition.y, args.ImpactPosition.z};
-    uint32_t n = 0;
-    check(surtr_scene_outside(ctx_, (uint32_t)t.size(), t.data(), (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, 0, &n, nullptr), "surtr_scene_outside");
-    std::vector<uint8_t> mask(n + 1);
-    check(surtr_scene_outside(ctx_, (uint32_t)t.size(), t.data(), (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, n, &n, mask.data()), "surtr_scene_outside");
-    mask.resize(n);
-    return mask;
+    return outside_mask(compound_numbers(compounds, "OutsideMask"), flat_points(cloud), org, args.ImpactRadius);
 }
 
 std::vector<int> FractureEngine::ExecuteFractureRoutine(const std::vector<int>& compounds, float maxAxisScale, const FractureArgs& args,
@@ -762,38 +802,16 @@ std::vector<int> FractureEngine::ExecuteFractureRoutine(const std::vector<int>& 
     const float s2 = maxAxisScale * 2.f;
     SetRefittingPointLimit(args.RefittingPointLimit);
     PlacePattern(Vector3(s2, s2, s2), args.ImpactPosition);
-    std::vector<Vector3> cloud = spherePointCloud;
-    for (auto& v : cloud)
-    {
-        v.x *= args.ImpactRadius; v.y *= args.ImpactRadius; v.z *= args.ImpactRadius;
-        v.x += args.ImpactPosition.x; v.y += args.ImpactPosition.y; v.z += args.ImpactPosition.z;
-    }
-    const std::vector<float> fc = flat_points(cloud);
+    const std::vector<float> fc = placed_cloud(spherePointCloud, args.ImpactRadius, args.ImpactPosition);
     const float org[3] = {args.ImpactPosition.x, args.ImpactPosition.y, args.ImpactPosition.z};
     std::vector<uint8_t> mask;
-    if (args.PartialFracture) mask = OutsideMask(sorted, args, cloud);
+    if (args.PartialFracture) mask = outside_mask(t, fc, org, args.ImpactRadius);
     const bool any = std::find_if(mask.begin(), mask.end(), [](uint8_t o) { return o != 0; }) != mask.end();
     check(surtr_scene_fracture_bodies(ctx_, (uint32_t)t.size(), t.data(), 0, n_cells_, any ? mask.data() : nullptr, 0u, &counts_), "surtr_scene_fracture_bodies");
     const int partial = args.PartialFracture ? 1 : 0;
-    uint32_t np = 0, nc = 0, nb = 0;
-    check(surtr_event_regroup_bodies(ctx_, partial, (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, &np, &nc, nullptr, nullptr, &nb, nullptr),
-          "surtr_event_regroup_bodies");
-    std::vector<uint32_t> off((size_t)np + nb + 1), body(nb + 1);
-    std::vector<int32_t> piece(np + 1);
-    check(surtr_event_regroup_bodies(ctx_, partial, (uint32_t)cloud.size(), fc.data(), org, args.ImpactRadius, &np, &nc, off.data(), piece.data(), &nb, body.data()),
-          "surtr_event_regroup_bodies");
-    check(surtr_event_refit(ctx_), "surtr_event_refit");
-    check(surtr_event_counts(ctx_, &counts_), "surtr_event_counts");
-    flagged_ = FlaggedUnits();
-    flagged_.n_failed = counts_.n_failed;
-    if (counts_.n_failed && !allow_flagged_)
-        throw Error(SURTR_E_TOPOLOGY, "ExecuteFractureRoutine: the event flagged " + std::to_string(counts_.n_failed) + " unit(s); nothing was committed");
-    uint32_t n = 0, first = 0, n_new = 0;
-    check(surtr_scene_commit(ctx_, nc, off.data(), piece.data(), &n, &first, &n_new, nullptr), "surtr_scene_commit");
-    n_pieces_ = n;
-    std::vector<int> made(n_new);
-    for (uint32_t k = 0; k < n_new; ++k) made[k] = (int)(first + k);
-    return made;
+    return regroup_refit_commit("surtr_event_regroup_bodies", [&](uint32_t* np, uint32_t* nc, uint32_t* off, int32_t* piece, uint32_t* nb, uint32_t* body) {
+        return surtr_event_regroup_bodies(ctx_, partial, (uint32_t)(fc.size() / 3), fc.data(), org, args.ImpactRadius, np, nc, off, piece, nb, body);
+    });
 }
 
 std::vector<int> FractureEngine::OnMouseDown(const Vector3& origin, const Vector3& dir, FractureArgs& args, float maxAxisScale,
@@ -802,15 +820,7 @@ std::vector<int> FractureEngine::OnMouseDown(const Vector3& origin, const Vector
     std::vector<int> hit = PickImpact(origin, dir, args);
     if (hitCompounds) *hitCompounds = hit;
     if (oneEvent) return hit.empty() ? std::vector<int>() : ExecuteFractureRoutine(hit, maxAxisScale, args, spherePointCloud);
-    std::vector<int> made;
-    // descending: a commit moves only the compounds above its target, and those have been dealt with
-    for (auto it = hit.rbegin(); it != hit.rend(); ++it)
-    {
-        for (int& c : made) --c;      // (the compounds made so far sit above every target still to come: each moves down by one)
-        const std::vector<int> more = ExecuteFractureRoutine(*it, {}, maxAxisScale, args, spherePointCloud);
-        made.insert(made.end(), more.begin(), more.end());
-    }
-    return made;
+    return fracture_descending(hit, maxAxisScale, args, spherePointCloud);
 }
 
 void FractureEngine::SetPoses(const std::vector<Matrix>& world)
@@ -949,14 +959,7 @@ std::vector<int> FractureEngine::OnMouseDownBodies(const Vector3& origin, const 
     std::vector<int> hit = PickBodies(origin, dir, args, hitOut, bodyMask);
     if (hitCompounds) *hitCompounds = hit;
     if (oneEvent) return hit.empty() ? std::vector<int>() : ExecuteFractureRoutine(hit, maxAxisScale, args, spherePointCloud);
-    std::vector<int> made;
-    for (auto it = hit.rbegin(); it != hit.rend(); ++it)
-    {
-        for (int& c : made) --c;      // (as in OnMouseDown)
-        const std::vector<int> more = ExecuteFractureRoutine(*it, {}, maxAxisScale, args, spherePointCloud);
-        made.insert(made.end(), more.begin(), more.end());
-    }
-    return made;
+    return fracture_descending(hit, maxAxisScale, args, spherePointCloud);
 }
 
 std::vector<int> FractureEngine::ExecuteFractureRoutine(const std::vector<Impact>& impacts, float maxAxisScale, const FractureArgs& args,
@@ -980,13 +983,7 @@ std::vector<int> FractureEngine::ExecuteFractureRoutine(const std::vector<Impact
         scale3.insert(scale3.end(), {s2, s2, s2});
         shift3.insert(shift3.end(), {im.position.x, im.position.y, im.position.z});
         rad.push_back(im.radius);
-        std::vector<Vector3> cloud = spherePointCloud;
-        for (auto& v : cloud)
-        {
-            v.x *= im.radius; v.y *= im.radius; v.z *= im.radius;
-            v.x += im.position.x; v.y += im.position.y; v.z += im.position.z;
-        }
-        const std::vector<float> one = flat_points(cloud);
+        const std::vector<float> one = placed_cloud(spherePointCloud, im.radius, im.position);
         fc.insert(fc.end(), one.begin(), one.end()); soff.push_back((uint32_t)(fc.size() / 3));
     }
     {
@@ -1000,35 +997,15 @@ std::vector<int> FractureEngine::ExecuteFractureRoutine(const std::vector<Impact
     if (fc.empty()) fc.assign(3, 0.f);
     std::vector<uint8_t> mask;
     if (args.PartialFracture)
-    {
-        uint32_t n = 0;
-        check(surtr_scene_outside_impacts(ctx_, K, toff.data(), t.data(), soff.data(), fc.data(), shift3.data(), rad.data(), 0, &n, nullptr), "surtr_scene_outside_impacts");
-        mask.resize(n + 1);
-        check(surtr_scene_outside_impacts(ctx_, K, toff.data(), t.data(), soff.data(), fc.data(), shift3.data(), rad.data(), n, &n, mask.data()), "surtr_scene_outside_impacts");
-        mask.resize(n);
-    }
+        mask = two_call_mask("surtr_scene_outside_impacts", [&](uint32_t cap, uint32_t* n, uint8_t* bytes) {
+            return surtr_scene_outside_impacts(ctx_, K, toff.data(), t.data(), soff.data(), fc.data(), shift3.data(), rad.data(), cap, n, bytes);
+        });
     const bool any = std::find_if(mask.begin(), mask.end(), [](uint8_t o) { return o != 0; }) != mask.end();
     check(surtr_scene_fracture_impacts(ctx_, K, toff.data(), t.data(), 0, n_cells_, any ? mask.data() : nullptr, 0u, &counts_), "surtr_scene_fracture_impacts");
     const int partial = args.PartialFracture ? 1 : 0;
-    uint32_t np = 0, nc = 0, nb = 0;
-    check(surtr_event_regroup_impacts(ctx_, partial, K, soff.data(), fc.data(), shift3.data(), rad.data(), &np, &nc, nullptr, nullptr, &nb, nullptr),
-          "surtr_event_regroup_impacts");
-    std::vector<uint32_t> off((size_t)np + nb + 1), body(nb + 1);
-    std::vector<int32_t> piece(np + 1);
-    check(surtr_event_regroup_impacts(ctx_, partial, K, soff.data(), fc.data(), shift3.data(), rad.data(), &np, &nc, off.data(), piece.data(), &nb, body.data()),
-          "surtr_event_regroup_impacts");
-    check(surtr_event_refit(ctx_), "surtr_event_refit");
-    check(surtr_event_counts(ctx_, &counts_), "surtr_event_counts");
-    flagged_ = FlaggedUnits();
-    flagged_.n_failed = counts_.n_failed;
-    if (counts_.n_failed && !allow_flagged_)
-        throw Error(SURTR_E_TOPOLOGY, "ExecuteFractureRoutine: the event flagged " + std::to_string(counts_.n_failed) + " unit(s); nothing was committed");
-    uint32_t n = 0, first = 0, n_new = 0;
-    check(surtr_scene_commit(ctx_, nc, off.data(), piece.data(), &n, &first, &n_new, nullptr), "surtr_scene_commit");
-    n_pieces_ = n;
-    std::vector<int> made(n_new);
-    for (uint32_t k = 0; k < n_new; ++k) made[k] = (int)(first + k);
-    return made;
+    return regroup_refit_commit("surtr_event_regroup_impacts", [&](uint32_t* np, uint32_t* nc, uint32_t* off, int32_t* piece, uint32_t* nb, uint32_t* body) {
+        return surtr_event_regroup_impacts(ctx_, partial, K, soff.data(), fc.data(), shift3.data(), rad.data(), np, nc, off, piece, nb, body);
+    });
 }
 
 std::vector<int> FractureEngine::OnImpacts(const std::vector<Impact>& spheres, const FractureArgs& args, float maxAxisScale,

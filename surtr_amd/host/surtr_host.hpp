@@ -10,6 +10,7 @@
 #include <cfloat>
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -391,6 +392,12 @@ private:
     void check(int rc, const char* what);
     std::vector<Fragment> download_fragments(bool render);
     void report_flagged(const std::vector<Fragment>& frags, uint32_t cellBegin, uint32_t cellEnd, const char* what);
+    // what the three ExecuteFractureRoutine share (surtr_host.cpp)
+    static std::vector<float> placed_cloud(const std::vector<Vector3>& spherePointCloud, float radius, const Vector3& position);
+    std::vector<int> regroup_refit_commit(const char* what, const std::function<int(uint32_t*, uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*)>& regroup);
+    std::vector<int> fracture_descending(const std::vector<int>& hit, float maxAxisScale, const FractureArgs& args, const std::vector<Vector3>& spherePointCloud);
+    std::vector<uint8_t> two_call_mask(const char* what, const std::function<int(uint32_t, uint32_t*, uint8_t*)>& call);
+    std::vector<uint8_t> outside_mask(const std::vector<uint32_t>& t, const std::vector<float>& fc, const float org[3], float radius);
     bool allow_flagged_ = false;
     FlaggedUnits flagged_;
     surtr_ctx* ctx_ = nullptr;
