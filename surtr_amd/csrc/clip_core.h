@@ -228,6 +228,92 @@ __device__ __forceinline__ int side_of(float s)
     return m > 0.f ? 1 : (m < 0.f ? -1 : 0);
 }
 
+// ---- The plane loops "test one point against the cell's planes, in order, up to the first plane that cuts it"  ----
+// The plane table is wave-uniform and lives in LDS; the point is the lane's.  Written as `for (k) { ...; if (cut) break; }` the
+// loop costs one LDS round trip per plane with nothing else in flight, and every bool a lane carries from plane to plane
+// (done / live / clear) becomes a 64-bit mask in scalar registers that the one scalar unit of the CU updates for every wave.
+// Here the planes come in chunks of C: all of a chunk's reads are issued before the first use, the body is selects on
+// integers in vector registers, and the wave asks once per chunk whether every lane has its plane.
+//   * Inside a chunk the planes are taken LAST TO FIRST and each result overwrites the one before: what is left is the first
+//     plane of the chunk with the property, with one select per plane and no "done" to carry.  A chunk merges into the lane's
+//     result with a min, so a plane past the lane's first cutting plane contributes nothing.
+//   * The last chunk of a cell whose plane count is no multiple of C reads plane F - 1 again in its spare places (a clamped
+//     index: no padded table, no mask).  The copy has the property exactly when plane F - 1 has, at a later place, so neither
+//     the overwrite nor the min ever prefers it.
+// The arithmetic is plane_dist's and the two thresholds of ComparePlanePoint, as in the loops these replace.
+#ifndef SURTR_PLANE_CHUNK
+#define SURTR_PLANE_CHUNK 4u         // the first-cut form in the record clipper (wave_clip.h): a float4 per plane in flight
+#endif
+#ifndef SURTR_PLANE_CHUNK_GEN
+#define SURTR_PLANE_CHUNK_GEN 2u     // the same in the general clipper, whose kernels sit at their register limit
+#endif
+#ifndef SURTR_PLANE_CHUNK_P1
+#define SURTR_PLANE_CHUNK_P1 2u      // the P1 form: a plane and its margin, seven registers per plane, in a kernel held to 72
+#endif
+#define SURTR_PLANE_NONE 0x100u     // "no plane of this chunk": above every plane index and every NEVER value, also after + k0
+
+__device__ __forceinline__ uint32_t umin32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+
+// First-cut form.  The first plane q in [q0, F) with side_of(plane_dist(planes[q], x, y, z)) < 0 (SURTR_NEVER: none); every
+// plane before it with side_of == 0 is handed to on_zero(q), in ascending order.  (side_of(s) < 0 <=> s >= 1e-10f;
+// side_of(s) == 0 <=> !(|s| >= 1e-10f), which holds for a NaN as side_of's own comparisons do.)  In-plane points are rare:
+// the chunks only find out whether the lane has one before its cutting plane, and a lane that has walks its planes again.
+template <uint32_t C, class ZF>
+__device__ __forceinline__ uint32_t planes_first_cut(const float4* planes, const uint32_t q0, const uint32_t F, const float x, const float y, const float z, ZF&& on_zero)
+{
+    uint32_t f = SURTR_NEVER, zf = SURTR_NEVER;
+    for (uint32_t k0 = q0; k0 < F; k0 += C)
+    {
+        float4 pl[C];
+#pragma unroll
+        for (uint32_t c = 0; c < C; ++c) pl[c] = planes[umin32(k0 + c, F - 1u)];
+        uint32_t fc = SURTR_PLANE_NONE, zc = SURTR_PLANE_NONE;
+#pragma unroll
+        for (uint32_t c = C; c-- > 0u;)
+        {
+            const float s = plane_dist(pl[c], x, y, z);
+            fc = s >= 1.0e-10f ? c : fc;
+            zc = !(fabsf(s) >= 1.0e-10f) ? c : zc;
+        }
+        f = umin32(f, k0 + fc); zf = umin32(zf, k0 + zc);
+        if (__all(f != SURTR_NEVER)) break;
+    }
+    if (zf < f)
+        for (uint32_t q = zf; q < F && q < f; ++q)
+            if (side_of(plane_dist(planes[q], x, y, z)) == 0) on_zero(q);
+    return f;
+}
+
+// P1 form (prep_sorted.h).  For a point, the radius of its ball and mag = |x| + |y| + |z|, against planes [0, F) and their
+// margins (Shared::pmar): f = the first plane with s >= 1e-10f (NEVER: none); inplane = the point lies in a plane (|s| < 1e-10f)
+// before that one; clear = every plane up to and including that one has |s| above the ball's margin.  Lanes with !active only
+// ride along (their results mean nothing).  Requires F <= NEVER.
+template <uint32_t C, uint32_t NEVER>
+__device__ __forceinline__ void planes_first_cut_ball(const float4* planes, const float4* pmar, const uint32_t F, const float x, const float y, const float z,
+                                                      const float rad, const float mag, const bool active, uint32_t& f_out, bool& inplane_out, bool& clear_out)
+{
+    uint32_t f = NEVER, zf = NEVER, nf = NEVER;      // first plane: that cuts, that the point lies in, that is not far
+    for (uint32_t k0 = 0; k0 < F; k0 += C)
+    {
+        float4 pl[C], mk[C];
+#pragma unroll
+        for (uint32_t c = 0; c < C; ++c) { const uint32_t k = umin32(k0 + c, F - 1u); pl[c] = planes[k]; mk[c] = pmar[k]; }
+        uint32_t fc = SURTR_PLANE_NONE, zc = SURTR_PLANE_NONE, nc = SURTR_PLANE_NONE;
+#pragma unroll
+        for (uint32_t c = C; c-- > 0u;)
+        {
+            const float s = plane_dist(pl[c], x, y, z);
+            const float margin = __builtin_fmaf(rad, mk[c].x, __builtin_fmaf(mk[c].z, mag, mk[c].y));      // (a bound with slack: contraction is welcome)
+            fc = s >= 1.0e-10f ? c : fc;
+            zc = fabsf(s) < 1.0e-10f ? c : zc;
+            nc = fabsf(s) > margin ? nc : c;
+        }
+        f = umin32(f, k0 + fc); zf = umin32(zf, k0 + zc); nf = umin32(nf, k0 + nc);
+        if (__all(!active | (f != NEVER))) break;
+    }
+    f_out = f; inplane_out = zf < f; clear_out = (nf > f) | (nf == NEVER);
+}
+
 // Size of the launched group and its wave count (kernels for small solids run one wave per task).
 __device__ __forceinline__ uint32_t group_size() { return blockDim.x; }
 __device__ __forceinline__ uint32_t group_waves() { return blockDim.x >> SURTR_LSH; }
@@ -1283,13 +1369,7 @@ __device__ __attribute__((always_inline)) inline int clip_planes(Topo<TT>& T, co
                 {
                     // the first later plane that clips the new vertex, and those it lies in before that
                     const float nx = T.pos[3 * fresh], ny = T.pos[3 * fresh + 1], nz = T.pos[3 * fresh + 2];
-                    uint32_t f = SURTR_NEVER;
-                    for (uint32_t q = k + 1u; q < F; ++q)
-                    {
-                        const int cq = side_of(plane_dist(sh.planes[q], nx, ny, nz));
-                        if (cq < 0) { f = q; break; }
-                        if (cq == 0) atomicAdd(&sh.nzero[q], 1u);
-                    }
+                    const uint32_t f = planes_first_cut<SURTR_PLANE_CHUNK_GEN>(sh.planes, k + 1u, F, nx, ny, nz, [&](uint32_t q) { atomicAdd(&sh.nzero[q], 1u); });
                     T.fc[fresh] = (uint8_t)f;
                     if (T.zmode) T.gcomp[fresh] = 2;
                 }

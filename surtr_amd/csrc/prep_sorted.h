@@ -46,6 +46,8 @@ struct SortedRings
 // (conservative margins: prepass_select, A0)
 // k0: the first plane to look at (the enclosing sphere of the level above was wholly on the kept side of the planes before it);
 // kstop: the plane the test stopped at -- the first one the sphere is not wholly on the kept side of (F: none).
+// (A plain loop: every lane has its own sphere and its own k0, so the table reads are per lane.  The chunked form of
+// clip_core.h's plane loops was measured here with two planes in flight: 0.527 -> 0.529 ms for the kernel, not kept.)
 __device__ __forceinline__ uint32_t ps_sphere_fc(const Shared& sh, const uint32_t F, const float4 sp, const uint32_t k0, uint32_t& kstop)
 {
     const float mag = fabsf(sp.x) + fabsf(sp.y) + fabsf(sp.z) + sp.w;
@@ -216,29 +218,34 @@ __device__ __attribute__((always_inline)) inline void prepass_select_sorted(cons
     //      faces) stays strictly on its side of every plane up to its first clipping plane is dropped here, the others go to P2 ----
     constexpr uint32_t GPW = SURTR_LANES / SURTR_SB;      // groups per wave-load
     const uint32_t nWork = (nUnd + GPW - 1u) / GPW;
-    for (uint32_t wb = w; wb < nWork; wb += nw)
+    // The group of a wave-load comes from und[], its vertex from posr_s[]: two dependent loads.  They are asked for ahead of
+    // the plane loop that hides them: the group two wave-loads ahead, the vertex one ahead.
+    auto und_at = [&](uint32_t wb) -> uint32_t {          // the lane's group of wave-load wb (0xFFFFFFFF: none)
+        const uint32_t sub = wb * GPW + l / SURTR_SB;
+        return sub < nUnd ? (uint32_t)und[sub] : 0xFFFFFFFFu;
+    };
+    auto vert_of = [&](uint32_t g) -> uint32_t {          // its sorted vertex (0xFFFFFFFF: none)
+        const uint32_t i = g * SURTR_SB + (l % SURTR_SB);
+        return (g != 0xFFFFFFFFu && i < V) ? i : 0xFFFFFFFFu;
+    };
+    const uint32_t wu = SURTR_UNIFORM(w);                 // (a scalar: the loop over wave-loads branches on it)
+    uint32_t i_nx = vert_of(und_at(wu));
+    uint32_t g_nx2 = und_at(wu + nw);
+    float4 pr_nx = in.posr_s[i_nx != 0xFFFFFFFFu ? i_nx : 0u];
+    for (uint32_t wb = wu; wb < nWork; wb += nw)
     {
         const uint32_t sub = wb * GPW + l / SURTR_SB;
-        const bool okg = sub < nUnd;
-        const uint32_t i = (okg ? (uint32_t)und[sub] : 0u) * SURTR_SB + (l % SURTR_SB);
-        const bool valid = okg && i < V;
-        const float4 pr = in.posr_s[valid ? i : 0u];
+        const uint32_t i = i_nx;
+        const bool valid = i != 0xFFFFFFFFu;
+        const float4 pr = pr_nx;
+        i_nx = vert_of(g_nx2);
+        g_nx2 = und_at(wb + 2u * nw);
+        pr_nx = in.posr_s[i_nx != 0xFFFFFFFFu ? i_nx : 0u];
         const float mag = fabsf(pr.x) + fabsf(pr.y) + fabsf(pr.z);
         // (starting the loop at the plane the group's sphere test stopped at was measured: +-0 -- the band lies ON the early planes)
-        uint32_t f = PS_NEVER, z = 0u;
-        bool done = !valid, clear = true;
-        for (uint32_t k = 0; k < F; ++k)
-        {
-            if (__all(done)) break;
-            const float4 mk = sh.pmar[k];
-            const float s = plane_dist(sh.planes[k], pr.x, pr.y, pr.z);
-            const bool cut = s >= 1.0e-10f, zz = fabsf(s) < 1.0e-10f, live = !done;
-            const bool far = fabsf(s) > __builtin_fmaf(pr.w, mk.x, __builtin_fmaf(mk.z, mag, mk.y));      // (a bound with slack: contraction is welcome)
-            clear = clear & (far | !live);
-            z |= (live & zz) ? 0x80u : 0u;
-            f = (live & cut) ? k : f;
-            done = done | cut;
-        }
+        uint32_t f; bool inpl, clear;
+        planes_first_cut_ball<SURTR_PLANE_CHUNK_P1, PS_NEVER>(sh.planes, sh.pmar, F, pr.x, pr.y, pr.z, pr.w, mag, valid, f, inpl, clear);
+        const uint32_t z = inpl ? 0x80u : 0u;
         const uint32_t at = sub * SURTR_SB + (l % SURTR_SB);
         if (valid) { if (at < kCap) vfc[at] = (uint8_t)(f | z); else vfc_g[at] = (uint8_t)(f | z); }
         const bool never = valid && f == PS_NEVER;

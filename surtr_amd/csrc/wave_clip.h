@@ -746,13 +746,8 @@ __device__ __attribute__((always_inline)) inline int wc_planes(LT& W, const uint
             const float inv = 1.f / (sb - sa);
             const float nx = (pa.x * sb - pb.x * sa) * inv, ny = (pa.y * sb - pb.y * sa) * inv, nz = (pa.z * sb - pb.z * sa) * inv;
             g.cpos[ux] = make_float4(nx, ny, nz, 0.f);
-            uint32_t f = SURTR_NEVER;
-            for (uint32_t q = k + 1u; q < F; ++q)
-            {
-                const int cq = side_of(plane_dist(W.planes[q], nx, ny, nz));
-                if (cq < 0) { f = q; break; }
-                if (cq == 0) { if (q < 32u) myz0 |= 1u << q; else myz1 |= 1u << (q - 32u); }
-            }
+            const uint32_t f = planes_first_cut<SURTR_PLANE_CHUNK>(W.planes, k + 1u, F, nx, ny, nz,
+                                                                   [&](uint32_t q) { if (q < 32u) myz0 |= 1u << q; else myz1 |= 1u << (q - 32u); });
             // the record but for its slots 0 and 1, which the walks that end on X and start from X write
             wc_st32(B, 4u * ux + 2u, u | ((f | (3u << 8)) << 16));
             nnow[keepn + t] = (uint16_t)X;
