@@ -673,7 +673,7 @@ int surtr_scene_fracture_impacts_async(surtr_ctx* ctx, uint32_t n_impacts, const
  * buffers kept in the context, which are then swapped in; the derived data of the whole scene is rebuilt.  From the second commit
  * of a scene of steady size on, surtr_upload_stats reports 0 allocations.
  * SURTR_E_STATE: no scene event; the event failed; the event was committed already; the resident pieces were replaced or
- * transformed, or the compound table set, since the event.  SURTR_E_INVALID: the compounds do not cover pieces 0 .. n-1 exactly once
+ * transformed, the compound table set, or the scene edited (surtr_scene_remove / _append / _cull), since the event.  SURTR_E_INVALID: the compounds do not cover pieces 0 .. n-1 exactly once
  * (or nothing would be left).  On any error the scene is unchanged.
  * After surtr_scene_fracture_bodies: every target is erased, with its pose; the other compounds stay first, in their old order;
  * the returned compounds (all bodies', as surtr_event_regroup_bodies gave them) are appended in order, the skipped pieces of any
@@ -717,6 +717,8 @@ int surtr_scene_commit_times(surtr_ctx* ctx, float* gather_ms, float* derive_ms)
  *                             compounds it makes get the identity -- the event ran on baked, world-space pieces, which is what
  *                             InitCompound(compound, false) without a translate does (:1874-1875).  On any commit error the poses
  *                             are unchanged, as the scene is.
+ *   surtr_scene_remove / _append / _cull: every surviving compound keeps its pose and moves down with it, an appended compound gets
+ *                             the pose given with it (scene upkeep, below); on any error the poses are unchanged.
  * surtr_scene_get_poses: count-then-fill as surtr_scene_get_compounds (cap = the matrices world has room for).
  * surtr_scene_apply_pose: a pose that is bit for bit the identity matrix does nothing and forgets nothing; any other is exactly
  * surtr_scene_transform_compound(compound, n, that matrix n times) followed by pose := identity (the derived data is rebuilt, the
@@ -834,6 +836,67 @@ int surtr_pieces_hulls_dev(surtr_ctx* ctx, void* dev_records, size_t records_byt
  * small; some but not all arrays NULL is SURTR_E_INVALID). */
 int surtr_event_hulls(surtr_ctx* ctx, uint32_t* n, surtr_hull* records, uint32_t* n_polys, surtr_hull_polygon* polys, uint32_t* n_idx, uint16_t* idx);
 int surtr_pieces_hulls(surtr_ctx* ctx, uint32_t* n, surtr_hull* records, uint32_t* n_polys, surtr_hull_polygon* polys, uint32_t* n_idx, uint16_t* idx);
+
+/* ---- scene upkeep: world bounds per body; remove, append and cull bodies (upkeep_dev.hip) ---- */
+/* BOUNDS.  What a solver's broad phase, a renderer's culling and a kill volume ask every frame: the world-space box of every body,
+ * taken on the device from the resident pieces and the poses.  set 0 = Mesh, 1 = Convex.  For body c with float pose W the box is the
+ * componentwise min / max over the positions surtr_scene_apply_pose(c) would write for its pieces: the arithmetic of
+ * surtr_transform_pieces in float, operation for operation (one function computes both).  A body whose pose is bit for bit the
+ * identity (or a scene without poses) gives the box of its resident positions, as apply_pose then rewrites nothing.  min and max are
+ * exact and associative: the result does not depend on how the reduction is arranged (plain stores and wave reductions, no atomics);
+ * results compare equal as numbers, -0 and +0 may differ.  Each of the three coordinates is taken by itself: one that is not finite
+ * sets SURTR_BOUNDS_NONFINITE and takes no part, so lo / hi cover the finite ones (lo = FLT_MAX, hi = -FLT_MAX on an axis without any).
+ * The per-piece boxes of surtr_pieces_derived (SURTR_DERIVED_BOX) are body-frame boxes: these are not boxes of those. */
+typedef struct surtr_bounds { float lo[3]; float hi[3]; uint32_t n_vertices; uint32_t status; } surtr_bounds;   /* 32 bytes */
+#define SURTR_BOUNDS_NONFINITE 1u   /* some coordinate of the body is not finite; lo / hi then cover the finite ones only */
+/* One record per compound into dev_body (device memory, body_cap_bytes >= 32 * n_compounds) and, with dev_piece_or_null, the same
+ * record per resident piece (piece_cap_bytes >= 32 * n_pieces), each piece under its body's pose.  Two launches on the context's
+ * stream, no host synchronisation: one workgroup per piece, then one wave per body over its contiguous piece records.  The float
+ * poses (64 bytes per compound) are brought to the device by the first call after the poses or the table change.  Without a piece
+ * buffer the piece records go to a buffer of the context that is reallocated (which waits for the device) only when the scene has
+ * more pieces than ever before.  SURTR_E_STATE without resident pieces, SURTR_E_CAPACITY when a buffer is too small; nothing is
+ * written in either case. */
+int surtr_scene_bounds_dev(surtr_ctx* ctx, int set, void* dev_body, size_t body_cap_bytes, void* dev_piece_or_null, size_t piece_cap_bytes);
+/* Host form, synchronous, count-then-fill as surtr_scene_mass: the records of the compounds. */
+int surtr_scene_bounds(surtr_ctx* ctx, int set, uint32_t* n, surtr_bounds* out);
+
+/* EDITS.  The set of bodies changes without a solid leaving HBM: one gather of the kept pieces into the spare buffers of
+ * surtr_scene_commit, a swap, and the derived data of the whole scene again -- the commit's own path (the layout code is shared).
+ * From the second edit of a scene of steady size on, surtr_upload_stats reports 0 allocations.
+ * State rules, for surtr_scene_remove, surtr_scene_append and a surtr_scene_cull that removes:
+ *   the pieces move:          a surtr_scene_commit after an edit is SURTR_E_STATE, as after a transform;
+ *   the last event:           its fragments stay downloadable, as after a commit; its `outside` mask and its compound numbers are
+ *                             forgotten (surtr_event_regroup after an edit sees an event without a mask);
+ *   poses:                    every surviving compound keeps its pose and moves down with it; appended compounds get the pose given;
+ *   on any error:             the scene, the poses and the table are unchanged, bit for bit;
+ *   surtr_set_events_in_flight and a non-default stream behave as for the commit.
+ *
+ * surtr_scene_remove: compounds[n] in any order, each in range and named once, else SURTR_E_INVALID; removing every body is
+ * SURTR_E_INVALID, as a commit that keeps nothing is.  The surviving pieces keep their order, and so do the surviving compounds.
+ * src (may be NULL; room for the resident pieces): the old resident piece of every new piece.  *n_pieces = the new count. */
+int surtr_scene_remove(surtr_ctx* ctx, uint32_t n, const uint32_t* compounds, uint32_t* n_pieces, int32_t* src_or_null);
+/* surtr_scene_append: n_bodies >= 1 new compounds go to the back (push_back); body b owns the new pieces
+ * [body_piece_off[b], body_piece_off[b + 1]) (ascending from 0, no empty body).  The eight arrays are those of surtr_upload_pieces
+ * for the new pieces alone.  No existing piece is uploaded again.  world_or_null: 16 floats per new body, rigid as
+ * surtr_scene_set_poses demands (else SURTR_E_INVALID); NULL: the identity.  Existing poses stay; a scene without a pose table gets
+ * one only if a pose arrives that is not bit for bit the identity.  The new pieces are vetted exactly as an upload vets them -- the
+ * host checks of surtr_upload_pieces, then the link check on the device, run on the pieces where they are staged, before the scene
+ * is touched: the same faults give the same codes, but unlike a refused upload a refused append leaves the scene as it was.
+ * *first_new_compound = the number of the first appended compound. */
+int surtr_scene_append(surtr_ctx* ctx, uint32_t n_bodies, const uint32_t* body_piece_off, const uint32_t* mvo, const float* mpos, const uint32_t* moff,
+                       const int32_t* mnbr, const uint32_t* cvo, const float* cpos, const uint32_t* coff, const int32_t* cnbr,
+                       const float* world_or_null, uint32_t* first_new_compound);
+/* surtr_scene_cull: marks, on the device, the bodies a solver drops, and with apply != 0 removes them (surtr_scene_remove's path).
+ * reason[c]: SURTR_CULL_LIGHT when the body's surtr_scene_mass record (set, density) has status == 0 and mass <= min_mass -- the
+ * reference's gate 1e-4 of Src/Surtr.cpp:228 turned into a removal rule; SURTR_CULL_OUTSIDE when keep_box6_or_null (lo xyz, hi xyz;
+ * a NaN in it is SURTR_E_INVALID) is given, the body's bounds of the CONVEX set have status == 0 and its box is disjoint from the
+ * keep box: for some k, hi[k] < keep.lo[k] or lo[k] > keep.hi[k].  Masses and bounds stay on the device; one lane per body marks;
+ * only the reason bytes come back.  Count-then-fill: reason == NULL returns *n_compounds only; with it, *n_compounds must hold its
+ * capacity (SURTR_E_CAPACITY and the count when too small).  *n_removed = the bodies removed (0 without apply).  If every body is
+ * marked, nothing is removed, the reasons are still filled and the call is SURTR_E_INVALID. */
+enum { SURTR_CULL_LIGHT = 1, SURTR_CULL_OUTSIDE = 2 };
+int surtr_scene_cull(surtr_ctx* ctx, int set, float density, float min_mass, const float* keep_box6_or_null, int apply,
+                     uint32_t* n_compounds, uint8_t* reason, uint32_t* n_removed);
 
 #ifdef __cplusplus
 }

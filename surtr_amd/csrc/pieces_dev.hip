@@ -277,25 +277,17 @@ __global__ void k_piece_row_s(uint32_t V, uint32_t n, const uint32_t* __restrict
     row_s[i] = r;
 }
 
-// Poly::Transform (Src/Poly.cpp:580-585): Position = XMVector3TransformCoord(Position, XMMatrixTranspose(matrix)).
-// XMVector3TransformCoord (DirectXMath, not in the reference tree): r = z*M.r[2] + M.r[3]; r = y*M.r[1] + r;
-// r = x*M.r[0] + r; result = r.xyz / r.w -- with M = the transpose, M.r[k][c] = world[4*c + k].
-// Vertices [v0, V) of pieces p0 ..: world holds the matrix of piece p0 first.
+// Poly::Transform (Src/Poly.cpp:580-585) of vertices [v0, V) of pieces p0 ..: world holds the matrix of piece p0 first.  The
+// arithmetic is transform_coord's (surtr_ctx.h).
 __global__ void k_transform(uint32_t V, uint32_t n, const uint32_t* __restrict__ vo, const float* __restrict__ world, float* __restrict__ pos,
                             uint32_t v0, uint32_t p0)
 {
     const uint32_t v = v0 + blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= V) return;
     const float* W = world + 16 * (size_t)(piece_of(vo, n, v) - p0);
-    const float x = pos[3 * (size_t)v], y = pos[3 * (size_t)v + 1], z = pos[3 * (size_t)v + 2];
-    float r[4];
-    for (int c = 0; c < 4; ++c)
-    {
-        float t = z * W[4 * c + 2] + W[4 * c + 3];
-        t = y * W[4 * c + 1] + t;
-        r[c] = x * W[4 * c] + t;
-    }
-    pos[3 * (size_t)v] = r[0] / r[3]; pos[3 * (size_t)v + 1] = r[1] / r[3]; pos[3 * (size_t)v + 2] = r[2] / r[3];
+    float r[3];
+    transform_coord(W, pos[3 * (size_t)v], pos[3 * (size_t)v + 1], pos[3 * (size_t)v + 2], r);
+    pos[3 * (size_t)v] = r[0]; pos[3 * (size_t)v + 1] = r[1]; pos[3 * (size_t)v + 2] = r[2];
 }
 
 // Fragments of the last event -> piece buffers.  One workgroup per kept fragment and set (blockIdx = 2*piece + set).
@@ -371,6 +363,32 @@ int derive_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, const std::v
     // the rings in sorted space
     hipLaunchKernelGGL(k_piece_iperm, gridV, blk, 0, st, V, n, S.vo, S.perm, S.iperm);
     hipLaunchKernelGGL(k_piece_row_s, gridV, blk, 0, st, V, n, S.vo, S.perm, S.loff, S.llen, S.nbr, S.tri, S.iperm, S.row_s);
+    HIPCHK(hipGetLastError());
+    return SURTR_OK;
+}
+
+// What a host upload checks of one set before anything is copied; ho: the first ring entry of every piece (n + 1).
+int host_offsets(uint32_t n, const uint32_t* vo, const uint32_t* off, std::vector<uint32_t>& ho)
+{
+    if (vo[0] != 0) return SURTR_E_INVALID;
+    for (uint32_t p = 0; p < n; ++p)
+    {
+        const uint32_t a = vo[p], b = vo[p + 1];
+        if (b < a || b - a < 4 || b - a >= (1u << 24)) return SURTR_E_INVALID;     // the pre-pass packs (vertex, plane) in 32 bits
+        if (off[b] < off[a]) return SURTR_E_INVALID;
+    }
+    ho.resize(n + 1);
+    for (uint32_t p = 0; p <= n; ++p) ho[p] = off[vo[p]];
+    return SURTR_OK;
+}
+
+// k_piece_check with `check` on over one set of solids that lie by themselves (offsets from 0), as derive_set runs it on an upload:
+// llen, dup and the context's error word are written, nothing else.  surtr_scene_append vets its staged pieces with it.
+int vet_solids(surtr_ctx* ctx, uint32_t n, uint32_t V, uint32_t H, const uint32_t* vo, const uint32_t* loff, const int32_t* nbr, uint32_t* llen, uint8_t* dup)
+{
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipMemsetAsync(dup, 0, (size_t)n + 1, st));
+    hipLaunchKernelGGL(k_piece_check, dim3((V + 255) / 256), dim3(256), 0, st, V, n, vo, loff, nbr, llen, 1u, ctx->d_upload_err.p, dup, H);
     HIPCHK(hipGetLastError());
     return SURTR_OK;
 }
@@ -466,19 +484,8 @@ int surtr_upload_pieces(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const f
     (void)hipSetDevice(ctx->device);
     Timer timer(ctx);
     ctx->n_pieces = 0;
-    std::vector<uint32_t> mho(n + 1), cho(n + 1);
-    for (int set = 0; set < 2; ++set)
-    {
-        const uint32_t* vo = set ? cvo : mvo; const uint32_t* off = set ? coff : moff;
-        if (vo[0] != 0) return SURTR_E_INVALID;
-        for (uint32_t p = 0; p < n; ++p)
-        {
-            const uint32_t a = vo[p], b = vo[p + 1];
-            if (b < a || b - a < 4 || b - a >= (1u << 24)) return SURTR_E_INVALID;     // the pre-pass packs (vertex, plane) in 32 bits
-            if (off[b] < off[a]) return SURTR_E_INVALID;
-        }
-        for (uint32_t p = 0; p <= n; ++p) (set ? cho : mho)[p] = off[vo[p]];
-    }
+    std::vector<uint32_t> mho, cho;
+    if (host_offsets(n, mvo, moff, mho) || host_offsets(n, cvo, coff, cho)) return SURTR_E_INVALID;
     hipStream_t st = ctx->stream;
     HIPCHK(hipStreamSynchronize(st));       // an event may still be reading the pieces
     if (!ctx->d_upload_err) { if (ctx->d_upload_err.grow(ctx, 4)) return SURTR_E_HIP; ++ctx->upload_allocs; }

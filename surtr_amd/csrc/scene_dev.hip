@@ -25,25 +25,25 @@
 #include "surtr_ctx.h"
 
 using namespace pieces;
+using scene::IDENTITY; using scene::rigid_pose; using scene::SolidsIn;
 
 namespace {
 
 // What piece p of the new scene is made from, per set s (0 = Mesh, 1 = Convex): src[p] >= 0 an old resident piece, -(f + 1)
-// fragment f; sv / sh its first vertex / ring entry in its source (the old set, or the arena), dv / dh in the new set
-// (n + 1 entries: the last is the total).
+// fragment f (or staged piece f of an append); sv / sh its first vertex / ring entry in its source (the old set, or the arena / the
+// staged set), dv / dh in the new set (n + 1 entries: the last is the total).  The device copy of scene::Layout.
 struct GatherTab { const int32_t* src; const uint32_t* sv[2]; const uint32_t* sh[2]; const uint32_t* dv[2]; const uint32_t* dh[2]; };
-struct SolidsIn { const float* pos; const uint32_t* loff; const int32_t* nbr; };
 struct SolidsOut { float* pos; uint32_t* loff; int32_t* nbr; };
 
 // One workgroup per (new piece, set): positions and rings are copied, ring offsets rebased; the last piece writes the closing
 // sentinel.  Plain stores to disjoint ranges, no atomics.
-__global__ __launch_bounds__(SURTR_WG) void k_scene_gather(uint32_t n, GatherTab T, Arena A, SolidsIn old0, SolidsIn old1, SolidsOut new0, SolidsOut new1)
+__global__ __launch_bounds__(SURTR_WG) void k_scene_gather(uint32_t n, GatherTab T, SolidsIn other0, SolidsIn other1, SolidsIn old0, SolidsIn old1, SolidsOut new0, SolidsOut new1)
 {
     const uint32_t p = blockIdx.x >> 1, set = blockIdx.x & 1u;
     if (p >= n) return;
     const bool frag = T.src[p] < 0;
-    const SolidsIn O = set ? old1 : old0; const SolidsOut D = set ? new1 : new0;
-    const float* spos = frag ? A.pos : O.pos; const uint32_t* sloff = frag ? A.loff : O.loff; const int32_t* snbr = frag ? A.nbr : O.nbr;
+    const SolidsIn O = frag ? (set ? other1 : other0) : (set ? old1 : old0); const SolidsOut D = set ? new1 : new0;
+    const float* spos = O.pos; const uint32_t* sloff = O.loff; const int32_t* snbr = O.nbr;
     const uint32_t sv = T.sv[set][p], sh = T.sh[set][p], dv = T.dv[set][p], dh = T.dh[set][p];
     const uint32_t nv = T.dv[set][p + 1] - dv, nh = T.dh[set][p + 1] - dh;
     for (uint32_t i = threadIdx.x; i < 3u * nv; i += group_size()) D.pos[3 * (size_t)dv + i] = spos[3 * (size_t)sv + i];
@@ -106,26 +106,6 @@ bool valid_table(uint32_t n_compounds, const uint32_t* off, uint32_t n_pieces)
     return true;
 }
 
-const float IDENTITY[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
-
-// Rigid: finite, last row exactly (0, 0, 0, 1), max |A^T A - I| <= 1e-4, det A > 0; in double from the floats.
-bool rigid_pose(const float* W)
-{
-    for (int i = 0; i < 16; ++i) if (!(std::fabs(W[i]) <= 3.4028235e38f)) return false;
-    if (W[12] != 0.f || W[13] != 0.f || W[14] != 0.f || W[15] != 1.f) return false;
-    double A[3][3];
-    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) A[r][k] = (double)W[4 * r + k];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
-        {
-            const double g = A[0][i] * A[0][j] + A[1][i] * A[1][j] + A[2][i] * A[2][j] - (i == j ? 1.0 : 0.0);
-            if (!(std::fabs(g) <= 1e-4)) return false;
-        }
-    const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
-                       A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
-    return det > 0.0;
-}
-
 // The event of every scene entrance.  Impact i owns compounds[target_off[i] .. target_off[i + 1]), all checked by the caller; the
 // one-compound and the bodies entrance are one "impact" over the plain placement.  The pairs are impact-major, then target-major in
 // the order given, then cell-major over the target's pieces, as surtr_fracture_event takes them: every target's fragments come out as
@@ -168,6 +148,89 @@ int scene_event(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, 
 }
 
 } // namespace
+
+namespace scene {
+
+const float IDENTITY[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+
+// Rigid: finite, last row exactly (0, 0, 0, 1), max |A^T A - I| <= 1e-4, det A > 0; in double from the floats.
+bool rigid_pose(const float* W)
+{
+    for (int i = 0; i < 16; ++i) if (!(std::fabs(W[i]) <= 3.4028235e38f)) return false;
+    if (W[12] != 0.f || W[13] != 0.f || W[14] != 0.f || W[15] != 1.f) return false;
+    double A[3][3];
+    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) A[r][k] = (double)W[4 * r + k];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+        {
+            const double g = A[0][i] * A[0][j] + A[1][i] * A[1][j] + A[2][i] * A[2][j] - (i == j ? 1.0 : 0.0);
+            if (!(std::fabs(g) <= 1e-4)) return false;
+        }
+    const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+                       A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+    return det > 0.0;
+}
+
+int regather(surtr_ctx* ctx, const Layout& L, const SolidsIn other[2], std::vector<float>&& pose, std::chrono::steady_clock::time_point* gathered)
+{
+    hipStream_t st = ctx->stream;
+    const std::vector<int32_t>& src = L.src;
+    const std::vector<uint32_t>* sv = L.sv; const std::vector<uint32_t>* sh = L.sh; const std::vector<uint32_t>* dv = L.dv; const std::vector<uint32_t>* dh = L.dh;
+    const uint32_t n = (uint32_t)src.size();
+    // ---- spare buffers, tables, gather
+    for (int s = 0; s < 2; ++s)
+    {
+        auto& B = ctx->spare[s];
+        if (grow_pieces(ctx, B.pos, 3 * (size_t)dv[s][n] + 3) || grow_pieces(ctx, B.loff, (size_t)dv[s][n] + 1) || grow_pieces(ctx, B.nbr, (size_t)dh[s][n] + 1) ||
+            grow_pieces(ctx, B.vo, n + 1))
+            return SURTR_E_HIP;
+    }
+    if (grow_pieces(ctx, ctx->d_commit_src, n) || grow_pieces(ctx, ctx->d_commit_tab, (size_t)8 * (n + 1))) return SURTR_E_HIP;
+    if (!ctx->d_upload_err) { if (ctx->d_upload_err.grow(ctx, 4)) return SURTR_E_HIP; ++ctx->upload_allocs; }
+    HIPCHK(hipMemsetAsync(ctx->d_upload_err, 0, 4, st));
+    uint32_t* d = ctx->d_commit_tab; const size_t w = (size_t)n + 1;
+    GatherTab T{ctx->d_commit_src, {d, d + w}, {d + 2 * w, d + 3 * w}, {d + 4 * w, d + 5 * w}, {d + 6 * w, d + 7 * w}};
+    HIPCHK(hipMemcpyAsync(ctx->d_commit_src, src.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    for (int s = 0; s < 2; ++s)
+    {
+        HIPCHK(hipMemcpyAsync((void*)T.sv[s], sv[s].data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((void*)T.sh[s], sh[s].data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((void*)T.dv[s], dv[s].data(), w * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((void*)T.dh[s], dh[s].data(), w * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->spare[s].vo, dv[s].data(), w * 4, hipMemcpyHostToDevice, st));
+    }
+    PieceSet& M = ctx->mset; PieceSet& C = ctx->cset;
+    hipLaunchKernelGGL(k_scene_gather, dim3(2 * n), dim3(SURTR_WG), 0, st, n, T, other[0], other[1], SolidsIn{M.pos, M.loff, M.nbr}, SolidsIn{C.pos, C.loff, C.nbr},
+                       SolidsOut{ctx->spare[0].pos, ctx->spare[0].loff, ctx->spare[0].nbr}, SolidsOut{ctx->spare[1].pos, ctx->spare[1].loff, ctx->spare[1].nbr});
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));      // (the old buffers may be freed below)
+    if (gathered) *gathered = std::chrono::steady_clock::now();
+    // ---- the gathered solids become the resident ones; the buffers they came from are the next gather's spare ones and get the
+    //      same room now, so that a scene of steady size commits (or is edited) without an allocation from the second time on
+    for (int s = 0; s < 2; ++s)
+    {
+        PieceSet& S = s ? C : M; auto& B = ctx->spare[s];
+        std::swap(S.pos, B.pos); std::swap(S.loff, B.loff); std::swap(S.nbr, B.nbr); std::swap(S.vo, B.vo);
+        if (grow_pieces(ctx, B.pos, 3 * (size_t)dv[s][n] + 3) || grow_pieces(ctx, B.loff, (size_t)dv[s][n] + 1) || grow_pieces(ctx, B.nbr, (size_t)dh[s][n] + 1) ||
+            grow_pieces(ctx, B.vo, n + 1))
+            return SURTR_E_HIP;
+    }
+    const std::vector<uint32_t> bo[2] = {sphere_offsets(n, dv[0].data()), sphere_offsets(n, dv[1].data())};
+    for (int s = 0; s < 2; ++s)
+    {
+        PieceSet& S = s ? C : M;
+        int rc = reserve_set(ctx, S, n, dv[s][n], dh[s][n], bo[s][n]);
+        if (rc) return rc;
+        rc = derive_set(ctx, S, n, dv[s][n], bo[s], false);
+        if (rc) return rc;
+    }
+    set_piece_stats(ctx, n, dv[0].data(), dh[0].data(), dv[1].data(), dh[1].data());      // (resets the table and the poses)
+    ctx->scene_off = L.table;
+    ctx->scene_pose = std::move(pose); ctx->scene_dev_stale = true;
+    return SURTR_OK;
+}
+
+} // namespace scene
 
 extern "C" {
 
@@ -457,7 +520,6 @@ int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* com
     (void)hipSetDevice(ctx->device);
     Timer timer(ctx);
     const auto clock0 = std::chrono::steady_clock::now();
-    hipStream_t st = ctx->stream;
     surtr_counts c;
     if (surtr_event_counts(ctx, &c) != SURTR_OK) return SURTR_E_STATE;      // the event failed: nothing to commit
     // ---- everything is checked and laid out before anything is written
@@ -492,24 +554,15 @@ int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* com
         HIPCHK(hipMemcpy(fr.data(), ctx->d_frags, (size_t)c.n_frag * sizeof(FragRec), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(fstat.data(), ctx->d_frag_status, (size_t)c.n_frag * 4, hipMemcpyDeviceToHost));
     }
-    std::vector<int32_t> src;
-    std::vector<uint32_t> sv[2], sh[2], dv[2] = {{0u}, {0u}}, dh[2] = {{0u}, {0u}}, table{0u};
-    auto push_old = [&](uint32_t p) {
-        src.push_back((int32_t)p);
-        for (int s = 0; s < 2; ++s)
-        {
-            sv[s].push_back(ctx->h_vo[s][p]); sh[s].push_back(ctx->h_ho[s][p]);
-            dv[s].push_back(dv[s].back() + (ctx->h_vo[s][p + 1] - ctx->h_vo[s][p])); dh[s].push_back(dh[s].back() + (ctx->h_ho[s][p + 1] - ctx->h_ho[s][p]));
-        }
-    };
+    scene::Layout L;
     // the pieces of every other compound first, in their old order: a compound moves down by the number of targets below it
     for (uint32_t k = 0; k + 1 < ctx->scene_off.size(); ++k)
     {
         if (is_target[k]) continue;
-        for (uint32_t p = ctx->scene_off[k]; p < ctx->scene_off[k + 1]; ++p) push_old(p);
-        table.push_back((uint32_t)src.size());
+        for (uint32_t p = ctx->scene_off[k]; p < ctx->scene_off[k + 1]; ++p) L.push_old(ctx, p);
+        L.table.push_back((uint32_t)L.src.size());
     }
-    const uint32_t first_new = (uint32_t)table.size() - 1u;
+    const uint32_t first_new = (uint32_t)L.table.size() - 1u;
     // then the members of every returned compound: skipped pieces as they stand, fragments from the arena with the Convex the
     // context holds.  A fragment that is no solid, or a flagged one, is left out; a compound left without pieces is not created.
     for (uint32_t k = 0; k < n_compounds; ++k)
@@ -517,74 +570,30 @@ int surtr_scene_commit(surtr_ctx* ctx, uint32_t n_compounds, const uint32_t* com
         for (uint32_t i = compound_off[k]; i < compound_off[k + 1]; ++i)
         {
             const uint32_t q = (uint32_t)compound_piece[i];
-            if (q < n_skip) { push_old(skipped[q]); continue; }
+            if (q < n_skip) { L.push_old(ctx, skipped[q]); continue; }
             const uint32_t f = q - n_skip;
             if (fr[f].mv_n < 4 || fr[f].cv_n < 4 || fstat[f] != 0u) continue;
-            src.push_back(-(int32_t)(f + 1u));
-            sv[0].push_back(fr[f].mv_off); sh[0].push_back(fr[f].mh_off); dv[0].push_back(dv[0].back() + fr[f].mv_n); dh[0].push_back(dh[0].back() + fr[f].mh_n);
-            sv[1].push_back(fr[f].cv_off); sh[1].push_back(fr[f].ch_off); dv[1].push_back(dv[1].back() + fr[f].cv_n); dh[1].push_back(dh[1].back() + fr[f].ch_n);
+            L.push_other(f, 0, fr[f].mv_off, fr[f].mv_n, fr[f].mh_off, fr[f].mh_n);
+            L.push_other(f, 1, fr[f].cv_off, fr[f].cv_n, fr[f].ch_off, fr[f].ch_n);
         }
-        if (src.size() != table.back()) table.push_back((uint32_t)src.size());
+        L.close_compound();
     }
-    const uint32_t n = (uint32_t)src.size();
+    const uint32_t n = (uint32_t)L.src.size();
     if (n == 0) return SURTR_E_INVALID;      // (a scene without a piece: as surtr_pieces_from_event refuses to keep nothing)
-    // ---- spare buffers, tables, gather
-    for (int s = 0; s < 2; ++s)
-    {
-        auto& B = ctx->spare[s];
-        if (grow_pieces(ctx, B.pos, 3 * (size_t)dv[s][n] + 3) || grow_pieces(ctx, B.loff, (size_t)dv[s][n] + 1) || grow_pieces(ctx, B.nbr, (size_t)dh[s][n] + 1) ||
-            grow_pieces(ctx, B.vo, n + 1))
-            return SURTR_E_HIP;
-    }
-    if (grow_pieces(ctx, ctx->d_commit_src, n) || grow_pieces(ctx, ctx->d_commit_tab, (size_t)8 * (n + 1))) return SURTR_E_HIP;
-    if (!ctx->d_upload_err) { if (ctx->d_upload_err.grow(ctx, 4)) return SURTR_E_HIP; ++ctx->upload_allocs; }
-    HIPCHK(hipMemsetAsync(ctx->d_upload_err, 0, 4, st));
-    uint32_t* d = ctx->d_commit_tab; const size_t w = (size_t)n + 1;
-    GatherTab T{ctx->d_commit_src, {d, d + w}, {d + 2 * w, d + 3 * w}, {d + 4 * w, d + 5 * w}, {d + 6 * w, d + 7 * w}};
-    HIPCHK(hipMemcpyAsync(ctx->d_commit_src, src.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    for (int s = 0; s < 2; ++s)
-    {
-        HIPCHK(hipMemcpyAsync((void*)T.sv[s], sv[s].data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync((void*)T.sh[s], sh[s].data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync((void*)T.dv[s], dv[s].data(), w * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync((void*)T.dh[s], dh[s].data(), w * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->spare[s].vo, dv[s].data(), w * 4, hipMemcpyHostToDevice, st));
-    }
-    PieceSet& M = ctx->mset; PieceSet& C = ctx->cset;
-    hipLaunchKernelGGL(k_scene_gather, dim3(2 * n), dim3(SURTR_WG), 0, st, n, T, ctx->arena, SolidsIn{M.pos, M.loff, M.nbr}, SolidsIn{C.pos, C.loff, C.nbr},
-                       SolidsOut{ctx->spare[0].pos, ctx->spare[0].loff, ctx->spare[0].nbr}, SolidsOut{ctx->spare[1].pos, ctx->spare[1].loff, ctx->spare[1].nbr});
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));      // (the old buffers may be freed below)
-    const auto clock1 = std::chrono::steady_clock::now();
-    // ---- the gathered solids become the resident ones; the buffers they came from are the next commit's spare ones and get the
-    //      same room now, so that a scene of steady size commits without an allocation from its second commit on
-    for (int s = 0; s < 2; ++s)
-    {
-        PieceSet& S = s ? C : M; auto& B = ctx->spare[s];
-        std::swap(S.pos, B.pos); std::swap(S.loff, B.loff); std::swap(S.nbr, B.nbr); std::swap(S.vo, B.vo);
-        if (grow_pieces(ctx, B.pos, 3 * (size_t)dv[s][n] + 3) || grow_pieces(ctx, B.loff, (size_t)dv[s][n] + 1) || grow_pieces(ctx, B.nbr, (size_t)dh[s][n] + 1) ||
-            grow_pieces(ctx, B.vo, n + 1))
-            return SURTR_E_HIP;
-    }
-    const std::vector<uint32_t> bo[2] = {sphere_offsets(n, dv[0].data()), sphere_offsets(n, dv[1].data())};
-    for (int s = 0; s < 2; ++s)
-    {
-        PieceSet& S = s ? C : M;
-        int rc = reserve_set(ctx, S, n, dv[s][n], dh[s][n], bo[s][n]);
-        if (rc) return rc;
-        rc = derive_set(ctx, S, n, dv[s][n], bo[s], false);
-        if (rc) return rc;
-    }
     // the poses of the surviving compounds move down with them; what the event made is in world space already (InitCompound(compound, false))
-    std::vector<float> pose = std::move(ctx->scene_pose);
+    std::vector<float> pose = ctx->scene_pose;
     if (!pose.empty())
     {
         for (uint32_t target : targets) pose.erase(pose.begin() + 16 * (size_t)target, pose.begin() + 16 * (size_t)(target + 1u));      // (highest first)
-        for (size_t k = first_new; k + 1 < table.size(); ++k) pose.insert(pose.end(), IDENTITY, IDENTITY + 16);
+        for (size_t k = first_new; k + 1 < L.table.size(); ++k) pose.insert(pose.end(), IDENTITY, IDENTITY + 16);
     }
-    set_piece_stats(ctx, n, dv[0].data(), dh[0].data(), dv[1].data(), dh[1].data());
-    ctx->scene_off = table;
-    ctx->scene_pose = std::move(pose); ctx->scene_dev_stale = true;
+    const SolidsIn arena[2] = {{ctx->arena.pos, ctx->arena.loff, ctx->arena.nbr}, {ctx->arena.pos, ctx->arena.loff, ctx->arena.nbr}};
+    auto clock1 = clock0;
+    {
+        const int rc = scene::regather(ctx, L, arena, std::move(pose), &clock1);
+        if (rc) return rc;
+    }
+    const std::vector<int32_t>& src = L.src; const std::vector<uint32_t>& table = L.table;
     ctx->have_event = true;       // the event's fragments are still in the arena, as after surtr_pieces_from_event
     ctx->frags_of_pieces = false; // (but the pieces they came from have moved)
     if (n_pieces_out) *n_pieces_out = n;

@@ -342,6 +342,13 @@ struct surtr_ctx
     DevBuf<uint32_t> d_piece_comp;       // per resident piece: its compound; then the compound table (n_compounds + 1 offsets)
     struct { DevBuf<float> pos; DevBuf<uint32_t> loff; DevBuf<int32_t> nbr; DevBuf<uint32_t> vo; } spare[2];   // surtr_scene_commit gathers into these, then swaps
     DevBuf<int32_t> d_commit_src; DevBuf<uint32_t> d_commit_tab;      // its gather tables
+    // scene upkeep (upkeep_dev.hip).  The float poses as surtr_scene_bounds reads them, 16 floats per compound, brought up to date
+    // after scene_sync_device has refreshed the tables (which raises scene_posef_stale); empty scene_pose: no copy, every pose the identity
+    DevBuf<float> d_posef; bool scene_posef_stale = true; std::vector<float> h_posef_stage;
+    DevBuf<surtr_bounds> d_bounds_piece;                 // surtr_scene_bounds_dev without a piece buffer of the caller's: the per-piece records
+    DevBuf<char> d_cull;                                 // surtr_scene_cull: mass records, bounds and reason bytes of every compound
+    // surtr_scene_append: the new pieces as the host gave them (offsets from 0 per set), vetted here by k_piece_check before the scene is touched
+    struct { DevBuf<float> pos; DevBuf<uint32_t> loff, llen, vo; DevBuf<int32_t> nbr; DevBuf<uint8_t> dup; } stage[2];
     // surtr_scene_fragments: the tables it lays out on the host (fragment records, cursors, counts, size-class slots, chunk table), kept
     // between calls so that the _async form leaves nothing behind that goes out of scope; the device copy of the last two
     std::vector<uint32_t> h_frag_stage; DevBuf<uint32_t> d_frag_tab;
@@ -452,6 +459,8 @@ struct Timer
 int reserve_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, uint32_t H, uint32_t NB);
 int derive_set(surtr_ctx* ctx, PieceSet& S, uint32_t n, uint32_t V, const std::vector<uint32_t>& bo_h, bool check, uint32_t H = 0xFFFFFFFFu);
 std::vector<uint32_t> sphere_offsets(uint32_t n, const uint32_t* vo);
+int host_offsets(uint32_t n, const uint32_t* vo, const uint32_t* off, std::vector<uint32_t>& ho);
+int vet_solids(surtr_ctx* ctx, uint32_t n, uint32_t V, uint32_t H, const uint32_t* vo, const uint32_t* loff, const int32_t* nbr, uint32_t* llen, uint8_t* dup);
 void set_piece_stats(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const uint32_t* mho, const uint32_t* cvo, const uint32_t* cho);
 int finish_upload(surtr_ctx* ctx, uint32_t n, bool check);
 // Poly::Transform of resident pieces [p0, p0 + n) by world[16 * (p - p0) ..], the derived data again; the other pieces keep their bits
@@ -460,6 +469,22 @@ int transform_range(surtr_ctx* ctx, uint32_t p0, uint32_t n, const float* world)
 // one k_transform per range and set, the derived data once per set
 int transform_ranges(surtr_ctx* ctx, uint32_t n_ranges, const uint32_t* p0, const uint32_t* n, const float* world);
 }
+// Poly::Transform of one position (Src/Poly.cpp:580-585): XMVector3TransformCoord(Position, XMMatrixTranspose(matrix)) with
+// XMVector3TransformCoord (DirectXMath, not in the reference tree): r = z*M.r[2] + M.r[3]; r = y*M.r[1] + r; r = x*M.r[0] + r;
+// result = r.xyz / r.w -- with M = the transpose, M.r[k][c] = W[4*c + k].  k_transform (pieces_dev.hip) writes it, the bounds of
+// surtr_scene_bounds (upkeep_dev.hip) take min / max of it: one function, so that the two agree bit for bit.
+__host__ __device__ static inline void transform_coord(const float* W, float x, float y, float z, float out[3])
+{
+    float r[4];
+    for (int c = 0; c < 4; ++c)
+    {
+        float t = z * W[4 * c + 2] + W[4 * c + 3];
+        t = y * W[4 * c + 1] + t;
+        r[c] = x * W[4 * c] + t;
+    }
+    out[0] = r[0] / r[3]; out[1] = r[1] / r[3]; out[2] = r[2] / r[3];
+}
+
 // The scene's tables as the posed queries (query_dev.hip) and surtr_scene_mass (mass_dev.hip) read them on the device.  Fields only:
 // every translation unit that needs them brings them up to date itself, on the context's stream, when the host's have changed.
 struct SceneDev { const double* pose; const uint32_t* piece_comp; const uint32_t* comp_off; uint32_t n_comp; };
@@ -492,9 +517,44 @@ static inline int scene_sync_device(surtr_ctx* ctx, SceneDev* out)
         HIPCHK(hipMemcpyAsync(ctx->d_pose.p, P.data(), P.size() * 8, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(ctx->d_piece_comp.p, C.data(), C.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         ctx->scene_dev_stale = false;
+        ctx->scene_posef_stale = true;      // (the float poses of surtr_scene_bounds follow on their first use)
     }
     *out = SceneDev{ctx->d_pose.p, ctx->d_piece_comp.p, ctx->d_piece_comp.p + np, nc};
     return SURTR_OK;
+}
+
+// A new resident set laid out on the host from the small tables, and the one gather that makes it (scene_dev.hip): shared by
+// surtr_scene_commit and the scene edits (upkeep_dev.hip).  Piece p of the new set comes from src[p] >= 0, an old resident piece, or
+// from -(k + 1), solid k of the call's other source (the event arena for the commit, the staged pieces for an append); sv / sh: its
+// first vertex / ring entry there, dv / dh in the new set (n + 1 entries: the last is the total); table: the new compound table.
+namespace scene {
+struct SolidsIn { const float* pos; const uint32_t* loff; const int32_t* nbr; };
+struct Layout
+{
+    std::vector<int32_t> src;
+    std::vector<uint32_t> sv[2], sh[2], dv[2] = {{0u}, {0u}}, dh[2] = {{0u}, {0u}}, table{0u};
+    void push_old(const surtr_ctx* ctx, uint32_t p)
+    {
+        src.push_back((int32_t)p);
+        for (int s = 0; s < 2; ++s)
+        {
+            sv[s].push_back(ctx->h_vo[s][p]); sh[s].push_back(ctx->h_ho[s][p]);
+            dv[s].push_back(dv[s].back() + (ctx->h_vo[s][p + 1] - ctx->h_vo[s][p])); dh[s].push_back(dh[s].back() + (ctx->h_ho[s][p + 1] - ctx->h_ho[s][p]));
+        }
+    }
+    void push_other(uint32_t k, int s, uint32_t v0, uint32_t nv, uint32_t h0, uint32_t nh)      // (once per set; src once)
+    {
+        if (s == 0) src.push_back(-(int32_t)(k + 1u));
+        sv[s].push_back(v0); sh[s].push_back(h0); dv[s].push_back(dv[s].back() + nv); dh[s].push_back(dh[s].back() + nh);
+    }
+    void close_compound() { if (src.size() != table.back()) table.push_back((uint32_t)src.size()); }
+};
+// Gathers L into the spare buffers (other[s]: where the src < 0 pieces of set s lie), swaps them in, rebuilds the derived data of the
+// whole scene and installs the table and `pose` (empty: every pose the identity).  Synchronises after the gather (*gathered: when)
+// but not after the derived data: the caller ends with finish_upload.  Nothing of the scene is touched before the swap.
+int regather(surtr_ctx* ctx, const Layout& L, const SolidsIn other[2], std::vector<float>&& pose, std::chrono::steady_clock::time_point* gathered);
+extern const float IDENTITY[16];
+bool rigid_pose(const float* W);
 }
 
 // an event over an explicit pair list with an `outside` mask over all resident pieces (surtr_hip.hip); NULL: no mask

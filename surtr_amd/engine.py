@@ -67,6 +67,11 @@ SCENE_RAY_HIT_DTYPE = np.dtype([("piece", "<i4"), ("status", "<u4"), ("t", "<f4"
 assert SCENE_RAY_HIT_DTYPE.itemsize == 48
 RAY_STARTS_INSIDE, RAY_INVALID = 1, 2
 QUERY_FEW, QUERY_OPEN, QUERY_FLAT, QUERY_LONG = 1, 2, 4, 8
+# surtr_bounds (include/surtr_hip.h), 32 bytes: the world-space box of a body or a piece; the reason bits of scene_cull
+BOUNDS_DTYPE = np.dtype([("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("n_vertices", "<u4"), ("status", "<u4")])
+assert BOUNDS_DTYPE.itemsize == 32
+BOUNDS_NONFINITE = 1
+CULL_LIGHT, CULL_OUTSIDE = 1, 2
 
 
 # the arrays of surtr_pieces_derived, in the order of the SURTR_DERIVED_* enumeration (include/surtr_hip.h)
@@ -867,6 +872,65 @@ class Engine:
     def scene_mass_dev(self, dev_ptr, capacity, set=1, density=10.0):
         self._ck(lib().surtr_scene_mass_dev(self._h, ctypes.c_int(int(set)), ctypes.c_float(density), ctypes.c_void_p(dev_ptr),
                                             ctypes.c_size_t(capacity)))
+
+    # ---- scene upkeep: world bounds per body; remove, append and cull bodies (include/surtr_hip.h, upkeep_dev.hip)
+    def scene_bounds(self, set=1):
+        """surtr_scene_bounds: one BOUNDS_DTYPE record per compound, the world-space box of the body under its pose."""
+        n = ctypes.c_uint32()
+        self._ck(lib().surtr_scene_bounds(self._h, ctypes.c_int(int(set)), ctypes.byref(n), None))
+        out = np.zeros(n.value, BOUNDS_DTYPE)
+        self._ck(lib().surtr_scene_bounds(self._h, ctypes.c_int(int(set)), ctypes.byref(n), _p(out)))
+        return out
+
+    def scene_bounds_dev(self, dev_body, body_capacity, dev_piece=None, piece_capacity=0, set=1):
+        """surtr_scene_bounds_dev: the records of the compounds (and, with dev_piece, of the resident pieces) into device memory, on
+        the context's stream; nothing is read back."""
+        self._ck(lib().surtr_scene_bounds_dev(self._h, ctypes.c_int(int(set)), ctypes.c_void_p(dev_body), ctypes.c_size_t(body_capacity),
+                                              ctypes.c_void_p(dev_piece), ctypes.c_size_t(piece_capacity)))
+
+    def scene_remove(self, compounds):
+        """surtr_scene_remove: erases the listed compounds (any order).  Returns (n_pieces, src): src[p] the old resident piece of
+        new piece p."""
+        t = np.ascontiguousarray(compounds, np.uint32).reshape(-1)
+        n = ctypes.c_uint32()
+        src = np.zeros(int(self.scene_compounds()[-1]) + 1, np.int32)
+        self._ck(lib().surtr_scene_remove(self._h, ctypes.c_uint32(t.shape[0]), _p(t if t.shape[0] else np.zeros(1, np.uint32)), ctypes.byref(n), _p(src)))
+        return n.value, src[:n.value].copy()
+
+    def scene_append(self, bodies, world=None):
+        """surtr_scene_append: bodies is a list of bodies, each a list of pieces {'mesh', 'conv'} (solids as upload_pieces takes
+        them); world: f32[n_bodies, 4, 4] or None (identity).  Returns the number of the first new compound."""
+        off = np.zeros(len(bodies) + 1, np.uint32)
+        off[1:] = np.cumsum([len(b) for b in bodies])
+        flat = [p for b in bodies for p in b]
+        if not flat:
+            raise SurtrError(E_INVALID, "no piece to append")
+        m = pack_solids([p["mesh"] for p in flat])
+        c = pack_solids([p["conv"] for p in flat])
+        w = None if world is None else np.ascontiguousarray(world, np.float32).reshape(-1, 16)
+        if w is not None and w.shape[0] != len(bodies):
+            raise SurtrError(E_INVALID, "%d poses for %d bodies" % (w.shape[0], len(bodies)))
+        first = ctypes.c_uint32()
+        self._ck(lib().surtr_scene_append(self._h, ctypes.c_uint32(len(bodies)), _p(off), _p(m[0]), _p(m[1]), _p(m[2]), _p(m[3]),
+                                          _p(c[0]), _p(c[1]), _p(c[2]), _p(c[3]), _p(w), ctypes.byref(first)))
+        return first.value
+
+    def scene_cull(self, min_mass=1e-4, keep_box=None, set=1, density=10.0, apply=True):
+        """surtr_scene_cull: marks the bodies of mass <= min_mass (CULL_LIGHT) and those whose Convex bounds are disjoint from
+        keep_box = (lo xyz, hi xyz) (CULL_OUTSIDE) on the device and, with apply, removes them.  Returns (reason uint8[n_compounds] as
+        of before the removal, n_removed).  If every body is marked nothing is removed and SurtrError(E_INVALID) carries the reasons
+        in its `reason` attribute."""
+        kb = None if keep_box is None else np.ascontiguousarray(keep_box, np.float32).reshape(6)
+        n, removed = ctypes.c_uint32(), ctypes.c_uint32()
+        args = [self._h, ctypes.c_int(int(set)), ctypes.c_float(density), ctypes.c_float(min_mass), _p(kb)]
+        self._ck(lib().surtr_scene_cull(*args, ctypes.c_int(0), ctypes.byref(n), None, ctypes.byref(removed)))
+        reason = np.zeros(max(n.value, 1), np.uint8)
+        rc = lib().surtr_scene_cull(*args, ctypes.c_int(int(bool(apply))), ctypes.byref(n), _p(reason), ctypes.byref(removed))
+        if rc:
+            e = SurtrError(rc, lib().surtr_last_error(self._h).decode())
+            e.reason = reason[:n.value].copy()
+            raise e
+        return reason[:n.value].copy(), removed.value
 
     def upload_stats(self):
         ms, na = ctypes.c_float(), ctypes.c_uint32()

@@ -17,6 +17,8 @@
 //                 frame (OnImpacts: one overlap query for all of them, a body to the first impact that reaches it).  Without
 //                 --one-event the impacts run one after the other through the several-compound routine; with it through one event,
 //                 one regrouping and one commit.  One JSON line: the compounds each impact acted on, then what --body-clicks prints.
+// --bounds, --cull-mass M [--keep-box lx,ly,lz,hx,hy,hz] (with --body-clicks): after every click, CullBodies and BodyBounds; one more
+//                 JSON line per click ({"upkeep": ...}: reasons, table, bounds).
 // --one-event (with --scene-clicks or --body-clicks): every compound a click hits goes through ONE event, one regrouping and one
 //                 commit (ExecuteFractureRoutine over several compounds) instead of one of each per compound; the JSON is the same.
 // --init-compounds [--init-compounds-obj DIR] (with --scene-clicks or --body-clicks): after each click, InitCompounds on the compounds it
@@ -487,6 +489,39 @@ static void scene_clicks(FractureEngine& eng, const std::vector<std::array<float
     }
 }
 
+// --bounds / --cull-mass M [--keep-box lx,ly,lz,hx,hy,hz] (with --body-clicks): scene upkeep after every click -- CullBodies with the
+// mass threshold (and the keep box), then BodyBounds of the Convex set.  One JSON line per click: the reasons per compound as numbered
+// before the removal, the table after it, and the bounds (lo, hi, vertices, status per compound).
+static bool g_bounds = false, g_cull = false, g_keep = false;
+static float g_cull_mass = 1e-4f, g_keep_box[6] = {0, 0, 0, 0, 0, 0};
+static void upkeep(FractureEngine& eng, size_t q)
+{
+    if (!g_bounds && !g_cull) return;
+    printf("{\"upkeep\": %zu", q);
+    if (g_cull)
+    {
+        const std::pair<Vector3, Vector3> box(Vector3(g_keep_box[0], g_keep_box[1], g_keep_box[2]), Vector3(g_keep_box[3], g_keep_box[4], g_keep_box[5]));
+        const std::vector<uint8_t> why = eng.CullBodies(g_cull_mass, g_keep ? &box : nullptr);
+        printf(", \"reasons\": [");
+        for (size_t i = 0; i < why.size(); ++i) printf("%s%d", i ? ", " : "", (int)why[i]);
+        printf("]");
+    }
+    const std::vector<uint32_t> table = eng.SceneCompounds();
+    printf(", \"table\": [");
+    for (size_t i = 0; i < table.size(); ++i) printf("%s%u", i ? ", " : "", table[i]);
+    printf("]");
+    if (g_bounds)
+    {
+        const std::vector<surtr_bounds> b = eng.BodyBounds(1);
+        printf(", \"bounds\": [");
+        for (size_t i = 0; i < b.size(); ++i)
+            printf("%s[%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %u, %u]", i ? ", " : "", b[i].lo[0], b[i].lo[1], b[i].lo[2], b[i].hi[0], b[i].hi[1], b[i].hi[2],
+                   b[i].n_vertices, b[i].status);
+        printf("]");
+    }
+    printf("}\n");
+}
+
 // --body-clicks: OnMouseDownBodies per click on the posed scene; one JSON line per click.
 static void body_clicks(FractureEngine& eng, const std::vector<std::array<float, 6>>& clicks, const std::vector<std::pair<int, Matrix>>& poses,
                         float impact_radius, bool radial, bool one_event)
@@ -511,6 +546,7 @@ static void body_clicks(FractureEngine& eng, const std::vector<std::array<float,
         for (size_t i = 0; i < hitc.size(); ++i) printf("%s%d", i ? ", " : "", hitc[i]);
         print_made_and_scene(made, table, world, bm);
         init_compounds(eng, q, made);
+        upkeep(eng, q);
     }
 }
 
@@ -564,6 +600,13 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--one-event")) one_event = true;
         else if (!strcmp(argv[i], "--init-compounds")) g_init_compounds = true;
         else if (!strcmp(argv[i], "--hulls")) g_hulls = true;
+        else if (!strcmp(argv[i], "--bounds")) g_bounds = true;
+        else if (!strcmp(argv[i], "--cull-mass") && i + 1 < argc) { g_cull = true; g_cull_mass = (float)atof(argv[++i]); }
+        else if (!strcmp(argv[i], "--keep-box") && i + 1 < argc)
+        {
+            g_keep = sscanf(argv[++i], "%f,%f,%f,%f,%f,%f", g_keep_box, g_keep_box + 1, g_keep_box + 2, g_keep_box + 3, g_keep_box + 4, g_keep_box + 5) == 6;
+            if (!g_keep) { fprintf(stderr, "surtr_harness: --keep-box takes lx,ly,lz,hx,hy,hz\n"); return 2; }
+        }
         else if (!strcmp(argv[i], "--init-compounds-obj") && i + 1 < argc) { g_init_compounds = true; g_init_obj = argv[++i]; }
         else if (!strcmp(argv[i], "--scene-poses") && i + 1 < argc)
         {

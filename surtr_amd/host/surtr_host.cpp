@@ -870,6 +870,62 @@ std::vector<surtr_mass> FractureEngine::BodyMassProperties(int set, float densit
     return out;
 }
 
+std::vector<surtr_bounds> FractureEngine::BodyBounds(int set)
+{
+    uint32_t n = 0;
+    check(surtr_scene_bounds(ctx_, set, &n, nullptr), "surtr_scene_bounds");
+    std::vector<surtr_bounds> out(n);
+    if (n) check(surtr_scene_bounds(ctx_, set, &n, out.data()), "surtr_scene_bounds");
+    return out;
+}
+
+void FractureEngine::RemoveBodies(const std::vector<int>& compounds)
+{
+    std::vector<uint32_t> t;
+    for (int c : compounds)
+    {
+        if (c < 0) throw Error(SURTR_E_INVALID, "RemoveBodies: no such compound");
+        t.push_back((uint32_t)c);
+    }
+    uint32_t n = n_pieces_;
+    check(surtr_scene_remove(ctx_, (uint32_t)t.size(), t.data(), &n, nullptr), "surtr_scene_remove");
+    n_pieces_ = n;
+}
+
+int FractureEngine::AddBodies(const std::vector<Compound>& compoundVec, const std::vector<Matrix>& poses)
+{
+    if (compoundVec.empty()) throw Error(SURTR_E_INVALID, "AddBodies: no compound");
+    if (!poses.empty() && poses.size() != compoundVec.size()) throw Error(SURTR_E_INVALID, "AddBodies: one pose per compound");
+    Flat m, c;
+    std::vector<uint32_t> off(1, 0u);
+    for (const auto& comp : compoundVec)
+    {
+        if (comp.PieceVec.empty()) throw Error(SURTR_E_INVALID, "AddBodies: a compound without pieces");
+        for (const auto& p : comp.PieceVec) { m.add(p.Mesh); c.add(p.Convex); }
+        off.push_back(off.back() + (uint32_t)comp.PieceVec.size());
+    }
+    std::vector<float> w;
+    for (const auto& x : poses) w.insert(w.end(), x.m, x.m + 16);
+    uint32_t first = 0;
+    check(surtr_scene_append(ctx_, (uint32_t)compoundVec.size(), off.data(), m.vert_off.data(), m.pos.data(), m.nbr_off.data(), m.nbr.data(),
+                             c.vert_off.data(), c.pos.data(), c.nbr_off.data(), c.nbr.data(), w.empty() ? nullptr : w.data(), &first), "surtr_scene_append");
+    n_pieces_ += off.back();
+    return (int)first;
+}
+
+std::vector<uint8_t> FractureEngine::CullBodies(float minMass, const std::pair<Vector3, Vector3>* keepBox, bool apply)
+{
+    float box[6] = {};
+    if (keepBox) { box[0] = keepBox->first.x; box[1] = keepBox->first.y; box[2] = keepBox->first.z; box[3] = keepBox->second.x; box[4] = keepBox->second.y; box[5] = keepBox->second.z; }
+    // (minMass < 0: no body is light -- a mass record with status 0 has a positive volume)
+    uint32_t n = 0, removed = 0;
+    check(surtr_scene_cull(ctx_, 1, 10.f, minMass, keepBox ? box : nullptr, 0, &n, nullptr, &removed), "surtr_scene_cull");
+    std::vector<uint8_t> reason(n);
+    check(surtr_scene_cull(ctx_, 1, 10.f, minMass, keepBox ? box : nullptr, apply ? 1 : 0, &n, reason.data(), &removed), "surtr_scene_cull");
+    if (removed) n_pieces_ = SceneCompounds().back();
+    return reason;
+}
+
 std::vector<uint8_t> FractureEngine::OverlapBodies(const Vector3& centre, float radius, float minMass)
 {
     const float sphere[4] = {centre.x, centre.y, centre.z, radius};

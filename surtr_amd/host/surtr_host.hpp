@@ -339,6 +339,21 @@ public:
     // One record per compound in its body frame, added up on the device (surtr_scene_mass): what setMass / setCMassLocalPose /
     // setMassSpaceInertiaTensor take for a body whose pose the solver holds.
     std::vector<surtr_mass> BodyMassProperties(int set, float density = 10.f);
+    // ---- scene upkeep (surtr_scene_bounds / _remove / _append / _cull): what a frame loop does besides clicking ----
+    // BodyBounds: the world-space box of every compound under its pose, taken on the device (set 0 = Mesh, 1 = Convex): a broad
+    // phase's, a renderer's and a kill volume's input.
+    std::vector<surtr_bounds> BodyBounds(int set = 1);
+    // RemoveBodies: erases the listed compounds (any order; one out of range or named twice, or all of them, throws
+    // Error(SURTR_E_INVALID)); the others keep their order and their poses.  No solid leaves the device.
+    void RemoveBodies(const std::vector<int>& compounds);
+    // AddBodies: push_back of new compounds from host pieces, vetted as SetCompound vets them; poses: one per new compound, or empty
+    // for the identity.  Returns the number of the first new compound.  A refused call leaves the scene as it was.
+    int AddBodies(const std::vector<Compound>& compoundVec, const std::vector<Matrix>& poses = {});
+    // CullBodies: removes the bodies of mass <= minMass (Convex set, density 10: the gate of Src/Surtr.cpp:228 as a removal rule;
+    // minMass < 0: none) and, with keepBox = {lo, hi}, those whose Convex bounds are disjoint from it.  Returns the reason bits per
+    // compound as numbered BEFORE the removal (SURTR_CULL_*).  When every body is marked nothing is removed and Error(SURTR_E_INVALID)
+    // is thrown.  apply = false only marks.
+    std::vector<uint8_t> CullBodies(float minMass = 1e-4f, const std::pair<Vector3, Vector3>* keepBox = nullptr, bool apply = true);
     // OnMouseDown's picking with the reference's semantics (:207-233): the ray is cast on the posed scene; a hit sets
     // args.ImpactPosition = hit + dir * args.TargetAdder; with args.RadialMode the compounds whose body mask is 1 for the sphere of
     // radius args.ImpactRadius / 2 are returned (the gate is on the mass of the BODY), else the compound hit.  Ascending.
