@@ -19,6 +19,14 @@
 //                 one regrouping and one commit.  One JSON line: the compounds each impact acted on, then what --body-clicks prints.
 // --bounds, --cull-mass M [--keep-box lx,ly,lz,hx,hy,hz] (with --body-clicks): after every click, CullBodies and BodyBounds; one more
 //                 JSON line per click ({"upkeep": ...}: reasons, table, bounds).
+// --edit-bodies "16 floats;16 floats;16 floats" (with --body-clicks): after the last click, the scene edits a frame loop makes.  First the
+//                 refusals, each caught as surtr::Error and printed with its code on one JSON line: RemoveBodies of a compound past the
+//                 last, AddBodies with one pose for two compounds, TransformCompound with one matrix too few.  Then RemoveBodies of the
+//                 last compound and compound 0; AddBodies of two bodies from the generated mesh (the piece as it was fractured; the piece
+//                 moved by 8 and by 16 along x) under the first two matrices as poses; TransformCompound with the third matrix on the
+//                 pieces of the second new body and the identity on all others.  After each edit one JSON line: the table, the poses, the
+//                 bodies' masses and their bounds.  Last PieceHulls: the hulls of all resident pieces, their polygons and indices, how
+//                 many HullUsable accepts, and an FNV-1a of polygons + indices (as --hulls).
 // --one-event (with --scene-clicks or --body-clicks): every compound a click hits goes through ONE event, one regrouping and one
 //                 commit (ExecuteFractureRoutine over several compounds) instead of one of each per compound; the JSON is the same.
 // --init-compounds [--init-compounds-obj DIR] (with --scene-clicks or --body-clicks): after each click, InitCompounds on the compounds it
@@ -34,6 +42,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <functional>
 #include <array>
 #include <set>
 #include <vector>
@@ -522,9 +531,72 @@ static void upkeep(FractureEngine& eng, size_t q)
     printf("}\n");
 }
 
+// --edit-bodies: RemoveBodies, AddBodies, TransformCompound and PieceHulls on the scene the clicks left (see the head of the file).
+static std::vector<Matrix> g_edit;
+static void print_scene_state(FractureEngine& eng, const char* edit)
+{
+    const std::vector<uint32_t> table = eng.SceneCompounds();
+    const std::vector<Matrix> world = eng.Poses();
+    const std::vector<surtr_mass> bm = eng.BodyMassProperties(1);
+    const std::vector<surtr_bounds> b = eng.BodyBounds(1);
+    printf("{\"edit\": \"%s\", \"table\": [", edit);
+    for (size_t i = 0; i < table.size(); ++i) printf("%s%u", i ? ", " : "", table[i]);
+    printf("], \"poses\": [");
+    for (size_t c = 0; c < world.size(); ++c)
+    {
+        printf("%s[", c ? ", " : "");
+        for (int k = 0; k < 16; ++k) printf("%s%.9g", k ? ", " : "", world[c].m[k]);
+        printf("]");
+    }
+    printf("], \"mass\": [");
+    for (size_t i = 0; i < bm.size(); ++i) printf("%s%.17g", i ? ", " : "", bm[i].mass);
+    printf("], \"bounds\": [");
+    for (size_t i = 0; i < b.size(); ++i)
+        printf("%s[%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %u, %u]", i ? ", " : "", b[i].lo[0], b[i].lo[1], b[i].lo[2], b[i].hi[0], b[i].hi[1], b[i].hi[2],
+               b[i].n_vertices, b[i].status);
+    printf("]}\n");
+}
+
+static void edit_bodies(FractureEngine& eng, const Piece& piece)
+{
+    auto moved = [&](float dx) { Piece p = piece; for (auto& v : p.Mesh) v.Position.x += dx; for (auto& v : p.Convex) v.Position.x += dx; return p; };
+    std::vector<Compound> bodies(2);
+    bodies[0].PieceVec.push_back(piece);
+    bodies[1].PieceVec.push_back(moved(8.f)); bodies[1].PieceVec.push_back(moved(16.f));
+    const std::vector<Matrix> poses(g_edit.begin(), g_edit.begin() + 2);
+    std::vector<uint32_t> table = eng.SceneCompounds();
+    const int nc = (int)table.size() - 1;
+    // the refusals: the layer's exception with the C ABI's code; the scene stays as it was
+    auto code_of = [](const std::function<void()>& call) { try { call(); } catch (const Error& e) { return e.code; } return (int)SURTR_OK; };
+    const int r0 = code_of([&] { eng.RemoveBodies({nc}); });
+    const int r1 = code_of([&] { eng.AddBodies(bodies, std::vector<Matrix>(1, poses[0])); });
+    const int r2 = code_of([&] { eng.TransformCompound(std::vector<Matrix>(table.back() - 1u)); });
+    printf("{\"refused\": {\"remove_out_of_range\": %d, \"add_pose_count\": %d, \"transform_matrix_count\": %d}}\n", r0, r1, r2);
+    print_scene_state(eng, "refused");
+    eng.RemoveBodies({nc - 1, 0});
+    print_scene_state(eng, "remove");
+    const int first = eng.AddBodies(bodies, poses);
+    printf("{\"first_new\": %d}\n", first);
+    print_scene_state(eng, "add");
+    table = eng.SceneCompounds();
+    std::vector<Matrix> world(table.back());
+    for (uint32_t p = table[(size_t)first + 1]; p < table[(size_t)first + 2]; ++p) world[p] = g_edit[2];
+    eng.TransformCompound(world);
+    print_scene_state(eng, "transform");
+    const HullSet h = eng.PieceHulls();
+    unsigned long long fnv = 0xCBF29CE484222325ull;
+    auto eat = [&](const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { fnv ^= b[i]; fnv *= 0x100000001B3ull; } };
+    eat(h.Polygons.data(), h.Polygons.size() * sizeof(surtr_hull_polygon));
+    eat(h.Indices.data(), h.Indices.size() * 2);
+    size_t usable = 0;
+    for (const auto& r : h.Records) usable += HullUsable(r) ? 1 : 0;
+    printf("{\"edit\": \"piece_hulls\", \"hulls\": %zu, \"hull_polygons\": %zu, \"hull_indices\": %zu, \"hulls_usable\": %zu, \"hull_fnv\": \"%016llx\"}\n",
+           h.Records.size(), h.Polygons.size(), h.Indices.size(), usable, fnv);
+}
+
 // --body-clicks: OnMouseDownBodies per click on the posed scene; one JSON line per click.
 static void body_clicks(FractureEngine& eng, const std::vector<std::array<float, 6>>& clicks, const std::vector<std::pair<int, Matrix>>& poses,
-                        float impact_radius, bool radial, bool one_event)
+                        float impact_radius, bool radial, bool one_event, const Piece& piece)
 {
     paired_scene(eng, poses);
     const std::vector<Vector3> cloud = lattice_cloud();
@@ -548,6 +620,7 @@ static void body_clicks(FractureEngine& eng, const std::vector<std::array<float,
         init_compounds(eng, q, made);
         upkeep(eng, q);
     }
+    if (!g_edit.empty()) edit_bodies(eng, piece);
 }
 
 // --impacts: OnImpacts with every sphere of the list on the posed scene of --body-clicks; one JSON line for the frame.
@@ -608,6 +681,23 @@ int main(int argc, char** argv)
             if (!g_keep) { fprintf(stderr, "surtr_harness: --keep-box takes lx,ly,lz,hx,hy,hz\n"); return 2; }
         }
         else if (!strcmp(argv[i], "--init-compounds-obj") && i + 1 < argc) { g_init_compounds = true; g_init_obj = argv[++i]; }
+        else if (!strcmp(argv[i], "--edit-bodies") && i + 1 < argc)
+        {
+            const char* c = argv[++i];
+            while (*c)
+            {
+                Matrix w; int used = 0;
+                for (int k = 0; k < 16; ++k)
+                {
+                    if (sscanf(c, "%f%n", &w.m[k], &used) != 1) { fprintf(stderr, "surtr_harness: --edit-bodies takes three matrices of 16 floats, separated by ;\n"); return 2; }
+                    c += used;
+                    if (*c == ',') ++c;
+                }
+                g_edit.push_back(w);
+                if (*c == ';') ++c;
+            }
+            if (g_edit.size() != 3) { fprintf(stderr, "surtr_harness: --edit-bodies takes three matrices of 16 floats, separated by ;\n"); return 2; }
+        }
         else if (!strcmp(argv[i], "--scene-poses") && i + 1 < argc)
         {
             const char* c = argv[++i];
@@ -699,7 +789,7 @@ int main(int argc, char** argv)
                c.mesh_nbrs, c.conv_verts, c.n_idx);
         if (do_pick) pick(eng, frags, pick_ray, impact_radius);
         if (!clicks.empty()) scene_clicks(eng, clicks, impact_radius, one_event);
-        else if (!bclicks.empty()) body_clicks(eng, bclicks, poses, impact_radius, radial, one_event);
+        else if (!bclicks.empty()) body_clicks(eng, bclicks, poses, impact_radius, radial, one_event, piece);
         else if (!impacts.empty()) impacts_frame(eng, impacts, poses, one_event);
         if (!obj.empty())
         {

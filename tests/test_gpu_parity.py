@@ -205,27 +205,33 @@ def test_repeatable(gpu_engine):
     eng.close()
 
 
-def test_cpp_host_layer_and_harness(gpu_engine, oracle):
-    """The C++ host layer (reference API names over the C ABI) through the headless harness binary."""
+HOST_LAYER_SIZES = {"torus": (256, 100, 60), "blob": (3, 16)}      # torus: cells, nu, nv; blob: subdivision level, cells
+API_SURFACE_SIZES = {"torus": (64, 60, 36)}
+
+
+def check_cpp_host_layer_and_harness(E, oracle, exe, sizes):
+    """The C++ host layer (reference API names over the C ABI) through the headless harness binary `exe`, with engine module E beside
+    it; sizes as HOST_LAYER_SIZES (tests/test_host_cpu.py runs the same on the emulation)."""
     import json as js
     import subprocess
-    exe = host_program("surtr_harness")
+    cells, nu, nv = sizes["torus"]
+    level, blob_cells = sizes["blob"]
     out = js.loads(subprocess.check_output([exe, "--mesh", "cube", "--cells", "8"]).decode().strip().splitlines()[-1])
     sc = scenes.cube_scene(8)
     planes = oracle.place_cells(sc["v012"], sc["scale"], sc["translate"])
     ref = oracle.event([sc["mesh"]], [sc["convex"]], sc["face_off"], planes)
     assert out["fragments"] == ref["frag_ids"].shape[0] and out["mesh_verts"] == ref["mesh_pos"].shape[0]
     assert out["indices"] == ref["idx"].shape[0] and out["conv_verts"] == ref["conv_pos"].shape[0]
-    out = js.loads(subprocess.check_output([exe, "--mesh", "torus", "--cells", "256", "--nu", "100", "--nv", "60"]).decode().strip().splitlines()[-1])
+    out = js.loads(subprocess.check_output([exe, "--mesh", "torus", "--cells", str(cells), "--nu", str(nu), "--nv", str(nv)]).decode().strip().splitlines()[-1])
     from surtr_amd import meshgen
-    sc = scenes.make_scene(*meshgen.bumpy_torus(100, 60), 256)
+    sc = scenes.make_scene(*meshgen.bumpy_torus(nu, nv), cells)
     planes = oracle.place_cells(sc["v012"], sc["scale"], sc["translate"])
     ref = oracle.event([sc["mesh"]], [sc["convex"]], sc["face_off"], planes, threads=8)
     assert out["fragments"] == ref["frag_ids"].shape[0] and out["mesh_verts"] == ref["mesh_pos"].shape[0]
     assert out["indices"] == ref["idx"].shape[0] and out["mesh_nbrs"] == ref["mesh_nbr"].shape[0]
     # rows f2 + f3: a mesh file in (LoadModelData conventions), PrepareFracture end to end (--ach), fragments out as OBJ
     import tempfile
-    v, t = meshgen.blob(3, scale=2.0)
+    v, t = meshgen.blob(level, scale=2.0)
     with tempfile.TemporaryDirectory() as d:
         src, dst = os.path.join(d, "in.obj"), os.path.join(d, "out.obj")
         with open(src, "w") as f:
@@ -233,14 +239,18 @@ def test_cpp_host_layer_and_harness(gpu_engine, oracle):
                 f.write("v %.9g %.9g %.9g\n" % (-a[0], a[1], a[2]))
             for a, b, c in t:
                 f.write("f %d %d %d\n" % (c + 1, b + 1, a + 1))
-        out = js.loads(subprocess.check_output([exe, "--obj-in", src, "--cells", "16", "--ach", "--obj", dst]).decode().strip().splitlines()[-1])
-        rv, rt = gpu_engine.read_obj(src)
-        eng = gpu_engine.Engine(0)
-        sc, c, got = scenes.prepare_fracture(eng, rv, rt, n_cells=16)
+        out = js.loads(subprocess.check_output([exe, "--obj-in", src, "--cells", str(blob_cells), "--ach", "--obj", dst]).decode().strip().splitlines()[-1])
+        rv, rt = E.read_obj(src)
+        eng = E.Engine(0)
+        sc, c, got = scenes.prepare_fracture(eng, rv, rt, n_cells=blob_cells)
         eng.close()
         assert out["fragments"] == c.n_frag and out["mesh_verts"] == c.mesh_verts and out["indices"] == c.n_idx and out["conv_verts"] == c.conv_verts
         text = open(dst).read()
         assert text.count("\no ") + 1 == c.n_frag and text.count("\nf ") == c.n_idx // 3
+
+
+def test_cpp_host_layer_and_harness(gpu_engine, oracle):
+    check_cpp_host_layer_and_harness(gpu_engine, oracle, host_program("surtr_harness"), HOST_LAYER_SIZES)
 
 
 def test_torus_with_ach_convex(gpu_engine, oracle):
@@ -400,16 +410,17 @@ def test_torus_4096_repeat_run_digest(gpu_engine, torus_run):
     eng.close()
 
 
-def test_cpp_api_surface(gpu_engine, oracle):
+def check_cpp_api_surface(E, oracle, exe, sizes):
     """The reference-named C++ API (Poly::ExtractFaces / RenderPolyhedron / Transform / Moments / ClipPolyhedron(polygon3D),
-    Kdop::KdopContainer, GenerateICHNormal) through the harness, every result held against the oracle."""
+    Kdop::KdopContainer, GenerateICHNormal) through the harness binary `exe`, every result held against the oracle; sizes as
+    API_SURFACE_SIZES."""
     import json as js
     import subprocess
     import tempfile
-    exe = host_program("surtr_harness")
+    cells, nu, nv = sizes["torus"]
     with tempfile.TemporaryDirectory() as d:
         dump = os.path.join(d, "api.json")
-        subprocess.check_output([exe, "--mesh", "torus", "--cells", "64", "--nu", "60", "--nv", "36", "--api-dump", dump])
+        subprocess.check_output([exe, "--mesh", "torus", "--cells", str(cells), "--nu", str(nu), "--nv", str(nv), "--api-dump", dump])
         data = js.load(open(dump))
 
     def solid(j):
@@ -475,6 +486,10 @@ def test_cpp_api_surface(gpu_engine, oracle):
         a, b = int(ref2["idx_off"][k]), int(ref2["idx_off"][k + 1])
         assert tk["init"][k]["idx"] == ref2["idx"][a:b].tolist() and tk["init"][k]["nv"] == fragment(ref2, k, "mesh")["pos"].shape[0]
         assert tk["init"][k]["points"] == fragment(ref2, k, "conv")["pos"].shape[0]
+
+
+def test_cpp_api_surface(gpu_engine, oracle):
+    check_cpp_api_surface(gpu_engine, oracle, host_program("surtr_harness"), API_SURFACE_SIZES)
 
 
 # ---- Voronoi cells on the device (row A2) -------------------------------------------------------------------------------

@@ -571,10 +571,10 @@ def run_streams(E, oracle, torch):
     eng.close()
 
 
-def check_harness(E, root):
+def check_harness(E, root, exe=None):
     """surtr_harness --scene-clicks ... --init-compounds --hulls against the Python calls, and without --hulls against the lines the
     harness printed before the flag existed (test_scene_fragments.check_harness states them)."""
-    exe = os.path.join(root, "surtr_amd", "host", "surtr_harness")
+    exe = exe or os.path.join(root, "surtr_amd", "host", "surtr_harness")
     clicks = [([-10.0, 0.3, 0.2], [1.0, 0.0, 0.0]), ([0.3, 0.2, 10.0], [0.0, 0.0, -1.0])]
     arg = ";".join(",".join("%r" % x for x in o + d) for o, d in clicks)
     base = [exe, "--mesh", "cube", "--cells", "8", "--scene-clicks", arg, "--impact-radius", "2.0", "--init-compounds"]

@@ -586,9 +586,9 @@ GPU_CHILD = textwrap.dedent("""
 """)
 
 
-def check_harness(E, root):
+def check_harness(E, root, exe=None):
     """surtr_harness --pick on scene (a) against Engine.pieces_raycast / pieces_overlap, and PickImpact's contract."""
-    exe = os.path.join(root, "surtr_amd", "host", "surtr_harness")
+    exe = exe or os.path.join(root, "surtr_amd", "host", "surtr_harness")
     o, d = [-10.0, 0.3, 0.2], [1.0, 0.0, 0.0]
     p = subprocess.run([exe, "--mesh", "cube", "--cells", "8", "--pick", ",".join("%r" % x for x in o + d), "--impact-radius", "3.0"],
                        capture_output=True, text=True, timeout=120)

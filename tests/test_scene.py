@@ -531,9 +531,9 @@ def python_click(eng, o, d, r, n_cells):
                 table=[int(x) for x in table], mass=[float(x) for x in mass])
 
 
-def check_harness(E, root):
+def check_harness(E, root, exe=None):
     """surtr_harness --scene-clicks (FractureEngine::OnMouseDown) against the same clicks through the Python calls."""
-    exe = os.path.join(root, "surtr_amd", "host", "surtr_harness")
+    exe = exe or os.path.join(root, "surtr_amd", "host", "surtr_harness")
     clicks = [([-10.0, 0.3, 0.2], [1.0, 0.0, 0.0]), ([0.3, 0.2, 10.0], [0.0, 0.0, -1.0])]
     arg = ";".join(",".join("%r" % x for x in o + d) for o, d in clicks)
     p = subprocess.run([exe, "--mesh", "cube", "--cells", "8", "--scene-clicks", arg, "--impact-radius", "2.0"], capture_output=True, text=True, timeout=120)

@@ -551,9 +551,9 @@ def python_one_event_click(eng, o, d, r, n_cells):
                 compounds_made=list(range(first, first + n_new)), table=[int(x) for x in table], mass=[float(x) for x in eng.scene_mass(set=1)["mass"]])
 
 
-def check_harness(E, root):
+def check_harness(E, root, exe=None):
     """surtr_harness --body-clicks ... --radial --one-event against the run without --one-event and against the Python calls."""
-    exe = os.path.join(root, "surtr_amd", "host", "surtr_harness")
+    exe = exe or os.path.join(root, "surtr_amd", "host", "surtr_harness")
     clicks = [([-10.0, 6.3, 0.2], [1.0, 0.0, 0.0]), ([0.3, 0.2, 10.0], [0.0, 0.0, -1.0])]
     arg = ";".join(",".join("%r" % x for x in o + d) for o, d in clicks)
     pose_arg = ";".join("%d:" % c + ",".join("%r" % float(x) for x in W.reshape(-1)) for c, W in ((1, TP.HARNESS_POSE), (3, TP.HARNESS_FAR)))

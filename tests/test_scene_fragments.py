@@ -359,9 +359,9 @@ def fnv1a(*arrays):
     return "%016x" % h
 
 
-def check_harness(E, root):
+def check_harness(E, root, exe=None):
     """Case 14: surtr_harness --scene-clicks ... --init-compounds against the Python calls: totals and hashes of every compound made."""
-    exe = os.path.join(root, "surtr_amd", "host", "surtr_harness")
+    exe = exe or os.path.join(root, "surtr_amd", "host", "surtr_harness")
     clicks = [([-10.0, 0.3, 0.2], [1.0, 0.0, 0.0]), ([0.3, 0.2, 10.0], [0.0, 0.0, -1.0])]
     arg = ";".join(",".join("%r" % x for x in o + d) for o, d in clicks)
     p = subprocess.run([exe, "--mesh", "cube", "--cells", "8", "--scene-clicks", arg, "--impact-radius", "2.0", "--init-compounds"],

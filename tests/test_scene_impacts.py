@@ -502,12 +502,12 @@ def run_dev(E, torch):
     eng.close(); ref.close()
 
 
-def run_harness(E):
+def run_harness(E, exe=None):
     """surtr_harness --impacts ... --one-event against the same line without --one-event (the loop of existing routines), text for
     text.  The scene is --body-clicks' (four bodies of two pieces, body 1 posed, body 3 far away).  The first sphere reaches the
     posed body 1 alone, the second bodies 0 and 2 (so that impact 0's target lies between impact 1's), the third body 2 only, which
     the second has taken: it is dropped (found with scene_overlap on the CPU tier)."""
-    exe = os.path.join(ROOT, "surtr_amd", "host", "surtr_harness")
+    exe = exe or os.path.join(ROOT, "surtr_amd", "host", "surtr_harness")
     pose_arg = ";".join("%d:" % c + ",".join("%r" % float(x) for x in W.reshape(-1)) for c, W in ((1, TP.HARNESS_POSE), (3, TP.HARNESS_FAR)))
     cmd = [exe, "--mesh", "cube", "--cells", "8", "--scene-poses", pose_arg, "--impacts", "-1.0,6.3,0.2,5.0;0.3,0.2,3.2,4.0;-2.5,2.5,0.0,3.0"]
     runs = []

@@ -591,11 +591,11 @@ def run_dev_forms(E, torch):
     eng.close()
 
 
-def check_harness(E, root):
+def check_harness(E, root, exe=None):
     """surtr_harness --body-clicks ... --bounds --cull-mass M --keep-box ... (FractureEngine::CullBodies and BodyBounds after every
     click) against the same clicks, cull and bounds through the Python calls.  The keep box ends below the body that test_scene_poses'
     harness scene parks 20 units up the z axis: the first cull removes it."""
-    exe = os.path.join(root, "surtr_amd", "host", "surtr_harness")
+    exe = exe or os.path.join(root, "surtr_amd", "host", "surtr_harness")
     clicks = [([-10.0, 6.3, 0.2], [1.0, 0.0, 0.0]), ([0.3, 0.2, 10.0], [0.0, 0.0, -1.0])]
     arg = ";".join(",".join("%r" % x for x in o + d) for o, d in clicks)
     pose_arg = ";".join("%d:" % c + ",".join("%r" % float(x) for x in W.reshape(-1)) for c, W in ((1, TSP.HARNESS_POSE), (3, TSP.HARNESS_FAR)))
