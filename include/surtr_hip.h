@@ -204,9 +204,51 @@ int surtr_place_cells(surtr_ctx* ctx, const float scale[3], const float translat
  * surtr_upload_planes) forgets the instances. */
 int surtr_place_cells_impacts(surtr_ctx* ctx, uint32_t n_impacts, const float* scale3, const float* translate3);
 /* Diagnostic, for tests: the placed planes (4 floats each, face after face) of the plain placement (impacts == 0: n_faces planes) or
- * of surtr_place_cells_impacts (impacts != 0: n_impacts * n_faces, instance-major).  Count-then-fill: planes == NULL returns *n only;
+ * of surtr_place_cells_impacts / surtr_place_cells_patterns (impacts != 0: every instance's faces, instance-major).  Count-then-fill: planes == NULL returns *n only;
  * cap = the planes it has room for.  Synchronises the stream. */
 int surtr_download_planes(surtr_ctx* ctx, int impacts, uint32_t cap, uint32_t* n, float* planes);
+
+/* ---- the pattern library: several fracture patterns resident on the device ----
+ * The reference keeps a partial and a general pattern for the whole session and picks one per event (Src/Surtr.cpp:1806-1807, 1887).
+ * The library keeps any number of patterns (face offsets + v012) in device memory beside the installed one, so that a switch of
+ * pattern is a device-to-device copy, and so that every impact of a frame can have a pattern of its own
+ * (surtr_place_cells_patterns).  It belongs to its context.
+ * surtr_pattern_store: copies the installed pattern into the library and returns its id; ids count from 0 in order of storing.
+ *   Works after surtr_upload_pattern, surtr_build_cells and surtr_pattern_select alike.  SURTR_E_STATE: no pattern, or one given as
+ *   planes (surtr_upload_planes: it has no v012 and cannot be placed).  SURTR_E_CAPACITY: more than 0x7FFFFFFF faces or offsets.
+ *   The stored patterns share two grow-only buffers; a growth keeps the patterns already stored bit for bit.
+ * surtr_pattern_count / surtr_pattern_info: how many are stored / the cells and faces of one (either pointer may be NULL).
+ * surtr_pattern_clear: drops every stored pattern (ids start at 0 again) and forgets the instances of surtr_place_cells_patterns;
+ *   the installed pattern, the plain placement and the instances of surtr_place_cells_impacts stay.
+ * surtr_pattern_select: installs stored pattern id as the context's pattern, device to device, without a host array.  Afterwards
+ *   the context is in the state surtr_upload_pattern of the same arrays leaves: no plain placement, no placed instances, the pair
+ *   order forgotten, the cell arrays of the last surtr_build_cells untouched; every later call gives bit-identical results.
+ * An unknown id is SURTR_E_INVALID; a failed allocation is SURTR_E_HIP with the reason in surtr_last_error.  After any error the
+ * library, the installed pattern and the placements are as they were.
+ * The device: every copy is enqueued on the context's stream, behind an event in flight and before any later placement; none of
+ * these calls synchronises.  Only a growth waits for the device, when it frees the smaller block: surtr_pattern_store when the
+ * library has to grow, surtr_pattern_select when the selected pattern is larger than any the context has held.  count, info and
+ * clear touch no device memory. */
+#define SURTR_CELLS_ALL 0xFFFFFFFFu
+int surtr_pattern_store(surtr_ctx* ctx, uint32_t* id);
+int surtr_pattern_count(surtr_ctx* ctx, uint32_t* n);
+int surtr_pattern_info(surtr_ctx* ctx, uint32_t id, uint32_t* n_cells, uint32_t* n_faces);
+int surtr_pattern_clear(surtr_ctx* ctx);
+int surtr_pattern_select(surtr_ctx* ctx, uint32_t id);
+/* surtr_place_cells_impacts with a stored pattern per impact, in one launch (k_place_cells_patterns): instance i is stored pattern
+ * pattern_id[i] under scale3[3i..] / translate3[3i..].  Ids may repeat and come in any order.  Instance i owns the global cells
+ * [cell_base[i], cell_base[i + 1]), cell_base being the prefix sum of its pattern's n_cells, and its planes follow instance i - 1's;
+ * they are bit for bit what surtr_pattern_select(pattern_id[i]) + surtr_place_cells writes.  The instances share the tables of
+ * surtr_place_cells_impacts: the newer of the two placements replaces the older.  The installed pattern and the plain placement are
+ * untouched.  SURTR_E_INVALID: n_impacts == 0 or an id that is not stored; SURTR_E_CAPACITY: more than 0x7FFFFFFF faces or cells
+ * over all instances.  A new installed pattern (upload, build, select) or surtr_pattern_clear forgets the instances.
+ * The event over them: surtr_scene_fracture_impacts(_async) with cell_begin = 0, cell_end = SURTR_CELLS_ALL takes every cell of every
+ * instance (any other range: SURTR_E_INVALID; after surtr_place_cells_impacts SURTR_CELLS_ALL is SURTR_E_INVALID as before).
+ * frag_ids carry the global cell number; cell - cell_base[i] is the pattern's own cell. */
+int surtr_place_cells_patterns(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* pattern_id, const float* scale3, const float* translate3);
+/* cell_base of the placed instances, after either placement (surtr_place_cells_impacts: i * n_cells).  Count-then-fill: *n =
+ * n_impacts + 1; cell_base == NULL returns *n only.  SURTR_E_STATE: no instances. */
+int surtr_placed_cells(surtr_ctx* ctx, uint32_t cap, uint32_t* n, uint32_t* cell_base);
 
 /* Alternative to pattern+place: give the cell planes directly. */
 int surtr_upload_planes(surtr_ctx* ctx, uint32_t n_cells, const uint32_t* plane_off, const float* planes);
@@ -461,6 +503,14 @@ int surtr_event_regroup_bodies(surtr_ctx* ctx, int partial, uint32_t n_sphere, c
 int surtr_event_regroup_impacts(surtr_ctx* ctx, int partial, uint32_t n_impacts, const uint32_t* sphere_off, const float* sphere_points,
                                 const float* origins, const float* radii, uint32_t* n_pieces, uint32_t* n_compounds, uint32_t* compound_off,
                                 int32_t* compound_piece, uint32_t* n_bodies, uint32_t* body_compound_off);
+
+/* surtr_event_regroup_impacts with a flag per impact (one byte each): the bodies of an impact with partial[i] == 0 are tested against
+ * no sphere and see no MergeOutOfImpact; its cloud range may be empty, and its origin and radius are not used.  The bodies of the
+ * other impacts are treated as surtr_event_regroup_impacts(partial = 1) treats them.  All ones equals
+ * surtr_event_regroup_impacts(1, ...), all zeros surtr_event_regroup_impacts(0, ...), bit for bit.  After either placement. */
+int surtr_event_regroup_impacts_partial(surtr_ctx* ctx, const uint8_t* partial, uint32_t n_impacts, const uint32_t* sphere_off, const float* sphere_points,
+                                        const float* origins, const float* radii, uint32_t* n_pieces, uint32_t* n_compounds, uint32_t* compound_off,
+                                        int32_t* compound_piece, uint32_t* n_bodies, uint32_t* body_compound_off);
 
 /* Runs m_refittingTask (and the output scan) on the fragments of the last event: the reference regroups on the
  * un-refitted Convex solids and refits afterwards (Src/Surtr.cpp:1921-1939). */

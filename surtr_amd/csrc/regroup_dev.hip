@@ -120,11 +120,13 @@ __global__ __launch_bounds__(SURTR_LANES) void k_rg_faces(uint32_t n_pieces, RgS
     __shared__ uint32_t sh_in;
     const uint32_t p = blockIdx.x;
     if (p >= n_pieces) return;
+    bool no_sphere = false;      // surtr_event_regroup_impacts_partial: the piece's impact is not partial, its byte is 0 untested
     if (piece_imp)      // surtr_event_regroup_impacts: the sphere of the impact this piece's body belongs to
     {
         const ImpSphere s = imp_tab[piece_imp[p]];
         ox = s.ox; oy = s.oy; oz = s.oz; radius = s.radius;
         sphere += 3 * (size_t)s.cloud_begin; n_sphere = s.cloud_n;
+        no_sphere = s.no_sphere != 0u;
     }
     const RgSolid S = rg_solid(p, src, frags, A, cpos, cloff, cnbr, cvo);
     if (threadIdx.x == 0)
@@ -132,7 +134,7 @@ __global__ __launch_bounds__(SURTR_LANES) void k_rg_faces(uint32_t n_pieces, RgS
         uint32_t nf = 0, np = 0, cur_n = 0, cur_start = 0;
         const uint32_t f0 = pass ? face_off[p] : 0u, p0 = pass ? pts_off[p] : 0u;
         bool inside_possible = true;      // ConvexOutOfSphere part 1: every vertex at least `radius` from the origin (:2420-2427)
-        if (pass && out_flag)
+        if (pass && out_flag && !no_sphere)
             for (uint32_t v = 0; v < S.nv; ++v)
             {
                 const P3 d = sub3(P3{ox, oy, oz}, rg_pos(S, (int)v));
@@ -165,7 +167,7 @@ __global__ __launch_bounds__(SURTR_LANES) void k_rg_faces(uint32_t n_pieces, RgS
     {
         // ConvexOutOfSphere part 2 (:2429-2455): no point of the sphere cloud inside the Convex (all its face planes)
         const uint32_t nf = sh_in;
-        bool hit = nf == 0xFFFFFFFFu;
+        bool hit = no_sphere || nf == 0xFFFFFFFFu;
         if (!hit)
             for (uint32_t q = threadIdx.x; q < n_sphere && !hit; q += group_size())
             {
@@ -435,7 +437,7 @@ extern "C" void surtr_regroup_forget(const surtr_ctx* ctx)
 }
 
 // The spheres of surtr_event_regroup_impacts: impact i's origin, radius and points [sphere_off[i], sphere_off[i + 1]) of the cloud.
-struct ImpactSpheres { uint32_t n; const uint32_t* sphere_off; const float* origins; const float* radii; };
+struct ImpactSpheres { uint32_t n; const uint32_t* sphere_off; const float* origins; const float* radii; const uint8_t* partial = nullptr; };
 
 // The bodies of the event: after surtr_scene_fracture_bodies one per target, in the order the targets were given (a bind set belongs
 // to one body); after any other event one body holding everything, which is the regrouping as it was before there were bodies.
@@ -528,7 +530,7 @@ static int regroup_event(surtr_ctx* ctx, int partial, uint32_t n_sphere, const f
         for (uint32_t p = 0; p < n_outside; ++p) pimp[p] = impact_of(body_of(skipped[p]));
         for (uint32_t f = 0; f < c.n_frag; ++f) pimp[n_outside + f] = impact_of(frag_body[f]);
         imptab.resize(impacts->n);
-        fill_spheres(imptab.data(), impacts->n, impacts->sphere_off, impacts->origins, impacts->radii);
+        fill_spheres(imptab.data(), impacts->n, impacts->sphere_off, impacts->origins, impacts->radii, impacts->partial);
         if (!alloc(d_pimp, n) || !alloc(d_imptab, imptab.size())) return SURTR_E_HIP;
         HIPCHK(hipMemcpyAsync(d_pimp.p, pimp.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_imptab.p, imptab.data(), imptab.size() * sizeof(ImpSphere), hipMemcpyHostToDevice, st));
@@ -681,6 +683,25 @@ extern "C" int surtr_event_regroup_impacts(surtr_ctx* ctx, int partial, uint32_t
     const int rc = spheres_valid(n_impacts, sphere_off, origins, radii, sphere_points != nullptr);
     if (rc) return rc;
     const ImpactSpheres imp{n_impacts, sphere_off, origins, radii};
+    return regroup_event(ctx, 1, sphere_off[n_impacts], sphere_points, origins, radii[0], n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off, &imp);
+}
+
+// The same with a flag per impact: the bodies of an impact with partial[i] == 0 are tested against no sphere (a "no sphere" entry of
+// the table, for which k_rg_faces writes 0) and so see no MergeOutOfImpact; their cloud range may be empty.
+extern "C" int surtr_event_regroup_impacts_partial(surtr_ctx* ctx, const uint8_t* partial, uint32_t n_impacts, const uint32_t* sphere_off, const float* sphere_points,
+                                                   const float* origins, const float* radii, uint32_t* n_pieces_out, uint32_t* n_compounds,
+                                                   uint32_t* compound_off, int32_t* compound_piece, uint32_t* n_bodies, uint32_t* body_compound_off)
+{
+    if (!ctx || !n_bodies || !n_impacts || !partial) return SURTR_E_INVALID;
+    if (!ctx->have_event || ctx->scene_event_compound.empty() || ctx->scene_event_impacts.size() != (size_t)n_impacts + 1 ||
+        ctx->scene_event_impacts.back() != ctx->scene_event_compound.size())
+        return SURTR_E_STATE;
+    *n_bodies = (uint32_t)ctx->scene_event_compound.size();
+    if (std::find_if(partial, partial + n_impacts, [](uint8_t f) { return f != 0; }) == partial + n_impacts)      // no sphere at all
+        return regroup_event(ctx, 0, 0, nullptr, nullptr, 0.f, n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off);
+    const int rc = spheres_valid(n_impacts, sphere_off, origins, radii, sphere_points != nullptr);
+    if (rc) return rc;
+    const ImpactSpheres imp{n_impacts, sphere_off, origins, radii, partial};
     return regroup_event(ctx, 1, sphere_off[n_impacts], sphere_points, origins, radii[0], n_pieces_out, n_compounds, compound_off, compound_piece, body_compound_off, &imp);
 }
 

@@ -111,23 +111,33 @@ bool valid_table(uint32_t n_compounds, const uint32_t* off, uint32_t n_pieces)
 // the order given, then cell-major over the target's pieces, as surtr_fracture_event takes them: every target's fragments come out as
 // the event of that target alone gives them.  `outside` holds one byte per piece of the listed compounds in that order and is spread
 // over all resident pieces.  instance_cells (surtr_scene_fracture_impacts): impact i's cells are those of its own instance of the
-// pattern, i * n_cells + c, and the event reads the instance planes.
+// pattern, i * n_cells + c (after surtr_place_cells_patterns: imp_cell_base[i] + c), and the event reads the instance planes.
 int scene_event(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds, uint32_t cell_begin, uint32_t cell_end,
                 const uint8_t* outside, uint32_t flags, bool instance_cells)
 {
-    const uint32_t n_targets = target_off[n_impacts], nc = cell_end - cell_begin;
-    uint64_t total = 0;
-    for (uint32_t t = 0; t < n_targets; ++t) total += ctx->scene_off[compounds[t] + 1] - ctx->scene_off[compounds[t]];
-    if ((uint64_t)nc * total > 0xFFFFFFFFull) return SURTR_E_INVALID;
+    const uint32_t n_targets = target_off[n_impacts];
+    // the cells of impact i: [cell_begin, cell_end) of its instance, or of the plain placement; after surtr_place_cells_patterns every
+    // cell of its instance, which has as many as its own pattern
+    const bool library = instance_cells && ctx->imp_library;
+    auto first_cell = [&](uint32_t i) { return library ? ctx->imp_cell_base[i] : (instance_cells ? i * ctx->n_cells : 0u) + cell_begin; };
+    auto cell_count = [&](uint32_t i) { return library ? ctx->imp_cell_base[i + 1] - ctx->imp_cell_base[i] : cell_end - cell_begin; };
+    uint64_t n_pairs = 0;
+    for (uint32_t i = 0; i < n_impacts; ++i)
+    {
+        uint64_t total = 0;
+        for (uint32_t t = target_off[i]; t < target_off[i + 1]; ++t) total += ctx->scene_off[compounds[t] + 1] - ctx->scene_off[compounds[t]];
+        n_pairs += (uint64_t)cell_count(i) * total;
+    }
+    if (n_pairs > 0xFFFFFFFFull) return SURTR_E_INVALID;
     std::vector<uint32_t> cell, piece;
-    cell.reserve((size_t)nc * total); piece.reserve((size_t)nc * total);
+    cell.reserve((size_t)n_pairs); piece.reserve((size_t)n_pairs);
     std::vector<uint8_t> mask;
     if (outside) mask.assign(ctx->n_pieces, 0);
     size_t at = 0;
     for (uint32_t i = 0; i < n_impacts; ++i)
         for (uint32_t t = target_off[i]; t < target_off[i + 1]; ++t)
         {
-            const uint32_t p0 = ctx->scene_off[compounds[t]], m = ctx->scene_off[compounds[t] + 1] - p0, c0 = (instance_cells ? i * ctx->n_cells : 0u) + cell_begin;
+            const uint32_t p0 = ctx->scene_off[compounds[t]], m = ctx->scene_off[compounds[t] + 1] - p0, c0 = first_cell(i), nc = cell_count(i);
             for (uint32_t c = 0; c < nc; ++c)
                 for (uint32_t q = 0; q < m; ++q) { cell.push_back(c0 + c); piece.push_back(p0 + q); }
             if (outside) memcpy(mask.data() + p0, outside + at, m);
@@ -368,7 +378,8 @@ int surtr_scene_fracture_impacts_async(surtr_ctx* ctx, uint32_t n_impacts, const
     if (!ctx->n_pieces || !ctx->n_impacts_placed || ctx->n_impacts_placed != n_impacts) return SURTR_E_STATE;
     const int rc = impacts_valid(ctx, n_impacts, target_off, compounds);
     if (rc) return rc;
-    if (cell_end > ctx->n_cells || cell_begin > cell_end) return SURTR_E_INVALID;
+    // (after surtr_place_cells_patterns the instances differ in their cells: all of them, or nothing)
+    if (ctx->imp_library ? cell_begin != 0u || cell_end != SURTR_CELLS_ALL : cell_end > ctx->n_cells || cell_begin > cell_end) return SURTR_E_INVALID;
     return scene_event(ctx, n_impacts, target_off, compounds, cell_begin, cell_end, outside, flags, true);
 }
 

@@ -368,6 +368,16 @@ struct surtr_ctx
     uint32_t n_impacts_placed = 0;
     DevBuf<float4> d_planes_imp; DevBuf<uint32_t> d_plane_off_imp; DevBuf<float> d_imp_xf;
     std::vector<uint32_t> h_plane_off_imp; std::vector<float> h_imp_xf;
+    // ... or surtr_place_cells_patterns (imp_library): instance i is a stored pattern of its own, in the same tables.  After either
+    // placement instance i owns global cells [imp_cell_base[i], imp_cell_base[i + 1]) and the tables hold imp_faces planes.
+    bool imp_library = false; std::vector<uint32_t> imp_cell_base; uint32_t imp_faces = 0;
+    DevBuf<uint32_t> d_imp_tab; std::vector<uint32_t> h_imp_tab;      // k_place_cells_patterns: face prefix [n + 1], library face base [n]
+    // the pattern library (surtr_pattern_store): v012 and face offsets (each pattern's from 0) of every stored pattern, one after the
+    // other in two grow-only buffers; lib[k]: where pattern k lies.  h_lib_off: the offsets once more, for the host's plane counts.
+    struct LibPattern { uint32_t n_cells, n_faces, face_base, off_base; };
+    std::vector<LibPattern> lib;
+    DevBuf<uint32_t> d_lib_v012 /* floats, kept as words */, d_lib_off; std::vector<uint32_t> h_lib_off;
+    uint32_t lib_faces = 0;      // faces stored so far (h_lib_off.size(): offset words)
     // scratch + arena
     uint32_t user_cv = 0, user_ch = 0;
     uint64_t user_av = 0, user_ah = 0, user_ai = 0;
@@ -584,7 +594,8 @@ extern "C" int surtr_place_cells_groups_dev(surtr_ctx* ctx, uint32_t n_groups, c
 // ---- several impacts in one event (surtr_place_cells_impacts, surtr_scene_outside_impacts, surtr_scene_fracture_impacts,
 //      surtr_event_regroup_impacts) ----
 // One impact's sphere as the kernels read it: origin, radius, and its points [cloud_begin, cloud_begin + cloud_n) of the cloud.
-struct alignas(16) ImpSphere { float ox, oy, oz, radius; uint32_t cloud_begin, cloud_n, pad0, pad1; };
+// no_sphere (surtr_event_regroup_impacts_partial): the impact is not partial, k_rg_faces tests none of its pieces and writes 0 for them.
+struct alignas(16) ImpSphere { float ox, oy, oz, radius; uint32_t cloud_begin, cloud_n, no_sphere, pad1; };
 // The target lists of a call: impact i owns compounds[target_off[i] .. target_off[i + 1]).  K >= 1, no impact without a target, every
 // compound in range and named once over all impacts, strictly descending inside an impact.  Anything else: SURTR_E_INVALID.
 static inline int impacts_valid(const surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* target_off, const uint32_t* compounds)
@@ -611,19 +622,21 @@ static inline int spheres_valid(uint32_t n_impacts, const uint32_t* sphere_off, 
     for (uint32_t i = 0; i < n_impacts; ++i) if (sphere_off[i + 1] < sphere_off[i]) return SURTR_E_INVALID;
     return sphere_off[n_impacts] && !have_points ? SURTR_E_INVALID : SURTR_OK;
 }
-static inline void fill_spheres(ImpSphere* tab, uint32_t n_impacts, const uint32_t* sphere_off, const float* origins, const float* radii)
+static inline void fill_spheres(ImpSphere* tab, uint32_t n_impacts, const uint32_t* sphere_off, const float* origins, const float* radii,
+                                const uint8_t* partial = nullptr)
 {
     for (uint32_t i = 0; i < n_impacts; ++i)
-        tab[i] = ImpSphere{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], radii[i], sphere_off[i], sphere_off[i + 1] - sphere_off[i], 0u, 0u};
+        tab[i] = ImpSphere{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], radii[i], sphere_off[i], sphere_off[i + 1] - sphere_off[i],
+                           partial && !partial[i] ? 1u : 0u, 0u};
 }
-// While one of these lives the event's kernels read the instance planes of surtr_place_cells_impacts: the plain placement's tables are
-// swapped out and come back, untouched, when it goes.
+// While one of these lives the event's kernels read the instance planes of surtr_place_cells_impacts or surtr_place_cells_patterns, and
+// n_cells is the number of cells of all instances: the plain placement's tables are swapped out and come back, untouched, when it goes.
 struct ImpactPlanesScope
 {
-    surtr_ctx* ctx; bool ready;
+    surtr_ctx* ctx; bool ready; uint32_t n_cells;
     void flip() { std::swap(ctx->d_planes, ctx->d_planes_imp); std::swap(ctx->d_plane_off, ctx->d_plane_off_imp); std::swap(ctx->h_plane_off, ctx->h_plane_off_imp); }
-    explicit ImpactPlanesScope(surtr_ctx* c) : ctx(c), ready(c->planes_ready) { flip(); ctx->n_cells *= ctx->n_impacts_placed; ctx->planes_ready = true; }
-    ~ImpactPlanesScope() { flip(); ctx->n_cells /= ctx->n_impacts_placed; ctx->planes_ready = ready; }
+    explicit ImpactPlanesScope(surtr_ctx* c) : ctx(c), ready(c->planes_ready), n_cells(c->n_cells) { flip(); ctx->n_cells = ctx->imp_cell_base.back(); ctx->planes_ready = true; }
+    ~ImpactPlanesScope() { flip(); ctx->n_cells = n_cells; ctx->planes_ready = ready; }
     ImpactPlanesScope(const ImpactPlanesScope&) = delete;
     ImpactPlanesScope& operator=(const ImpactPlanesScope&) = delete;
 };

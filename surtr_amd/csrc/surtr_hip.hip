@@ -4,6 +4,7 @@
 // k_clip_pairs_half beside k_clip_pairs_big, k_refit beside k_faces -- fenced by events; inputs resident in HBM):
 //   k_place_cells   A3   Polygon3D::Scale/Translate + ConstructFacePlane      (Src/VMACH.cpp:302-310, 506-534)
 //   k_place_cells_impacts  the same for several instances of the pattern, one per impact of a frame (surtr_place_cells_impacts)
+//   k_place_cells_patterns the same with a stored pattern of its own per instance (surtr_place_cells_patterns)
 //   k_clip_convex   A7   Convex of every (cell, piece) pair, one wave per task (Src/Surtr.cpp:1466-1468)
 //   k_prep_pairs    A7   pre-pass of the Mesh of every pair whose Convex survived: the vertices the planes can touch,
 //                        left in HBM in the layout of the LDS topology
@@ -292,6 +293,32 @@ __global__ void k_place_cells_impacts(uint32_t nfaces, uint32_t n_imp, const flo
         const float tx = shift3[3 * g], ty = shift3[3 * g + 1], tz = shift3[3 * g + 2];
         planes[(size_t)g * nfaces + f] = placed_plane(v, sx, sy, sz, tx, ty, tz);
     }
+}
+
+// One stored pattern per instance (surtr_place_cells_patterns): a thread per face of the concatenation of all instances, each with as
+// many faces as its own pattern.  face_prefix[i] (n_imp + 1 words, ascending, face_prefix[n_imp] = ntotal) is the first plane of
+// instance i: a thread finds its instance by bisection (the last i with face_prefix[i] <= g; an instance without faces is skipped),
+// reads its face's nine floats from the library at lib_face_base[i] and places them with the expressions of k_place_cells, so
+// instance i carries the bits surtr_place_cells writes for that pattern, scale and translate.
+__global__ void k_place_cells_patterns(uint32_t ntotal, uint32_t n_imp, const uint32_t* __restrict__ face_prefix, const uint32_t* __restrict__ lib_face_base,
+                                       const float* __restrict__ lib_v012, const float* __restrict__ scale3, const float* __restrict__ shift3,
+                                       float4* __restrict__ planes)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= ntotal) return;
+    uint32_t lo = 0, hi = n_imp;      // face_prefix[lo] <= g < face_prefix[hi]
+    while (hi - lo > 1u)
+    {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (face_prefix[mid] <= g) lo = mid; else hi = mid;
+    }
+    const uint32_t f = g - face_prefix[lo];
+    const float* src = lib_v012 + 9 * ((size_t)lib_face_base[lo] + f);
+    float v[9];
+    for (int i = 0; i < 9; ++i) v[i] = src[i];
+    const float sx = scale3[3 * lo], sy = scale3[3 * lo + 1], sz = scale3[3 * lo + 2];
+    const float tx = shift3[3 * lo], ty = shift3[3 * lo + 1], tz = shift3[3 * lo + 2];
+    planes[g] = placed_plane(v, sx, sy, sz, tx, ty, tz);
 }
 
 // A pair whose Mesh clip has no valid answer in the reference (SURTR_E_TOPOLOGY: the degenerate policy of literal_clip.h) yields
@@ -3654,7 +3681,151 @@ int surtr_place_cells_impacts(surtr_ctx* ctx, uint32_t n_impacts, const float* s
         hipLaunchKernelGGL(k_place_cells_impacts, dim3((nf + 255) / 256), dim3(256), 0, st, nf, n_impacts, (const float*)ctx->d_v012, (const float*)ctx->d_imp_xf,
                            (const float*)ctx->d_imp_xf + 3 * (size_t)n_impacts, (float4*)ctx->d_planes_imp);
     HIPCHK(hipGetLastError());
-    ctx->n_impacts_placed = n_impacts;
+    ctx->n_impacts_placed = n_impacts; ctx->imp_library = false; ctx->imp_faces = n_impacts * nf;
+    ctx->imp_cell_base.resize((size_t)n_impacts + 1);
+    for (uint32_t i = 0; i <= n_impacts; ++i) ctx->imp_cell_base[i] = i * nc;
+    return SURTR_OK;
+}
+
+// ---- the pattern library ----
+// Room for `need` words in a library buffer that holds `used`: a larger block is allocated beside the old one, the stored patterns
+// are copied over on the context's stream, and the old block is freed (which waits for the device).  A failed allocation leaves the
+// buffer as it was.  (Both buffers hold 4-byte words: floats and offsets.)
+static int lib_reserve(surtr_ctx* ctx, DevBuf<uint32_t>& b, size_t used, size_t need)
+{
+    if (b.p && b.cap >= need) return SURTR_OK;
+    DevBuf<uint32_t> larger;
+    const int rc = larger.grow(ctx, need, need + need / 2 + 64);
+    if (rc) return rc;
+    if (used) HIPCHK(hipMemcpyAsync(larger.p, b.p, used * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    b = std::move(larger);
+    return SURTR_OK;
+}
+
+int surtr_pattern_store(surtr_ctx* ctx, uint32_t* id)
+{
+    if (!ctx || !id) return SURTR_E_INVALID;
+    if (!ctx->d_v012 || !ctx->n_cells) return SURTR_E_STATE;      // no pattern, or planes without v012 (surtr_upload_planes)
+    const uint32_t nc = ctx->n_cells, nf = ctx->n_faces;
+    const size_t offs = ctx->h_lib_off.size();
+    if ((uint64_t)ctx->lib_faces + nf > 0x7FFFFFFFull || (uint64_t)offs + nc + 1 > 0x7FFFFFFFull) return SURTR_E_CAPACITY;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    int rc = lib_reserve(ctx, ctx->d_lib_v012, 9 * (size_t)ctx->lib_faces, std::max<size_t>(9 * ((size_t)ctx->lib_faces + nf), 4));
+    if (rc == SURTR_OK) rc = lib_reserve(ctx, ctx->d_lib_off, offs, offs + nc + 1);
+    if (rc) return rc;
+    if (nf) HIPCHK(hipMemcpyAsync((float*)ctx->d_lib_v012.p + 9 * (size_t)ctx->lib_faces, ctx->d_v012.p, (size_t)nf * 36, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctx->d_lib_off.p + offs, ctx->d_plane_off.p, ((size_t)nc + 1) * 4, hipMemcpyDeviceToDevice, st));
+    ctx->lib.push_back(surtr_ctx::LibPattern{nc, nf, ctx->lib_faces, (uint32_t)offs});
+    ctx->h_lib_off.insert(ctx->h_lib_off.end(), ctx->h_plane_off.begin(), ctx->h_plane_off.begin() + nc + 1);
+    ctx->lib_faces += nf;
+    *id = (uint32_t)ctx->lib.size() - 1u;
+    return SURTR_OK;
+}
+
+int surtr_pattern_count(surtr_ctx* ctx, uint32_t* n)
+{
+    if (!ctx || !n) return SURTR_E_INVALID;
+    *n = (uint32_t)ctx->lib.size();
+    return SURTR_OK;
+}
+
+int surtr_pattern_info(surtr_ctx* ctx, uint32_t id, uint32_t* n_cells, uint32_t* n_faces)
+{
+    if (!ctx || id >= ctx->lib.size()) return SURTR_E_INVALID;
+    if (n_cells) *n_cells = ctx->lib[id].n_cells;
+    if (n_faces) *n_faces = ctx->lib[id].n_faces;
+    return SURTR_OK;
+}
+
+int surtr_pattern_clear(surtr_ctx* ctx)
+{
+    if (!ctx) return SURTR_E_INVALID;
+    // (the buffers stay: a placement kernel in flight may read them, and the next store fills them from the start)
+    ctx->lib.clear(); ctx->h_lib_off.clear(); ctx->lib_faces = 0;
+    if (ctx->imp_library) { ctx->n_impacts_placed = 0; ctx->imp_library = false; }
+    return SURTR_OK;
+}
+
+int surtr_pattern_select(surtr_ctx* ctx, uint32_t id)
+{
+    if (!ctx || id >= ctx->lib.size()) return SURTR_E_INVALID;
+    const surtr_ctx::LibPattern P = ctx->lib[id];
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    // the pattern buffers, with the room surtr_build_cells gives them.  All three are made before one is replaced, so that a failed
+    // allocation leaves the installed pattern as it was; replacing one frees the old block, which waits for the device.
+    const size_t capf = (size_t)P.n_faces + P.n_faces / 8 + 16, capc = (size_t)P.n_cells + P.n_cells / 8 + 16;
+    const bool fv = !ctx->d_v012.p || ctx->d_v012.cap < std::max<size_t>(4, 9 * (size_t)P.n_faces), fp = !ctx->d_planes.p || ctx->d_planes.cap < std::max(P.n_faces, 1u),
+               fo = !ctx->d_plane_off.p || ctx->d_plane_off.cap < (size_t)P.n_cells + 1;
+    DevBuf<float> v; DevBuf<float4> pl; DevBuf<uint32_t> off;
+    if ((fv && v.grow(ctx, 9 * capf)) || (fp && pl.grow(ctx, capf)) || (fo && off.grow(ctx, capc + 1))) return SURTR_E_HIP;
+    if (fv) ctx->d_v012 = std::move(v);
+    if (fp) ctx->d_planes = std::move(pl);
+    if (fo) ctx->d_plane_off = std::move(off);
+    ctx->planes_ready = false;
+    // device to device on the context's stream: behind an event in flight, before any later placement
+    if (P.n_faces) HIPCHK(hipMemcpyAsync(ctx->d_v012.p, (const float*)ctx->d_lib_v012.p + 9 * (size_t)P.face_base, (size_t)P.n_faces * 36, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctx->d_plane_off.p, ctx->d_lib_off.p + P.off_base, ((size_t)P.n_cells + 1) * 4, hipMemcpyDeviceToDevice, st));
+    ctx->h_plane_off.assign(ctx->h_lib_off.begin() + P.off_base, ctx->h_lib_off.begin() + P.off_base + P.n_cells + 1);
+    ctx->n_cells = P.n_cells; ctx->n_faces = P.n_faces; ctx->planes_ready = false; ctx->pair_order_count = 0; ctx->n_impacts_placed = 0;
+    return SURTR_OK;
+}
+
+int surtr_place_cells_patterns(surtr_ctx* ctx, uint32_t n_impacts, const uint32_t* pattern_id, const float* scale3, const float* translate3)
+{
+    if (!ctx || !n_impacts || !pattern_id || !scale3 || !translate3) return SURTR_E_INVALID;
+    uint64_t F = 0, C = 0;
+    for (uint32_t i = 0; i < n_impacts; ++i)
+    {
+        if (pattern_id[i] >= ctx->lib.size()) return SURTR_E_INVALID;
+        F += ctx->lib[pattern_id[i]].n_faces; C += ctx->lib[pattern_id[i]].n_cells;
+    }
+    if (F > 0x7FFFFFFFull || C > 0x7FFFFFFFull) return SURTR_E_CAPACITY;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    // (an event in flight may read the tables: hipFree, which a growth goes through, waits for the device)
+    int rc = ctx->d_planes_imp.grow(ctx, std::max<size_t>((size_t)F, 1));
+    if (rc == SURTR_OK) rc = ctx->d_plane_off_imp.grow(ctx, (size_t)C + 1);
+    if (rc == SURTR_OK) rc = ctx->d_imp_xf.grow(ctx, (size_t)6 * n_impacts);
+    if (rc == SURTR_OK) rc = ctx->d_imp_tab.grow(ctx, 2 * (size_t)n_impacts + 1);
+    if (rc) { ctx->n_impacts_placed = 0; return rc; }
+    // instance i's cells follow instance i - 1's, and so do its planes.  The staging vectors are the context's (pageable memory has
+    // left its source when hipMemcpyAsync returns, as for the tables of surtr_scene_commit).
+    std::vector<uint32_t>& off = ctx->h_plane_off_imp; std::vector<uint32_t>& tab = ctx->h_imp_tab; std::vector<uint32_t>& base = ctx->imp_cell_base;
+    off.clear(); off.reserve((size_t)C + 1);
+    tab.assign(2 * (size_t)n_impacts + 1, 0u); base.assign((size_t)n_impacts + 1, 0u);
+    for (uint32_t i = 0; i < n_impacts; ++i)
+    {
+        const surtr_ctx::LibPattern& P = ctx->lib[pattern_id[i]];
+        for (uint32_t c = 0; c < P.n_cells; ++c) off.push_back(tab[i] + ctx->h_lib_off[(size_t)P.off_base + c]);
+        tab[i + 1] = tab[i] + P.n_faces; base[i + 1] = base[i] + P.n_cells;
+        tab[(size_t)n_impacts + 1 + i] = P.face_base;
+    }
+    off.push_back((uint32_t)F);
+    std::vector<float>& xf = ctx->h_imp_xf;
+    xf.assign(scale3, scale3 + 3 * (size_t)n_impacts);
+    xf.insert(xf.end(), translate3, translate3 + 3 * (size_t)n_impacts);
+    HIPCHK(hipMemcpyAsync(ctx->d_plane_off_imp, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctx->d_imp_xf, xf.data(), xf.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctx->d_imp_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+    if (F)
+        hipLaunchKernelGGL(k_place_cells_patterns, dim3(((uint32_t)F + 255) / 256), dim3(256), 0, st, (uint32_t)F, n_impacts, (const uint32_t*)ctx->d_imp_tab,
+                           (const uint32_t*)ctx->d_imp_tab + n_impacts + 1, (const float*)ctx->d_lib_v012.p, (const float*)ctx->d_imp_xf,
+                           (const float*)ctx->d_imp_xf + 3 * (size_t)n_impacts, (float4*)ctx->d_planes_imp);
+    HIPCHK(hipGetLastError());
+    ctx->n_impacts_placed = n_impacts; ctx->imp_library = true; ctx->imp_faces = (uint32_t)F;
+    return SURTR_OK;
+}
+
+int surtr_placed_cells(surtr_ctx* ctx, uint32_t cap, uint32_t* n, uint32_t* cell_base)
+{
+    if (!ctx || !n) return SURTR_E_INVALID;
+    if (!ctx->n_impacts_placed) return SURTR_E_STATE;
+    *n = ctx->n_impacts_placed + 1u;
+    if (!cell_base) return SURTR_OK;
+    if (cap < *n) return SURTR_E_CAPACITY;
+    memcpy(cell_base, ctx->imp_cell_base.data(), (size_t)*n * 4);
     return SURTR_OK;
 }
 
@@ -3662,7 +3833,7 @@ int surtr_download_planes(surtr_ctx* ctx, int impacts, uint32_t cap, uint32_t* n
 {
     if (!ctx || !n) return SURTR_E_INVALID;
     if (impacts ? ctx->n_impacts_placed == 0u : !ctx->planes_ready) return SURTR_E_STATE;
-    *n = impacts ? ctx->n_impacts_placed * ctx->n_faces : ctx->n_faces;
+    *n = impacts ? ctx->imp_faces : ctx->n_faces;
     if (!planes) return SURTR_OK;
     if (cap < *n) return SURTR_E_CAPACITY;
     (void)hipSetDevice(ctx->device);

@@ -14,6 +14,7 @@ _LIB = None
 
 OK, E_INVALID, E_TOPOLOGY, E_CAPACITY, E_HIP, E_STATE, E_NOGPU = range(7)
 EVT_REFIT, EVT_RENDER = 1, 2
+CELLS_ALL = 0xFFFFFFFF      # SURTR_CELLS_ALL: every cell of every instance of place_cells_patterns
 
 
 class SurtrError(RuntimeError):
@@ -344,6 +345,59 @@ class Engine:
         if s.shape[0] != t.shape[0]:
             raise SurtrError(E_INVALID, "%d scales, %d translates" % (s.shape[0], t.shape[0]))
         self._ck(lib().surtr_place_cells_impacts(self._h, ctypes.c_uint32(s.shape[0]), _p(s), _p(t)))
+
+    # ---- the pattern library (include/surtr_hip.h): several patterns resident on the device
+    def pattern_store(self):
+        """surtr_pattern_store: the installed pattern into the library, device to device -> its id (0, 1, ... in order of storing)."""
+        i = ctypes.c_uint32()
+        self._ck(lib().surtr_pattern_store(self._h, ctypes.byref(i)))
+        return i.value
+
+    def pattern_count(self):
+        n = ctypes.c_uint32()
+        self._ck(lib().surtr_pattern_count(self._h, ctypes.byref(n)))
+        return n.value
+
+    def pattern_info(self, id):
+        """surtr_pattern_info -> (n_cells, n_faces) of stored pattern id."""
+        nc, nf = ctypes.c_uint32(), ctypes.c_uint32()
+        self._ck(lib().surtr_pattern_info(self._h, ctypes.c_uint32(int(id)), ctypes.byref(nc), ctypes.byref(nf)))
+        return nc.value, nf.value
+
+    def pattern_select(self, id):
+        """surtr_pattern_select: stored pattern id becomes the installed pattern, as upload_pattern of the same arrays leaves it."""
+        self._ck(lib().surtr_pattern_select(self._h, ctypes.c_uint32(int(id))))
+
+    def pattern_clear(self):
+        self._ck(lib().surtr_pattern_clear(self._h))
+
+    def place_cells_patterns(self, pattern_ids, scales, translates):
+        """surtr_place_cells_patterns: one instance per impact, instance i being stored pattern pattern_ids[i] under scales[i] /
+        translates[i]; its cells are [b[i], b[i + 1]) of placed_cells().  The event over them: scene_fracture_impacts(targets, 0,
+        CELLS_ALL)."""
+        ids = np.ascontiguousarray(pattern_ids, np.uint32).reshape(-1)
+        s = np.ascontiguousarray(scales, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(translates, np.float32).reshape(-1, 3)
+        if not ids.shape[0] == s.shape[0] == t.shape[0]:
+            raise SurtrError(E_INVALID, "%d ids, %d scales, %d translates" % (ids.shape[0], s.shape[0], t.shape[0]))
+        self._ck(lib().surtr_place_cells_patterns(self._h, ctypes.c_uint32(ids.shape[0]), _p(ids), _p(s), _p(t)))
+
+    def placed_cells(self):
+        """surtr_placed_cells: cell_base of the placed instances (uint32[K + 1]) after place_cells_impacts or place_cells_patterns."""
+        n = ctypes.c_uint32()
+        self._ck(lib().surtr_placed_cells(self._h, ctypes.c_uint32(0), ctypes.byref(n), None))
+        out = np.zeros(n.value, np.uint32)
+        self._ck(lib().surtr_placed_cells(self._h, ctypes.c_uint32(n.value), ctypes.byref(n), _p(out)))
+        return out
+
+    def event_regroup_impacts_partial(self, partial, sphere_points=None, origins=None, radii=None):
+        """surtr_event_regroup_impacts_partial: event_regroup_impacts with a flag per impact (a sequence): the bodies of an impact
+        whose flag is 0 are tested against no sphere (its cloud may be None or empty).  -> as event_regroup_impacts."""
+        flags = np.ascontiguousarray([1 if f else 0 for f in partial], np.uint8)
+        k, so, sp, org, rad = _impact_spheres(sphere_points, origins, radii, flags.shape[0])
+        if k != flags.shape[0]:
+            raise SurtrError(E_INVALID, "%d spheres for %d flags" % (k, flags.shape[0]))
+        return self._regroup("surtr_event_regroup_impacts_partial", [self._h, _p(flags), ctypes.c_uint32(k), _p(so), _p(sp), _p(org), _p(rad)], True)
 
     def download_planes(self, impacts=False):
         """surtr_download_planes (diagnostic): the placed planes as f32[n,4]; impacts: those of place_cells_impacts, instance-major."""

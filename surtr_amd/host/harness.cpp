@@ -623,21 +623,46 @@ static void body_clicks(FractureEngine& eng, const std::vector<std::array<float,
     if (!g_edit.empty()) edit_bodies(eng, piece);
 }
 
-// --impacts: OnImpacts with every sphere of the list on the posed scene of --body-clicks; one JSON line for the frame.
-static void impacts_frame(FractureEngine& eng, const std::vector<std::array<float, 4>>& spheres, const std::vector<std::pair<int, Matrix>>& poses, bool one_event)
+// --impacts: OnImpacts with every sphere of the list on the posed scene of --body-clicks; one JSON line for the frame.  A sphere is
+// x,y,z,r[,pattern[,partial]]: the stored pattern of --patterns its cells come from and its own PartialFracture (-1 or left out: the
+// installed pattern / the frame's flag).  --patterns "cells:mean[:seed];...": GenerateFracturePattern + StorePattern for each, ids
+// from 0 in the order given; the pattern of --cells stays the installed one.  With either field in use the line gains "cell_base".
+struct PatternSpec { int cells; double mean; int seed; };
+static void impacts_frame(FractureEngine& eng, const std::vector<std::array<float, 6>>& spheres, const std::vector<PatternSpec>& patterns,
+                          const std::vector<Vector3>& seeds, const std::vector<std::pair<int, Matrix>>& poses, bool one_event)
 {
     paired_scene(eng, poses);
+    if (!patterns.empty())
+    {
+        for (const PatternSpec& p : patterns) { eng.GenerateFracturePattern(p.cells, p.mean, p.seed); eng.StorePattern(); }
+        eng.SetPattern(eng.GenerateVoronoi(seeds));      // (as main installed it)
+    }
     const std::vector<Vector3> cloud = lattice_cloud();
     std::vector<Impact> in, acted;
     float rmax = 0.f;
-    for (const auto& s : spheres) { in.push_back(Impact{Vector3(s[0], s[1], s[2]), s[3], {}}); rmax = std::max(rmax, s[3]); }
+    bool library = false;
+    for (const auto& s : spheres)
+    {
+        Impact im{Vector3(s[0], s[1], s[2]), s[3], {}};
+        im.pattern = (int)s[4]; im.partial = (int)s[5];
+        library = library || im.pattern >= 0 || im.partial >= 0;
+        in.push_back(im); rmax = std::max(rmax, s[3]);
+    }
     FractureArgs args;
     args.PartialFracture = true; args.RadialMode = true;
     const std::vector<int> made = eng.OnImpacts(in, args, rmax, cloud, &acted, one_event);
     const std::vector<uint32_t> table = eng.SceneCompounds();
     const std::vector<Matrix> world = eng.Poses();
     const std::vector<surtr_mass> bm = eng.BodyMassProperties(1);
-    printf("{\"impacts\": %zu, \"compounds_hit\": [", acted.size());
+    printf("{\"impacts\": %zu, ", acted.size());
+    if (library && !acted.empty())
+    {
+        const std::vector<uint32_t>& base = eng.LastCellBase();
+        printf("\"cell_base\": [");
+        for (size_t i = 0; i < base.size(); ++i) printf("%s%u", i ? ", " : "", base[i]);
+        printf("], ");
+    }
+    printf("\"compounds_hit\": [");
     for (size_t i = 0; i < acted.size(); ++i)
     {
         printf("%s[", i ? ", " : "");
@@ -648,14 +673,49 @@ static void impacts_frame(FractureEngine& eng, const std::vector<std::array<floa
     init_compounds(eng, 0, made);
 }
 
+// --pattern-pair (with --patterns "cells:mean[:seed];cells:mean"): FractureEngine::PrepareFracturePatterns with the two specs as the
+// partial and the general pattern, UsePatternPair, then DoFracture of the event's fragments as one compound with PartialFracture on and
+// off ("pair"); then the same two calls after GenerateFracturePattern of the pattern Src/Surtr.cpp:1887 picks ("built").  One JSON line
+// per call: what came out, which must not depend on the route.
+static void pattern_pair(FractureEngine& eng, const std::vector<Fragment>& frags, const std::vector<PatternSpec>& p, const Vector3& ext, const Vector3& cen)
+{
+    if (p.size() != 2) throw Error(SURTR_E_INVALID, "--pattern-pair takes --patterns with two patterns");
+    FractureArgs args;
+    args.PartialFracturePatternCellCnt = p[0].cells; args.PartialFracturePatternDist = (float)p[0].mean;
+    args.GeneralFracturePatternCellCnt = p[1].cells; args.GeneralFracturePatternDist = (float)p[1].mean;
+    args.Seed = p[0].seed;
+    Compound comp;
+    for (const auto& fr : frags) comp.PieceVec.push_back(fr.piece_data);
+    const float maxAxis = std::max(ext.x, std::max(ext.y, ext.z));
+    args.ImpactPosition = Vector3(cen.x + 0.2f * ext.x, cen.y + 0.1f * ext.y, cen.z); args.ImpactRadius = 0.3f * maxAxis;
+    const std::vector<Vector3> cloud = lattice_cloud();
+    auto line = [&](const char* route, bool partial) {
+        args.PartialFracture = partial;
+        const std::vector<Compound> res = eng.DoFracture(comp, maxAxis, args, cloud);
+        const surtr_counts c = eng.LastCounts();
+        printf("{\"pattern_pair\": \"%s\", \"partial\": %d, \"patterns\": %d, \"compounds\": [", route, partial ? 1 : 0, eng.PatternCount());
+        for (size_t i = 0; i < res.size(); ++i) printf("%s%zu", i ? ", " : "", res[i].PieceVec.size());
+        printf("], \"fragments\": %u, \"mesh_verts\": %u, \"mesh_nbrs\": %u, \"conv_verts\": %u}\n", c.n_frag, c.mesh_verts, c.mesh_nbrs, c.conv_verts);
+    };
+    const std::pair<int, int> ids = eng.PrepareFracturePatterns(args);
+    eng.UsePatternPair(ids.first, ids.second);
+    line("pair", true); line("pair", false); line("pair", true);
+    eng.UsePatternPair(-1, -1);
+    eng.GenerateFracturePattern(args.PartialFracturePatternCellCnt, args.PartialFracturePatternDist, args.Seed);
+    line("built", true);
+    eng.GenerateFracturePattern(args.GeneralFracturePatternCellCnt, args.GeneralFracturePatternDist, args.Seed);
+    line("built", false);
+}
+
 int main(int argc, char** argv)
 {
     std::string mesh = "cube", obj, obj_in, dump;
     int cells = 8, nu = 250, nv = 200;
     std::vector<std::array<float, 6>> clicks, bclicks;
     std::vector<std::pair<int, Matrix>> poses;
-    std::vector<std::array<float, 4>> impacts;
-    bool radial = false, one_event = false;
+    std::vector<std::array<float, 6>> impacts;
+    std::vector<PatternSpec> patterns;
+    bool radial = false, one_event = false, pair = false;
     bool ach = false, do_pick = false; float in_scale = 1.f, pick_ray[6] = {0, 0, 0, 1, 0, 0}, impact_radius = 1.f;
     for (int i = 1; i < argc; ++i)
     {
@@ -671,6 +731,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--impact-radius") && i + 1 < argc) impact_radius = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--radial")) radial = true;
         else if (!strcmp(argv[i], "--one-event")) one_event = true;
+        else if (!strcmp(argv[i], "--pattern-pair")) pair = true;
         else if (!strcmp(argv[i], "--init-compounds")) g_init_compounds = true;
         else if (!strcmp(argv[i], "--hulls")) g_hulls = true;
         else if (!strcmp(argv[i], "--bounds")) g_bounds = true;
@@ -736,12 +797,33 @@ int main(int argc, char** argv)
             const char* c = argv[++i];
             while (*c)
             {
-                std::array<float, 4> r; int used = 0;
+                std::array<float, 6> r{0.f, 0.f, 0.f, 0.f, -1.f, -1.f}; int used = 0;
                 if (sscanf(c, "%f,%f,%f,%f%n", &r[0], &r[1], &r[2], &r[3], &used) != 4)
-                { fprintf(stderr, "surtr_harness: --impacts takes x,y,z,r;...\n"); return 2; }
-                impacts.push_back(r);
+                { fprintf(stderr, "surtr_harness: --impacts takes x,y,z,r[,pattern[,partial]];...\n"); return 2; }
                 c += used;
+                for (int k = 4; k < 6 && *c == ','; ++k)      // the two optional fields
+                {
+                    if (sscanf(c, ",%f%n", &r[k], &used) != 1) { fprintf(stderr, "surtr_harness: --impacts takes x,y,z,r[,pattern[,partial]];...\n"); return 2; }
+                    c += used;
+                }
+                impacts.push_back(r);
                 if (*c == ';') ++c;
+                else if (*c) { fprintf(stderr, "surtr_harness: --impacts takes x,y,z,r[,pattern[,partial]];...\n"); return 2; }
+            }
+        }
+        else if (!strcmp(argv[i], "--patterns") && i + 1 < argc)
+        {
+            const char* c = argv[++i];
+            while (*c)
+            {
+                PatternSpec p{0, 0.0, 46354}; int used = 0;
+                if (sscanf(c, "%d:%lf%n", &p.cells, &p.mean, &used) != 2 || p.cells <= 0 || !(p.mean > 0.0))
+                { fprintf(stderr, "surtr_harness: --patterns takes cells:mean[:seed];...\n"); return 2; }
+                c += used;
+                if (*c == ':') { if (sscanf(c, ":%d%n", &p.seed, &used) != 1) { fprintf(stderr, "surtr_harness: --patterns takes cells:mean[:seed];...\n"); return 2; } c += used; }
+                patterns.push_back(p);
+                if (*c == ';') ++c;
+                else if (*c) { fprintf(stderr, "surtr_harness: --patterns takes cells:mean[:seed];...\n"); return 2; }
             }
         }
         else if (!strcmp(argv[i], "--pick") && i + 1 < argc)
@@ -788,9 +870,10 @@ int main(int argc, char** argv)
                "\"conv_verts\": %u, \"indices\": %u}\n", mesh.c_str(), verts.size(), tris.size() / 3, cells, c.n_frag, c.mesh_verts,
                c.mesh_nbrs, c.conv_verts, c.n_idx);
         if (do_pick) pick(eng, frags, pick_ray, impact_radius);
+        if (pair) { pattern_pair(eng, frags, patterns, ext, cen); return 0; }
         if (!clicks.empty()) scene_clicks(eng, clicks, impact_radius, one_event);
         else if (!bclicks.empty()) body_clicks(eng, bclicks, poses, impact_radius, radial, one_event, piece);
-        else if (!impacts.empty()) impacts_frame(eng, impacts, poses, one_event);
+        else if (!impacts.empty()) impacts_frame(eng, impacts, patterns, seeds, poses, one_event);
         if (!obj.empty())
         {
             FILE* f = fopen(obj.c_str(), "w");

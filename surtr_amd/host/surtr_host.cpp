@@ -304,6 +304,7 @@ void FractureEngine::SetPattern(const std::vector<VMACH::Polygon3D>& voroPolyVec
         face_off.push_back((uint32_t)(v012.size() / 9));
     }
     n_cells_ = (uint32_t)voroPolyVec.size();
+    installed_id_ = -1;
     check(surtr_upload_pattern(ctx_, n_cells_, face_off.data(), v012.data()), "surtr_upload_pattern");
 }
 
@@ -342,6 +343,7 @@ std::vector<VMACH::Polygon3D> FractureEngine::GenerateVoronoi(const std::vector<
     uint32_t nf = 0, nfv = 0;
     check(surtr_build_cells(ctx_, 1, group_off, seeds.data(), &nf, &nfv), "surtr_build_cells");
     n_cells_ = n;                                       // the cells are this engine's pattern now
+    installed_id_ = -1;
     std::vector<uint32_t> cfo(n + 1), fvo(nf + 1);
     std::vector<double> verts(3 * (size_t)nfv + 3);
     check(surtr_download_cells(ctx_, cfo.data(), nullptr, fvo.data(), verts.data(), nullptr), "surtr_download_cells");
@@ -398,6 +400,60 @@ void FractureEngine::PlacePattern(const Vector3& scale, const Vector3& translate
 {
     const float s[3] = {scale.x, scale.y, scale.z}, t[3] = {translate.x, translate.y, translate.z};
     check(surtr_place_cells(ctx_, s, t), "surtr_place_cells");
+}
+
+int FractureEngine::StorePattern()
+{
+    uint32_t id = 0;
+    check(surtr_pattern_store(ctx_, &id), "surtr_pattern_store");
+    installed_id_ = (int)id;
+    return (int)id;
+}
+
+void FractureEngine::SelectPattern(int id)
+{
+    if (id < 0) throw Error(SURTR_E_INVALID, "SelectPattern: no such pattern");
+    uint32_t nc = 0;
+    check(surtr_pattern_info(ctx_, (uint32_t)id, &nc, nullptr), "surtr_pattern_info");
+    check(surtr_pattern_select(ctx_, (uint32_t)id), "surtr_pattern_select");
+    n_cells_ = nc; installed_id_ = id;
+}
+
+int FractureEngine::PatternCount()
+{
+    uint32_t n = 0;
+    check(surtr_pattern_count(ctx_, &n), "surtr_pattern_count");
+    return (int)n;
+}
+
+void FractureEngine::ClearPatterns()
+{
+    check(surtr_pattern_clear(ctx_), "surtr_pattern_clear");
+    installed_id_ = pair_partial_ = pair_general_ = -1;
+}
+
+int FractureEngine::installed_pattern_id() { return installed_id_ >= 0 ? installed_id_ : StorePattern(); }
+
+// (before the installed pattern is stored for the impacts that name none: that store must not make a wrong id a right one)
+void FractureEngine::check_impact_patterns(const std::vector<Impact>& impacts)
+{
+    const int n = PatternCount();
+    for (const Impact& im : impacts)
+        if (im.pattern >= n) throw Error(SURTR_E_INVALID, "Impact::pattern " + std::to_string(im.pattern) + ": " + std::to_string(n) + " patterns are stored");
+}
+
+std::pair<int, int> FractureEngine::PrepareFracturePatterns(const FractureArgs& args)
+{
+    GenerateFracturePattern(args.PartialFracturePatternCellCnt, args.PartialFracturePatternDist, args.Seed);
+    const int partialId = StorePattern();
+    GenerateFracturePattern(args.GeneralFracturePatternCellCnt, args.GeneralFracturePatternDist, args.Seed);
+    return {partialId, StorePattern()};
+}
+
+void FractureEngine::UsePatternPair(int partialId, int generalId)
+{
+    if ((partialId < 0) != (generalId < 0) || partialId >= PatternCount() || generalId >= PatternCount()) throw Error(SURTR_E_INVALID, "UsePatternPair: no such pattern");
+    pair_partial_ = partialId; pair_general_ = generalId;
 }
 
 void FractureEngine::SetCompound(const Compound& compound)
@@ -1049,8 +1105,46 @@ std::vector<int> FractureEngine::ExecuteFractureRoutine(const std::vector<Impact
     }
     ApplyPoses(all);
     SetRefittingPointLimit(args.RefittingPointLimit);
-    check(surtr_place_cells_impacts(ctx_, K, scale3.data(), shift3.data()), "surtr_place_cells_impacts");
     if (fc.empty()) fc.assign(3, 0.f);
+    if (std::find_if(impacts.begin(), impacts.end(), [](const Impact& im) { return im.pattern >= 0 || im.partial >= 0; }) != impacts.end())
+    {
+        // ---- the pattern library: a stored pattern and a flag per impact
+        check_impact_patterns(impacts);
+        std::vector<uint32_t> ids; std::vector<uint8_t> flags;
+        for (const Impact& im : impacts)
+        {
+            ids.push_back((uint32_t)(im.pattern >= 0 ? im.pattern : installed_pattern_id()));
+            flags.push_back(im.partial >= 0 ? (im.partial ? 1 : 0) : (args.PartialFracture ? 1 : 0));
+        }
+        check(surtr_place_cells_patterns(ctx_, K, ids.data(), scale3.data(), shift3.data()), "surtr_place_cells_patterns");
+        uint32_t nb = 0;
+        check(surtr_placed_cells(ctx_, 0, &nb, nullptr), "surtr_placed_cells");
+        cell_base_.assign(nb, 0u);
+        check(surtr_placed_cells(ctx_, nb, &nb, cell_base_.data()), "surtr_placed_cells");
+        std::vector<uint8_t> lmask;
+        if (std::find(flags.begin(), flags.end(), (uint8_t)1) != flags.end())
+        {
+            lmask = two_call_mask("surtr_scene_outside_impacts", [&](uint32_t cap, uint32_t* n, uint8_t* bytes) {
+                return surtr_scene_outside_impacts(ctx_, K, toff.data(), t.data(), soff.data(), fc.data(), shift3.data(), rad.data(), cap, n, bytes);
+            });
+            // the bytes of the impacts that are not partial are cleared: their pieces are all broken
+            const std::vector<uint32_t> table = SceneCompounds();
+            size_t at = 0;
+            for (uint32_t i = 0; i < K; ++i)
+                for (uint32_t k = toff[i]; k < toff[i + 1]; ++k)
+                {
+                    const size_t m = table[(size_t)t[k] + 1] - table[t[k]];
+                    if (!flags[i]) std::fill(lmask.begin() + at, lmask.begin() + at + m, (uint8_t)0);
+                    at += m;
+                }
+        }
+        const bool lany = std::find_if(lmask.begin(), lmask.end(), [](uint8_t o) { return o != 0; }) != lmask.end();
+        check(surtr_scene_fracture_impacts(ctx_, K, toff.data(), t.data(), 0, SURTR_CELLS_ALL, lany ? lmask.data() : nullptr, 0u, &counts_), "surtr_scene_fracture_impacts");
+        return regroup_refit_commit("surtr_event_regroup_impacts_partial", [&](uint32_t* np, uint32_t* nc, uint32_t* off, int32_t* piece, uint32_t* nbod, uint32_t* body) {
+            return surtr_event_regroup_impacts_partial(ctx_, flags.data(), K, soff.data(), fc.data(), shift3.data(), rad.data(), np, nc, off, piece, nbod, body);
+        });
+    }
+    check(surtr_place_cells_impacts(ctx_, K, scale3.data(), shift3.data()), "surtr_place_cells_impacts");
     std::vector<uint8_t> mask;
     if (args.PartialFracture)
         mask = two_call_mask("surtr_scene_outside_impacts", [&](uint32_t cap, uint32_t* n, uint8_t* bytes) {
@@ -1081,7 +1175,8 @@ std::vector<int> FractureEngine::OnImpacts(const std::vector<Impact>& spheres, c
     std::vector<Impact> impacts;
     for (size_t s = 0; s < spheres.size(); ++s)
     {
-        Impact im{spheres[s].position, spheres[s].radius, {}};
+        Impact im = spheres[s];
+        im.compounds.clear();
         for (uint32_t c = 0; c < nc; ++c)
             if (mask[s * nc + c] == 1 && !taken[c]) { taken[c] = 1; im.compounds.push_back((int)c); }      // (the first impact in list order has it)
         if (!im.compounds.empty()) impacts.push_back(im);
@@ -1093,12 +1188,29 @@ std::vector<int> FractureEngine::OnImpacts(const std::vector<Impact>& spheres, c
     // erased ones below it, and the compounds made so far (which sit above every old one) by all of them
     std::vector<int> made;
     std::vector<int> gone;
+    // (impacts with a pattern or a flag of their own: the pattern is selected before each cycle, and the one installed now comes back)
+    const bool library = std::find_if(impacts.begin(), impacts.end(), [](const Impact& im) { return im.pattern >= 0 || im.partial >= 0; }) != impacts.end();
+    if (library) check_impact_patterns(impacts);
+    const int installed = library ? installed_pattern_id() : -1;
+    struct Reinstall { FractureEngine* e; int id; ~Reinstall() { if (id >= 0) { try { e->SelectPattern(id); } catch (const Error&) {} } } } reinstall{this, installed};
+    if (library)
+    {
+        cell_base_.assign(1, 0u);
+        for (const Impact& im : impacts)
+        {
+            uint32_t nc1 = 0;
+            check(surtr_pattern_info(ctx_, (uint32_t)(im.pattern >= 0 ? im.pattern : installed), &nc1, nullptr), "surtr_pattern_info");
+            cell_base_.push_back(cell_base_.back() + nc1);
+        }
+    }
     for (const Impact& im : impacts)
     {
         std::vector<int> now;
         for (int c : im.compounds) now.push_back(c - (int)std::count_if(gone.begin(), gone.end(), [c](int g) { return g < c; }));
         FractureArgs one = args;
         one.ImpactPosition = im.position; one.ImpactRadius = im.radius;
+        if (library) SelectPattern(im.pattern >= 0 ? im.pattern : installed);
+        if (im.partial >= 0) one.PartialFracture = im.partial != 0;
         for (int& c : made) c -= (int)now.size();
         const std::vector<int> more = ExecuteFractureRoutine(now, maxAxisScale, one, spherePointCloud);
         made.insert(made.end(), more.begin(), more.end());
@@ -1279,6 +1391,8 @@ void HandleConvexIsland(CompoundInfo& compoundInfo)
 std::vector<Compound> FractureEngine::DoFracture(const Compound& targetCompound, float maxAxisScale, const FractureArgs& args,
                                                  const std::vector<Vector3>& spherePointCloud, FractureTrace* trace)
 {
+    // localFracturePattern (:1887), when a pair is in use
+    if (pair_partial_ >= 0) SelectPattern(args.PartialFracture ? pair_partial_ : pair_general_);
     // Scale + alignment of the pattern (Src/Surtr.cpp:1890-1896): every cell scaled by MaxAxisScale * 2, moved to the impact
     const float s2 = maxAxisScale * 2.f;
     SetRefittingPointLimit(args.RefittingPointLimit);      // (before the event: its arena is sized for the refit's planes)

@@ -148,11 +148,18 @@ struct FractureArgs
     int RefittingPointLimit = 4;      // points of the limited hull behind a fragment's slab planes (Inc/Surtr.h:93): 4 .. 32 here
     bool RadialMode = true;           // Inc/Surtr.h:100: an impact takes every body its sphere touches, not only the one hit
     float TargetAdder = 0.01f;        // Inc/Surtr.h:109: how far behind the hit the impact is placed, along the ray
+    // the two resident fracture patterns (Inc/Surtr.h:102-107; built at Src/Surtr.cpp:1806-1807): PrepareFracturePatterns
+    float PartialFracturePatternDist = 0.01f;
+    float GeneralFracturePatternDist = 1.0f;
+    int PartialFracturePatternCellCnt = 128;
+    int GeneralFracturePatternCellCnt = 1024;
 };
 
 // DirectX::SimpleMath::Ray as OnMouseDown builds it (Src/Surtr.cpp:178-200): the direction is expected to be of unit length.
 // One contact of a frame above the report threshold: where, how large, and the compounds it breaks.
-struct Impact { Vector3 position; float radius = 0.f; std::vector<int> compounds; };
+// pattern: the stored pattern (FractureEngine::StorePattern) its cells come from, -1 the engine's installed pattern; partial: 0 / 1
+// FractureArgs::PartialFracture for this impact alone, -1 what the call's args say.  Left at -1, both mean what they meant before.
+struct Impact { Vector3 position; float radius = 0.f; std::vector<int> compounds; int pattern = -1; int partial = -1; };
 struct Ray { Vector3 position, direction; Ray() = default; Ray(const Vector3& p, const Vector3& d) : position(p), direction(d) {} };
 // Surtr::ConvexRayIntersection (Src/Surtr.cpp:2460-2497), on the host from the definition of include/surtr_hip.h: the ray's
 // interval [0, inf) clipped by the half-space of every face plane (FacePlane; built from the first three vertices where it was
@@ -223,6 +230,20 @@ public:
     static std::vector<VMACH::Polygon3D> GenerateVoronoiHost(const std::vector<Vector3>& cellPointVec);
     // voro.Scale(scale); voro.Translate(translate) for every cell (Src/Surtr.cpp:1799-1803, 1891-1896).
     void PlacePattern(const Vector3& scale, const Vector3& translate);
+    // ---- the pattern library (surtr_pattern_store / _select / _count / _clear): several patterns resident on the device ----
+    // StorePattern: the installed pattern (SetPattern / GenerateVoronoi / GenerateFracturePattern / SelectPattern) into the library
+    // -> its id.  SelectPattern: a stored pattern becomes the installed one, device to device.  ClearPatterns drops all of them.
+    int StorePattern();
+    void SelectPattern(int id);
+    int PatternCount();
+    void ClearPatterns();
+    // The two patterns the reference keeps for the session (Src/Surtr.cpp:1806-1807), built and stored in its order: the partial one
+    // (PartialFracturePatternCellCnt cells at mean PartialFracturePatternDist), then the general one -> {partialId, generalId}.  The
+    // general pattern is the installed one afterwards.
+    std::pair<int, int> PrepareFracturePatterns(const FractureArgs& args);
+    // After this DoFracture selects by args.PartialFracture as :1887 does: the partial pattern when it is set, else the general
+    // one.  (-1, -1): DoFracture uses the installed pattern again, as it does when this was never called.
+    void UsePatternPair(int partialId, int generalId);
     void SetCompound(const Compound& compound);
     // ExecuteFractureRoutine's pre-transform (Src/Surtr.cpp:1846-1851): Poly::Transform of every resident piece's Convex and
     // Mesh by its world matrix, on the device.
@@ -374,6 +395,11 @@ public:
     // regrouping with each body's own sphere, one refit, one commit.  Returns the compounds made: the scene is the one the
     // several-compound routine called per impact, in the order given, leaves.  When the event flagged a unit and AllowFlagged is off,
     // NOTHING is committed.
+    // When an impact sets `pattern` or `partial`, the frame takes the pattern library instead: one instance of each impact's own
+    // stored pattern (surtr_place_cells_patterns), the mask bytes of the impacts that are not partial cleared, one event over every
+    // cell of every instance, the regrouping with a flag per impact (surtr_event_regroup_impacts_partial).  An impact that leaves
+    // `pattern` at -1 there uses the installed pattern, which is stored for it once.  The installed pattern stays installed.
+    // LastCellBase(): the first global cell of every instance of the last such frame (n + 1 entries).
     std::vector<int> ExecuteFractureRoutine(const std::vector<Impact>& impacts, float maxAxisScale, const FractureArgs& args,
                                             const std::vector<Vector3>& spherePointCloud);
     // The contact callback's work: which bodies does each sphere reach (ONE surtr_scene_overlap call with all the spheres, each of
@@ -382,8 +408,11 @@ public:
     // several impacts goes to the FIRST of them in list order: the later ones do not see it (sequentially they would meet its
     // fragments; that takes a second call).  An impact left without a body is dropped.  acted (may be null) receives the impacts as
     // they ran.  Returns the compounds made, numbered as after the last commit.
+    // Impacts that set `pattern` or `partial` keep them.  With oneEvent off such a frame runs the sequential cycles with SelectPattern
+    // before each and the impact's own flag in its args; the pattern installed before the call is installed again after it.
     std::vector<int> OnImpacts(const std::vector<Impact>& spheres, const FractureArgs& args, float maxAxisScale,
                                const std::vector<Vector3>& spherePointCloud, std::vector<Impact>* acted = nullptr, bool oneEvent = true);
+    const std::vector<uint32_t>& LastCellBase() const { return cell_base_; }
     surtr_counts LastCounts() const { return counts_; }
     // The degenerate policy at this level (include/surtr_hip.h, surtr_counts::n_failed): where the reference leaves its own
     // arrays the engine flags the unit instead of emulating what the reference's memory happens to hold -- a flagged (cell,
@@ -416,6 +445,11 @@ private:
     bool allow_flagged_ = false;
     FlaggedUnits flagged_;
     surtr_ctx* ctx_ = nullptr;
+    void check_impact_patterns(const std::vector<Impact>& impacts);
+    int installed_pattern_id();      // the library id of the installed pattern, stored now if it is not yet
+    int installed_id_ = -1;          // ... -1: not stored, or another pattern has been installed since
+    int pair_partial_ = -1, pair_general_ = -1;      // UsePatternPair
+    std::vector<uint32_t> cell_base_;
     uint32_t n_cells_ = 0, n_pieces_ = 0;
     surtr_counts counts_{};
 };
