@@ -948,6 +948,113 @@ enum { SURTR_CULL_LIGHT = 1, SURTR_CULL_OUTSIDE = 2 };
 int surtr_scene_cull(surtr_ctx* ctx, int set, float density, float min_mass, const float* keep_box6_or_null, int apply,
                      uint32_t* n_compounds, uint8_t* reason, uint32_t* n_removed);
 
+/* ---- cooked hulls: weld, convex hull and coplanar merge of the points of a Convex (cook_dev.hip) ---- */
+/* For the solids surtr::HullUsable refuses (a sliver in the rings: SURTR_HULL_FLAT or a large convexity): the convex hull of the
+ * solid's POINTS, built on the device, as the arrays PxConvexMeshDesc takes (points, PxHullPolygon records, 16-bit indices).  The
+ * rings are not read.  What CookingConvex (Src/Surtr.cpp:2531-2553: eWELD_VERTICES, eCOMPUTE_CONVEX, planeTolerance 7e-6) asks of
+ * PhysX.  Input per solid: float positions p_0 .. p_(n-1), weld_dist >= 0, plane_tol >= 0 (both absolute).  All arithmetic is double,
+ * positions converted to double, every product, sum, division and square root a separate operation, in the order written.
+ *
+ * 1 WELD.  In ascending index, point i is KEPT iff no kept j < i has ((dx dx + dy dy) + dz dz) <= weld_dist * weld_dist (d = p_i -
+ *   p_j).  At 0 that drops equal values (-0 == +0).  n_welded = the points dropped.  The kept points are K_0 .. K_(m-1), ascending.
+ * 2 HULL of the kept points.  The plane of a triangle (a, b, c) is N = (b - a) x (c - a), n = N / sqrt((Nx Nx + Ny Ny) + Nz Nz),
+ *   d = -((n.x a.x + n.y a.y) + n.z a.z); the distance of q is ((n.x q.x + n.y q.y) + n.z q.z) + d.
+ *   START.  A = K_0.  B = the kept point with the largest squared distance from A.  C = the one with the largest |(B - A) x (q - A)|^2.
+ *   D = the one with the largest |distance| from the plane of (A, B, C).  Every tie goes to the lowest index.  DEGENERATE when
+ *   |B - A|^2 <= plane_tol^2, when |(B - A) x (C - A)|^2 <= plane_tol^2 |B - A|^2, or when |distance(D)| <= plane_tol (at plane_tol 0: when any of the three is zero).  With D in front of
+ *   (A, B, C), B and C change places.  The four triangles are (A, B, C), (A, D, B), (B, D, C), (C, D, A), in table slots 0 .. 3.
+ *   INSERTION.  Repeat: over all kept points that have not been a vertex of the table and all triangles of the table, take the largest distance;
+ *   ties go to the lowest point.  Stop when it is not above plane_tol.  Otherwise that point P goes in: the triangles with distance(P) > 0
+ *   are removed, the edges between a removed and a remaining triangle (the horizon, one closed walk) each give a triangle (a, b, P).
+ *   The i-th edge of the walk -- it starts at the lowest removed slot's first horizon edge and runs counter-clockwise -- takes the i-th
+ *   removed slot in ascending order and, past them, the two slots after the table's end; removed slots left over (a vertex all of
+ *   whose triangles went has left the hull) are filled, lowest first, by the triangles from the table's end, last first.  When the loop stops, every kept point is
+ *   at most plane_tol in front of every triangle.  The result does not depend on lanes, stream or batch.
+ * 3 MERGE.  Every triangle starts as a class of its own.  Passes over (triangle slot t, edge k) in ascending order, for the
+ *   neighbour u > t in another class, until a pass merges nothing (eight passes at most): the two classes become one when
+ *   - the boundary of their union is one simple loop (no vertex twice),
+ *   - every vertex of the union's triangles lies within plane_tol of the loop's plane (|distance| <= plane_tol; the plane of a loop is the
+ *     one of the collision hulls above: Newell normal from the loop's smallest vertex, mid-range offset), and
+ *   - every kept point lies at most 2 plane_tol in front of that plane (a small face far from a point tilts against it).
+ *   A class whose boundary is not one simple loop is never formed: its triangles stay apart.
+ *   FIX-UP.  A vertex left on fewer than three loops leaves the loops and the points; the plane of a face is the plane of its FINAL
+ *   loop, from its smallest remaining vertex.  Repeated until nothing changes: a merged class goes back to its triangles when a
+ *   vertex that leaves would leave fewer than three vertices on one of the faces it lies on, or when its final plane, rounded to
+ *   float, misses one of the two BOUNDS of 5.  A hull of triangles alone passes, so this ends.
+ * 4 FACES.  Each loop starts at its smallest vertex and runs counter-clockwise seen from outside; the faces come ordered by
+ *   (smallest vertex, second vertex of the loop).  Inside is n.x + d <= 0.  The plane of a face is the plane of its final loop,
+ *   rounded to float.  Output vertices are bit copies of input positions in ascending source index; src[k] names the input point.
+ * 5 ERRORS, as for surtr_hull, from the FLOAT planes as written, evaluated in double and rounded to float: convexity = the largest
+ *   distance over (EVERY INPUT POINT, welded ones included, face); planarity = the largest |distance| over the faces and their own
+ *   vertices; extent = the largest edge of the box of the input points; reach = their largest coordinate magnitude.
+ *   BOUNDS.  With s_f = 2^-24 ((|n_x| + |n_y| + |n_z|) reach + |d|), the rounding of a written plane: a solid is handed out only if, on
+ *   the planes as written, every face's own vertices lie within plane_tol + s_f of it and every KEPT point at most 2 plane_tol + s_f in
+ *   front of it (the FIX-UP below establishes this, the closing check tests it once more; a solid that misses it is FAILED).  A
+ *   welded point lies within weld_dist of a kept one: convexity <= 2 plane_tol + weld_dist + s_f.
+ * 6 STATUS.  SKIPPED: not selected.  NONFINITE: a coordinate is not finite (decided first).  LARGE: more than 65 535 input points, or
+ *   more kept points than surtr_cook_max_vertices().  FEW: fewer than four kept points.  DEGENERATE: see START.  FAILED: the cooker's own
+ *   closing check did not hold -- a triangle without area, a horizon or a class boundary that does not close, a loop of fewer than
+ *   three vertices, a directed edge that does not occur exactly once with its reverse exactly once, V - E + F != 2, or a bound of 5 missed: such a solid
+ *   is withheld, never handed out wrong.  OVER_255: more than 255 vertices or faces (PhysX's limit), information only.  Every bit but
+ *   OVER_255 withholds the output: nv = n_faces = n_idx = max_loop = 0, the four floats 0; nv_in, status and n_welded (where the weld
+ *   ran to its end) are still set.
+ * Capacity bounds per written solid (Euler): points <= nv_in, polygons <= 2 nv_in - 4, indices <= 6 nv_in - 12. */
+typedef struct surtr_cooked {            /* 64 bytes per solid */
+    uint32_t nv_in, nv, n_faces, n_idx;     /* input points; hull vertices, polygons and indices WRITTEN for this solid */
+    uint32_t status;                        /* SURTR_COOK_* bits */
+    uint32_t pt_off, face_off, idx_off;     /* first point (and src entry) / polygon / index: exclusive sums over the solids before it */
+    uint32_t max_loop, n_welded;
+    float convexity, planarity, extent;
+    float reach;                            /* the largest coordinate magnitude of the input points: the scale of a plane's rounding */
+    uint32_t reserved[2];
+} surtr_cooked;
+enum { SURTR_COOK_SKIPPED = 1, SURTR_COOK_FEW = 2, SURTR_COOK_DEGENERATE = 4, SURTR_COOK_NONFINITE = 8, SURTR_COOK_LARGE = 16,
+       SURTR_COOK_FAILED = 32, SURTR_COOK_OVER_255 = 64 };
+/* The largest number of kept points the cooker takes per solid (at least 256). */
+uint32_t surtr_cook_max_vertices(void);
+/* The Convex of every current fragment / of every resident piece, in order.  dev_records takes one 64-byte header and one surtr_cooked
+ * per solid; the header's nv_in = the solids, nv / n_faces / n_idx = the totals, status = SURTR_OK or SURTR_E_CAPACITY.  dev_points
+ * (3 floats each) and dev_src (the solid-local input index of each point) have room for points_cap points, dev_polys for polys_cap
+ * polygons, dev_idx for idx_cap indices (16-bit, solid-local).  Selection: with dev_hull_records_or_null -- the buffer
+ * surtr_event_hulls_dev / surtr_pieces_hulls_dev wrote for the same solids, header included, on the same stream -- solid f is cooked iff
+ * its hull record is not usable: a FEW / OPEN / IRREGULAR / LARGE / FLAT bit, or convexity or planarity above (float) rel_tol * extent.
+ * A hull header that reports an error or another number of solids gives the header status SURTR_E_STATE and nothing else.  With NULL
+ * every solid is cooked.  The rules of surtr_event_hulls_dev hold: enqueued on the context's stream, no host synchronisation, one
+ * temporary allocation ordered on that stream, no profiling slot (all sixteen are taken); SURTR_E_STATE with no event or after an event
+ * that failed (before any upload for the pieces); SURTR_E_CAPACITY before anything is enqueued when records_bytes cannot hold the
+ * header or, where the host knows the count, the records; every other capacity is checked on the device: the header is written with
+ * SURTR_E_CAPACITY and the totals needed, and nothing else is.  SURTR_E_INVALID for a tolerance that is negative or not finite. */
+int surtr_event_cook_dev(surtr_ctx* ctx, const void* dev_hull_records_or_null, float rel_tol, float weld_dist, float plane_tol, void* dev_records,
+                         size_t records_bytes, float* dev_points, size_t points_cap, uint32_t* dev_src, surtr_hull_polygon* dev_polys,
+                         size_t polys_cap, uint16_t* dev_idx, size_t idx_cap);
+int surtr_pieces_cook_dev(surtr_ctx* ctx, const void* dev_hull_records_or_null, float rel_tol, float weld_dist, float plane_tol, void* dev_records,
+                          size_t records_bytes, float* dev_points, size_t points_cap, uint32_t* dev_src, surtr_hull_polygon* dev_polys,
+                          size_t polys_cap, uint16_t* dev_idx, size_t idx_cap);
+/* Host forms, synchronous, count-then-fill as surtr_event_hulls: with the five arrays NULL the four counts come back (records without
+ * the header, points, polygons, indices); with all five given the counts must hold the capacities.  hull_records_or_null: n_hull
+ * surtr_hull records in host memory (what surtr_event_hulls / surtr_pieces_hulls returned; n_hull must be the number of solids, else
+ * SURTR_E_INVALID) select as above; NULL cooks every solid. */
+int surtr_event_cook(surtr_ctx* ctx, const surtr_hull* hull_records_or_null, uint32_t n_hull, float rel_tol, float weld_dist, float plane_tol,
+                     uint32_t* n, surtr_cooked* records, uint32_t* n_points, float* points, uint32_t* src, uint32_t* n_polys,
+                     surtr_hull_polygon* polys, uint32_t* n_idx, uint16_t* idx);
+int surtr_pieces_cook(surtr_ctx* ctx, const surtr_hull* hull_records_or_null, uint32_t n_hull, float rel_tol, float weld_dist, float plane_tol,
+                      uint32_t* n, surtr_cooked* records, uint32_t* n_points, float* points, uint32_t* src, uint32_t* n_polys,
+                      surtr_hull_polygon* polys, uint32_t* n_idx, uint16_t* idx);
+/* The whole collision hand-off of the current fragments in one call: surtr_event_hulls_dev, surtr_event_cook_dev right behind it on the
+ * context's stream (the selection is made on the device from the records where they lie), one read of the two headers and ONE download
+ * of both answers.  Every array is given, and every count holds the capacity of its array on entry and what was written on return
+ * (SURTR_E_CAPACITY and the counts when one is too small; nothing is written then).  Always enough, from surtr_event_counts: n_frag
+ * records of each kind, conv_nbrs hull polygons and hull indices, conv_verts points, 2 conv_verts polygons, 6 conv_verts indices. */
+int surtr_event_hulls_cook(surtr_ctx* ctx, float rel_tol, float weld_dist, float plane_tol, uint32_t* n, surtr_hull* hulls, uint32_t* n_hull_polys,
+                           surtr_hull_polygon* hull_polys, uint32_t* n_hull_idx, uint16_t* hull_idx, surtr_cooked* records, uint32_t* n_points,
+                           float* points, uint32_t* src, uint32_t* n_polys, surtr_hull_polygon* polys, uint32_t* n_idx, uint16_t* idx);
+/* The same kernels on point sets in host memory: solid s has the points [vert_off[s], vert_off[s + 1]) of pos (vert_off ascending from
+ * 0, n_solids + 1 entries; an empty solid is FEW).  Every solid is cooked.  For the ACH of PrepareFracture, and for point sets no
+ * Convex has.  The context's event and pieces are not touched. */
+int surtr_cook_points(surtr_ctx* ctx, uint32_t n_solids, const uint32_t* vert_off, const float* pos, float weld_dist, float plane_tol,
+                      uint32_t* n, surtr_cooked* records, uint32_t* n_points, float* points, uint32_t* src, uint32_t* n_polys,
+                      surtr_hull_polygon* polys, uint32_t* n_idx, uint16_t* idx);
+
 #ifdef __cplusplus
 }
 #endif

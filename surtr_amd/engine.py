@@ -58,6 +58,32 @@ def hull_usable(record, rel_tol=1e-5):
     return bool(record["convexity"] <= tol and record["planarity"] <= tol)
 
 
+# surtr_cooked (include/surtr_hip.h), 64 bytes: one record per solid of event_cook / pieces_cook / cook_points
+COOK_DTYPE = np.dtype([("nv_in", "<u4"), ("nv", "<u4"), ("n_faces", "<u4"), ("n_idx", "<u4"), ("status", "<u4"), ("pt_off", "<u4"),
+                       ("face_off", "<u4"), ("idx_off", "<u4"), ("max_loop", "<u4"), ("n_welded", "<u4"), ("convexity", "<f4"),
+                       ("planarity", "<f4"), ("extent", "<f4"), ("reach", "<f4"), ("reserved", "<u4", (2,))])
+assert COOK_DTYPE.itemsize == 64
+COOK_SKIPPED, COOK_FEW, COOK_DEGENERATE, COOK_NONFINITE, COOK_LARGE, COOK_FAILED, COOK_OVER_255 = 1, 2, 4, 8, 16, 32, 64
+COOK_WITHHELD = COOK_SKIPPED | COOK_FEW | COOK_DEGENERATE | COOK_NONFINITE | COOK_LARGE | COOK_FAILED
+
+
+def cooked_usable(record, plane_tol=7e-6, weld_dist=0.0):
+    """surtr::CookedUsable: no withholding bit, planarity <= plane_tol + s and convexity <= 2 plane_tol + weld_dist + s, where
+    s = 2^-24 * 3.5 * reach bounds the rounding of a written plane: |n_x| + |n_y| + |n_z| <= sqrt(3) and |d| <= sqrt(3) reach for a
+    unit normal and a plane that passes among points of coordinates within reach."""
+    if int(record["status"]) & COOK_WITHHELD:
+        return False
+    s = 2.0 ** -24 * 3.5 * float(record["reach"])
+    return bool(record["planarity"] <= plane_tol + s and record["convexity"] <= 2.0 * plane_tol + weld_dist + s)
+
+
+def cook_max_vertices():
+    """surtr_cook_max_vertices: the most kept points the cooker takes per solid."""
+    f = lib().surtr_cook_max_vertices
+    f.restype = ctypes.c_uint32
+    return int(f())
+
+
 # surtr_ray_hit (include/surtr_hip.h), 48 bytes; status bits and the per-piece status bits of a query
 RAY_HIT_DTYPE = np.dtype([("piece", "<i4"), ("status", "<u4"), ("t", "<f4"), ("pos", "<f4", (3,)), ("normal", "<f4", (3,)),
                           ("reserved", "<u4", (3,))])
@@ -542,6 +568,55 @@ class Engine:
     def pieces_hulls_dev(self, dev_records, records_bytes, dev_polys, polys_cap, dev_idx, idx_cap):
         self._ck(lib().surtr_pieces_hulls_dev(self._h, ctypes.c_void_p(dev_records), ctypes.c_size_t(records_bytes), ctypes.c_void_p(dev_polys),
                                               ctypes.c_size_t(polys_cap), ctypes.c_void_p(dev_idx), ctypes.c_size_t(idx_cap)))
+
+    def _cook(self, call):
+        c = [ctypes.c_uint32() for _ in range(4)]
+        self._ck(call(ctypes.byref(c[0]), None, ctypes.byref(c[1]), None, None, ctypes.byref(c[2]), None, ctypes.byref(c[3]), None))
+        rec, pts, src = np.zeros(c[0].value, COOK_DTYPE), np.zeros((c[1].value, 3), np.float32), np.zeros(c[1].value, np.uint32)
+        poly, idx = np.zeros(c[2].value, POLY_DTYPE), np.zeros(c[3].value, np.uint16)
+        self._ck(call(ctypes.byref(c[0]), _p(rec), ctypes.byref(c[1]), _p(pts), _p(src), ctypes.byref(c[2]), _p(poly), ctypes.byref(c[3]), _p(idx)))
+        return {"records": rec, "points": pts, "src": src, "polygons": poly, "idx": idx}
+
+    def _cook_sel(self, fn, hulls, rel_tol, weld_dist, plane_tol):
+        h = None if hulls is None else np.ascontiguousarray(hulls, HULL_DTYPE)
+        return self._cook(lambda *a: fn(self._h, None if h is None else _p(h), ctypes.c_uint32(0 if h is None else h.shape[0]),
+                                        ctypes.c_float(rel_tol), ctypes.c_float(weld_dist), ctypes.c_float(plane_tol), *a))
+
+    def event_cook(self, hulls=None, rel_tol=1e-5, weld_dist=0.0, plane_tol=7e-6):
+        """surtr_event_cook: weld, convex hull and coplanar merge of the points of the Convex of every current fragment, on the
+        device -> {records (COOK_DTYPE), points f32[n, 3], src (the input point of each), polygons (POLY_DTYPE), idx (uint16)}.
+        hulls: the records of event_hulls; only the solids hull_usable refuses at rel_tol are cooked.  None: every solid."""
+        return self._cook_sel(lib().surtr_event_cook, hulls, rel_tol, weld_dist, plane_tol)
+
+    def pieces_cook(self, hulls=None, rel_tol=1e-5, weld_dist=0.0, plane_tol=7e-6):
+        """surtr_pieces_cook: the same for the Convex solids of the resident pieces (hulls: the records of pieces_hulls)."""
+        return self._cook_sel(lib().surtr_pieces_cook, hulls, rel_tol, weld_dist, plane_tol)
+
+    def cook_points(self, solids, weld_dist=0.0, plane_tol=7e-6):
+        """surtr_cook_points: the same kernels on point sets of the host (a list of f32[n, 3] arrays), every one cooked."""
+        arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in solids]
+        vo = np.concatenate([[0], np.cumsum([a.shape[0] for a in arrs])]).astype(np.uint32)
+        pos = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros((0, 3), np.float32), np.float32)
+        return self._cook(lambda *a: lib().surtr_cook_points(self._h, ctypes.c_uint32(len(arrs)), _p(vo), _p(pos), ctypes.c_float(weld_dist),
+                                                             ctypes.c_float(plane_tol), *a))
+
+    def _cook_dev(self, fn, dev_hulls, rel_tol, weld_dist, plane_tol, dev_records, records_bytes, dev_points, points_cap, dev_src, dev_polys,
+                  polys_cap, dev_idx, idx_cap):
+        self._ck(fn(self._h, ctypes.c_void_p(dev_hulls or None), ctypes.c_float(rel_tol), ctypes.c_float(weld_dist), ctypes.c_float(plane_tol),
+                    ctypes.c_void_p(dev_records), ctypes.c_size_t(records_bytes), ctypes.c_void_p(dev_points), ctypes.c_size_t(points_cap),
+                    ctypes.c_void_p(dev_src), ctypes.c_void_p(dev_polys), ctypes.c_size_t(polys_cap), ctypes.c_void_p(dev_idx), ctypes.c_size_t(idx_cap)))
+
+    def event_cook_dev(self, dev_hulls, rel_tol, weld_dist, plane_tol, dev_records, records_bytes, dev_points, points_cap, dev_src, dev_polys,
+                       polys_cap, dev_idx, idx_cap):
+        """surtr_event_cook_dev: header + records, points, src, polygons and indices into device buffers, on the context's stream,
+        without a synchronisation.  dev_hulls: the buffer event_hulls_dev wrote (0 / None: every solid is cooked)."""
+        self._cook_dev(lib().surtr_event_cook_dev, dev_hulls, rel_tol, weld_dist, plane_tol, dev_records, records_bytes, dev_points, points_cap,
+                       dev_src, dev_polys, polys_cap, dev_idx, idx_cap)
+
+    def pieces_cook_dev(self, dev_hulls, rel_tol, weld_dist, plane_tol, dev_records, records_bytes, dev_points, points_cap, dev_src, dev_polys,
+                        polys_cap, dev_idx, idx_cap):
+        self._cook_dev(lib().surtr_pieces_cook_dev, dev_hulls, rel_tol, weld_dist, plane_tol, dev_records, records_bytes, dev_points, points_cap,
+                       dev_src, dev_polys, polys_cap, dev_idx, idx_cap)
 
     def pieces_raycast(self, rays):
         """surtr_pieces_raycast: rays f32[n, 7] (origin, direction, max_dist) against the Convex solids of the resident pieces,

@@ -31,6 +31,9 @@
 //                 commit (ExecuteFractureRoutine over several compounds) instead of one of each per compound; the JSON is the same.
 // --init-compounds [--init-compounds-obj DIR] (with --scene-clicks or --body-clicks): after each click, InitCompounds on the compounds it
 //                 made -- their render buffers straight from the resident scene (surtr_scene_fragments) --, one JSON line per compound.
+// --cook (with --init-compounds --hulls): InitCompounds(..., cookUnusable): every line also carries the pieces HullUsable refuses and
+//                 the cooker took (cooked), how many of them CookedUsable accepts, the OR of their status words, their points,
+//                 polygons and indices, and an FNV-1a of points + polygons + indices.
 // --hulls (with --init-compounds): InitCompounds with the collision hulls (InitCompoundResult::Hull); every line also carries the
 //                 compound's hull polygons and indices, the number of its hulls HullUsable accepts, and an FNV-1a of polygons + indices;
 //                 SetExtract of the same fragments is checked against the loops (a difference ends the run with status 3).
@@ -355,11 +358,12 @@ static void pick(FractureEngine& eng, const std::vector<Fragment>& frags, const 
 // writes them as DIR/click<q>_compound<c>.obj, one object per piece.
 static bool g_init_compounds = false;
 static bool g_hulls = false;
+static bool g_cook = false;
 static std::string g_init_obj;
 static void init_compounds(FractureEngine& eng, size_t click, const std::vector<int>& made)
 {
     if (!g_init_compounds || made.empty()) return;
-    const std::vector<std::vector<InitCompoundResult>> res = eng.InitCompounds(made, false, g_hulls);
+    const std::vector<std::vector<InitCompoundResult>> res = eng.InitCompounds(made, false, g_hulls, g_hulls && g_cook);
     const std::vector<uint32_t> table = eng.SceneCompounds();
     if (g_hulls)
     {
@@ -398,6 +402,25 @@ static void init_compounds(FractureEngine& eng, size_t click, const std::vector<
             for (const auto& r : res[k]) { eat(r.Hull.Polygons.data(), r.Hull.Polygons.size() * sizeof(surtr_hull_polygon)); np += r.Hull.Polygons.size(); }
             for (const auto& r : res[k]) { eat(r.Hull.Indices.data(), r.Hull.Indices.size() * 2); nx += r.Hull.Indices.size(); usable += HullUsable(r.Hull.Record) ? 1 : 0; }
             printf(", \"hull_polygons\": %zu, \"hull_indices\": %zu, \"hulls_usable\": %zu, \"hull_fnv\": \"%016llx\"", np, nx, usable, h);
+        }
+        if (g_hulls && g_cook)
+        {
+            // the pieces HullUsable refuses, cooked: how many, how many CookedUsable accepts, the OR of their status words, the totals,
+            // and an FNV-1a of points, then polygons, then indices, piece after piece each
+            size_t nc = 0, ok = 0, npt = 0, np = 0, nx = 0;
+            unsigned st = 0;
+            h = 0xCBF29CE484222325ull;
+            for (const auto& r : res[k])
+            {
+                if (r.Cooked.Record.status & SURTR_COOK_SKIPPED) continue;
+                ++nc; ok += CookedUsable(r.Cooked.Record) ? 1 : 0; st |= r.Cooked.Record.status;
+                npt += r.Cooked.Points.size(); np += r.Cooked.Polygons.size(); nx += r.Cooked.Indices.size();
+            }
+            for (const auto& r : res[k]) for (const auto& p : r.Cooked.Points) { const float xyz[3] = {p.x, p.y, p.z}; eat(xyz, 12); }
+            for (const auto& r : res[k]) eat(r.Cooked.Polygons.data(), r.Cooked.Polygons.size() * sizeof(surtr_hull_polygon));
+            for (const auto& r : res[k]) eat(r.Cooked.Indices.data(), r.Cooked.Indices.size() * 2);
+            printf(", \"cooked\": %zu, \"cooked_usable\": %zu, \"cook_status\": %u, \"cook_points\": %zu, \"cook_polygons\": %zu, \"cook_indices\": %zu, "
+                   "\"cook_fnv\": \"%016llx\"", nc, ok, st, npt, np, nx, h);
         }
         printf("}\n");
         if (g_init_obj.empty()) continue;
@@ -734,6 +757,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--pattern-pair")) pair = true;
         else if (!strcmp(argv[i], "--init-compounds")) g_init_compounds = true;
         else if (!strcmp(argv[i], "--hulls")) g_hulls = true;
+        else if (!strcmp(argv[i], "--cook")) g_cook = true;
         else if (!strcmp(argv[i], "--bounds")) g_bounds = true;
         else if (!strcmp(argv[i], "--cull-mass") && i + 1 < argc) { g_cull = true; g_cull_mass = (float)atof(argv[++i]); }
         else if (!strcmp(argv[i], "--keep-box") && i + 1 < argc)

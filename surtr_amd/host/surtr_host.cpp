@@ -626,6 +626,43 @@ HullSet FractureEngine::PieceHulls()
                     "surtr_pieces_hulls");
 }
 
+namespace {
+template <class F>
+CookedSet cooked_of(const HullSet* hulls, F call, const char* what)
+{
+    CookedSet c;
+    const surtr_hull* hr = hulls && !hulls->Records.empty() ? hulls->Records.data() : nullptr;
+    const uint32_t nh = hulls ? (uint32_t)hulls->Records.size() : 0u;
+    uint32_t n = 0, nv = 0, np = 0, ni = 0;
+    int rc = call(hr, nh, &n, nullptr, &nv, nullptr, nullptr, &np, nullptr, &ni, nullptr);
+    if (rc) throw Error(rc, what);
+    c.Records.resize(n); c.Points.resize(3 * (size_t)nv); c.Source.resize(nv); c.Polygons.resize(np); c.Indices.resize(ni);
+    surtr_cooked r0; float f0[3]; uint32_t s0; surtr_hull_polygon p0; uint16_t i0;
+    rc = call(hr, nh, &n, n ? c.Records.data() : &r0, &nv, nv ? c.Points.data() : f0, nv ? c.Source.data() : &s0, &np, np ? c.Polygons.data() : &p0, &ni,
+              ni ? c.Indices.data() : &i0);
+    if (rc) throw Error(rc, what);
+    return c;
+}
+}
+
+CookedSet FractureEngine::CookHulls(bool unusableOnly, float relTol, float weldDistance, float planeTolerance)
+{
+    HullSet h;
+    if (unusableOnly) h = Hulls();
+    return cooked_of(unusableOnly ? &h : nullptr, [&](const surtr_hull* hr, uint32_t nh, uint32_t* n, surtr_cooked* r, uint32_t* nv, float* pts, uint32_t* src,
+                                                      uint32_t* np, surtr_hull_polygon* p, uint32_t* ni, uint16_t* i) {
+        return surtr_event_cook(ctx_, hr, nh, relTol, weldDistance, planeTolerance, n, r, nv, pts, src, np, p, ni, i); }, "surtr_event_cook");
+}
+
+CookedSet FractureEngine::CookPieceHulls(bool unusableOnly, float relTol, float weldDistance, float planeTolerance)
+{
+    HullSet h;
+    if (unusableOnly) h = PieceHulls();
+    return cooked_of(unusableOnly ? &h : nullptr, [&](const surtr_hull* hr, uint32_t nh, uint32_t* n, surtr_cooked* r, uint32_t* nv, float* pts, uint32_t* src,
+                                                      uint32_t* np, surtr_hull_polygon* p, uint32_t* ni, uint16_t* i) {
+        return surtr_pieces_cook(ctx_, hr, nh, relTol, weldDistance, planeTolerance, n, r, nv, pts, src, np, p, ni, i); }, "surtr_pieces_cook");
+}
+
 std::vector<Poly::Extract> FractureEngine::SetExtract()
 {
     const HullSet h = Hulls();
@@ -1011,8 +1048,10 @@ std::vector<int> FractureEngine::PickBodies(const Vector3& origin, const Vector3
     return out;
 }
 
-std::vector<std::vector<InitCompoundResult>> FractureEngine::InitCompounds(const std::vector<int>& compounds, bool renderConvex, bool withHulls)
+std::vector<std::vector<InitCompoundResult>> FractureEngine::InitCompounds(const std::vector<int>& compounds, bool renderConvex, bool withHulls, bool cookUnusable,
+                                                                           const FractureArgs& cookArgs)
 {
+    if (cookUnusable && !withHulls) throw Error(SURTR_E_INVALID, "InitCompounds: cookUnusable needs withHulls");
     std::vector<std::vector<InitCompoundResult>> out;
     if (compounds.empty()) return out;
     std::vector<uint32_t> list;
@@ -1034,7 +1073,20 @@ std::vector<std::vector<InitCompoundResult>> FractureEngine::InitCompounds(const
         throw Error(SURTR_E_TOPOLOGY, "InitCompounds: " + std::to_string(flagged_.fragments.size()) +
                     " piece(s) flagged (their faces cannot be extracted; AllowFlagged(true) returns the rest)");
     HullSet hulls;
-    if (withHulls) hulls = Hulls();
+    CookedSet cooked;
+    if (cookUnusable)
+    {
+        // both answers from one call: arrays at the bounds that are always enough, cut to what was written
+        uint32_t n = c.n_frag, hp = std::max(c.conv_nbrs, 1u), hi = hp, nv = std::max(c.conv_verts, 1u), np = 2 * nv, ni = 6 * nv;
+        hulls.Records.resize(std::max(n, 1u)); hulls.Polygons.resize(hp); hulls.Indices.resize(hi);
+        cooked.Records.resize(std::max(n, 1u)); cooked.Points.resize(3 * (size_t)nv); cooked.Source.resize(nv); cooked.Polygons.resize(np); cooked.Indices.resize(ni);
+        check(surtr_event_hulls_cook(ctx_, cookArgs.HullRelTolerance, cookArgs.CookWeldDistance, cookArgs.CookPlaneTolerance, &n, hulls.Records.data(), &hp,
+                                     hulls.Polygons.data(), &hi, hulls.Indices.data(), cooked.Records.data(), &nv, cooked.Points.data(), cooked.Source.data(), &np,
+                                     cooked.Polygons.data(), &ni, cooked.Indices.data()), "surtr_event_hulls_cook");
+        hulls.Records.resize(n); hulls.Polygons.resize(hp); hulls.Indices.resize(hi);
+        cooked.Records.resize(n); cooked.Points.resize(3 * (size_t)nv); cooked.Source.resize(nv); cooked.Polygons.resize(np); cooked.Indices.resize(ni);
+    }
+    else if (withHulls) hulls = Hulls();
     uint32_t f = 0;
     for (uint32_t comp : list)
     {
@@ -1052,6 +1104,15 @@ std::vector<std::vector<InitCompoundResult>> FractureEngine::InitCompounds(const
                 r.Hull.Record = h;
                 r.Hull.Polygons.assign(hulls.Polygons.begin() + h.face_off, hulls.Polygons.begin() + h.face_off + h.n_faces);
                 r.Hull.Indices.assign(hulls.Indices.begin() + h.idx_off, hulls.Indices.begin() + h.idx_off + h.n_idx);
+            }
+            if (cookUnusable)
+            {
+                const surtr_cooked& k = cooked.Records[f];
+                r.Cooked.Record = k;
+                for (uint32_t v = k.pt_off; v < k.pt_off + k.nv; ++v) r.Cooked.Points.emplace_back(cooked.Points[3 * (size_t)v], cooked.Points[3 * (size_t)v + 1], cooked.Points[3 * (size_t)v + 2]);
+                r.Cooked.Source.assign(cooked.Source.begin() + k.pt_off, cooked.Source.begin() + k.pt_off + k.nv);
+                r.Cooked.Polygons.assign(cooked.Polygons.begin() + k.face_off, cooked.Polygons.begin() + k.face_off + k.n_faces);
+                r.Cooked.Indices.assign(cooked.Indices.begin() + k.idx_off, cooked.Indices.begin() + k.idx_off + k.n_idx);
             }
             out.back().push_back(std::move(r));
         }

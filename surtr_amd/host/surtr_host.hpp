@@ -153,6 +153,11 @@ struct FractureArgs
     float GeneralFracturePatternDist = 1.0f;
     int PartialFracturePatternCellCnt = 128;
     int GeneralFracturePatternCellCnt = 1024;
+    // the cooker's tolerances, absolute, as CookingConvex sets them (Src/Surtr.cpp:2531-2553: eWELD_VERTICES with no weld distance,
+    // planeTolerance 0.000007f): FractureEngine::CookHulls / CookPieceHulls / InitCompounds(..., cookUnusable)
+    float CookWeldDistance = 0.f;
+    float CookPlaneTolerance = 7e-6f;
+    float HullRelTolerance = 1e-5f;   // HullUsable's relTol: which pieces the cooker takes
 };
 
 // DirectX::SimpleMath::Ray as OnMouseDown builds it (Src/Surtr.cpp:178-200): the direction is expected to be of unit length.
@@ -187,7 +192,30 @@ void RefittingTask(Piece* piece);
 // Compound::PieceExtractedConvex -- the Convex's face loops as PxHullPolygon records with 16-bit indices into ConvexPoints, the planes
 // as include/surtr_hip.h defines them, and the record that says whether the hull can skip quickhull (HullUsable).
 struct HullData { surtr_hull Record{}; std::vector<surtr_hull_polygon> Polygons; std::vector<uint16_t> Indices; };
-struct InitCompoundResult { std::vector<Vector3> ConvexPoints; FragmentRender Mesh; HullData Hull; };
+// Cooked (filled only with cookUnusable, and only for a piece HullUsable refuses; else Record.status == SURTR_COOK_SKIPPED): the
+// convex hull of ConvexPoints built on the device (include/surtr_hip.h, "cooked hulls") -- Points / Polygons / Indices go into
+// PxConvexMeshDesc as they are (16-bit indices), Source names the ConvexPoints entry of every point.
+struct CookedData
+{
+    surtr_cooked Record{}; std::vector<Vector3> Points; std::vector<uint32_t> Source; std::vector<surtr_hull_polygon> Polygons; std::vector<uint16_t> Indices;
+};
+struct InitCompoundResult { std::vector<Vector3> ConvexPoints; FragmentRender Mesh; HullData Hull; CookedData Cooked; };
+// No withholding bit, planarity within planeTol and convexity within 2 planeTol + weldDist, each plus the rounding of a written
+// plane at its largest: 2^-24 * 3.5 * reach (|n_x| + |n_y| + |n_z| <= sqrt 3, |d| <= sqrt 3 * reach).  A cooked hull that fails --
+// a flat or otherwise withheld solid -- is left to PxConvexFlag::eCOMPUTE_CONVEX.
+inline bool CookedUsable(const surtr_cooked& c, float planeTol = 7e-6f, float weldDist = 0.f)
+{
+    if (c.status & ~(uint32_t)SURTR_COOK_OVER_255) return false;
+    const double s = 3.5 * (double)c.reach / 16777216.0;
+    return (double)c.planarity <= (double)planeTol + s && (double)c.convexity <= 2.0 * (double)planeTol + (double)weldDist + s;
+}
+// The cooked hulls of a set of solids as the device wrote them: Records[k]'s points are Points[3 pt_off ..) (and Source[pt_off ..)),
+// its polygons Polygons[face_off ..), its indices Indices[idx_off ..), solid-local.
+struct CookedSet
+{
+    std::vector<surtr_cooked> Records; std::vector<float> Points; std::vector<uint32_t> Source; std::vector<surtr_hull_polygon> Polygons;
+    std::vector<uint16_t> Indices;
+};
 // No withholding bit, no flat face, and both errors within relTol of the solid's extent.  A hull that fails falls back to
 // ConvexPoints (PxConvexFlag::eCOMPUTE_CONVEX, CookingConvex :2531-2553).
 inline bool HullUsable(const surtr_hull& h, float relTol = 1e-5f)
@@ -289,6 +317,10 @@ public:
     // fragments as Compound::PieceExtractedConvex holds them, from the same download.
     HullSet Hulls();
     HullSet PieceHulls();
+    // Cooked hulls (surtr_event_cook / surtr_pieces_cook) of the current fragments / the resident pieces.  unusableOnly: only the
+    // solids whose ring hull HullUsable refuses at relTol are cooked (the rest come back SURTR_COOK_SKIPPED); else every solid.
+    CookedSet CookHulls(bool unusableOnly = true, float relTol = 1e-5f, float weldDistance = 0.f, float planeTolerance = 7e-6f);
+    CookedSet CookPieceHulls(bool unusableOnly = true, float relTol = 1e-5f, float weldDistance = 0.f, float planeTolerance = 7e-6f);
     std::vector<Poly::Extract> SetExtract();
     std::vector<surtr_mass> MassProperties(int set, float density = 10.f);
     std::vector<surtr_mass> PieceMassProperties(int set, float density = 10.f);
@@ -343,7 +375,11 @@ public:
     // be extracted is flagged: as everywhere, that throws unless AllowFlagged(true); then it comes back without triangles and
     // LastFlagged().fragments names it by its position in the call's piece order.
     // withHulls: InitCompoundResult::Hull of every piece as well (surtr_event_hulls on the fragments the call presents).
-    std::vector<std::vector<InitCompoundResult>> InitCompounds(const std::vector<int>& compounds, bool renderConvex, bool withHulls = false);
+    // cookUnusable (with withHulls): InitCompoundResult::Cooked for the pieces HullUsable refuses at cookArgs.HullRelTolerance, cooked
+    // at cookArgs.CookWeldDistance / CookPlaneTolerance; hulls and cooker run behind each other on the device and come back in one
+    // download (surtr_event_hulls_cook).  Every other member is what the call without the flag returns.
+    std::vector<std::vector<InitCompoundResult>> InitCompounds(const std::vector<int>& compounds, bool renderConvex, bool withHulls = false,
+                                                               bool cookUnusable = false, const FractureArgs& cookArgs = FractureArgs());
     std::vector<InitCompoundResult> InitCompound(int compound, bool renderConvex, bool withHulls = false);
     // ---- bodies that move (Update writes each body's pose into m_structuredBufferData[i].WorldMatrix, Src/Surtr.cpp:347-352) ----
     // One rigid pose per compound of the scene (surtr_scene_set_poses: Matrix::m in the layout TransformCompound takes); the resident
