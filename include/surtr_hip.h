@@ -1055,6 +1055,63 @@ int surtr_cook_points(surtr_ctx* ctx, uint32_t n_solids, const uint32_t* vert_of
                       uint32_t* n, surtr_cooked* records, uint32_t* n_points, float* points, uint32_t* src, uint32_t* n_polys,
                       surtr_hull_polygon* polys, uint32_t* n_idx, uint16_t* idx);
 
+/* ---- lit render buffers: the face normal on every triangle vertex (shade_dev.hip) ---- */
+/* What Poly::RenderPolyhedronNormal (Inc/Poly.h:50-61, Src/Poly.cpp:619-679; VMACH::PolygonFace::Render, Src/VMACH.cpp:99-141) hands a
+ * renderer: three unshared VertexNormalColor per triangle, each with the normal of its face, and running indices.  k_faces writes
+ * Poly::RenderPolyhedron's buffers, whose normals are zero and which the reference's pixel shader draws unlit.
+ *
+ * INPUT.  The current fragments (an event's, surtr_load_fragments' or surtr_scene_fragments') after they have been triangulated:
+ * SURTR_EVT_RENDER was set or surtr_event_triangulate ran.  The solid in the Mesh slot and its idx are the input, whatever
+ * render_convex / is_convex was.
+ * FACES.  The loops Poly::ExtractFaces yields, numbered in its order: by leading half-edge, i.e. by (start vertex, ring slot), each loop
+ * from its smallest vertex -- the definition the collision hulls use.  The half-edge (a -> b) is the entry b of ring(a); its id is its
+ * position in the fragment's packed rings; its successor is the entry of ring(b) listed just before a (the last one when a is first).
+ * NORMAL of a loop q_0 .. q_(k-1), positions converted to double: T_i = (q_i - q_0) x (q_(i+1) - q_0), i = 1 .. k-2; N = sum T_i in
+ *   double; n = N / sqrt((Nx Nx + Ny Ny) + Nz Nz) rounded to float; n = (0, 0, 0) when N.N is zero or not finite or k < 3 (drawn
+ *   unlit, as the reference's shader does).  In loop order this is outward, the direction RenderPolyhedronNormal's IsCCW flip settles
+ *   on.  THE ORDER OF THE SUM IS FIXED: the loop's terms lie in loop order and are added as a balanced tree -- in round d = 1, 2, 4, ...
+ *   entry i with i mod 2d == 0 takes entry i + d (where there is one) -- so the bits are the same from run to run, on any stream,
+ *   under any in-flight hint and beside any other work; nothing is accumulated with floating-point atomics.  Deviation, stated: the
+ *   reference takes the magnitude from the loop's first three vertices, which does not hold on slivers; this is no bit-parity item.
+ * FACE OF A TRIANGLE (a, b, c) of idx: the face that owns a half-edge leaving a, one leaving b and one leaving c; the lowest-numbered
+ *   when several do.  Triangles are not counted per face: a face that stalled and wrote none disturbs nothing.
+ * FALLBACK.  A fragment whose successor is no permutation of its half-edges (a ring lists a neighbour twice, a link lacks its way
+ *   back, an entry names no vertex, the rings are not packed in vertex order) takes it as a whole and has n_faces == 0; a single
+ *   triangle takes it when no face is common to its corners.  Then n = (b - a) x (c - a) in double, normalised (zero stays zero), the
+ *   face number is SURTR_SHADE_NO_FACE and the fragment's record carries SURTR_SHADE_PER_TRIANGLE.
+ * OUTPUT.  Vertex j is the 36-byte VertexNormalColor {position, normal, colour} of index j of the packed idx (fragment order, at the
+ *   idx_off surtr_event_download reports): the position of Mesh vertex idx[j] of its fragment, the normal above, `color` (NULL: 0.25
+ *   grey, as surtr_triangulate).  The index buffer is 0, 1, 2, ... and is not written.  tri_face[j / 3] (optional): the face number
+ *   within the fragment.  One surtr_shaded record per fragment behind a 16-byte header of the same shape: first_vertex = the
+ *   fragments, n_vertices = the vertices of all, n_faces = the faces of all, status = SURTR_OK or SURTR_E_CAPACITY.  A fragment
+ *   without triangles writes nothing and has n_vertices == 0 (its faces are still counted). */
+typedef struct surtr_shaded {
+    uint32_t first_vertex, n_vertices;     /* = idx_off, idx_n of the fragment */
+    uint32_t n_faces;                      /* loops of the fragment; 0 when it took the fallback as a whole */
+    uint32_t status;                       /* SURTR_SHADE_* bits */
+} surtr_shaded;
+enum { SURTR_SHADE_PER_TRIANGLE = 1 };
+#define SURTR_SHADE_NO_FACE 0xFFFFFFFFu
+/* Into device buffers: dev_records has records_bytes bytes (16 per fragment + the header), dev_vnc room for vnc_cap vertices (36 bytes
+ * each), dev_tri_face (may be NULL, then tri_cap must be 0) for tri_cap triangles.  Enqueued on the context's stream with no host
+ * synchronisation; one temporary device allocation ordered on that stream; no profiling slot (all sixteen of surtr_kernel_times are
+ * taken).  SURTR_E_STATE with no current fragments, after an event that failed, or when they were never triangulated.
+ * SURTR_E_CAPACITY before anything is enqueued where the host holds the event's counts (surtr_counts::n_idx vertices, n_idx / 3
+ * triangles and n_frag + 1 records always suffice); where only the device knows them, the header is written with SURTR_E_CAPACITY and
+ * the totals needed, and nothing else is.  SURTR_E_INVALID for a NULL context or record buffer, or an array that is NULL with a
+ * capacity (or the reverse).  On any error the context and the current fragments are unchanged; the call never changes them. */
+int surtr_event_shaded_dev(surtr_ctx* ctx, const float color[3], void* dev_records, size_t records_bytes, float* dev_vnc, size_t vnc_cap,
+                           uint32_t* dev_tri_face, size_t tri_cap);
+/* Host form, synchronous, count-then-fill as surtr_event_hulls: with records and vnc NULL, *n, *n_vertices and *n_faces come back
+ * (fragments, vertices, faces of all); with both given *n and *n_vertices must hold their capacities (SURTR_E_CAPACITY and the counts
+ * when one is too small, nothing written); tri_face (may be NULL) has room for *n_vertices / 3 entries.  One of records / vnc without
+ * the other, or tri_face without them, is SURTR_E_INVALID. */
+int surtr_event_shaded(surtr_ctx* ctx, const float color[3], uint32_t* n, surtr_shaded* records, uint32_t* n_vertices, float* vnc,
+                       uint32_t* tri_face, uint32_t* n_faces);
+/* Diagnostic, for tests: fragments of up to `half_edges` half-edges keep their topology and partial sums in LDS, larger ones in global
+ * scratch.  0: the built-in limit, which is also the largest value taken.  The result does not depend on it. */
+int surtr_set_shade_tier(surtr_ctx* ctx, uint32_t half_edges);
+
 #ifdef __cplusplus
 }
 #endif

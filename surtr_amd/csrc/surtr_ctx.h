@@ -403,6 +403,7 @@ struct surtr_ctx
     DevBuf<uint2> d_pair_list;
     uint32_t refit_limit = 4;            // FractureArgs::RefittingPointLimit (surtr_set_refit_point_limit): above 4, k_refit_n refits
     DevBuf<uint32_t> d_hull_ws;          // k_refit_n: gain and "processed" mark of every arena vertex (2 x capV words)
+    uint32_t shade_lds_limit = 0;        // surtr_set_shade_tier: half-edges of a fragment k_sh_faces keeps in LDS (0: SURTR_SHADE_LH)
     float color[3] = {0.25f, 0.25f, 0.25f};      // VertexNormalColor::Color written by k_pack (Inc/Poly.h:68 default)
     surtr_counts last{}; bool last_current = false;     // `last` holds the counts of the event in the arena
     bool have_event = false; uint32_t last_flags = 0;

@@ -58,6 +58,13 @@ def hull_usable(record, rel_tol=1e-5):
     return bool(record["convexity"] <= tol and record["planarity"] <= tol)
 
 
+# surtr_shaded (include/surtr_hip.h), 16 bytes: one record per fragment of event_shaded
+SHADED_DTYPE = np.dtype([("first_vertex", "<u4"), ("n_vertices", "<u4"), ("n_faces", "<u4"), ("status", "<u4")])
+assert SHADED_DTYPE.itemsize == 16
+SHADE_PER_TRIANGLE = 1
+SHADE_NO_FACE = 0xFFFFFFFF
+
+
 # surtr_cooked (include/surtr_hip.h), 64 bytes: one record per solid of event_cook / pieces_cook / cook_points
 COOK_DTYPE = np.dtype([("nv_in", "<u4"), ("nv", "<u4"), ("n_faces", "<u4"), ("n_idx", "<u4"), ("status", "<u4"), ("pt_off", "<u4"),
                        ("face_off", "<u4"), ("idx_off", "<u4"), ("max_loop", "<u4"), ("n_welded", "<u4"), ("convexity", "<f4"),
@@ -568,6 +575,32 @@ class Engine:
     def pieces_hulls_dev(self, dev_records, records_bytes, dev_polys, polys_cap, dev_idx, idx_cap):
         self._ck(lib().surtr_pieces_hulls_dev(self._h, ctypes.c_void_p(dev_records), ctypes.c_size_t(records_bytes), ctypes.c_void_p(dev_polys),
                                               ctypes.c_size_t(polys_cap), ctypes.c_void_p(dev_idx), ctypes.c_size_t(idx_cap)))
+
+    def event_shaded(self, color=None, tri_face=False):
+        """surtr_event_shaded: the lit render buffers of the current (triangulated) fragments, computed on the device ->
+        (records (SHADED_DTYPE), vnc f32[n, 9]: position, face normal, colour of every index of the packed idx, tri_face u32[n / 3] or
+        None).  color: three floats (None: 0.25 grey)."""
+        col = None if color is None else (ctypes.c_float * 3)(*[float(x) for x in color])
+        fn = lib().surtr_event_shaded
+        n, nv, nf = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        self._ck(fn(self._h, col, ctypes.byref(n), None, ctypes.byref(nv), None, None, ctypes.byref(nf)))
+        rec, vnc = np.zeros(n.value, SHADED_DTYPE), np.zeros((nv.value, 9), np.float32)
+        tri = np.zeros(nv.value // 3, np.uint32) if tri_face else None
+        # (zero-length arrays still pass as non-NULL: numpy gives them an address)
+        self._ck(fn(self._h, col, ctypes.byref(n), _p(rec), ctypes.byref(nv), _p(vnc), _p(tri), ctypes.byref(nf)))
+        return rec, vnc, tri
+
+    def event_shaded_dev(self, dev_records, records_bytes, dev_vnc, vnc_cap, dev_tri_face=0, tri_cap=0, color=None):
+        """surtr_event_shaded_dev: header + records, vertices and (optionally) face numbers into device buffers, on the context's stream,
+        without a synchronisation (capacities in bytes, vertices, triangles)."""
+        col = None if color is None else (ctypes.c_float * 3)(*[float(x) for x in color])
+        self._ck(lib().surtr_event_shaded_dev(self._h, col, ctypes.c_void_p(dev_records or None), ctypes.c_size_t(records_bytes),
+                                              ctypes.c_void_p(dev_vnc or None), ctypes.c_size_t(vnc_cap), ctypes.c_void_p(dev_tri_face or None),
+                                              ctypes.c_size_t(tri_cap)))
+
+    def set_shade_tier(self, half_edges):
+        """surtr_set_shade_tier (diagnostic): fragments above this many half-edges take event_shaded's global-scratch tier; 0: built-in."""
+        self._ck(lib().surtr_set_shade_tier(self._h, ctypes.c_uint32(int(half_edges))))
 
     def _cook(self, call):
         c = [ctypes.c_uint32() for _ in range(4)]

@@ -37,6 +37,10 @@
 // --hulls (with --init-compounds): InitCompounds with the collision hulls (InitCompoundResult::Hull); every line also carries the
 //                 compound's hull polygons and indices, the number of its hulls HullUsable accepts, and an FNV-1a of polygons + indices;
 //                 SetExtract of the same fragments is checked against the loops (a difference ends the run with status 3).
+// --lit (with --init-compounds): InitCompounds under SetRenderNormals(true); every line also carries the compound's lit vertices, faces,
+//                 pieces that took the per-triangle fallback, and an FNV-1a of the lit vertices; ShadedRender of the same fragments is
+//                 checked against MeshLit, and after the last click Poly::RenderPolyhedronNormal (both overloads, behind a dummy
+//                 vertex) against the engine's call on the unit box (a difference ends the run with status 3), one line {"lit_box"}.
 // --pick: the event's fragments become the resident pieces (piece k in compound k / 2) and the ray is cast into them as
 // OnMouseDown does (Src/Surtr.cpp:207-240): the hit, the impact position, the overlap mask and the affected compounds, as JSON.
 // --ach runs Surtr::PrepareFracture end to end (ACH convex instead of the plain 2x box).
@@ -359,12 +363,31 @@ static void pick(FractureEngine& eng, const std::vector<Fragment>& frags, const 
 static bool g_init_compounds = false;
 static bool g_hulls = false;
 static bool g_cook = false;
+static bool g_lit = false;
 static std::string g_init_obj;
 static void init_compounds(FractureEngine& eng, size_t click, const std::vector<int>& made)
 {
     if (!g_init_compounds || made.empty()) return;
+    eng.SetRenderNormals(g_lit);
     const std::vector<std::vector<InitCompoundResult>> res = eng.InitCompounds(made, false, g_hulls, g_hulls && g_cook);
     const std::vector<uint32_t> table = eng.SceneCompounds();
+    if (g_lit)
+    {
+        // ShadedRender reads the same fragments: piece after piece in the order of the call, the bytes InitCompounds put into MeshLit
+        const std::vector<FragmentRender> lit = eng.ShadedRender();
+        size_t f = 0;
+        for (const auto& body : res)
+            for (const auto& r : body)
+            {
+                const bool same = f < lit.size() && lit[f].vertexData.size() == r.MeshLit.vertexData.size() && lit[f].indexData == r.MeshLit.indexData &&
+                                  r.MeshLit.vertexData.size() == r.Mesh.indexData.size() &&
+                                  (lit[f].vertexData.empty() ||
+                                   !memcmp(lit[f].vertexData.data(), r.MeshLit.vertexData.data(), lit[f].vertexData.size() * sizeof(VertexNormalColor)));
+                if (!same) { fprintf(stderr, "ShadedRender differs from InitCompounds' MeshLit at piece %zu of the call\n", f); exit(3); }
+                ++f;
+            }
+        if (f != lit.size()) { fprintf(stderr, "ShadedRender returned %zu pieces for %zu\n", lit.size(), f); exit(3); }
+    }
     if (g_hulls)
     {
         // SetExtract reads the same fragments: its loops are the polygons' indices, piece after piece in the order of the call
@@ -422,6 +445,18 @@ static void init_compounds(FractureEngine& eng, size_t click, const std::vector<
             printf(", \"cooked\": %zu, \"cooked_usable\": %zu, \"cook_status\": %u, \"cook_points\": %zu, \"cook_polygons\": %zu, \"cook_indices\": %zu, "
                    "\"cook_fnv\": \"%016llx\"", nc, ok, st, npt, np, nx, h);
         }
+        if (g_lit)
+        {
+            // the lit buffer of every piece: vertices, faces, pieces that took the per-triangle fallback, and an FNV-1a of the vertices
+            size_t lv = 0, lf = 0, fb = 0;
+            h = 0xCBF29CE484222325ull;
+            for (const auto& r : res[k])
+            {
+                eat(r.MeshLit.vertexData.data(), r.MeshLit.vertexData.size() * sizeof(VertexNormalColor));
+                lv += r.MeshLit.vertexData.size(); lf += r.Lit.n_faces; fb += (r.Lit.status & SURTR_SHADE_PER_TRIANGLE) ? 1 : 0;
+            }
+            printf(", \"lit_vertices\": %zu, \"lit_faces\": %zu, \"lit_fallback\": %zu, \"lit_fnv\": \"%016llx\"", lv, lf, fb, h);
+        }
         printf("}\n");
         if (g_init_obj.empty()) continue;
         std::vector<int32_t> ids; std::vector<uint32_t> vo{0u}, io{0u}, idx; std::vector<float> vnc;
@@ -438,6 +473,29 @@ static void init_compounds(FractureEngine& eng, size_t click, const std::vector<
         const int rc = surtr_write_obj(path.c_str(), (uint32_t)res[k].size(), ids.data(), vo.data(), vnc.data(), io.data(), idx.data());
         if (rc) throw Error(rc, "surtr_write_obj " + path);
     }
+}
+
+// --lit: Poly::RenderPolyhedronNormal, both overloads, on the unit box behind one dummy vertex (the vertex offset of the running indices),
+// against the engine's own call -- all three on the default engine, after the last click, so that the clicks' engine is left alone.
+static void lit_box()
+{
+    const Poly::Polyhedron box = Poly::GetBB();
+    const Vector3 col(0.5f, 0.25f, 0.125f);
+    std::vector<VertexNormalColor> va(1), vb(1); std::vector<uint32_t> ia, ib;
+    Poly::RenderPolyhedronNormal(va, ia, box, false, col);
+    Poly::Extract* ex = Poly::ExtractFaces(box);
+    Poly::RenderPolyhedronNormal(vb, ib, box, ex, false, col);
+    delete ex;
+    const FragmentRender own = DefaultEngine().RenderPolyhedronNormal(box, false, col);
+    bool same = va.size() == vb.size() && ia == ib && va.size() == own.vertexData.size() + 1 && ia.size() == own.indexData.size() &&
+                !memcmp(va.data() + 1, vb.data() + 1, (va.size() - 1) * sizeof(VertexNormalColor)) &&
+                !memcmp(va.data() + 1, own.vertexData.data(), own.vertexData.size() * sizeof(VertexNormalColor));
+    for (size_t i = 0; same && i < ia.size(); ++i) same = ia[i] == (uint32_t)i + 1u && own.indexData[i] == (uint32_t)i;
+    if (!same) { fprintf(stderr, "RenderPolyhedronNormal: the overloads and the engine's call differ\n"); exit(3); }
+    unsigned long long h = 0xCBF29CE484222325ull;
+    const unsigned char* bytes = (const unsigned char*)own.vertexData.data();
+    for (size_t i = 0; i < own.vertexData.size() * sizeof(VertexNormalColor); ++i) { h ^= bytes[i]; h *= 0x100000001B3ull; }
+    printf("{\"lit_box\": %zu, \"fnv\": \"%016llx\"}\n", own.vertexData.size(), h);
 }
 
 static std::vector<Vector3> lattice_cloud()
@@ -758,6 +816,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--init-compounds")) g_init_compounds = true;
         else if (!strcmp(argv[i], "--hulls")) g_hulls = true;
         else if (!strcmp(argv[i], "--cook")) g_cook = true;
+        else if (!strcmp(argv[i], "--lit")) g_lit = true;
         else if (!strcmp(argv[i], "--bounds")) g_bounds = true;
         else if (!strcmp(argv[i], "--cull-mass") && i + 1 < argc) { g_cull = true; g_cull_mass = (float)atof(argv[++i]); }
         else if (!strcmp(argv[i], "--keep-box") && i + 1 < argc)
@@ -898,6 +957,7 @@ int main(int argc, char** argv)
         if (!clicks.empty()) scene_clicks(eng, clicks, impact_radius, one_event);
         else if (!bclicks.empty()) body_clicks(eng, bclicks, poses, impact_radius, radial, one_event, piece);
         else if (!impacts.empty()) impacts_frame(eng, impacts, patterns, seeds, poses, one_event);
+        if (g_lit && g_init_compounds && (!clicks.empty() || !bclicks.empty())) lit_box();
         if (!obj.empty())
         {
             FILE* f = fopen(obj.c_str(), "w");

@@ -132,6 +132,21 @@ void Poly::RenderPolyhedron(std::vector<VertexNormalColor>& vertexData, std::vec
     for (uint32_t i : r.indexData) indexData.push_back(vertexOffset + i);
 }
 
+void Poly::RenderPolyhedronNormal(std::vector<VertexNormalColor>& vertexData, std::vector<uint32_t>& indexData, const Polyhedron& poly, bool isConvex,
+                                  Vector3 color)
+{
+    const FragmentRender r = DefaultEngine().RenderPolyhedronNormal(poly, isConvex, color);
+    const uint32_t vertexOffset = (uint32_t)vertexData.size();
+    vertexData.insert(vertexData.end(), r.vertexData.begin(), r.vertexData.end());
+    for (uint32_t i : r.indexData) indexData.push_back(vertexOffset + i);
+}
+void Poly::RenderPolyhedronNormal(std::vector<VertexNormalColor>& vertexData, std::vector<uint32_t>& indexData, const Polyhedron& poly,
+                                  const Extract* extract, bool isConvex, Vector3 color)
+{
+    (void)extract;      // == ExtractFaces(poly): the kernels derive the face loops themselves
+    RenderPolyhedronNormal(vertexData, indexData, poly, isConvex, color);
+}
+
 // ---- Kdop ------------------------------------------------------------------------------------------------------------
 Kdop::KdopContainer::KdopContainer(const std::vector<Vector3>& normalVec)
 {
@@ -620,6 +635,35 @@ HullSet FractureEngine::Hulls()
                     "surtr_event_hulls");
 }
 
+std::vector<FragmentRender> FractureEngine::ShadedRender(const Vector3& color, std::vector<surtr_shaded>* records)
+{
+    const float col[3] = {color.x, color.y, color.z};
+    uint32_t n = 0, nv = 0, nf = 0;
+    check(surtr_event_shaded(ctx_, col, &n, nullptr, &nv, nullptr, nullptr, &nf), "surtr_event_shaded");
+    // (the fill form wants both arrays: empty vectors lend it a place to stand)
+    std::vector<surtr_shaded> rec(std::max(n, 1u)); std::vector<VertexNormalColor> vnc(std::max(nv, 1u));
+    check(surtr_event_shaded(ctx_, col, &n, rec.data(), &nv, (float*)vnc.data(), nullptr, &nf), "surtr_event_shaded");
+    rec.resize(n);
+    std::vector<FragmentRender> out(n);
+    for (uint32_t f = 0; f < n; ++f)
+    {
+        out[f].vertexData.assign(vnc.begin() + rec[f].first_vertex, vnc.begin() + rec[f].first_vertex + rec[f].n_vertices);
+        out[f].indexData.resize(rec[f].n_vertices);
+        for (uint32_t i = 0; i < rec[f].n_vertices; ++i) out[f].indexData[i] = i;
+    }
+    if (records) *records = std::move(rec);
+    return out;
+}
+
+FragmentRender FractureEngine::RenderPolyhedronNormal(const Poly::Polyhedron& poly, bool isConvex, const Vector3& color)
+{
+    Flat in; in.add(poly);
+    uint32_t ni = 0;
+    check(surtr_triangulate(ctx_, (uint32_t)poly.size(), in.pos.data(), in.nbr_off.data(), in.nbr.data(), isConvex ? 1 : 0, nullptr, nullptr, &ni, nullptr),
+          "surtr_triangulate");
+    return std::move(ShadedRender(color).front());
+}
+
 HullSet FractureEngine::PieceHulls()
 {
     return hulls_of([&](uint32_t* n, surtr_hull* r, uint32_t* np, surtr_hull_polygon* p, uint32_t* ni, uint16_t* i) { return surtr_pieces_hulls(ctx_, n, r, np, p, ni, i); },
@@ -1087,6 +1131,8 @@ std::vector<std::vector<InitCompoundResult>> FractureEngine::InitCompounds(const
         cooked.Records.resize(n); cooked.Points.resize(3 * (size_t)nv); cooked.Source.resize(nv); cooked.Polygons.resize(np); cooked.Indices.resize(ni);
     }
     else if (withHulls) hulls = Hulls();
+    std::vector<FragmentRender> lit; std::vector<surtr_shaded> litRecords;
+    if (render_normals_) lit = ShadedRender(Vector3(0.25f, 0.25f, 0.25f), &litRecords);
     uint32_t f = 0;
     for (uint32_t comp : list)
     {
@@ -1098,6 +1144,7 @@ std::vector<std::vector<InitCompoundResult>> FractureEngine::InitCompounds(const
             r.Mesh.vertexData.resize(mvo[f + 1] - mvo[f]);
             if (!r.Mesh.vertexData.empty()) std::memcpy(r.Mesh.vertexData.data(), vnc.data() + 9 * (size_t)mvo[f], sizeof(VertexNormalColor) * r.Mesh.vertexData.size());
             r.Mesh.indexData.assign(idx.begin() + ioff[f], idx.begin() + ioff[f + 1]);
+            if (render_normals_) { r.MeshLit = std::move(lit[f]); r.Lit = litRecords[f]; }
             if (withHulls)
             {
                 const surtr_hull& h = hulls.Records[f];
@@ -1539,6 +1586,12 @@ InitCompoundResult InitCompoundTask(const Piece* piece, const Poly::Extract* ext
     InitCompoundResult r;
     for (const auto& v : piece->Convex) r.ConvexPoints.push_back(v.Position);
     r.Mesh = DefaultEngine().RenderPolyhedron(renderConvex ? piece->Convex : piece->Mesh, renderConvex, Vector3(0.25f, 0.25f, 0.25f));
+    if (DefaultEngine().RenderNormals())      // (RenderPolyhedron left the solid as the engine's only fragment, triangulated: the same device call)
+    {
+        std::vector<surtr_shaded> rec;
+        r.MeshLit = std::move(DefaultEngine().ShadedRender(Vector3(0.25f, 0.25f, 0.25f), &rec).front());
+        r.Lit = rec.front();
+    }
     return r;
 }
 

@@ -100,6 +100,13 @@ Polyhedron GetBB();                                                             
 // indices are appended after what the two vectors hold, indices offset by the vertices already there, as in the reference.
 void RenderPolyhedron(std::vector<VertexNormalColor>& vertexData, std::vector<uint32_t>& indexData, const Polyhedron& poly,
                       const Extract* extract, bool isConvex = true, Vector3 color = Vector3(0.25f, 0.25f, 0.25f));
+// Inc/Poly.h:50-61, Src/Poly.cpp:619-679: three unshared vertices per triangle, each with the normal of its face, and running indices
+// (offset by the vertices already there, as above).  The normals are those of include/surtr_hip.h, "lit render buffers" (the Newell sum of
+// the whole loop; the reference takes the first three vertices); the triangles are RenderPolyhedron's for the same isConvex.
+void RenderPolyhedronNormal(std::vector<VertexNormalColor>& vertexData, std::vector<uint32_t>& indexData, const Polyhedron& poly, bool isConvex,
+                            Vector3 color = Vector3(0.25f, 0.25f, 0.25f));
+void RenderPolyhedronNormal(std::vector<VertexNormalColor>& vertexData, std::vector<uint32_t>& indexData, const Polyhedron& poly,
+                            const Extract* extract, bool isConvex, Vector3 color = Vector3(0.25f, 0.25f, 0.25f));
 } // namespace Poly
 
 namespace Kdop {
@@ -199,7 +206,9 @@ struct CookedData
 {
     surtr_cooked Record{}; std::vector<Vector3> Points; std::vector<uint32_t> Source; std::vector<surtr_hull_polygon> Polygons; std::vector<uint16_t> Indices;
 };
-struct InitCompoundResult { std::vector<Vector3> ConvexPoints; FragmentRender Mesh; HullData Hull; CookedData Cooked; };
+// MeshLit / Lit (filled only under FractureEngine::SetRenderNormals(true)): the lit buffers of the same solid and triangles as Mesh --
+// one vertex per index, running indices -- and the piece's record (faces, SURTR_SHADE_PER_TRIANGLE).
+struct InitCompoundResult { std::vector<Vector3> ConvexPoints; FragmentRender Mesh; HullData Hull; CookedData Cooked; FragmentRender MeshLit; surtr_shaded Lit{}; };
 // No withholding bit, planarity within planeTol and convexity within 2 planeTol + weldDist, each plus the rounding of a written
 // plane at its largest: 2^-24 * 3.5 * reach (|n_x| + |n_y| + |n_z| <= sqrt 3, |d| <= sqrt 3 * reach).  A cooked hull that fails --
 // a flat or otherwise withheld solid -- is left to PxConvexFlag::eCOMPUTE_CONVEX.
@@ -299,6 +308,15 @@ public:
     Poly::Extract ExtractFaces(const Poly::Polyhedron& polyhedron);
     FragmentRender RenderPolyhedron(const Poly::Polyhedron& poly, bool isConvex, const Vector3& color);
     Poly::Polyhedron TransformSolid(const Poly::Polyhedron& polyhedron, const Matrix& matrix);
+    // Poly::RenderPolyhedronNormal on one solid: surtr_triangulate presents and triangulates it, surtr_event_shaded lights it.
+    FragmentRender RenderPolyhedronNormal(const Poly::Polyhedron& poly, bool isConvex, const Vector3& color);
+    // The lit buffers of every current fragment (surtr_event_shaded), one FragmentRender each with indices 0, 1, 2, ...; valid wherever
+    // Hulls() is, once the fragments are triangulated (ApplyFracture with render, InitCompounds).  records: the per-fragment records.
+    std::vector<FragmentRender> ShadedRender(const Vector3& color = Vector3(0.25f, 0.25f, 0.25f), std::vector<surtr_shaded>* records = nullptr);
+    // On: InitCompound(s) and InitCompoundTask fill InitCompoundResult::MeshLit / Lit from the same device call.  Off (the default):
+    // every result is byte for byte what it is without this switch.
+    void SetRenderNormals(bool on) { render_normals_ = on; }
+    bool RenderNormals() const { return render_normals_; }
     // What DoFracture regrouped (for tests and tools): the un-refitted Convex solids in piece order (the compound's pieces the
     // event skipped, ascending, then the event's fragments), the cell of every piece (-1: skipped), the bind sets found.
     struct FractureTrace { std::vector<Poly::Polyhedron> Convex; std::vector<int> PieceCell; uint32_t nOutside = 0; std::vector<std::set<int>> CompoundBind; };
@@ -479,6 +497,7 @@ private:
     std::vector<uint8_t> two_call_mask(const char* what, const std::function<int(uint32_t, uint32_t*, uint8_t*)>& call);
     std::vector<uint8_t> outside_mask(const std::vector<uint32_t>& t, const std::vector<float>& fc, const float org[3], float radius);
     bool allow_flagged_ = false;
+    bool render_normals_ = false;
     FlaggedUnits flagged_;
     surtr_ctx* ctx_ = nullptr;
     void check_impact_patterns(const std::vector<Impact>& impacts);
