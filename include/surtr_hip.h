@@ -110,6 +110,17 @@ int surtr_get_stream(surtr_ctx* ctx, void** hip_stream);
  * contexts: 0.65 -> 0.55 ms per step; one at a time 1.29 -> 1.37 ms).  The reference has no counterpart (one event at a time,
  * Src/Surtr.cpp:178-254). */
 int surtr_set_events_in_flight(surtr_ctx* ctx, uint32_t n);
+/* Diagnostic: the plan an event of n_pairs pairs (pair_list != 0: given as a pair list, otherwise a cell range) with `flags` gets
+ * from this context now -- which kernels and how many workgroups of each -- with the environment overrides as they stand.  No
+ * launch, no synchronisation; SURTR_E_STATE before the context's first event (the plan reads the capacities an event's launch
+ * sets).  out[0] n_pairs, [1] the events-in-flight hint, [2] bits: 1 record clipper, 2 split arrangement (main + catcher), 4
+ * half-size kernel, 8 Convex clip beside the pre-pass, 16 refit beside faces, 32 lean Convex kernel + second tier, 64 the queue
+ * kernels' grids are those of several events in flight, 128 pairs in cell order; [3] pre-pass kernel (0 none, 1 regular, 2 sorted,
+ * 3 wide); the grids: [4] Mesh clip, [5] k_clip_convex alone, [6] k_clip_convex_lean, [7] its second tier, [8] pre-pass,
+ * [9] k_clip_pairs_big, [10] half-size kernel, [11] its retry, [12] catcher, [13] the catcher's sweep, [14] polling catcher
+ * workgroups, [15] refit, [16] k_faces, [17] its second tier (0: the context has none), [18] threads of a k_faces workgroup,
+ * [19] the fragments the refit and k_faces grids were sized for, [20] threads of a pre-pass workgroup; the rest 0. */
+int surtr_event_plan(surtr_ctx* ctx, uint32_t n_pairs, int pair_list, uint32_t flags, uint32_t out[32]);
 /* Override the per-workgroup scratch capacities (vertices, neighbour entries); 0 = automatic. */
 int surtr_set_scratch(surtr_ctx* ctx, uint32_t max_verts, uint32_t max_nbrs);
 /* Override the result arena capacities (vertices, neighbour entries, indices); 0 = automatic. */

@@ -412,7 +412,7 @@ void set_piece_stats(surtr_ctx* ctx, uint32_t n, const uint32_t* mvo, const uint
     }
     ctx->vmin = n ? vmin : 0u;
     ctx->n_pieces = n; ctx->vmax = std::max(vmax, cvmax); ctx->hmax = std::max(hmax, chmax); ctx->cvmax = cvmax; ctx->chmax = chmax;
-    ctx->tot_mv = mvo[n]; ctx->tot_mh = mho[n]; ctx->pair_order_count = 0;
+    ctx->tot_mv = mvo[n]; ctx->tot_mh = mho[n]; ctx->pair_order_count = 0; ctx->frag_hint = 0;      // (other pieces: other fragments)
     ctx->half_on = 4ull * small >= 3ull * n;
     if (const char* e = getenv("SURTR_HALF")) ctx->half_on = atoi(e) != 0;      // tests: force either way
     ctx->have_event = false; ctx->frags_of_pieces = false;

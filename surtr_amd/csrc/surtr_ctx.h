@@ -407,6 +407,8 @@ struct surtr_ctx
     float color[3] = {0.25f, 0.25f, 0.25f};      // VertexNormalColor::Color written by k_pack (Inc/Poly.h:68 default)
     surtr_counts last{}; bool last_current = false;     // `last` holds the counts of the event in the arena
     bool have_event = false; uint32_t last_flags = 0;
+    // fragments and pairs of the last event over these pieces whose counts were read back (0: none yet), see plan_event
+    uint32_t frag_hint = 0, frag_hint_pairs = 0, event_pairs = 0;
     // staging for downloads
     DevBuf<char> d_blob;
     // per-kernel timing with HIP events on the work stream (surtr_set_profiling)

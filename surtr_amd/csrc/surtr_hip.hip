@@ -4100,9 +4100,47 @@ struct EventPlan
     uint32_t rec_on;                      // k_prep_pairs' mode word: 1 record images, 2 round 3's selection, 4 front_par, rec_maxn << 8
     uint32_t big_quota, big_n, walk0, n_catch, n_poll;
     uint32_t n_wg, n_wg_cvx, n_wg_lean, n_wg_cvx2, n_wg_prep, n_wg_big, n_wg_half, n_wg_retry, n_wg_sweep;      // grids
-    uint32_t g_refit, g_faces, t_faces;
+    uint32_t g_refit, g_faces, g_faces2, t_faces;      // (g_faces2: k_faces' second tier, where the context has one)
+    bool many_grids;                      // the queue kernels' grids are those of several events in flight (many_grid below)
+    uint32_t frag_tasks;                  // ... and the fragments they were sized for
     hipStream_t st_cvx, st_main, st_bigk, st_refit;
 };
+
+// Several events in flight: a persistent queue kernel whose length is its slowest task, not its amount of work, loses
+// little with fewer workgroups, and what it leaves of the CUs is another event's.  Its grid is then "as many workgroups as give each
+// about T tasks", never more than the single-event size `one` (which is what the device's CUs hold); T = 0 keeps that size: no smaller
+// grid of that kernel was worth more than the spread of the measurement (profiles/inflight_grids_bench.txt has every setting tried).
+// T is a fraction, {tasks, workgroups}.
+struct ManyT { uint32_t tasks, wgs; };
+#ifndef SURTR_MANY_T_REFIT
+#define SURTR_MANY_T_REFIT {0u, 1u}      // fragments per workgroup of k_refit / k_refit_n: kept (3/4 of the grid -0.006 ms per step, 1/2 +0.02)
+#endif
+#ifndef SURTR_MANY_T_FACES
+#define SURTR_MANY_T_FACES {0u, 1u}      // fragments per workgroup of k_faces, either tier: kept (3/4 -0.003, 1/2 -0.02 but a lone event +0.09)
+#endif
+#ifndef SURTR_MANY_T_LEAN
+#define SURTR_MANY_T_LEAN {8u, 3u}       // pairs per workgroup of k_clip_convex_lean: 1 536 workgroups at 4 096 pairs, where a context alone has 2 048
+#endif
+#ifndef SURTR_MANY_T_CVX2
+#define SURTR_MANY_T_CVX2 {0u, 1u}       // pairs of the event per workgroup of the lean kernel's second tier: kept (its list is empty as a rule)
+#endif
+#ifndef SURTR_MANY_T_CATCH
+#define SURTR_MANY_T_CATCH {0u, 1u}      // pairs of the event per workgroup of k_clip_pairs_catch and of its sweep: kept (3/4 +0.02, 1/2 +0.09)
+#endif
+#ifndef SURTR_MANY_T_BIG
+#define SURTR_MANY_T_BIG {128u, 1u}      // pairs of the event per whole-CU workgroup of k_clip_pairs_big: 32 at 4 096 pairs (about 35 large bands)
+#endif
+static uint32_t many_grid(uint32_t tasks, ManyT T, uint32_t one)
+{
+    if (T.tasks == 0u) return one;
+    const uint64_t g = ((uint64_t)tasks * T.wgs + T.tasks - 1u) / T.tasks;
+    return (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(one, g));
+}
+// An environment override of one grid (tests / A-B), read like SURTR_REFIT_WG_BOTH: taken if it is within [1, cap].
+static void grid_override(const char* name, uint32_t cap, uint32_t& grid)
+{
+    if (const char* e = getenv(name)) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= cap) grid = v; }
+}
 
 // The plan of an event.  No HIP call, no allocation, nothing written to the context: it reads the capacities the ensure_* calls
 // have set.  Every environment override of the launch sequence is read here, on every event (tests set them between events).
@@ -4210,10 +4248,41 @@ static EventPlan plan_event(const surtr_ctx* ctx, uint32_t n_pairs, bool pair_li
     // of k_refit's (measured on configs[3]: 3.72 -> 3.65 ms per event against both at their stand-alone sizes)
     pl.g_refit = ctx->n_wg_small;
     if (pl.both) pl.g_refit = std::min(pl.g_refit, ctx->max_wg_faces / 4u * 5u);
-    if (pl.both) if (const char* e = getenv("SURTR_REFIT_WG_BOTH")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= ctx->n_wg_small) pl.g_refit = v; }
     pl.g_faces = std::max(1u, ctx->max_wg_faces); pl.t_faces = SURTR_WG;
     if (pl.both) pl.g_faces = std::max(1u, ctx->max_wg_faces / 2u);
-    if (pl.both) if (const char* e = getenv("SURTR_FACES_WG_BOTH")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= ctx->n_wg_faces_alloc) pl.g_faces = v; }
+    pl.g_faces2 = ctx->n_wg_faces_big;
+    // Several events in flight: the grids of the event's queue kernels by many_grid, from what the host knows at launch -- the pairs,
+    // and the fragments of this context's last event whose counts were read back (the pairs where there was none: an upper bound).
+    // Only for the events that queue up on the lean arrangement: a small event (front_par), the general clipper arrangement and a
+    // context alone on the GPU keep the plan they had.
+    pl.many_grids = many && n_pairs != 0 && !pl.front_par && !prep_wide && pl.wave_on && pl.split_on;
+    pl.frag_tasks = n_pairs;
+    if (ctx->frag_hint && ctx->frag_hint_pairs)      // (in proportion to the pairs: a block of the event that was read back)
+        pl.frag_tasks = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, ((uint64_t)ctx->frag_hint * n_pairs + ctx->frag_hint_pairs - 1u) / ctx->frag_hint_pairs);
+    if (pl.many_grids)
+    {
+        pl.g_refit = many_grid(pl.frag_tasks, ManyT SURTR_MANY_T_REFIT, pl.g_refit);
+        pl.g_faces = many_grid(pl.frag_tasks, ManyT SURTR_MANY_T_FACES, pl.g_faces);
+        if (pl.g_faces2) pl.g_faces2 = many_grid(pl.frag_tasks, ManyT SURTR_MANY_T_FACES, pl.g_faces2);
+        pl.n_wg_lean = many_grid(n_pairs, ManyT SURTR_MANY_T_LEAN, pl.n_wg_lean);
+        pl.n_wg_cvx2 = many_grid(n_pairs, ManyT SURTR_MANY_T_CVX2, pl.n_wg_cvx2);
+        pl.n_catch = many_grid(n_pairs, ManyT SURTR_MANY_T_CATCH, pl.n_catch);
+        pl.n_wg_sweep = many_grid(n_pairs, ManyT SURTR_MANY_T_CATCH, pl.n_wg_sweep);
+        // (k_clip_pairs_big's few dozen workgroups; where the large bands are the rule, wave_big, the whole-CU record clipper keeps its grid)
+        if (!ctx->wave_big) pl.n_wg_big = many_grid(n_pairs, ManyT SURTR_MANY_T_BIG, pl.n_wg_big);
+    }
+    // (tests / A-B: each of those grids by hand, in a context told that it is one of several; within what the kernel has scratch for)
+    if (ctx->events_in_flight > 1u)
+    {
+        grid_override("SURTR_CVX_LEAN_WG_MANY", ctx->max_wg_lean, pl.n_wg_lean);
+        grid_override("SURTR_CVX2_WG_MANY", std::min(64u, ctx->n_wg_small), pl.n_wg_cvx2);
+        grid_override("SURTR_CATCH_WG_MANY", SURTR_CATCH_WG_MAX, pl.n_catch);
+        grid_override("SURTR_SWEEP_WG_MANY", SURTR_CATCH_WG_MAX, pl.n_wg_sweep);
+        grid_override("SURTR_BIG_WG_MANY", ctx->n_wg_big, pl.n_wg_big);
+        if (pl.g_faces2) grid_override("SURTR_FACES2_WG_MANY", ctx->n_wg_faces_big, pl.g_faces2);
+    }
+    if (pl.both) grid_override("SURTR_REFIT_WG_BOTH", ctx->n_wg_small, pl.g_refit);
+    if (pl.both) grid_override("SURTR_FACES_WG_BOTH", ctx->n_wg_faces_alloc, pl.g_faces);
     if (const char* e = getenv("SURTR_FACES_WG")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && v <= ctx->n_wg_faces_alloc) pl.g_faces = v; }
     if (const char* e = getenv("SURTR_FACES_THREADS")) { const uint32_t v = (uint32_t)atoi(e); if (v == 64 || v == 128 || v == 256) pl.t_faces = v; }
     return pl;
@@ -4422,7 +4491,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
                            ctx->blk_per_wg, ctx->arena, ctx->d_forder, ctx->cap_frags, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
                            ctx->d_frag_status, (const uint32_t*)nullptr, tiers ? ctx->d_face_list : (uint32_t*)nullptr);
         if (tiers)      // the fragments too large for the scratch of those workgroups
-            hipLaunchKernelGGL(k_faces, dim3(ctx->n_wg_faces_big), dim3(pl.t_faces), 0, st, ctx->d_frags, ctx->d_counts, ctx->fs_big, ctx->d_blk_big,
+            hipLaunchKernelGGL(k_faces, dim3(pl.g_faces2), dim3(pl.t_faces), 0, st, ctx->d_frags, ctx->d_counts, ctx->fs_big, ctx->d_blk_big,
                                ctx->blk_per_wg_big, ctx->arena, ctx->d_forder, ctx->cap_frags, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
                                ctx->d_frag_status, (const uint32_t*)ctx->d_face_list, (uint32_t*)nullptr);
         PROF_END(3);
@@ -4436,7 +4505,7 @@ static int launch_event(surtr_ctx* ctx, uint32_t cell_begin, uint32_t n_pairs, c
     hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(SURTR_WG_WIDE), 0, st, ctx->d_frags, ctx->d_scanblk, ctx->d_counts, ctx->arena);
     PROF_END(4);
     HIPCHK(hipGetLastError());
-    ctx->have_event = true; ctx->last_flags = flags; ctx->last_current = false; ctx->frags_of_pieces = true;
+    ctx->have_event = true; ctx->last_flags = flags; ctx->last_current = false; ctx->frags_of_pieces = true; ctx->event_pairs = n_pairs;
     ctx->scene_event_compound.clear(); ctx->scene_event_impacts.clear();      // (surtr_scene_fracture_event / _bodies / _impacts set them after this)
     return SURTR_OK;
 }
@@ -4774,6 +4843,8 @@ int surtr_event_counts(surtr_ctx* ctx, surtr_counts* counts)
     HIPCHK(hipMemcpyAsync(&ctx->last, ctx->d_counts, sizeof(surtr_counts), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     *counts = ctx->last; ctx->last_current = true;
+    // (what plan_event sizes the next events' fragment kernels by)
+    if (ctx->frags_of_pieces && ctx->last.status == 0 && ctx->event_pairs) { ctx->frag_hint = ctx->last.n_frag; ctx->frag_hint_pairs = ctx->event_pairs; }
     return ctx->last.status ? (int)ctx->last.status : SURTR_OK;
 }
 
@@ -4869,6 +4940,21 @@ int surtr_set_events_in_flight(surtr_ctx* ctx, uint32_t n)
 {
     if (!ctx) return SURTR_E_INVALID;
     ctx->events_in_flight = n ? n : 1u;
+    return SURTR_OK;
+}
+
+int surtr_event_plan(surtr_ctx* ctx, uint32_t n_pairs, int pair_list, uint32_t flags, uint32_t out[32])
+{
+    if (!ctx || !out) return SURTR_E_INVALID;
+    if (!ctx->have_event) return SURTR_E_STATE;      // (the capacities the plan reads are those the last event's launch set)
+    const EventPlan pl = plan_event(ctx, n_pairs, pair_list != 0, flags);
+    const uint32_t prep_kind = pl.prep == nullptr ? 0u : pl.prep == k_prep_pairs ? 1u : pl.prep == k_prep_pairs_sorted ? 2u : 3u;
+    const uint32_t v[32] = {n_pairs, ctx->events_in_flight,
+                            (pl.wave_on ? 1u : 0u) | (pl.split_on ? 2u : 0u) | (pl.use_half ? 4u : 0u) | (pl.front_par ? 8u : 0u) | (pl.both ? 16u : 0u) |
+                                (pl.cvx_lean ? 32u : 0u) | (pl.many_grids ? 64u : 0u) | (pl.cell_order ? 128u : 0u),
+                            prep_kind, pl.n_wg, pl.n_wg_cvx, pl.n_wg_lean, pl.n_wg_cvx2, pl.n_wg_prep, pl.n_wg_big, pl.n_wg_half, pl.n_wg_retry,
+                            pl.n_catch, pl.n_wg_sweep, pl.n_poll, pl.g_refit, pl.g_faces, pl.g_faces2, pl.t_faces, pl.frag_tasks, pl.prep_threads};
+    memcpy(out, v, sizeof(v));
     return SURTR_OK;
 }
 

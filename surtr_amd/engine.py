@@ -283,6 +283,21 @@ class Engine:
         """Tells the context how many contexts the host keeps busy on this GPU (include/surtr_hip.h: surtr_set_events_in_flight)."""
         self._ck(lib().surtr_set_events_in_flight(self._h, ctypes.c_uint32(int(n))))
 
+    PLAN_FIELDS = ("n_pairs", "events_in_flight", "bits", "prep_kind", "n_wg", "n_wg_cvx", "n_wg_lean", "n_wg_cvx2", "n_wg_prep", "n_wg_big",
+                   "n_wg_half", "n_wg_retry", "n_catch", "n_wg_sweep", "n_poll", "g_refit", "g_faces", "g_faces2", "t_faces", "frag_tasks",
+                   "prep_threads")
+    PLAN_BITS = {"wave": 1, "split": 2, "half": 4, "front_par": 8, "both": 16, "cvx_lean": 32, "many_grids": 64, "cell_order": 128}
+
+    def event_plan(self, n_pairs, flags=3, pair_list=False):
+        """The plan an event of n_pairs pairs gets from this context now (include/surtr_hip.h: surtr_event_plan): a dict of
+        PLAN_FIELDS, the bits of PLAN_BITS spelled out as booleans."""
+        out = (ctypes.c_uint32 * 32)()
+        self._ck(lib().surtr_event_plan(self._h, ctypes.c_uint32(int(n_pairs)), ctypes.c_int(int(bool(pair_list))), ctypes.c_uint32(int(flags)), out))
+        plan = {n: int(out[i]) for i, n in enumerate(self.PLAN_FIELDS)}
+        for n, b in self.PLAN_BITS.items():
+            plan[n] = bool(plan["bits"] & b)
+        return plan
+
     def kernel_history(self):
         """Durations (ms) of the Mesh clip kernel over the last events, oldest first (surtr_kernel_history)."""
         ms = (ctypes.c_float * 16)(); slot = (ctypes.c_int * 16)(); n = ctypes.c_uint32(0)
