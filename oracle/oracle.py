@@ -162,6 +162,14 @@ def links_off_the_array(reset=True):
     return int(f(ctypes.c_int(int(reset))))
 
 
+def inner_point_undefined(reset=True):
+    """How often, since the last reset, the limited hull asked for the inner point of a face that has none (FindInnerPoint falls
+    off its end, Src/VMACH.cpp:950-961): the reference's hull is undefined from there on."""
+    f = lib().orc_inner_point_undefined
+    f.restype = ctypes.c_long
+    return int(f(ctypes.c_int(int(reset))))
+
+
 def refit(convex, mesh, point_limit=4):
     cp, co, cn = _solid_args(convex)
     mp, mo, mn = _solid_args(mesh)

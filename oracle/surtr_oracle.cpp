@@ -12,12 +12,13 @@
 // for that pair or fragment instead of comparing results.
 //
 // PINNING STATUS: the reference ships no tests, fixtures or golden vectors
-//  and cannot be built in this image (every translation
-// unit includes Inc/pch.h -> Windows.h, d3d12.h, DirectXMath.h, none present;
-// no stand-ins are written).  The oracle is therefore pinned only against the
-// known answers that SURVEY.md section 6 / 8(c) records from the survey's run of the
-// reference kernels (tests/test_oracle_kat.py) -- full-vector parity is
-// "parity unpinned" beyond those.
+// (SURVEY.md section 4).  Its geometry units (Src/Poly.cpp, Src/Kdop.cpp,
+// Src/VMACH.cpp) are compiled by `make ref` against the stand-in headers of
+// oracle/ref_shim, and tests/test_reference_compiled.py compares every function
+// of this file that restates them with the compiled original (DESIGN section
+// 6.1): topology equal, every coordinate equal as a number.  The event loop
+// (Surtr.cpp) is pinned only against the known answers that SURVEY.md section
+// 6 / 8(c) records from the survey's run (tests/test_oracle_kat.py).
 //
 // Float semantics restated here (SimpleMath over DirectXMath, SSE2 path,
 // ThirdParty/Inc/SimpleMath.inl:729-1006, 2773-2788; DirectXMath itself is not
@@ -93,6 +94,10 @@ static inline Plane plane_from_point_normal(V3 p, V3 n)
 // --------------------------------------------------------------- solids ----
 // Poly::Vertex / Poly::Polyhedron (Inc/Poly.h:15-32) as struct-of-vectors.
 static std::atomic<long> g_links_off_the_array{0};      // see clip_polyhedron's compaction; read through orc_links_off_the_array()
+// FindInnerPoint (Src/VMACH.cpp:950-961) has no return after its loop: on a hull face whose three vertices all sit on the edge's
+// end points (a face that names one point twice) the reference's inner point is whatever its stack holds, and so is the winding
+// of the face made from it.  inner_point() counts those (orc_inner_point_undefined) and goes on with the face's first vertex.
+static std::atomic<long> g_inner_point_undefined{0};
 
 struct Solid
 {
@@ -736,6 +741,7 @@ struct Hull
             if (same(f->v[i], e.e[1])) continue;
             return f->v[i];
         }
+        ++g_inner_point_undefined;
         return f->v[0];
     }
     void add_point(V3 p)                                             // :994-1034
@@ -1303,6 +1309,12 @@ orc_bag* orc_kdop_planes(int n, const float* pts, int k, const float* normals, i
 long orc_links_off_the_array(int reset)
 {
     return reset ? orc::g_links_off_the_array.exchange(0) : orc::g_links_off_the_array.load();
+}
+
+// The same for the limited hull's inner point (see g_inner_point_undefined).
+long orc_inner_point_undefined(int reset)
+{
+    return reset ? orc::g_inner_point_undefined.exchange(0) : orc::g_inner_point_undefined.load();
 }
 
 orc_bag* orc_refit(int cnv, const float* cpos, const uint32_t* coff, const int32_t* cnbr,

@@ -1,13 +1,16 @@
 """Generates the committed golden fixtures from the CPU oracle (oracle/surtr_oracle.cpp).
 
-The reference ships no fixtures and cannot be built here (see oracle header), so these vectors are the
-oracle's outputs -- itself pinned by tests/test_oracle_kat.py -- on the BASELINE.json configurations:
+The reference ships no fixtures, so these vectors are the oracle's outputs -- itself pinned by tests/test_oracle_kat.py and,
+function by function, by tests/test_reference_compiled.py -- on the BASELINE.json configurations:
   cube8.npz        cfg1, complete inputs (seeds, planes) and complete outputs
   digests.json     cfg2 / cfg3 / cfg4: counts + sha256 of every output array; urchin64 / urchin1024: the deep-lobed mesh of
                    meshgen.urchin (cells with several islands, non-convex faces) at the cell counts of cfg2 / cfg3
   reference_models.npz  the reference's bunny (x70) and cube (x3) as engine.read_obj loads them (tests/test_reference_pin.py);
                    written only by --models DIR, DIR being the reference's Resources/Models
-Run from the repo root:  python tests/golden/make_golden.py [--models DIR]
+  reference_compiled.npz  inputs and outputs of the reference's own geometry code, compiled by `make -C oracle ref`, on the
+                   designed cases and 40 of the random clips of tests/reference_cases.py (tests/test_reference_compiled.py);
+                   written only by --reference-compiled, which needs the reference tree
+Run from the repo root:  python tests/golden/make_golden.py [--models DIR | --reference-compiled]
 """
 import hashlib
 import json
@@ -51,9 +54,21 @@ def models(src):
                         cube_tris=cube[1])
 
 
+def reference_compiled():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from oracle import ref_compiled as RC
+    import reference_cases as C
+    RC.build()
+    cases = C.designed() + C.recorded_random(C.random_clips(O))
+    RC.record(os.path.join(HERE, "reference_compiled.npz"), cases, RC.run(cases))
+    print("reference_compiled", len(cases), os.path.getsize(os.path.join(HERE, "reference_compiled.npz")))
+
+
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == "--models":
         return models(sys.argv[2])
+    if len(sys.argv) == 2 and sys.argv[1] == "--reference-compiled":
+        return reference_compiled()
     sc = scenes.cube_scene(8)
     planes, ev = run(sc)
     np.savez_compressed(os.path.join(HERE, "cube8.npz"), seeds=sc["seeds"], face_off=sc["face_off"], v012=sc["v012"], planes=planes,
