@@ -959,6 +959,66 @@ enum { SURTR_CULL_LIGHT = 1, SURTR_CULL_OUTSIDE = 2 };
 int surtr_scene_cull(surtr_ctx* ctx, int set, float density, float min_mass, const float* keep_box6_or_null, int apply,
                      uint32_t* n_compounds, uint8_t* reason, uint32_t* n_removed);
 
+/* ---- scene contacts: which bodies are within a margin of each other, through which pieces, how far apart, where (contact_dev.hip) ----
+ * What the fracture cycle takes as its input (surtr_scene_fracture_impacts: "a solver reports contacts"), from the resident Convex
+ * solids and the poses, every frame, without a download.  DEFINITION, so that a result can be checked:
+ *   World vertices   of piece p of body c: the float positions surtr_scene_apply_pose(c) would write for its Convex (transform_coord,
+ *                    operation for operation; a pose that is bit for bit the identity transforms nothing), converted to double.
+ *   Broad phase      on the surtr_bounds records of surtr_scene_bounds(set 1): bodies a < b are a candidate pair when, for every axis k,
+ *                    (double)lo_a[k] - (double)hi_b[k] <= (double)margin and (double)lo_b[k] - (double)hi_a[k] <= (double)margin.  A body
+ *                    whose record has SURTR_BOUNDS_NONFINITE is in no pair.
+ *   Mid phase        the same test on the per-piece records, for every piece p of a and q of b of a candidate body pair.  Pieces of
+ *                    one body are never paired.
+ *   Narrow phase     d = the Euclidean distance between the convex hulls of the two world vertex sets, in double (GJK); S = the largest
+ *                    absolute world coordinate of the two solids.  d <= 2^-24 * S: SURTR_CONTACT_OVERLAP, distance = 0, point_a =
+ *                    point_b = a point of both hulls, normal = 0 (below that the float input cannot tell touching from penetrating; no
+ *                    penetration depth is computed).  Otherwise point_a in hull(A) and point_b in hull(B) are closest points, normal =
+ *                    (point_b - point_a) / d, distance = d, each rounded to float.  Where closest points are not unique any closest
+ *                    pair is a valid answer.  A pair is REPORTED when it overlaps or d <= margin.
+ *   Order            records ascend by (piece_a, piece_b); compounds are contiguous ranges of pieces and a < b, so body_a never descends.
+ * GJK stops when the support vertex pair is already in the simplex, when |v|^2 - v.w <= 2^-36 |v|^2 + 2^-44 S |v| (v the simplex's
+ * closest point, w the new support point: d is then known to a relative 2^-36 and an absolute 2^-44 S, far below the float rounding
+ * of the output), when the simplex's new closest point is no nearer than its last (the old one lies in the new simplex: the arithmetic
+ * has reached its own rounding), or after 96 iterations (SURTR_CONTACT_ITER: the best answer so far).  Ties in the support function go to the lowest
+ * vertex number, nothing is accumulated with atomics, the lists are placed by count -> scan -> fill: two calls on the same scene give
+ * the same bits, whatever the stream, the events-in-flight hint or the other work on the GPU. */
+typedef struct surtr_contact {            /* 64 bytes */
+    uint32_t body_a, body_b;              /* a < b */
+    uint32_t piece_a, piece_b;            /* resident pieces; piece_a belongs to body_a */
+    float    distance;                    /* >= 0 */
+    uint32_t status;                      /* SURTR_CONTACT_* bits */
+    float    point_a[3], point_b[3], normal[3];
+    uint32_t reserved;                    /* zero */
+} surtr_contact;
+enum { SURTR_CONTACT_OVERLAP = 1, SURTR_CONTACT_ITER = 2 };
+typedef struct surtr_contact_header {     /* 64 bytes, in front of the records of the _dev form */
+    uint32_t status;                      /* SURTR_OK or SURTR_E_CAPACITY */
+    uint32_t n_records;                   /* records written (with SURTR_E_CAPACITY: needed) */
+    uint32_t n_body_pairs, n_piece_pairs; /* candidates of the broad / mid phase */
+    uint32_t n_bodies, n_pieces;          /* of the scene */
+    uint32_t lists;                       /* 0; bit 0 / bit 1: the body / piece candidates outgrew the call's lists (below) */
+    uint32_t reserved[9];                 /* zero */
+} surtr_contact_header;
+#define SURTR_CONTACT_MAX_PAIRS 2097152u  /* candidates of either kind one call has room for */
+/* dev_records (device memory) takes the header, then the records.  The rules of surtr_event_hulls_dev hold: enqueued on the context's
+ * stream, no host synchronisation, one temporary device allocation ordered on that stream (besides the bounds records, which go to
+ * buffers of the context as in surtr_scene_bounds_dev), no slot of surtr_kernel_times (all sixteen are taken; surtr_scene_contacts_times
+ * below).  SURTR_E_INVALID for a margin that is negative or not finite, SURTR_E_STATE without resident pieces, SURTR_E_CAPACITY before
+ * anything is enqueued when records_bytes cannot hold the header.  The totals are known only on the device: when the records do not fit,
+ * the header is written with SURTR_E_CAPACITY and the totals needed, and nothing else is.  The candidate lists are sized on the host for
+ * the worst case of the scene (every body near every other), up to SURTR_CONTACT_MAX_PAIRS entries each; a scene that outgrows that
+ * gives the header SURTR_E_CAPACITY, the bit in `lists`, the totals found so far and zero for those behind (the body stage is
+ * all-pairs; scenes of 10^5 bodies need a sweep or a grid in front of it, which is not here). */
+int surtr_scene_contacts_dev(surtr_ctx* ctx, float margin, void* dev_records, size_t records_bytes);
+/* Host form, count-then-fill, synchronises: out == NULL returns *n = the records; with out, *n must hold its capacity (SURTR_E_CAPACITY
+ * and the count when too small).  The pairs are found once; the records are gathered again into room for all of them. */
+int surtr_scene_contacts(surtr_ctx* ctx, float margin, uint32_t* n, surtr_contact* out);
+/* The header of a run alone, on the host (status SURTR_OK unless a list was outgrown); synchronises. */
+int surtr_scene_contacts_totals(surtr_ctx* ctx, float margin, surtr_contact_header* totals);
+/* With surtr_set_profiling: the device time of the last surtr_scene_contacts_dev by phase, in ms: [0] bounds, [1] body and piece pairs
+ * (count, scan, fill, twice), [2] distances, [3] flag scan, header and gather; -1 where not run.  Synchronises the context's stream. */
+int surtr_scene_contacts_times(surtr_ctx* ctx, float ms[4]);
+
 /* ---- cooked hulls: weld, convex hull and coplanar merge of the points of a Convex (cook_dev.hip) ---- */
 /* For the solids surtr::HullUsable refuses (a sliver in the rings: SURTR_HULL_FLAT or a large convexity): the convex hull of the
  * solid's POINTS, built on the device, as the arrays PxConvexMeshDesc takes (points, PxHullPolygon records, 16-bit indices).  The

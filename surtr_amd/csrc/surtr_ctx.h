@@ -347,6 +347,10 @@ struct surtr_ctx
     DevBuf<float> d_posef; bool scene_posef_stale = true; std::vector<float> h_posef_stage;
     DevBuf<surtr_bounds> d_bounds_piece;                 // surtr_scene_bounds_dev without a piece buffer of the caller's: the per-piece records
     DevBuf<char> d_cull;                                 // surtr_scene_cull: mass records, bounds and reason bytes of every compound
+    // surtr_scene_contacts(_dev) (contact_dev.hip): the body records its broad phase reads (the piece records go to d_bounds_piece), and
+    // -- only under surtr_set_profiling -- the five events between its phases (made on first use, destroyed with the context)
+    DevBuf<surtr_bounds> d_bounds_body;
+    struct ContactEvents { hipEvent_t e[5] = {}; bool valid = false; ~ContactEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } contact_ev;
     // surtr_scene_append: the new pieces as the host gave them (offsets from 0 per set), vetted here by k_piece_check before the scene is touched
     struct { DevBuf<float> pos; DevBuf<uint32_t> loff, llen, vo; DevBuf<int32_t> nbr; DevBuf<uint8_t> dup; } stage[2];
     // surtr_scene_fragments: the tables it lays out on the host (fragment records, cursors, counts, size-class slots, chunk table), kept

@@ -106,6 +106,13 @@ BOUNDS_DTYPE = np.dtype([("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("n_vertices"
 assert BOUNDS_DTYPE.itemsize == 32
 BOUNDS_NONFINITE = 1
 CULL_LIGHT, CULL_OUTSIDE = 1, 2
+# surtr_contact and surtr_contact_header (include/surtr_hip.h), 64 bytes each: a reported pair of pieces of two bodies; the totals of a run
+CONTACT_DTYPE = np.dtype([("body_a", "<u4"), ("body_b", "<u4"), ("piece_a", "<u4"), ("piece_b", "<u4"), ("distance", "<f4"), ("status", "<u4"),
+                          ("point_a", "<f4", (3,)), ("point_b", "<f4", (3,)), ("normal", "<f4", (3,)), ("reserved", "<u4")])
+CONTACT_HEADER_DTYPE = np.dtype([("status", "<u4"), ("n_records", "<u4"), ("n_body_pairs", "<u4"), ("n_piece_pairs", "<u4"), ("n_bodies", "<u4"),
+                                 ("n_pieces", "<u4"), ("lists", "<u4"), ("reserved", "<u4", (9,))])
+assert CONTACT_DTYPE.itemsize == 64 and CONTACT_HEADER_DTYPE.itemsize == 64
+CONTACT_OVERLAP, CONTACT_ITER = 1, 2
 
 
 # the arrays of surtr_pieces_derived, in the order of the SURTR_DERIVED_* enumeration (include/surtr_hip.h)
@@ -1064,6 +1071,34 @@ class Engine:
         the context's stream; nothing is read back."""
         self._ck(lib().surtr_scene_bounds_dev(self._h, ctypes.c_int(int(set)), ctypes.c_void_p(dev_body), ctypes.c_size_t(body_capacity),
                                               ctypes.c_void_p(dev_piece), ctypes.c_size_t(piece_capacity)))
+
+    # ---- scene contacts: bodies within a margin of each other, through which pieces, how far apart, where (contact_dev.hip)
+    def scene_contacts(self, margin):
+        """surtr_scene_contacts: one CONTACT_DTYPE record per reported pair of pieces of two bodies, ascending by (piece_a, piece_b)."""
+        n = ctypes.c_uint32()
+        self._ck(lib().surtr_scene_contacts(self._h, ctypes.c_float(margin), ctypes.byref(n), None))
+        out = np.zeros(n.value, CONTACT_DTYPE)
+        if n.value:
+            self._ck(lib().surtr_scene_contacts(self._h, ctypes.c_float(margin), ctypes.byref(n), _p(out)))
+        return out
+
+    def scene_contacts_totals(self, margin):
+        """surtr_scene_contacts_totals: the header of a run (one CONTACT_HEADER_DTYPE record): records, candidate body and piece
+        pairs, bodies and pieces of the scene."""
+        h = np.zeros(1, CONTACT_HEADER_DTYPE)
+        self._ck(lib().surtr_scene_contacts_totals(self._h, ctypes.c_float(margin), _p(h)))
+        return h[0]
+
+    def scene_contacts_dev(self, margin, dev_ptr, capacity):
+        """surtr_scene_contacts_dev: a 64-byte header (CONTACT_HEADER_DTYPE), then the records, into `capacity` bytes of device
+        memory, on the context's stream; nothing is read back."""
+        self._ck(lib().surtr_scene_contacts_dev(self._h, ctypes.c_float(margin), ctypes.c_void_p(dev_ptr), ctypes.c_size_t(capacity)))
+
+    def scene_contacts_times(self):
+        """surtr_scene_contacts_times (after set_profiling(True)): ms of bounds, pair lists, distances, gather of the last _dev call."""
+        ms = np.zeros(4, np.float32)
+        self._ck(lib().surtr_scene_contacts_times(self._h, _p(ms)))
+        return ms
 
     def scene_remove(self, compounds):
         """surtr_scene_remove: erases the listed compounds (any order).  Returns (n_pieces, src): src[p] the old resident piece of

@@ -17,6 +17,7 @@
 //                 frame (OnImpacts: one overlap query for all of them, a body to the first impact that reaches it).  Without
 //                 --one-event the impacts run one after the other through the several-compound routine; with it through one event,
 //                 one regrouping and one commit.  One JSON line: the compounds each impact acted on, then what --body-clicks prints.
+// --contacts MARGIN (with --body-clicks): after every click, Contacts at that margin and the impacts ImpactsFromContacts derives.
 // --bounds, --cull-mass M [--keep-box lx,ly,lz,hx,hy,hz] (with --body-clicks): after every click, CullBodies and BodyBounds; one more
 //                 JSON line per click ({"upkeep": ...}: reasons, table, bounds).
 // --edit-bodies "16 floats;16 floats;16 floats" (with --body-clicks): after the last click, the scene edits a frame loop makes.  First the
@@ -612,6 +613,27 @@ static void upkeep(FractureEngine& eng, size_t q)
     printf("}\n");
 }
 
+// --contacts MARGIN (with --body-clicks): after every click, FractureEngine::Contacts at that margin and what ImpactsFromContacts derives
+// (radius: the click's --impact-radius).  One JSON line per click: the three totals, an FNV-1a hash of the records' bytes, the impacts.
+static bool g_contacts = false;
+static float g_contact_margin = 0.f, g_contact_radius = 1.f;
+static void contacts(FractureEngine& eng, size_t q)
+{
+    if (!g_contacts) return;
+    surtr_contact_header h;
+    const std::vector<surtr_contact> rec = eng.Contacts(g_contact_margin, &h);
+    unsigned long long fnv = 0xCBF29CE484222325ull;
+    const unsigned char* b = (const unsigned char*)rec.data();
+    for (size_t i = 0; i < rec.size() * sizeof(surtr_contact); ++i) { fnv ^= b[i]; fnv *= 0x100000001B3ull; }
+    const std::vector<Impact> im = ImpactsFromContacts(rec, g_contact_radius);
+    printf("{\"contacts\": %zu, \"records\": %zu, \"body_pairs\": %u, \"piece_pairs\": %u, \"fnv\": \"%016llx\", \"impacts\": [", q, rec.size(),
+           h.n_body_pairs, h.n_piece_pairs, fnv);
+    for (size_t i = 0; i < im.size(); ++i)
+        printf("%s[%.9g, %.9g, %.9g, %.9g, %d, %d]", i ? ", " : "", im[i].position.x, im[i].position.y, im[i].position.z, im[i].radius, im[i].compounds[0],
+               im[i].compounds[1]);
+    printf("]}\n");
+}
+
 // --edit-bodies: RemoveBodies, AddBodies, TransformCompound and PieceHulls on the scene the clicks left (see the head of the file).
 static std::vector<Matrix> g_edit;
 static void print_scene_state(FractureEngine& eng, const char* edit)
@@ -700,6 +722,8 @@ static void body_clicks(FractureEngine& eng, const std::vector<std::array<float,
         print_made_and_scene(made, table, world, bm);
         init_compounds(eng, q, made);
         upkeep(eng, q);
+        g_contact_radius = impact_radius;
+        contacts(eng, q);
     }
     if (!g_edit.empty()) edit_bodies(eng, piece);
 }
@@ -818,6 +842,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--cook")) g_cook = true;
         else if (!strcmp(argv[i], "--lit")) g_lit = true;
         else if (!strcmp(argv[i], "--bounds")) g_bounds = true;
+        else if (!strcmp(argv[i], "--contacts") && i + 1 < argc) { g_contacts = true; g_contact_margin = (float)atof(argv[++i]); }
         else if (!strcmp(argv[i], "--cull-mass") && i + 1 < argc) { g_cull = true; g_cull_mass = (float)atof(argv[++i]); }
         else if (!strcmp(argv[i], "--keep-box") && i + 1 < argc)
         {

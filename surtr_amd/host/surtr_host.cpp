@@ -1016,6 +1016,36 @@ std::vector<surtr_bounds> FractureEngine::BodyBounds(int set)
     return out;
 }
 
+std::vector<surtr_contact> FractureEngine::Contacts(float margin, surtr_contact_header* totals)
+{
+    if (totals) check(surtr_scene_contacts_totals(ctx_, margin, totals), "surtr_scene_contacts_totals");
+    uint32_t n = 0;
+    check(surtr_scene_contacts(ctx_, margin, &n, nullptr), "surtr_scene_contacts");
+    std::vector<surtr_contact> out(n);
+    if (n) check(surtr_scene_contacts(ctx_, margin, &n, out.data()), "surtr_scene_contacts");
+    return out;
+}
+
+std::vector<Impact> ImpactsFromContacts(const std::vector<surtr_contact>& contacts, float radius)
+{
+    std::vector<Impact> out;
+    std::vector<size_t> best;      // per impact: the record it stands for
+    for (size_t i = 0; i < contacts.size(); ++i)
+    {
+        const surtr_contact& r = contacts[i];
+        size_t k = 0;
+        while (k < out.size() && !(contacts[best[k]].body_a == r.body_a && contacts[best[k]].body_b == r.body_b)) ++k;
+        if (k == out.size()) { out.push_back(Impact{}); best.push_back(i); }
+        else if (!(r.distance < contacts[best[k]].distance)) continue;
+        else best[k] = i;
+        Impact& im = out[k];
+        im.position = Vector3((r.point_a[0] + r.point_b[0]) * 0.5f, (r.point_a[1] + r.point_b[1]) * 0.5f, (r.point_a[2] + r.point_b[2]) * 0.5f);
+        im.radius = radius;
+        im.compounds = {(int)r.body_a, (int)r.body_b};
+    }
+    return out;
+}
+
 void FractureEngine::RemoveBodies(const std::vector<int>& compounds)
 {
     std::vector<uint32_t> t;

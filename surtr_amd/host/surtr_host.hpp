@@ -172,6 +172,9 @@ struct FractureArgs
 // pattern: the stored pattern (FractureEngine::StorePattern) its cells come from, -1 the engine's installed pattern; partial: 0 / 1
 // FractureArgs::PartialFracture for this impact alone, -1 what the call's args say.  Left at -1, both mean what they meant before.
 struct Impact { Vector3 position; float radius = 0.f; std::vector<int> compounds; int pattern = -1; int partial = -1; };
+// One Impact per pair of bodies the contacts name, in record order of the pair's first record: at the midpoint of the witness points
+// of that pair's closest record (ties: the first in record order), of the radius given, naming both bodies.  Ready for OnImpacts.
+std::vector<Impact> ImpactsFromContacts(const std::vector<surtr_contact>& contacts, float radius);
 struct Ray { Vector3 position, direction; Ray() = default; Ray(const Vector3& p, const Vector3& d) : position(p), direction(d) {} };
 // Surtr::ConvexRayIntersection (Src/Surtr.cpp:2460-2497), on the host from the definition of include/surtr_hip.h: the ray's
 // interval [0, inf) clipped by the half-space of every face plane (FacePlane; built from the first three vertices where it was
@@ -418,6 +421,11 @@ public:
     // BodyBounds: the world-space box of every compound under its pose, taken on the device (set 0 = Mesh, 1 = Convex): a broad
     // phase's, a renderer's and a kill volume's input.
     std::vector<surtr_bounds> BodyBounds(int set = 1);
+    // Contacts: the pairs of pieces of two bodies that overlap or are within `margin` of each other, with distance, witness points and
+    // normal, taken on the device from the Convex solids and the poses (surtr_scene_contacts), ascending by (piece_a, piece_b).
+    // totals (may be null): the candidate counts of the broad and mid phases.  With ImpactsFromContacts below it is the front of a
+    // frame loop: Contacts -> ImpactsFromContacts -> OnImpacts.
+    std::vector<surtr_contact> Contacts(float margin, surtr_contact_header* totals = nullptr);
     // RemoveBodies: erases the listed compounds (any order; one out of range or named twice, or all of them, throws
     // Error(SURTR_E_INVALID)); the others keep their order and their poses.  No solid leaves the device.
     void RemoveBodies(const std::vector<int>& compounds);
